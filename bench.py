@@ -15,13 +15,15 @@ Documents shard trivially: rank r encodes documents [r*1M, (r+1)*1M) of the gene
 with its own context; the only collective is an all-gather of the per-rank id totals
 (RCCL), inside every timed step.
 
-The JSON line also carries
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last
+timed step returned (ids.npy, offsets.npy: see dump_outputs).  The JSON line also carries
   roofline      algorithmic HBM bytes of the dominant kernel (k_tiles) / its mean duration from HIP
                 events recorded around it on the launch stream in every timed step, against 8 TB/s;
                 `wavefront_cycles`: where a resident wavefront's cycles go (committed PMC profile; shares of one
                 counter's unit, none can pass 1); `latency`: what does bind the kernel (occupancy A/B, L2 latency counters)
   strong        (N > 1) BASELINE config 4: the SAME 1,000,000 documents cut into N byte-balanced
                 contiguous shards (hutoken_amd.sharding.shard_by_bytes), rank r generating only its range
+With --full it carries besides (--no-extras, --no-cpu and --no-verify leave parts out):
   end_to_end    (N = 1) the drop-in's host entry points on the same workload: page-locked host buffers in
                 and out through hutk_encode_batch (PCIe inclusive), and the Python list API on a sample
   secondary     (N = 1) other configurations (config 5's single-GPU half and the merges path at 1 M documents) and
@@ -29,7 +31,7 @@ The JSON line also carries
   cpu_baseline  (N = 1) the reference itself (oracle/_ref, compiled from the reference sources; kind
                 "reference") timed on the host cores on a bounded sample of the same workload: its list API
                 (`value`) and, marshalling-free, its C core through the internal encode() seam (`seam`).
-Everything measured on the GPU is checked against the oracle on its first 2000 documents.
+  verified_vs_oracle  everything measured on the GPU is checked against the oracle on its first 2000 documents.
 """
 import argparse
 import glob
@@ -44,6 +46,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
 N_SIMD = 1024           # 256 CUs x 4 SIMDs
 VERIFY_DOCS = 2000
+DUMP_IDS = 1 << 23          # --dump-outputs: ids kept, float32 (exact below 2**24): 32 MiB
+DUMP_OFFSETS = 3_000_000    # offsets kept, float64 (exact below 2**53): 23 MiB
 
 
 def cpu_baseline(vp, sp, kw, corpus_name, n_sample, cores, mp=None):
@@ -154,6 +158,23 @@ def timed(batch, steps, warmup, sync):
         tile_ms.append(batch.ctx.last_timing()[0])
     sync()
     return (time.perf_counter() - t0) / steps, sum(tile_ms) / len(tile_ms)
+
+
+def dump_outputs(batch, out_dir):
+    """--dump-outputs: what the last pass handed its caller, the ids and the per-document offsets, as out_dir/ids.npy and
+    out_dir/offsets.npy.  An array longer than its budget is cut to a fixed seeded sample of its positions (sorted; the
+    same positions for the same length), so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    batch.check_err()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, n, keep, dtype in (("ids", batch.d_ids, batch.n_ids(), DUMP_IDS, np.float32),
+                                     ("offsets", batch.d_oo, batch.n_docs + 1, DUMP_OFFSETS, np.float64)):
+        t = t[:n]
+        if n > keep:
+            pos = np.sort(np.random.default_rng(0).integers(0, n, size=keep))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(dtype))
 
 
 class _Env:
@@ -393,10 +414,14 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="what `value` is at N > 1: weak = the corpus per GPU; strong = ONE corpus cut into N byte-balanced "
                          "shards.  The default run reports weak as `value` and, at N > 1, strong beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle check, end_to_end and secondary (N = 1) and cpu_baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's ids and offsets (rank 0) as DIR/<name>.npy")
     ap.add_argument("--cpu-docs", type=int, default=100_000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip end_to_end and secondary (N = 1)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the checks against the oracle")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip end_to_end and secondary (N = 1)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 code "
                          "path where RCCL cannot run, e.g. two ranks sharing one GPU with HUTK_BENCH_DEVICE=0)")
@@ -447,8 +472,9 @@ def main():
     def sync():
         torch.cuda.synchronize(dev)
 
-    def run_mode(first_doc, n_docs):
-        """Timed region of one scaling mode on this rank's documents [first_doc, first_doc + n_docs)."""
+    def run_mode(first_doc, n_docs, dump=False):
+        """Timed region of one scaling mode on this rank's documents [first_doc, first_doc + n_docs); dump: the mode of
+        `value`, whose last step --dump-outputs writes."""
         t_gen = time.perf_counter()
         data, offs = synth.corpus(args.corpus, n_docs, first_doc=first_doc, threads=gen_threads)
         t_gen = time.perf_counter() - t_gen
@@ -496,8 +522,10 @@ def main():
             tb = torch.tensor([batch.n_bytes, total_ids], dtype=torch.int64, device=cdev)
             dist.all_reduce(tb)
             total_bytes, total_ids = int(tb[0].item()), int(tb[1].item())
+        if dump and args.dump_outputs and rank == 0:
+            dump_outputs(batch, args.dump_outputs)
         verified = None
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             from oracle import oracle as O
             orc = O.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"], mp)
             verified = batch.verify(orc, data, offs, cores)
@@ -507,11 +535,11 @@ def main():
     # ---- weak: the whole corpus on every rank ------------------------------------------------------------
     modes = {}
     if args.scaling == "weak" or world > 1:
-        modes["weak"] = run_mode(rank * n_corpus, n_corpus)
+        modes["weak"] = run_mode(rank * n_corpus, n_corpus, dump=args.scaling == "weak")
     # ---- strong (BASELINE config 4): ONE corpus, N byte-balanced contiguous shards -------------------------
     if args.scaling == "strong" or world > 1:
         if world == 1:
-            modes["strong"] = modes.get("weak") or run_mode(0, n_corpus)
+            modes["strong"] = modes.get("weak") or run_mode(0, n_corpus, dump=True)
         else:
             if "weak" in modes:  # free the weak batch's buffers first
                 modes["weak"].pop("batch"); modes["weak"].pop("data"); modes["weak"].pop("offs")
@@ -520,7 +548,7 @@ def main():
             offs_all = np.zeros(n_corpus + 1, dtype=np.int64)
             np.cumsum(lens, out=offs_all[1:])
             first, count = sharding.shard_by_bytes(offs_all, world)[rank]
-            modes["strong"] = run_mode(first, count)
+            modes["strong"] = run_mode(first, count, dump=args.scaling == "strong")
             modes["strong"]["shard"] = (int(first), int(count))
 
     if rank == 0:
@@ -597,7 +625,7 @@ def main():
                                   workload=f"{args.corpus}: {n_corpus} docs in all, {world} byte-balanced shards "
                                            "(BASELINE config 4)",
                                   rank0_shard_docs=modes["strong"].get("shard", (0, n_corpus))[1])
-        if world == 1 and not args.no_extras and "batch" in m:
+        if world == 1 and args.full and not args.no_extras and "batch" in m:
             from oracle import oracle as O
             orc = O.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"], mp)
             try:
@@ -615,7 +643,7 @@ def main():
                 raise
             except Exception as e:
                 line["secondary"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(vp, sp, kw, args.corpus, min(args.cpu_docs, n_corpus), cores, mp)
         print(json.dumps(line), flush=True)
         if line.get("parity_failures"):

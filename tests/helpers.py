@@ -10,6 +10,7 @@ if ROOT not in sys.path:
 from hutoken_amd import vocab_files as vf  # noqa: E402
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+G12_PATH = os.path.join(GOLDEN_DIR, "g12_reference_answers.json.gz")
 
 BLOCK_DOCS = 100_000
 
@@ -195,3 +196,33 @@ def random_bytes_text(rng, n):
             b"\xc0\xa0", b"\xc1\xa1", b"\xc0\x80", b"\xc2\xa0", b"\xc2\x85", b"\xe0\x80\x80", b"\n"]
     out = b"".join(rng.choice(pool) for _ in range(n))
     return out
+
+
+_g12 = None
+
+
+def g12():
+    """tests/golden/g12_reference_answers.json.gz: the compiled reference's answers (tools/make_golden_g12.py)."""
+    global _g12
+    if _g12 is None:
+        import gzip
+        import json
+        with gzip.open(G12_PATH, "rt", encoding="ascii") as f:
+            _g12 = json.load(f)
+    return _g12
+
+
+def giant_word_docs():
+    """-> (documents with words of 1100 .. 30000 bytes that really merge, ONE document "q " + a word of 262143 bytes, the
+    reference's limit): tests/test_gpu_parity.py::test_giant_words, seeded."""
+    rng = random.Random(29)
+    pieces = [b"international", b"szolg", "árvíztűrő".encode(), b"xq", b"the", b"ation"]
+
+    def blob(n):
+        parts, size = [], 0
+        while size < n:
+            parts.append(rng.choice(pieces))
+            size += len(parts[-1])
+        return b"".join(parts)[:n]
+    docs = [b"a " + blob(1100) + b" b", blob(5000), b"x " + blob(30000), blob(2047) + b" " + blob(1025)]
+    return docs, b"q " + blob(262143)

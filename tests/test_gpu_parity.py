@@ -125,28 +125,20 @@ def test_long_words_exception_path(small_byte):
 def test_giant_words(vg_files, oracle_mod):
     """Words of tens of thousands of units that really merge (the two-level minimum structure of
     bpe_wave_big), up to the reference's limit of 262144 bytes.  The oracle's quadratic specification loop
-    checks 30000 units; the largest size is checked against the compiled reference when it is present."""
+    checks 30000 units; the largest size is checked against the compiled reference's ids (G12)."""
+    import hashlib
     vp, sp, kw = vg_files
     ctx = _ctx(vp, sp, kw["prefix"], kw["is_byte_encoder"])
     orc = oracle_mod.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"])
-    rng = random.Random(29)
-    def blob(n):
-        parts = []
-        while sum(map(len, parts)) < n:
-            parts.append(rng.choice([b"international", b"szolg", "árvíztűrő".encode(), b"xq", b"the", b"ation"]))
-        return b"".join(parts)[:n]
-    docs = [b"a " + blob(1100) + b" b", blob(5000), b"x " + blob(30000), blob(2047) + b" " + blob(1025)]
+    docs, big = H.giant_word_docs()
     _compare(ctx, orc, docs, "giant")
-    from oracle import ref
-    if ref.available():
-        big = blob(262143)
-        tok = ref.RefTokenizer(vp, sp, kw["prefix"], kw["is_byte_encoder"])
-        want, _err = tok.encode_bytes(b"q " + big)
-        from oracle import oracle as O
-        data, offs = O.pack([b"q " + big])
-        ids_g, oo_g, st_g, rc = ctx.encode_packed(data, offs)
-        assert rc == 0 and st_g.tolist() == [0]
-        assert ids_g.tolist() == list(want)
+    want = H.g12()["giant"]
+    from oracle import oracle as O
+    data, offs = O.pack([big])
+    ids_g, oo_g, st_g, rc = ctx.encode_packed(data, offs)
+    assert rc == 0 and st_g.tolist() == [0]
+    assert len(ids_g) == want["n_ids"]
+    assert hashlib.sha256(np.asarray(ids_g, dtype="<i4").tobytes()).hexdigest() == want["ids_sha256"]
 
 
 def test_words_of_65_to_1024_units(vg_files, vl_files, small_byte, oracle_mod):

@@ -3,6 +3,9 @@ reference pins (reference hutoken.py:22-43, 122-139; tests/test_tokenizer.py:43-
 import importlib
 import inspect
 import os
+import subprocess
+import sys
+import textwrap
 
 import pytest
 
@@ -24,12 +27,24 @@ def test_signatures(hutoken):
     assert list(sig.parameters) == ["model_or_path", "args", "kwargs"]
 
 
-def test_encode_before_initialize(hutoken):
-    msg = "Vocabulary is not initialized for encoding. Call 'initialize_encode' function first."
-    with pytest.raises(RuntimeError, match=msg):
-        hutoken.encode("szia")
-    with pytest.raises(RuntimeError, match=msg):
-        hutoken.batch_encode(["szia"])
+def in_fresh_process(code, env=None):
+    """Runs `code` (with pytest, helpers as H and hutoken_amd as hutoken imported) in a new interpreter: the compiled
+    module's process-global context outlives importlib.reload, and a GPU test earlier in this process may have set it."""
+    head = "import pytest\nimport helpers as H\nimport hutoken_amd as hutoken\n"
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", head + textwrap.dedent(code)],
+                       cwd=os.path.join(H.ROOT, "tests"), env=dict(os.environ, **(env or {})), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_encode_before_initialize():
+    in_fresh_process("""
+        msg = "Vocabulary is not initialized for encoding. Call 'initialize_encode' function first."
+        with pytest.raises(RuntimeError, match=msg):
+            hutoken.encode("szia")
+        with pytest.raises(RuntimeError, match=msg):
+            hutoken.batch_encode(["szia"])
+    """)
 
 
 def test_initialize_errors(hutoken, tmp_path):
@@ -59,13 +74,15 @@ def test_merges_file_arguments(hutoken, tmp_path):
         hutoken.initialize(vp, spath, merges_file_path=missing)
 
 
-def test_out_of_path_features_fail_loudly(hutoken, tmp_path):
+def test_out_of_path_features_fail_loudly(tmp_path):
     ents, sp = H.random_byte_vocab(1, n_merges=20)
     vp, spath = H.write_vocab(tmp_path, "v", ents, sp)
-    with pytest.raises(RuntimeError):  # (no GPU here: the context cannot be created)
-        hutoken.initialize(vp, spath, pattern="[a-z]+")
-    with pytest.raises(RuntimeError):
-        hutoken.decode([1, 2, 3])
+    in_fresh_process("""
+        with pytest.raises(RuntimeError):  # (no GPU visible: the context cannot be created)
+            hutoken.initialize(%r, %r, pattern="[a-z]+")
+        with pytest.raises(RuntimeError):
+            hutoken.decode([1, 2, 3])
+    """ % (vp, spath), env={"HIP_VISIBLE_DEVICES": "-1"})
 
 
 def test_pattern_argument(tmp_path):

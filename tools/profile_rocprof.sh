@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
-ARGS="--steps 10 --warmup 3 --no-cpu --no-extras"
+ARGS="--full --steps 10 --warmup 3 --no-cpu --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 bench.py $ARGS > "$OUT/bench_kt.json" 2> "$OUT/bench_kt.err" || exit 1
 echo "kernel trace done"
 PARGS="--steps 3 --warmup 1 --no-cpu --no-verify --no-extras"

@@ -23,7 +23,7 @@ one() {
   done
   echo "$name done"
 }
-one c5vl bench.py --corpus C5 --vocab VL --no-cpu --no-extras
-one merges bench.py --merges --no-cpu --no-extras
+one c5vl bench.py --full --corpus C5 --vocab VL --no-cpu --no-extras
+one merges bench.py --full --merges --no-cpu --no-extras
 one decode tools/bench_decode.py
 python3 tools/summarize_variant.py "$OUT" "$TAG"

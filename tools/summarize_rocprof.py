@@ -13,7 +13,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dst = os.path.join(root, "profiles")
 os.makedirs(dst, exist_ok=True)
 lines = [f"# rocprofv3 summary, round tag {tag}", "",
-         "Command: `python3 bench.py --steps 10 --warmup 3 --no-cpu` under `rocprofv3 --kernel-trace --stats` "
+         "Command: `python3 bench.py --full --steps 10 --warmup 3 --no-cpu --no-extras` under `rocprofv3 --kernel-trace --stats` "
          "(PMC passes: `--steps 3 --warmup 1`, one counter set per run, `--pmc ... --kernel-trace`).", ""]
 
 

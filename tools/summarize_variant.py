@@ -7,7 +7,7 @@ from collections import defaultdict
 src, tag = sys.argv[1], sys.argv[2]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = {"c5vl": "k_tiles", "merges": "k_tiles", "decode": "k_dec_tiles"}
-CMD = {"c5vl": "bench.py --corpus C5 --vocab VL --no-cpu --no-extras", "merges": "bench.py --merges --no-cpu --no-extras",
+CMD = {"c5vl": "bench.py --full --corpus C5 --vocab VL --no-cpu --no-extras", "merges": "bench.py --full --merges --no-cpu --no-extras",
        "decode": "tools/bench_decode.py"}
 for name, kern in KERNEL.items():
     if not os.path.isdir(os.path.join(src, name)):

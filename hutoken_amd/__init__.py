@@ -15,6 +15,10 @@ GPU every call raises.
 
 Also here (not in the reference): `encode_packed` / `encode_packed_device`, the
 zero-marshalling entry points for packed UTF-8 + offsets.
+
+Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
+`bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
+the batch-fed trainer and a writer of GPT-2-shaped vocab, special and merges files.
 """
 import os
 import sys
@@ -23,7 +27,7 @@ import traceback
 from . import _capi
 
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
-           "decode", "batch_decode", "context"]
+           "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -300,3 +304,152 @@ def batch_decode(tokens, num_threads=1):
     except Exception as e:
         traceback.print_exc(file=sys.stderr)
         raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+
+
+
+# ---- training -------------------------------------------------------------------------------------------------
+def _default_device(device):
+    return int(os.environ.get("HUTOKEN_DEVICE", "-1")) if device is None else int(device)
+
+
+class Trainer:
+    """Byte-level BPE training on the GPU (hutk_trainer_*, include/hutoken_amd.h).  Documents arrive over any number
+    of add() / add_packed() calls; run() once returns the merges.  Semantics: tools/train_vocab.cpp, "bytes" mode."""
+
+    def __init__(self, device=None):
+        self._t = _capi.Trainer(_default_device(device))
+
+    def add(self, texts):
+        """A list of str, one document each (cut at the first NUL, like batch_encode)."""
+        if not isinstance(texts, list):
+            raise TypeError("Invalid arguments. Expected a list of strings.")
+        data, offs = _pack(texts)
+        self._t.add_packed(data, offs)
+
+    def add_packed(self, data, offsets):
+        """Packed bytes (uint8 array or bytes) + int64 offsets[n+1].  A 0x00 byte in a document raises ValueError
+        and nothing of the call is counted."""
+        import numpy as np
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = np.frombuffer(bytes(data), dtype=np.uint8)
+        self._t.add_packed(data, offsets)
+
+    def run(self, n_merges):
+        """-> (pairs int32[m, 2], counts int64[m]); merge k creates symbol 256 + k."""
+        if not isinstance(n_merges, int) or n_merges < 0:
+            raise ValueError("n_merges must be a non-negative int")
+        return self._t.run(n_merges)
+
+    def stats(self):
+        return self._t.stats()
+
+    def close(self):
+        self._t.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _text_batches(texts):
+    if isinstance(texts, list) and all(isinstance(t, str) for t in texts):
+        yield texts
+        return
+    for batch in texts:
+        if not isinstance(batch, list) or not all(isinstance(t, str) for t in batch):
+            raise TypeError("texts must be a list of str or an iterable of such lists")
+        yield batch
+
+
+def train(texts, vocab_size, out_dir, name, end_of_text="<|endoftext|>", device=None):
+    """Train on `texts` (a list of str, or an iterable of such lists fed batch by batch) and write the GPT-2-shaped
+    files of tools/make_vocab.py: <name>_vocab.txt, <name>_special.txt, <name>_merges.txt under out_dir.
+    n_merges = vocab_size - 256 - (1 if end_of_text else 0).  -> dict(vocab_file, special_file, merges_file,
+    n_merges, stats).  The files load with initialize(vocab, special, is_byte_encoder=True)."""
+    from . import vocab_files as vf
+    if not isinstance(vocab_size, int) or isinstance(vocab_size, bool):
+        raise TypeError("vocab_size must be an int")
+    if not isinstance(out_dir, str) or not isinstance(name, str):
+        raise TypeError("out_dir and name must be str")
+    if end_of_text is not None and not isinstance(end_of_text, str):
+        raise TypeError("end_of_text must be a str or None")
+    n_merges = vocab_size - 256 - (1 if end_of_text else 0)
+    if n_merges < 0:
+        raise RuntimeError("vocab_size must be at least 256 to encode all bytes.")
+    if not os.path.isdir(out_dir):
+        raise FileNotFoundError(f"out_dir '{out_dir}' does not exist.")
+    with Trainer(device) as t:
+        for batch in _text_batches(texts):
+            t.add(batch)
+        pairs, _counts = t.run(n_merges)
+        stats = t.stats()
+    out = vf.write_gpt2_files(out_dir, name, pairs.tolist(), end_of_text)
+    out["n_merges"] = int(len(pairs))
+    out["stats"] = stats
+    return out
+
+
+def _check_train_args(args, kwargs):
+    # PyArg_ParseTuple(args, "sis", ...) of lib.c:81-83, then the checks of lib.c:85-95
+    if kwargs:
+        raise TypeError("function takes no keyword arguments")
+    if len(args) != 3:
+        raise TypeError(f"function takes exactly 3 arguments ({len(args)} given)")
+    data, vocab_size, name = args
+    if not isinstance(data, str):
+        raise TypeError(f"argument 1 must be str, not {type(data).__name__}")
+    if isinstance(vocab_size, float) or not hasattr(vocab_size, "__index__"):
+        raise TypeError(f"'{type(vocab_size).__name__}' object cannot be interpreted as an integer")
+    if not isinstance(name, str):
+        raise TypeError(f"argument 3 must be str, not {type(name).__name__}")
+    if "\0" in data or "\0" in name:
+        raise ValueError("embedded null character")
+    vocab_size = int(vocab_size)
+    if vocab_size < 256:
+        raise RuntimeError("vocab_size must be at least 256 to encode all bytes.")
+    if len(name.encode("utf-8")) < 4 or not name.encode("utf-8").endswith(b".txt"):
+        raise RuntimeError("vocab_file_name file extension must be .txt.")
+    return data, vocab_size, name
+
+
+def _native_bpe_train(which, args, kwargs):
+    data, vocab_size, name = _check_train_args(args, kwargs)
+    sh = _capi.shim()
+    if sh is not None:
+        return getattr(sh, which)(data, vocab_size, name)
+    from . import vocab_files as vf
+    import numpy as np
+    raw = data.encode("utf-8")
+    with Trainer(None) as t:
+        t.add_packed(np.frombuffer(raw, dtype=np.uint8), np.array([0, len(raw)], dtype=np.int64))
+        pairs, _ = t.run(vocab_size - 255)
+    home = os.environ.get("HOME")
+    if home is None:
+        sys.stderr.write("Unable to get HOME environment variable.")
+        return None
+    d = os.path.join(home, "config")
+    if os.path.isdir(d):
+        print(f"Directory already exists: {d}")
+    else:
+        os.mkdir(d, 0o700)
+        print(f"Directory created: {d}")
+    path = f"{d}/{name}"
+    with open(path, "w", encoding="ascii", newline="") as f:
+        f.write(vf.raw_vocab_text(pairs.tolist(), vocab_size))
+    print(f"Vocab saved to: {path}")
+    sys.stdout.flush()
+    return None
+
+
+def bpe_train(*args, **kwargs):
+    """hutoken.bpe_train(data, vocab_size, vocab_file_name) (reference hutoken.py:163-166, lib.c:76-101): trains on
+    `data` as one document and writes $HOME/config/<vocab_file_name>.  The file is a raw-byte vocabulary that
+    initialize(path) accepts: bytes 0x01..0xFF are ids 0..254, merge k is id 255 + k, at most vocab_size lines."""
+    return _native_bpe_train("bpe_train", args, kwargs)
+
+
+def bbpe_train(*args, **kwargs):
+    """hutoken.bbpe_train (reference hutoken.py:168-171, lib.c:103-126): the same byte-level model as bpe_train."""
+    return _native_bpe_train("bbpe_train", args, kwargs)

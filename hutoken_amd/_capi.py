@@ -23,6 +23,7 @@ EXPORTS = [
     "hutk_pair_table_entries", "hutk_device_ordinal", "hutk_table_stats", "hutk_last_timing",
     "hutk_set_timing", "hutk_debug_pairs_second", "hutk_debug_long_words", "hutk_debug_profile", "hutk_debug_profile_read", "hutk_debug_profile_raw", "hutk_debug_tile_bytes",
     "hutk_debug_seam", "hutk_debug_seam2_cut",
+    "hutk_trainer_create", "hutk_trainer_add", "hutk_trainer_run", "hutk_trainer_stats", "hutk_trainer_destroy",
 ]
 
 _lib = None
@@ -135,6 +136,17 @@ def load(build_if_missing=True):
     if hasattr(L, "hutk_debug_profile_raw"):
         L.hutk_debug_profile_raw.restype = i32
         L.hutk_debug_profile_raw.argtypes = [vp, i64, vp]
+    if hasattr(L, "hutk_trainer_create"):
+        L.hutk_trainer_create.restype = i32
+        L.hutk_trainer_create.argtypes = [C.POINTER(vp), i32]
+        L.hutk_trainer_add.restype = i32
+        L.hutk_trainer_add.argtypes = [vp, vp, vp, i64]
+        L.hutk_trainer_run.restype = i32
+        L.hutk_trainer_run.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
+        L.hutk_trainer_stats.restype = i32
+        L.hutk_trainer_stats.argtypes = [vp, vp]
+        L.hutk_trainer_destroy.restype = None
+        L.hutk_trainer_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -384,3 +396,55 @@ class Context:
         a, b = C.c_float(0), C.c_float(0)
         raise_for(load().hutk_last_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+TRAINER_STATS = ["docs", "bytes", "word_occurrences", "unique_words", "symbols", "pairs_at_start",
+                 "peak_device_bytes", "merge_loop_us"]
+
+
+class Trainer:
+    """Owns one hutk_trainer (byte-level BPE training on the GPU, include/hutoken_amd.h)."""
+
+    def __init__(self, device=-1):
+        h = C.c_void_p()
+        raise_for(load().hutk_trainer_create(C.byref(h), int(device)))
+        self._h = h
+
+    def add_packed(self, data, offsets):
+        """Packed bytes (uint8) + int64 offsets[n+1]: documents data[offsets[i]:offsets[i+1]]."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if n < 0:
+            raise ValueError("offsets must hold at least one entry")
+        if n and (int(offsets[0]) < 0 or int(offsets[n]) > len(data)):
+            raise ValueError("offsets point outside data")
+        raise_for(load().hutk_trainer_add(self._h, data.ctypes.data if len(data) else None, offsets.ctypes.data, n))
+
+    def run(self, n_merges):
+        """-> (pairs int32[m, 2], counts int64[m]), m <= n_merges."""
+        import numpy as np
+        n_merges = int(n_merges)
+        pairs = np.zeros((max(n_merges, 1), 2), dtype=np.int32)
+        counts = np.zeros(max(n_merges, 1), dtype=np.int64)
+        done = C.c_int32(0)
+        raise_for(load().hutk_trainer_run(self._h, n_merges, pairs.ctypes.data, counts.ctypes.data, C.byref(done)))
+        return pairs[:done.value].copy(), counts[:done.value].copy()
+
+    def stats(self):
+        import numpy as np
+        out = np.zeros(8, dtype=np.int64)
+        raise_for(load().hutk_trainer_stats(self._h, out.ctypes.data))
+        return dict(zip(TRAINER_STATS, out.tolist()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().hutk_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -75,6 +75,9 @@ struct DevBuf {
 };
 }  // namespace
 
+// the trainer (hutk_train.hip) reports through the same hutk_last_error()
+int hutk::api_set_error(int code, const std::string& msg) { return set_err(code, msg); }
+
 struct hutk_ctx {
     Tables tab;
     int device = -1;

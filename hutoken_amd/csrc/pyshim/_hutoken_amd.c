@@ -8,6 +8,8 @@
  *   batch_encode(texts, num_threads=1) -> list[list[int]]              lib.c:722-874, format "O|i"
  *   decode(tokens) -> str                                              lib.c:876-951
  *   batch_decode(tokens, num_threads=1) -> list[str]                   lib.c:954-1094
+ *   bpe_train(data, vocab_size, vocab_file_name) -> None               lib.c:76-101, format "sis"
+ *   bbpe_train(data, vocab_size, vocab_file_name) -> None              lib.c:103-126, format "sis"
  *   handle() -> int                                                    the hutk_ctx* of the module-global context
  *
  * What the reference does per DOCUMENT under the GIL (strdup of PyUnicode_AsUTF8, one EncodeTask and one IntVector
@@ -21,6 +23,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
+#include <sys/types.h>
 
 #include "hutoken_amd.h"
 
@@ -373,12 +377,127 @@ HUTK_ON_CONTEXT(p_batch_encode, batch_encode_on, NOT_INIT_ENCODE)
 HUTK_ON_CONTEXT(p_decode, decode_on, NOT_INIT_DECODE)
 HUTK_ON_CONTEXT(p_batch_decode, batch_decode_on, NOT_INIT_DECODE)
 
+/* bpe_train / bbpe_train (lib.c:76-126): same argument checks, messages and file location ($HOME/config/<name>,
+ * helper.c:129-186) as the reference; the model is trained on the GPU (hutk_trainer_*) with `data` as one document,
+ * and the file is a raw-byte vocabulary initialize(path) accepts: bytes 0x01..0xFF are ids 0..254, merge k is
+ * 255 + k, vocab_size lines at most, no 0x00 line.  Both names train the same byte-level model. */
+static PyObject* p_train(PyObject* self, PyObject* args) {
+    (void)self;
+    char* data = NULL;
+    char* vocab_file_name = NULL;
+    int vocab_size = 256;
+    if (!PyArg_ParseTuple(args, "sis", &data, &vocab_size, &vocab_file_name)) return NULL;
+    if (vocab_size < 256) {
+        PyErr_SetString(PyExc_RuntimeError, "vocab_size must be at least 256 to encode all bytes.");
+        return NULL;
+    }
+    size_t flen = strlen(vocab_file_name);
+    if (flen < 4 || strcmp(vocab_file_name + (flen - 4), ".txt") != 0) {
+        PyErr_SetString(PyExc_RuntimeError, "vocab_file_name file extension must be .txt.");
+        return NULL;
+    }
+    const char* env = getenv("HUTOKEN_DEVICE");
+    const int device = env && *env ? atoi(env) : -1;
+    const int32_t n_merges = vocab_size - 255;
+    int64_t offs[2] = {0, (int64_t)strlen(data)};
+    int32_t* pairs = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)n_merges);
+    if (!pairs) return PyErr_NoMemory();
+    hutk_trainer* t = NULL;
+    int32_t done = 0;
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = hutk_trainer_create(&t, device);
+    if (rc == HUTK_OK) rc = hutk_trainer_add(t, (const uint8_t*)data, offs, 1);
+    if (rc == HUTK_OK) rc = hutk_trainer_run(t, n_merges, pairs, NULL, &done);
+    Py_END_ALLOW_THREADS
+    if (t) hutk_trainer_destroy(t);
+    if (rc != HUTK_OK) {
+        free(pairs);
+        return raise_code(rc);
+    }
+    /* token bytes: symbol s < 256 is the byte s, 256 + k is token(a) + token(b) */
+    const int64_t n_sym = 256 + (int64_t)done;
+    int64_t* toff = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n_sym + 1));
+    int64_t total = 0;
+    if (!toff) {
+        free(pairs);
+        return PyErr_NoMemory();
+    }
+    int64_t* tlen = (int64_t*)malloc(sizeof(int64_t) * (size_t)n_sym);
+    if (!tlen) {
+        free(pairs), free(toff);
+        return PyErr_NoMemory();
+    }
+    for (int64_t i = 0; i < 256; i++) tlen[i] = 1;
+    for (int32_t k = 0; k < done; k++) tlen[256 + k] = tlen[pairs[2 * k]] + tlen[pairs[2 * k + 1]];
+    for (int64_t i = 0; i < n_sym; i++) toff[i] = total, total += tlen[i];
+    toff[n_sym] = total;
+    unsigned char* tb = (unsigned char*)malloc((size_t)(total ? total : 1));
+    if (!tb) {
+        free(pairs), free(toff), free(tlen);
+        return PyErr_NoMemory();
+    }
+    for (int64_t i = 0; i < 256; i++) tb[i] = (unsigned char)i;
+    for (int32_t k = 0; k < done; k++) {
+        const int32_t a = pairs[2 * k], b = pairs[2 * k + 1];
+        memcpy(tb + toff[256 + k], tb + toff[a], (size_t)tlen[a]);
+        memcpy(tb + toff[256 + k] + tlen[a], tb + toff[b], (size_t)tlen[b]);
+    }
+    free(pairs);
+    int ok = 0;
+    const char* home = getenv("HOME");
+    if (!home) {
+        (void)fputs("Unable to get HOME environment variable.", stderr);
+    } else {
+        size_t dl = strlen(home) + 8;
+        char* dir = (char*)malloc(dl);
+        char* path = (char*)malloc(dl + 1 + flen + 1);
+        if (dir && path) {
+            snprintf(dir, dl, "%s/config", home);
+            struct stat st;
+            int have = stat(dir, &st) == 0;
+            if (!have && mkdir(dir, 0700) == 0) {
+                printf("Directory created: %s\n", dir);
+                have = 1;
+            } else if (have) {
+                printf("Directory already exists: %s\n", dir);
+            } else {
+                (void)fputs("Error creating directory.", stderr);
+                (void)fputs("Failed to save vocab.", stderr);
+            }
+            if (have) {
+                snprintf(path, dl + 1 + flen + 1, "%s/%s", dir, vocab_file_name);
+                FILE* f = fopen(path, "w");
+                if (!f) {
+                    perror("Error creating file.\n");
+                } else {
+                    int64_t id = 0;
+                    for (int64_t sy = 1; sy < n_sym && id < vocab_size; sy++, id++) {
+                        for (int64_t j = 0; j < tlen[sy]; j++) fprintf(f, "0x%02X", tb[toff[sy] + j]);
+                        fprintf(f, " == %lld\n", (long long)id);
+                    }
+                    fclose(f);
+                    printf("Vocab saved to: %s\n", path);
+                    ok = 1;
+                }
+            }
+            fflush(stdout);
+        }
+        free(dir), free(path);
+    }
+    (void)ok;  /* the reference returns None whether or not the file could be written (lib.c:98-100) */
+    free(toff), free(tlen), free(tb);
+    Py_RETURN_NONE;
+}
+
 static PyMethodDef Methods[] = {
     {"initialize", (PyCFunction)p_initialize, METH_VARARGS | METH_KEYWORDS, "Initialize tokenizer"},
     {"encode", (PyCFunction)p_encode, METH_VARARGS, "Encodes string"},
     {"batch_encode", (PyCFunction)p_batch_encode, METH_VARARGS, "Encodes list of strings"},
     {"decode", p_decode, METH_VARARGS, "Decodes list of ints"},
     {"batch_decode", p_batch_decode, METH_VARARGS, "Decodes list of lists of ints"},
+    {"bpe_train", p_train, METH_VARARGS, "Trains a byte-level BPE vocabulary on the GPU"},
+    {"bbpe_train", p_train, METH_VARARGS, "Trains a byte-level BPE vocabulary on the GPU"},
     {"handle", p_handle, METH_NOARGS, "Address of the module-global hutk_ctx (0 before initialize)"},
     {NULL, NULL, 0, NULL}};
 

@@ -71,3 +71,58 @@ def llama_special_mapping():
     for b in list(range(0, 32)) + [127]:
         m[b] = "<0x%02X>" % b
     return m
+
+
+def merge_tokens(pairs):
+    """Byte strings of the symbols 256.. that merges (a, b) create: token(256 + k) = token(a) + token(b)."""
+    toks = [bytes([b]) for b in range(256)]
+    for a, b in pairs:
+        toks.append(toks[int(a)] + toks[int(b)])
+    return toks[256:]
+
+
+def gpt2_vocab_text(pairs, end_of_text="<|endoftext|>"):
+    """A GPT-2-shaped vocab file (tools/make_vocab.py): the 256 byte tokens in byte_token_order(), the merges in
+    order, visible-encoded, then the end token (if any).  ids = line order."""
+    t = bytes_to_unicode()
+    lines = [hex_line(encode_visible(bytes([b]), t), i) for i, b in enumerate(byte_token_order())]
+    for tok in merge_tokens(pairs):
+        lines.append(hex_line(encode_visible(tok, t), len(lines)))
+    if end_of_text:
+        lines.append(hex_line(end_of_text.encode("utf-8"), len(lines)))
+    return "".join(lines)
+
+
+def gpt2_merges_text(pairs):
+    """merges.txt: "#version: 0.2", then one visible-encoded "left right" line per merge."""
+    t = bytes_to_unicode()
+    toks = [bytes([b]) for b in range(256)] + merge_tokens(pairs)
+    out = ["#version: 0.2\n"]
+    for a, b in pairs:
+        out.append(encode_visible(toks[int(a)], t).decode("utf-8") + " " +
+                   encode_visible(toks[int(b)], t).decode("utf-8") + "\n")
+    return "".join(out)
+
+
+def gpt2_special_text():
+    return "".join("%d == %s\n" % (b, s) for b, s in sorted(gpt2_special_mapping().items()))
+
+
+def write_gpt2_files(out_dir, name, pairs, end_of_text="<|endoftext|>"):
+    """<name>_vocab.txt, <name>_special.txt, <name>_merges.txt under out_dir -> dict of the three paths."""
+    import os
+    paths = {"vocab_file": os.path.join(out_dir, name + "_vocab.txt"),
+             "special_file": os.path.join(out_dir, name + "_special.txt"),
+             "merges_file": os.path.join(out_dir, name + "_merges.txt")}
+    for key, text in (("vocab_file", gpt2_vocab_text(pairs, end_of_text)), ("special_file", gpt2_special_text()),
+                      ("merges_file", gpt2_merges_text(pairs))):
+        with open(paths[key], "w", encoding="utf-8", newline="") as f:
+            f.write(text)
+    return paths
+
+
+def raw_vocab_text(pairs, vocab_size):
+    """The vocabulary bpe_train / bbpe_train write: raw bytes, bytes 0x01..0xFF as ids 0..254, merge k as 255 + k;
+    vocab_size lines at most (no 0x00 line: a document cannot hold one and the loader rejects it)."""
+    toks = [bytes([b]) for b in range(1, 256)] + merge_tokens(pairs)
+    return "".join(hex_line(tk, i) for i, tk in enumerate(toks[:vocab_size]))

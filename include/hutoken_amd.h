@@ -237,6 +237,31 @@ int hutk_debug_profile_raw(hutk_ctx* ctx, int64_t n_tiles, long long* out); /* t
 /* Per-call profiling events cost a little; they are on by default. */
 void hutk_set_timing(hutk_ctx* ctx, int enabled);
 
+/* ---- training ------------------------------------------------------------------------------------------
+ * Byte-level BPE training on the GPU.  Replaces the reference's _hutoken.bpe_train / bbpe_train
+ * (src/lib.c:76-126, src/bpe.c, src/bbpe.c) with the exact semantics of tools/train_vocab.cpp in "bytes" mode:
+ *   documents  bytes[offsets[i] .. offsets[i+1]); they may arrive over several hutk_trainer_add calls and the word
+ *              counts accumulate.  A 0x00 byte inside a document fails the call with HUTK_E_NUL_BYTE and nothing
+ *              of that call is counted.  Empty documents are allowed.
+ *   words      the reference's splitter (src/parser.c, hutk_classify.h), never across documents, no length cap.
+ *   symbols    byte values 0..255; merge k (0-based) creates symbol 256 + k = bytes(a) + bytes(b).
+ *   counts     pair (a, b): sum over unique words of word count x adjacent (a, b) positions (overlaps count),
+ *              64-bit, integer atomics only: the result does not depend on the schedule.
+ *   selection  highest count; ties go to the smaller (uint64)a << 32 | b; training stops after n_merges merges or
+ *              when no pair has a count >= 1.
+ *   merge      in every word, left to right and non-overlapping (aaaa -> n n, aaa -> n a).
+ * hutk_trainer_create: device = HIP ordinal, -1 for the current device.
+ * hutk_trainer_run: may be called once per trainer (a second call returns HUTK_E_ARG); writes
+ *   pairs_out[2k], pairs_out[2k+1] = (a, b) of merge k and counts_out[k] (optional) for k < *n_done.
+ * hutk_trainer_stats: out8 = documents, bytes, word occurrences, unique words, symbols in unique words,
+ *   distinct pairs at the start, peak device workspace in bytes, microseconds of device time in the merge loop. */
+typedef struct hutk_trainer hutk_trainer;
+int hutk_trainer_create(hutk_trainer** out, int device);
+int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs);
+int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int64_t* counts_out, int32_t* n_done);
+int hutk_trainer_stats(const hutk_trainer* t, int64_t* out8);
+void hutk_trainer_destroy(hutk_trainer* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -343,6 +343,10 @@ class Trainer:
     def stats(self):
         return self._t.stats()
 
+    def debug_counters(self):
+        """Counters of the internal paths add() and run() took (for tests)."""
+        return self._t.debug_counters()
+
     def close(self):
         self._t.close()
 

@@ -24,6 +24,7 @@ EXPORTS = [
     "hutk_set_timing", "hutk_debug_pairs_second", "hutk_debug_long_words", "hutk_debug_profile", "hutk_debug_profile_read", "hutk_debug_profile_raw", "hutk_debug_tile_bytes",
     "hutk_debug_seam", "hutk_debug_seam2_cut",
     "hutk_trainer_create", "hutk_trainer_add", "hutk_trainer_run", "hutk_trainer_stats", "hutk_trainer_destroy",
+    "hutk_trainer_debug_counters",
 ]
 
 _lib = None
@@ -147,6 +148,9 @@ def load(build_if_missing=True):
         L.hutk_trainer_stats.argtypes = [vp, vp]
         L.hutk_trainer_destroy.restype = None
         L.hutk_trainer_destroy.argtypes = [vp]
+    if hasattr(L, "hutk_trainer_debug_counters"):
+        L.hutk_trainer_debug_counters.restype = i32
+        L.hutk_trainer_debug_counters.argtypes = [vp, vp, i32]
     _lib = L
     return L
 
@@ -400,6 +404,9 @@ class Context:
 
 TRAINER_STATS = ["docs", "bytes", "word_occurrences", "unique_words", "symbols", "pairs_at_start",
                  "peak_device_bytes", "merge_loop_us"]
+# hutk_trainer_debug_counters, in its order
+TRAINER_COUNTERS = ["pauses", "pair_grows", "pair_shrinks", "pair_rebuilds", "host_syncs", "pair_cap_max",
+                    "select_blocks_max", "word_rehashes", "deferred_words", "insert_rounds_max", "long_to_short"]
 
 
 class Trainer:
@@ -426,6 +433,10 @@ class Trainer:
         """-> (pairs int32[m, 2], counts int64[m]), m <= n_merges."""
         import numpy as np
         n_merges = int(n_merges)
+        if n_merges > 2**31 - 1:  # (the C ABI takes an int32_t; ctypes would truncate silently)
+            raise ValueError("n_merges must be at most 2**31 - 1")
+        if n_merges > 0:  # every merge removes a symbol: the C side never does more than the corpus holds
+            n_merges = min(n_merges, self.stats()["symbols"])
         pairs = np.zeros((max(n_merges, 1), 2), dtype=np.int32)
         counts = np.zeros(max(n_merges, 1), dtype=np.int64)
         done = C.c_int32(0)
@@ -437,6 +448,13 @@ class Trainer:
         out = np.zeros(8, dtype=np.int64)
         raise_for(load().hutk_trainer_stats(self._h, out.ctypes.data))
         return dict(zip(TRAINER_STATS, out.tolist()))
+
+    def debug_counters(self):
+        """Which internal paths add() and run() took (include/hutoken_amd.h, hutk_trainer_debug_counters)."""
+        import numpy as np
+        out = np.zeros(len(TRAINER_COUNTERS), dtype=np.int64)
+        raise_for(load().hutk_trainer_debug_counters(self._h, out.ctypes.data, len(out)))
+        return dict(zip(TRAINER_COUNTERS, out.tolist()))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -22,10 +22,21 @@
 //         The host synchronises every few merges to drop finished words and rebuild the pair table; a step
 //         that might not find room for its new keys pauses the loop instead (the host grows the table and
 //         resumes), so the table can never fill.
+//
+// Test-only schedule knobs, read by every hutk_trainer_run (unset: the constants below, the same code path)
+//   HUTK_TRAIN_SYNC_EVERY=n     merges enqueued between host synchronisations (n >= 1; default SYNC_EVERY = 64).
+//                               1 re-partitions the word lists and checks the table after every merge; a very large
+//                               value leaves the device-side pause as the only guard against a full pair table.
+//   HUTK_TRAIN_PAIR_CAP_LOG2=n  the pair table's floor, 2^n slots (default 16): the lower bound of the initial size
+//                               (4 * min(symbols, 65536) stays the other bound) and of every rebuild, and 2^(n-2) in
+//                               the shrink test.  A small floor makes pauses and shrinks frequent; 21 or more gives
+//                               k_select its full 1024 blocks with 8+ grid-stride trips per thread.
+// hutk_trainer_debug_counters reports which of these paths a run took (host values only, no added synchronisation).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -39,6 +50,7 @@ constexpr int TB = 256;              // threads per block
 constexpr int LONG_WORD = 64;        // words with more symbols take the wavefront-per-word kernels
 constexpr uint64_t PK_EMPTY = ~0ull; // pair table: empty key (a = b = -1 is no pair)
 constexpr int SYNC_EVERY = 64;       // merges enqueued between host synchronisations
+constexpr int PAIR_CAP_LOG2 = 16;    // the pair table's floor: 2^16 slots
 
 #define TR_TRY(expr)                                                                                        \
     do {                                                                                                    \
@@ -358,7 +370,7 @@ __global__ void __launch_bounds__(TB) k_select(PairTab T, uint64_t cap, Best* pa
                                                long long new_key_room, int32_t* out_pairs, int64_t* out_counts) {
     __shared__ Best sh[TB / 64];
     __shared__ bool last;
-    if (L->stop || L->pause) return;
+    if (L->stop || L->pause || *T.full) return;  // (full: the run fails at the next synchronisation; skip the rest)
     Best b{0, ~0ull};
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {
         const unsigned long long k = T.key[i];
@@ -518,6 +530,9 @@ struct hutk_trainer {
     // statistics
     int64_t n_docs = 0, n_bytes = 0, n_occ = 0, n_unique = 0, n_sym = 0, n_pairs0 = 0, peak = 0, cur = 0;
     int64_t loop_us = 0;
+    // path counters (hutk_trainer_debug_counters), all from values the host reads anyway
+    int64_t c_pauses = 0, c_grows = 0, c_shrinks = 0, c_rebuilds = 0, c_syncs = 0, c_pcap_max = 0, c_sel_blocks_max = 0,
+            c_word_rehash = 0, c_deferred = 0, c_insert_rounds_max = 0, c_long_to_short = 0;
     // word table + arena (persist across add calls)
     WordTab wt{};
     uint64_t wt_cap = 0;
@@ -670,8 +685,10 @@ int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offse
     if (need > t->wt_cap) {
         WordTab nt{};
         TR_TRY(wordtab_alloc(t, &nt, need));
-        if (t->wt_cap)
+        if (t->wt_cap) {
             hipLaunchKernelGGL(k_word_rehash, dim3(nblocks(t->wt_cap)), dim3(TB), 0, st, t->wt, t->wt_cap, nt, t->ctl);
+            t->c_word_rehash++;
+        }
         TR_TRY(hipStreamSynchronize(st));
         wordtab_free(t, &t->wt);
         t->wt = nt;
@@ -699,6 +716,8 @@ int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offse
         if (h.full) return hutk::api_set_error(HUTK_E_CAPACITY, "hutk_trainer_add: word table full");
         if (h.pend_n[which] == 0) break;
         if (round > 64) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_trainer_add: word insertion does not settle");
+        t->c_deferred += h.pend_n[which];
+        t->c_insert_rounds_max = std::max<int64_t>(t->c_insert_rounds_max, round + 1);
         TR_TRY(hipMemsetAsync(&t->ctl->pend_n[which ^ 1], 0, 4, st));
         hipLaunchKernelGGL(k_insert_pending, dim3(nblocks(h.pend_n[which])), dim3(TB), 0, st, t->d_bytes, t->wt,
                            t->arena, t->ctl, t->pend[which], which, t->pend[which ^ 1]);
@@ -720,6 +739,12 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     if (t->ran) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_run: run may be called once per trainer");
     t->ran = true;
     *n_done = 0;
+    // test-only knobs (header comment); unset, they are SYNC_EVERY and PAIR_CAP_LOG2
+    const char* e_sync = getenv("HUTK_TRAIN_SYNC_EVERY");
+    const int64_t sync_every = e_sync && atoll(e_sync) >= 1 ? std::min<int64_t>(atoll(e_sync), INT32_MAX) : SYNC_EVERY;
+    const char* e_cap = getenv("HUTK_TRAIN_PAIR_CAP_LOG2");
+    const int cap_log2 = e_cap ? std::min(std::max(atoi(e_cap), 2), 30) : PAIR_CAP_LOG2;
+    const uint64_t pair_floor = 1ull << cap_log2;
     // every merge removes at least one symbol, so no more than n_sym merges can happen
     n_merges = (int32_t)std::min<int64_t>(n_merges, t->arena_used);
     TR_TRY(hipSetDevice(t->device));
@@ -737,7 +762,7 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
 
     int32_t *sym = nullptr, *w_len = nullptr, *act[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     int64_t *w_off = nullptr, *w_cnt = nullptr;
-    unsigned int* cnt2 = nullptr;  // [0..1] active short / long, [2] words out
+    unsigned int* cnt2 = nullptr;  // [0..1] active short / long, [2] words out, [3] short before the long list
     const int64_t nw1 = std::max<int64_t>(n_words, 1);
     TR_TRY(t->alloc((void**)&sym, std::max<int64_t>(n_sym, 1) * 4));
     TR_TRY(t->alloc((void**)&w_len, nw1 * 4));
@@ -792,8 +817,9 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         return hipMemsetAsync(d_used, 0, 8, st);
     };
     // initial keys: at most min(symbols, 65536) distinct byte pairs
-    pcap = pow2_at_least((uint64_t)std::max<int64_t>(4 * std::min<int64_t>(n_sym, 65536), 1 << 16));
+    pcap = pow2_at_least(std::max<uint64_t>(4 * std::min<int64_t>(n_sym, 65536), pair_floor));
     TR_TRY(pair_alloc(&pt, pcap));
+    t->c_pcap_max = (int64_t)pcap;
     if (n_act[0])
         hipLaunchKernelGGL(k_init_short, dim3(nblocks(n_act[0])), dim3(TB), 0, st, sym, act[0][0], n_act[0], w_off, w_len,
                            w_cnt, pt);
@@ -818,7 +844,7 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     TR_TRY(hipMemsetAsync(lc, 0, sizeof(LoopCtl), st));
 
     auto rebuild = [&](uint64_t live_hint, uint64_t room_hint) -> int {
-        uint64_t cap = pow2_at_least(std::max<uint64_t>(4 * (live_hint + room_hint), 1 << 16));
+        uint64_t cap = pow2_at_least(std::max<uint64_t>(4 * (live_hint + room_hint), pair_floor));
         PairTab nt{};
         PairTab old = pt;
         const uint64_t old_cap = pcap;
@@ -842,6 +868,10 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         t->release(d_used);
         d_used = used_new;
         pt = nt;
+        t->c_rebuilds++;
+        t->c_grows += cap > old_cap;
+        t->c_shrinks += cap < old_cap;
+        t->c_pcap_max = std::max<int64_t>(t->c_pcap_max, (int64_t)cap);
         pcap = cap;
         return HUTK_OK;
     };
@@ -856,7 +886,8 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     while (k < n_merges) {
         const unsigned sel_blocks = (unsigned)std::min<uint64_t>(SEL_BLOCKS_MAX, nblocks(pcap, TB * 4));
         const long long room = (long long)(pcap / 2);
-        const int end = std::min(n_merges, k + SYNC_EVERY);
+        const int end = (int)std::min<int64_t>(n_merges, k + sync_every);
+        t->c_sel_blocks_max = std::max<int64_t>(t->c_sel_blocks_max, sel_blocks);
         for (int j = k; j < end; j++) {
             hipLaunchKernelGGL(k_select, dim3(sel_blocks), dim3(TB), 0, st, pt, pcap, partial, lc, j, room, d_pairs,
                                d_counts);
@@ -873,6 +904,8 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         TR_TRY(hipMemcpyAsync(&full, d_full, 4, hipMemcpyDeviceToHost, st));
         TR_TRY(hipMemcpyAsync(&used, d_used, 8, hipMemcpyDeviceToHost, st));
         TR_TRY(hipStreamSynchronize(st));
+        t->c_syncs++;
+        t->c_pauses += hl.pause != 0;
         if (full) {
             rc = hutk::api_set_error(HUTK_E_CAPACITY, "hutk_trainer_run: pair table full");
             break;
@@ -884,15 +917,21 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         const int nxt = cur_list ^ 1;
         {
             TR_TRY(hipMemsetAsync(cnt2, 0, 8, st));
-                if (na0)
+            if (na0)
                 hipLaunchKernelGGL(k_partition, dim3(nblocks(na0)), dim3(TB), 0, st, act[cur_list][0], na0, w_len,
                                    act[nxt][0], act[nxt][1], cnt2);
+            // (the short count before the long list goes in: cnt2[3], so that the host learns how many long words
+            // became short from the same copy; short words never become long)
+            if (na1) TR_TRY(hipMemcpyAsync(cnt2 + 3, cnt2, 4, hipMemcpyDeviceToDevice, st));
             if (na1)
                 hipLaunchKernelGGL(k_partition, dim3(nblocks(na1)), dim3(TB), 0, st, act[cur_list][1], na1, w_len,
                                    act[nxt][0], act[nxt][1], cnt2);
             TR_TRY(hipGetLastError());
-            TR_TRY(hipMemcpyAsync(n_act, cnt2, 8, hipMemcpyDeviceToHost, st));
+            unsigned n4[4] = {0, 0, 0, 0};
+            TR_TRY(hipMemcpyAsync(n4, cnt2, na1 ? 16 : 8, hipMemcpyDeviceToHost, st));
             TR_TRY(hipStreamSynchronize(st));
+            n_act[0] = n4[0], n_act[1] = n4[1];
+            if (na1) t->c_long_to_short += n4[0] - n4[3];
             cur_list = nxt;
         }
         // the table: grow when a step paused, rebuild (dropping dead keys) when it is half used
@@ -900,7 +939,8 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         const uint64_t step_room = (uint64_t)(hl.n_done ? std::min<long long>(2 * hl.best_cnt, sym_room) : sym_room);
         // (k_select scans the whole table every merge: room for one worst-case step is enough, a step that does not
         // fit pauses and comes back here)
-        if (hl.pause || used + 2 * step_room > pcap / 2 || pcap > 16 * std::max<uint64_t>(used + step_room, 1 << 14)) {
+        if (hl.pause || used + 2 * step_room > pcap / 2 ||
+            pcap > 16 * std::max<uint64_t>(used + step_room, pair_floor >> 2)) {
             if ((rc = rebuild(used, step_room))) break;
             TR_TRY(hipMemsetAsync(&lc->pause, 0, 4, st));
         }
@@ -932,6 +972,16 @@ int hutk_trainer_stats(const hutk_trainer* t, int64_t* out8) {
     const int64_t v[8] = {t->n_docs, t->n_bytes, t->n_occ, t->n_unique, t->ran ? t->n_sym : t->arena_used,
                           t->n_pairs0, t->peak, t->loop_us};
     memcpy(out8, v, sizeof v);
+    return HUTK_OK;
+}
+
+int hutk_trainer_debug_counters(const hutk_trainer* t, int64_t* out, int n) {
+    if (!t || n < 0 || (n > 0 && !out)) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_debug_counters: bad arguments");
+    const int64_t v[] = {t->c_pauses,        t->c_grows,         t->c_shrinks,      t->c_rebuilds,
+                         t->c_syncs,         t->c_pcap_max,      t->c_sel_blocks_max, t->c_word_rehash,
+                         t->c_deferred,      t->c_insert_rounds_max, t->c_long_to_short};
+    const int nv = (int)(sizeof v / sizeof v[0]);
+    if (n > 0) memcpy(out, v, sizeof(int64_t) * std::min(n, nv));
     return HUTK_OK;
 }
 

@@ -260,6 +260,11 @@ int hutk_trainer_create(hutk_trainer** out, int device);
 int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs);
 int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int64_t* counts_out, int32_t* n_done);
 int hutk_trainer_stats(const hutk_trainer* t, int64_t* out8);
+/* Which internal paths the trainer took (for tests; host-side values, no added synchronisation).  Writes the first
+ * min(n, 11) of: pauses, pair-table rebuilds that grew it, that shrank it, all rebuilds, host synchronisations of the
+ * merge loop, largest pair-table capacity, largest k_select grid, word-table rehashes, deferred word insertions,
+ * largest number of deferred-insertion rounds in one add, words that moved from the long to the short list. */
+int hutk_trainer_debug_counters(const hutk_trainer* t, int64_t* out, int n);
 void hutk_trainer_destroy(hutk_trainer* t);
 
 #ifdef __cplusplus

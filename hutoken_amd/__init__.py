@@ -18,7 +18,8 @@ zero-marshalling entry points for packed UTF-8 + offsets.
 
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
-the batch-fed trainer and a writer of GPT-2-shaped vocab, special and merges files.
+the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
+SentencePiece/Llama-shaped (mode="chars") vocab, special and merges files.
 """
 import os
 import sys
@@ -312,12 +313,23 @@ def _default_device(device):
     return int(os.environ.get("HUTOKEN_DEVICE", "-1")) if device is None else int(device)
 
 
-class Trainer:
-    """Byte-level BPE training on the GPU (hutk_trainer_*, include/hutoken_amd.h).  Documents arrive over any number
-    of add() / add_packed() calls; run() once returns the merges.  Semantics: tools/train_vocab.cpp, "bytes" mode."""
+_TRAIN_MODES = {"bytes": _capi.TRAIN_BYTES, "chars": _capi.TRAIN_CHARS}
 
-    def __init__(self, device=None):
-        self._t = _capi.Trainer(_default_device(device))
+
+def _train_mode(mode):
+    if not isinstance(mode, str) or mode not in _TRAIN_MODES:
+        raise ValueError("mode must be 'bytes' or 'chars', not %r" % (mode,))
+    return _TRAIN_MODES[mode]
+
+
+class Trainer:
+    """BPE training on the GPU (hutk_trainer_*, include/hutoken_amd.h).  Documents arrive over any number of add() /
+    add_packed() calls; run() once returns the merges.  Semantics: tools/train_vocab.cpp in the same mode:
+    "bytes" (the 256 byte values are the initial symbols) or "chars" (words holding a control byte are dropped,
+    ' ' becomes U+2581 and the initial symbols are the UTF-8 characters seen, sorted as byte strings)."""
+
+    def __init__(self, device=None, mode="bytes"):
+        self._t = _capi.Trainer(_default_device(device), _train_mode(mode))
 
     def add(self, texts):
         """A list of str, one document each (cut at the first NUL, like batch_encode)."""
@@ -334,8 +346,14 @@ class Trainer:
             data = np.frombuffer(bytes(data), dtype=np.uint8)
         self._t.add_packed(data, offsets)
 
+    def alphabet(self):
+        """The initial symbols in id order, a list of bytes: the 256 single bytes in bytes mode, the characters of
+        the kept words in chars mode.  Ends the adding phase: a later add() raises."""
+        return self._t.alphabet()
+
     def run(self, n_merges):
-        """-> (pairs int32[m, 2], counts int64[m]); merge k creates symbol 256 + k."""
+        """-> (pairs int32[m, 2], counts int64[m]); merge k creates symbol len(alphabet()) + k (256 + k in bytes
+        mode)."""
         if not isinstance(n_merges, int) or n_merges < 0:
             raise ValueError("n_merges must be a non-negative int")
         return self._t.run(n_merges)
@@ -367,11 +385,18 @@ def _text_batches(texts):
         yield batch
 
 
-def train(texts, vocab_size, out_dir, name, end_of_text="<|endoftext|>", device=None):
-    """Train on `texts` (a list of str, or an iterable of such lists fed batch by batch) and write the GPT-2-shaped
-    files of tools/make_vocab.py: <name>_vocab.txt, <name>_special.txt, <name>_merges.txt under out_dir.
-    n_merges = vocab_size - 256 - (1 if end_of_text else 0).  -> dict(vocab_file, special_file, merges_file,
-    n_merges, stats).  The files load with initialize(vocab, special, is_byte_encoder=True)."""
+def train(texts, vocab_size, out_dir, name, end_of_text="<|endoftext|>", device=None, mode="bytes"):
+    """Train on `texts` (a list of str, or an iterable of such lists fed batch by batch) and write the files of
+    tools/make_vocab.py under out_dir: <name>_vocab.txt, <name>_special.txt, <name>_merges.txt.
+
+    mode="bytes": GPT-2 shape (VG).  n_merges = vocab_size - 256 - (1 if end_of_text else 0).  The files load with
+    initialize(vocab, special, is_byte_encoder=True).
+    mode="chars": SentencePiece/Llama shape (VL): <unk>, <s>, </s>, <0x00>..<0xFF>, the alphabet (A characters), then
+    the merges; n_merges = vocab_size - 259 - A, and a vocab_size below 259 + A raises RuntimeError before the merge
+    loop.  end_of_text is not used.  The files load with initialize(vocab, special, prefix="▁",
+    is_byte_encoder=False).
+
+    -> dict(vocab_file, special_file, merges_file, n_merges, stats), and alphabet_size in chars mode."""
     from . import vocab_files as vf
     if not isinstance(vocab_size, int) or isinstance(vocab_size, bool):
         raise TypeError("vocab_size must be an int")
@@ -379,17 +404,34 @@ def train(texts, vocab_size, out_dir, name, end_of_text="<|endoftext|>", device=
         raise TypeError("out_dir and name must be str")
     if end_of_text is not None and not isinstance(end_of_text, str):
         raise TypeError("end_of_text must be a str or None")
-    n_merges = vocab_size - 256 - (1 if end_of_text else 0)
-    if n_merges < 0:
-        raise RuntimeError("vocab_size must be at least 256 to encode all bytes.")
+    chars = _train_mode(mode) == _capi.TRAIN_CHARS
+    if chars:
+        if vocab_size < vf.LLAMA_FIXED_TOKENS:
+            raise RuntimeError("vocab_size must be at least %d (3 special and 256 byte-fallback tokens) in chars mode."
+                               % vf.LLAMA_FIXED_TOKENS)
+    else:
+        n_merges = vocab_size - 256 - (1 if end_of_text else 0)
+        if n_merges < 0:
+            raise RuntimeError("vocab_size must be at least 256 to encode all bytes.")
     if not os.path.isdir(out_dir):
         raise FileNotFoundError(f"out_dir '{out_dir}' does not exist.")
-    with Trainer(device) as t:
+    with Trainer(device, mode) as t:
         for batch in _text_batches(texts):
             t.add(batch)
+        if chars:
+            alphabet = t.alphabet()
+            n_merges = vocab_size - vf.LLAMA_FIXED_TOKENS - len(alphabet)
+            if n_merges < 0:
+                raise RuntimeError("vocab_size %d is below %d + A = %d: the corpus has A = %d distinct characters."
+                                   % (vocab_size, vf.LLAMA_FIXED_TOKENS, vf.LLAMA_FIXED_TOKENS + len(alphabet),
+                                      len(alphabet)))
         pairs, _counts = t.run(n_merges)
         stats = t.stats()
-    out = vf.write_gpt2_files(out_dir, name, pairs.tolist(), end_of_text)
+    if chars:
+        out = vf.write_llama_files(out_dir, name, alphabet, pairs.tolist())
+        out["alphabet_size"] = len(alphabet)
+    else:
+        out = vf.write_gpt2_files(out_dir, name, pairs.tolist(), end_of_text)
     out["n_merges"] = int(len(pairs))
     out["stats"] = stats
     return out

@@ -24,8 +24,9 @@ EXPORTS = [
     "hutk_set_timing", "hutk_debug_pairs_second", "hutk_debug_long_words", "hutk_debug_profile", "hutk_debug_profile_read", "hutk_debug_profile_raw", "hutk_debug_tile_bytes",
     "hutk_debug_seam", "hutk_debug_seam2_cut",
     "hutk_trainer_create", "hutk_trainer_add", "hutk_trainer_run", "hutk_trainer_stats", "hutk_trainer_destroy",
-    "hutk_trainer_debug_counters",
+    "hutk_trainer_debug_counters", "hutk_trainer_create_mode", "hutk_trainer_alphabet",
 ]
+TRAIN_BYTES, TRAIN_CHARS = 0, 1
 
 _lib = None
 
@@ -151,6 +152,11 @@ def load(build_if_missing=True):
     if hasattr(L, "hutk_trainer_debug_counters"):
         L.hutk_trainer_debug_counters.restype = i32
         L.hutk_trainer_debug_counters.argtypes = [vp, vp, i32]
+    if hasattr(L, "hutk_trainer_create_mode"):
+        L.hutk_trainer_create_mode.restype = i32
+        L.hutk_trainer_create_mode.argtypes = [C.POINTER(vp), i32, i32]
+        L.hutk_trainer_alphabet.restype = i32
+        L.hutk_trainer_alphabet.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     _lib = L
     return L
 
@@ -406,16 +412,29 @@ TRAINER_STATS = ["docs", "bytes", "word_occurrences", "unique_words", "symbols",
                  "peak_device_bytes", "merge_loop_us"]
 # hutk_trainer_debug_counters, in its order
 TRAINER_COUNTERS = ["pauses", "pair_grows", "pair_shrinks", "pair_rebuilds", "host_syncs", "pair_cap_max",
-                    "select_blocks_max", "word_rehashes", "deferred_words", "insert_rounds_max", "long_to_short"]
+                    "select_blocks_max", "word_rehashes", "deferred_words", "insert_rounds_max", "long_to_short",
+                    "dropped_words", "charset_grows"]
 
 
 class Trainer:
-    """Owns one hutk_trainer (byte-level BPE training on the GPU, include/hutoken_amd.h)."""
+    """Owns one hutk_trainer (BPE training on the GPU, include/hutoken_amd.h); mode TRAIN_BYTES or TRAIN_CHARS."""
 
-    def __init__(self, device=-1):
+    def __init__(self, device=-1, mode=TRAIN_BYTES):
         h = C.c_void_p()
-        raise_for(load().hutk_trainer_create(C.byref(h), int(device)))
+        raise_for(load().hutk_trainer_create_mode(C.byref(h), int(device), int(mode)))
         self._h = h
+
+    def alphabet(self):
+        """The initial symbols in id order (list of bytes); ends the adding phase."""
+        import numpy as np
+        n_sym, n_bytes = C.c_int64(0), C.c_int64(0)
+        raise_for(load().hutk_trainer_alphabet(self._h, None, 0, None, 0, C.byref(n_sym), C.byref(n_bytes)))
+        data = np.zeros(max(n_bytes.value, 1), dtype=np.uint8)
+        offs = np.zeros(n_sym.value + 1, dtype=np.int64)
+        raise_for(load().hutk_trainer_alphabet(self._h, data.ctypes.data, len(data), offs.ctypes.data, len(offs),
+                                               C.byref(n_sym), C.byref(n_bytes)))
+        raw = data.tobytes()
+        return [raw[offs[i]:offs[i + 1]] for i in range(n_sym.value)]
 
     def add_packed(self, data, offsets):
         """Packed bytes (uint8) + int64 offsets[n+1]: documents data[offsets[i]:offsets[i+1]]."""

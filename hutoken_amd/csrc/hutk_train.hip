@@ -1,9 +1,12 @@
-// hutk_train.hip -- byte-level BPE training on the GPU (hutk_trainer_*, include/hutoken_amd.h).
+// hutk_train.hip -- BPE training on the GPU (hutk_trainer_*, include/hutoken_amd.h).
 //
 // Replaces the reference's trainers (src/lib.c:76-126, src/bpe.c, src/bbpe.c) with the semantics of
-// tools/train_vocab.cpp in "bytes" mode, bit for bit:
+// tools/train_vocab.cpp in "bytes" or "chars" mode, bit for bit:
 //   words    the reference's splitter (hutk_classify.h, exact form), never across documents, no length cap
-//   symbols  byte values 0..255; merge k creates 256 + k
+//   symbols  bytes: byte values 0..255, A = 256.  chars: unique words holding a byte < 0x20 or 0x7F are dropped, ' '
+//            becomes E2 96 81, each word is cut left to right into characters (length from the lead byte: < 0x80 1,
+//            110xxxxx 2, 1110xxxx 3, any other 4; cut short at the word's end), and the distinct characters, sorted
+//            as byte strings, are 0..A-1.  Merge k creates A + k
 //   count    pair (a, b): sum over unique words of count x adjacent (a, b) positions (overlaps count)
 //   select   highest count, ties to the smaller (uint64)a << 32 | b, stop when no count >= 1
 //   apply    left to right, non-overlapping (aaaa -> n n, aaa -> n a)
@@ -14,7 +17,12 @@
 //         equality = full byte compare against the arena copy).  A slot is claimed by CAS on its key, then its
 //         bytes are copied into the arena and it is published with a release store; a word that meets a claimed
 //         but unpublished slot with its own hash is deferred to the next round (no spinning).
-//   run   the arena is the CSR of the unique words' symbols; k_init_* count the pairs into an open-addressing
+//   symbolise (hutk_trainer_alphabet, or the start of run; once)  k_words_from_table lists the unique words; bytes
+//         mode copies the arena to the symbol CSR (k_bytes_to_sym).  Chars mode: k_chars_xform applies the skip and
+//         space rules, k_chars_walk<false> cuts characters and inserts them into a device hash set, the host sorts
+//         the compacted keys, k_cset_number numbers them, and k_chars_walk<true> writes the ids into the CSR; all
+//         three a wavefront per word, 64 bytes per trip.
+//   run   the CSR holds the unique words' symbols; k_init_* count the pairs into an open-addressing
 //         table (u64 key, i64 count, integer atomics only); then per merge two kernels, no host round trip:
 //         k_select (grid reduction, the last block decides) and k_apply_short (a lane per word) /
 //         k_apply_long (a wavefront per word finds the first occurrence, one lane rewrites from there).
@@ -23,7 +31,7 @@
 //         that might not find room for its new keys pauses the loop instead (the host grows the table and
 //         resumes), so the table can never fill.
 //
-// Test-only schedule knobs, read by every hutk_trainer_run (unset: the constants below, the same code path)
+// Test-only knobs, read by every symbolisation and run (unset: the constants below, the same code path)
 //   HUTK_TRAIN_SYNC_EVERY=n     merges enqueued between host synchronisations (n >= 1; default SYNC_EVERY = 64).
 //                               1 re-partitions the word lists and checks the table after every merge; a very large
 //                               value leaves the device-side pause as the only guard against a full pair table.
@@ -31,6 +39,9 @@
 //                               (4 * min(symbols, 65536) stays the other bound) and of every rebuild, and 2^(n-2) in
 //                               the shrink test.  A small floor makes pauses and shrinks frequent; 21 or more gives
 //                               k_select its full 1024 blocks with 8+ grid-stride trips per thread.
+//   HUTK_TRAIN_CHARSET_CAP_LOG2=n  chars mode: the character set's first size, 2^n slots (default: 2 * min(symbols,
+//                               2^20), at least 2^12).  A small size makes the set pass half load, grow eightfold and
+//                               repeat its pass.
 // hutk_trainer_debug_counters reports which of these paths a run took (host values only, no added synchronisation).
 #include <hip/hip_runtime.h>
 
@@ -297,6 +308,156 @@ __global__ void k_bytes_to_sym(const uint8_t* arena, int64_t n, int32_t* sym) {
         sym[i] = arena[i];
 }
 
+// ---- chars mode: UTF-8 characters as the initial symbols ----------------------------------------------------
+// A wavefront per unique word (grid-stride over words), 64 bytes per trip, so a long word is never walked by one
+// lane.  The transformed word (' ' -> E2 96 81) of the word at arena offset o lives at tbuf + 3 * o: it is never more
+// than three times as long, so no offsets need to be computed.  Every word has at most as many characters as bytes (a
+// space's expansion starts at most one character), so the sym CSR keeps the arena's offsets.
+struct CharSet {                // distinct character keys: big-endian bytes, zero padded (0 = empty slot)
+    unsigned int* key;
+    int32_t* id;                // the key's symbol id, after numbering
+    uint64_t mask;
+    unsigned long long* used;
+    unsigned int* full;         // more than half of the slots used: the host grows the set and repeats
+};
+
+__device__ inline int char_len(uint32_t lead) {  // from the lead byte; stray continuations and F0..FF take 4
+    return lead < 0x80 ? 1 : (lead & 0xE0) == 0xC0 ? 2 : (lead & 0xF0) == 0xE0 ? 3 : 4;
+}
+
+__device__ void cset_insert(CharSet C, uint32_t k) {
+    uint64_t s = mix64(k) & C.mask;
+    for (uint64_t probe = 0; probe <= C.mask; probe++, s = (s + 1) & C.mask) {
+        unsigned int cur = __hip_atomic_load(&C.key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0) {
+            cur = atomicCAS(&C.key[s], 0u, k);
+            if (cur == 0) {
+                if (2 * (atomicAdd(C.used, 1ull) + 1) > C.mask + 1) atomicOr(C.full, 1u);
+                return;
+            }
+        }
+        if (cur == k) return;
+    }
+    atomicOr(C.full, 1u);
+}
+
+__device__ int32_t cset_find(CharSet C, uint32_t k) {  // k is present (inserted by k_chars_walk<false>)
+    uint64_t s = mix64(k) & C.mask;
+    while (C.key[s] != k) s = (s + 1) & C.mask;
+    return C.id[s];
+}
+
+// rules 2 and 3: a word holding a byte < 0x20 or 0x7F is dropped (t_len = -1); ' ' becomes E2 96 81
+__global__ void __launch_bounds__(TB) k_chars_xform(const uint8_t* arena, const int64_t* w_off, const int32_t* w_len,
+                                                    int64_t n_words, uint8_t* tbuf, int64_t* t_len,
+                                                    unsigned long long* n_dropped) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1;
+    const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < n_words; w += n_waves) {
+        const int64_t off = w_off[w];
+        const int32_t len = w_len[w];
+        const uint8_t* src = arena + off;
+        uint8_t* dst = tbuf + 3 * off;
+        int64_t tpos = 0;  // (a word of 2^31 - 1 spaces is 3 * (2^31 - 1) bytes long)
+        bool bad = false;
+        for (int64_t base = 0; base < len; base += 64) {
+            const int64_t j = base + lane;
+            const bool in = j < len;
+            const uint32_t c = in ? src[j] : 0x61u;
+            const unsigned long long sp = __ballot(in && c == 0x20);
+            if (__ballot(in && (c < 0x20 || c == 0x7F))) {
+                bad = true;
+                break;
+            }
+            const int64_t p = tpos + lane + 2 * __popcll(sp & below);
+            if (in && c == 0x20) {
+                dst[p] = 0xE2;
+                dst[p + 1] = 0x96;
+                dst[p + 2] = 0x81;
+            } else if (in) {
+                dst[p] = (uint8_t)c;
+            }
+            tpos += std::min<int64_t>(64, len - base) + 2 * __popcll(sp);
+        }
+        if (lane == 0) {
+            t_len[w] = bad ? -1 : tpos;
+            if (bad) atomicAdd(n_dropped, 1ull);
+        }
+    }
+}
+
+// rules 4 and 5: cut the transformed word into characters, left to right.  NUMBER = false: insert every character
+// into the set and write the word's character count to w_len (0 for a dropped word); NUMBER = true: write the
+// characters' ids into the sym CSR.
+template <bool NUMBER>
+__global__ void __launch_bounds__(TB) k_chars_walk(const uint8_t* tbuf, const int64_t* w_off, const int64_t* t_len,
+                                                   int64_t n_words, CharSet C, int32_t* w_len, int32_t* sym) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1;
+    const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < n_words; w += n_waves) {
+        if (!NUMBER && __builtin_amdgcn_readfirstlane(__hip_atomic_load(C.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
+            return;  // the set is being outgrown: the host repeats this pass
+        const int64_t tl = t_len[w];
+        const int64_t off = w_off[w];
+        const uint8_t* s = tbuf + 3 * off;
+        int32_t carry = 0, n_ch = 0;  // carry: the first character start of the next 64 bytes, past their start
+        for (int64_t base = 0; base < tl; base += 64) {
+            const int64_t j = base + lane;
+            const uint32_t c = j < tl ? s[j] : 0u;
+            const int L = char_len(c);
+            const unsigned long long m2 = __ballot(L == 2), m3 = __ballot(L == 3), m4 = __ballot(L == 4);
+            const int lim = (int)std::min<int64_t>(64, tl - base);
+            unsigned long long starts;
+            int p;
+            if ((m2 | m3 | m4) == 0) {  // all single bytes
+                starts = (lim == 64 ? ~0ull : (1ull << lim) - 1) & (~0ull << carry);
+                p = lim;
+            } else {
+                starts = 0;
+                for (p = carry; p < lim;) {
+                    starts |= 1ull << p;
+                    p += 1 + (int)((m2 >> p) & 1) + 2 * (int)((m3 >> p) & 1) + 3 * (int)((m4 >> p) & 1);
+                }
+            }
+            carry = p - 64;
+            if ((starts >> lane) & 1) {
+                uint32_t k = c << 24;
+                for (int q = 1; q < L && j + q < tl; q++) k |= (uint32_t)s[j + q] << (24 - 8 * q);
+                if (NUMBER)
+                    sym[off + n_ch + __popcll(starts & below)] = cset_find(C, k);
+                else
+                    cset_insert(C, k);
+            }
+            n_ch += __popcll(starts);
+        }
+        if (!NUMBER && lane == 0) w_len[w] = tl > 0 ? n_ch : 0;
+    }
+}
+
+__global__ void k_cset_compact(CharSet C, uint64_t cap, uint32_t* out, unsigned int* n_out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap || C.key[i] == 0) return;
+    out[atomicAdd(n_out, 1u)] = C.key[i];
+}
+
+// sorted[i] gets id i
+__global__ void k_cset_number(CharSet C, const uint32_t* sorted, unsigned n) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t s = mix64(sorted[i]) & C.mask;
+    while (C.key[s] != sorted[i]) s = (s + 1) & C.mask;
+    C.id[s] = (int32_t)i;
+}
+
+__global__ void k_sum_len(const int32_t* w_len, int64_t n, unsigned long long* tot) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long v = i < n ? (unsigned long long)w_len[i] : 0ull;
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(tot, v);
+}
+
 // active lists: words with >= 2 symbols, split by length.  One atomic per wavefront and list (a per-lane atomic on
 // the two counters serialises 800k lanes: 9 ms a call on VG)
 __global__ void k_partition(const int32_t* ids_in, unsigned n_in, const int32_t* w_len, int32_t* short_out,
@@ -366,7 +527,7 @@ __device__ Best block_best(Best b, Best* sh) {
 }
 
 // merge `step`: the best pair over the table (count desc, key asc, count >= 1), decided by the last block
-__global__ void __launch_bounds__(TB) k_select(PairTab T, uint64_t cap, Best* partial, LoopCtl* L, int step,
+__global__ void __launch_bounds__(TB) k_select(PairTab T, uint64_t cap, Best* partial, LoopCtl* L, int base, int step,
                                                long long new_key_room, int32_t* out_pairs, int64_t* out_counts) {
     __shared__ Best sh[TB / 64];
     __shared__ bool last;
@@ -403,7 +564,7 @@ __global__ void __launch_bounds__(TB) k_select(PairTab T, uint64_t cap, Best* pa
         } else {
             // every new key holds the new symbol next to an occurrence: at most 2 per occurrence, and at most
             // 2 * (symbols so far) + 1 distinct ones
-            const long long sym_bound = 2LL * (256 + step) + 1;
+            const long long sym_bound = 2LL * (base + step) + 1;
             const long long bound = 2 * r.c < sym_bound ? 2 * r.c : sym_bound;
             if ((long long)*T.used + bound > new_key_room) {
                 L->pause = 1;
@@ -455,7 +616,7 @@ __device__ int32_t rewrite_word(int32_t* s, int32_t len, int32_t i0, int32_t a, 
 
 __global__ void __launch_bounds__(TB) k_apply_short(int32_t* sym, const int32_t* act, unsigned n_act,
                                                     const int64_t* w_off, int32_t* w_len, const int64_t* w_cnt,
-                                                    PairTab T, const LoopCtl* L, int step) {
+                                                    PairTab T, const LoopCtl* L, int base, int step) {
     if (L->stop || L->pause || L->n_done != step + 1) return;
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_act) return;
@@ -475,12 +636,12 @@ __global__ void __launch_bounds__(TB) k_apply_short(int32_t* sym, const int32_t*
         x = y;
     }
     if (i0 < 0) return;
-    w_len[w] = rewrite_word(s, l, i0, a, b, 256 + step, w_cnt[w], T);
+    w_len[w] = rewrite_word(s, l, i0, a, b, base + step, w_cnt[w], T);
 }
 
 __global__ void __launch_bounds__(TB) k_apply_long(int32_t* sym, const int32_t* act, unsigned n_act,
                                                    const int64_t* w_off, int32_t* w_len, const int64_t* w_cnt,
-                                                   PairTab T, const LoopCtl* L, int step) {
+                                                   PairTab T, const LoopCtl* L, int base, int step) {
     if (L->stop || L->pause || L->n_done != step + 1) return;
     const unsigned wv = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
@@ -501,7 +662,7 @@ __global__ void __launch_bounds__(TB) k_apply_long(int32_t* sym, const int32_t* 
         }
     }
     if (i0 < 0 || lane != 0) return;
-    w_len[w] = rewrite_word(s, l, i0, a, b, 256 + step, w_cnt[w], T);
+    w_len[w] = rewrite_word(s, l, i0, a, b, base + step, w_cnt[w], T);
 }
 
 // live keys of `src` into the empty table `dst`
@@ -525,14 +686,25 @@ inline uint64_t pow2_at_least(uint64_t x) {
 
 struct hutk_trainer {
     int device = 0;
+    int mode = HUTK_TRAIN_BYTES;
     hipStream_t st = nullptr;
     bool ran = false;
+    bool symbolised = false;  // the adding phase is over: sym / w_* below hold the words' initial symbols
+    int sym_rc = HUTK_OK;
     // statistics
     int64_t n_docs = 0, n_bytes = 0, n_occ = 0, n_unique = 0, n_sym = 0, n_pairs0 = 0, peak = 0, cur = 0;
     int64_t loop_us = 0;
     // path counters (hutk_trainer_debug_counters), all from values the host reads anyway
     int64_t c_pauses = 0, c_grows = 0, c_shrinks = 0, c_rebuilds = 0, c_syncs = 0, c_pcap_max = 0, c_sel_blocks_max = 0,
-            c_word_rehash = 0, c_deferred = 0, c_insert_rounds_max = 0, c_long_to_short = 0;
+            c_word_rehash = 0, c_deferred = 0, c_insert_rounds_max = 0, c_long_to_short = 0, c_dropped = 0,
+            c_cset_grows = 0;
+    // after symbolisation: the alphabet (symbol id order; chars mode: big-endian keys, bytes mode: empty) and the
+    // words' symbols (CSR at the arena offsets; w_len in symbols)
+    std::vector<uint32_t> alpha;
+    int32_t n_alpha = 0;
+    int32_t* sym = nullptr;
+    int32_t* w_len = nullptr;
+    int64_t *w_off = nullptr, *w_cnt = nullptr;
     // word table + arena (persist across add calls)
     WordTab wt{};
     uint64_t wt_cap = 0;
@@ -604,13 +776,148 @@ void wordtab_free(hutk_trainer* t, WordTab* w) {
     *w = WordTab{};
 }
 
+// chars mode, between k_words_from_table and the first k_partition: rules 2-5 of the header, then sym / w_len in
+// characters.  The distinct characters go into a device hash set (grown and refilled if it passes half load), are
+// sorted on the host (a few thousand keys, once) and numbered back into the set.
+int symbolise_chars(hutk_trainer* t, int64_t n_words) {
+    hipStream_t st = t->st;
+    const int64_t n_sym = t->arena_used;
+    const unsigned grid = (unsigned)std::min<uint64_t>(nblocks((uint64_t)n_words * 64), 8192);
+    uint8_t* tbuf = nullptr;
+    int64_t* t_len = nullptr;
+    unsigned long long* d_n = nullptr;  // [0] dropped words, [1] set slots used
+    unsigned int* d_u = nullptr;        // [0] set full, [1] compacted keys
+    TR_TRY(t->alloc((void**)&tbuf, std::max<int64_t>(3 * n_sym, 1)));
+    TR_TRY(t->alloc((void**)&t_len, std::max<int64_t>(n_words, 1) * 8));
+    TR_TRY(t->alloc((void**)&d_n, 16));
+    TR_TRY(t->alloc((void**)&d_u, 8));
+    TR_TRY(hipMemsetAsync(d_n, 0, 16, st));
+    if (n_words)
+        hipLaunchKernelGGL(k_chars_xform, dim3(grid), dim3(TB), 0, st, t->arena, t->w_off, t->w_len, n_words, tbuf,
+                           t_len, d_n);
+    TR_TRY(hipGetLastError());
+    CharSet cs{};
+    // (HUTK_TRAIN_CHARSET_CAP_LOG2, test only: the set's first size, so that a test can make it grow)
+    const char* e_cs = getenv("HUTK_TRAIN_CHARSET_CAP_LOG2");
+    uint64_t cap = e_cs ? 1ull << std::min(std::max(atoi(e_cs), 2), 30)
+                        : pow2_at_least(std::max<uint64_t>(2 * std::min<int64_t>(n_sym, 1 << 20), 1 << 12));
+    for (;;) {
+        TR_TRY(t->alloc((void**)&cs.key, cap * 4));
+        TR_TRY(t->alloc((void**)&cs.id, cap * 4));
+        TR_TRY(hipMemsetAsync(cs.key, 0, cap * 4, st));
+        TR_TRY(hipMemsetAsync(d_n + 1, 0, 8, st));
+        TR_TRY(hipMemsetAsync(d_u, 0, 8, st));
+        cs.mask = cap - 1;
+        cs.used = d_n + 1;
+        cs.full = d_u;
+        if (n_words)
+            hipLaunchKernelGGL(k_chars_walk<false>, dim3(grid), dim3(TB), 0, st, tbuf, t->w_off, t_len, n_words, cs,
+                               t->w_len, t->sym);
+        TR_TRY(hipGetLastError());
+        unsigned full = 0;
+        TR_TRY(hipMemcpyAsync(&full, d_u, 4, hipMemcpyDeviceToHost, st));
+        TR_TRY(hipStreamSynchronize(st));
+        if (!full) break;
+        t->release(cs.key);
+        t->release(cs.id);
+        cap *= 8;  // (a set of 2 * n_sym slots never passes half load: every character is a byte of the arena)
+        t->c_cset_grows++;
+    }
+    uint32_t* keys = nullptr;
+    TR_TRY(t->alloc((void**)&keys, cap / 2 * 4 + 4));
+    hipLaunchKernelGGL(k_cset_compact, dim3(nblocks(cap)), dim3(TB), 0, st, cs, cap, keys, d_u + 1);
+    TR_TRY(hipGetLastError());
+    unsigned n_keys = 0;
+    unsigned long long dropped = 0;
+    TR_TRY(hipMemcpyAsync(&n_keys, d_u + 1, 4, hipMemcpyDeviceToHost, st));
+    TR_TRY(hipMemcpyAsync(&dropped, d_n, 8, hipMemcpyDeviceToHost, st));
+    TR_TRY(hipStreamSynchronize(st));
+    t->alpha.resize(n_keys);
+    if (n_keys) TR_TRY(hipMemcpy(t->alpha.data(), keys, (size_t)n_keys * 4, hipMemcpyDeviceToHost));
+    std::sort(t->alpha.begin(), t->alpha.end());  // memcmp order of the characters: no byte is 0x00
+    if (n_keys) {
+        TR_TRY(hipMemcpyAsync(keys, t->alpha.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_cset_number, dim3(nblocks(n_keys)), dim3(TB), 0, st, cs, keys, n_keys);
+        hipLaunchKernelGGL(k_chars_walk<true>, dim3(grid), dim3(TB), 0, st, tbuf, t->w_off, t_len, n_words, cs,
+                           t->w_len, t->sym);
+        TR_TRY(hipGetLastError());
+    }
+    // characters in all words (the symbol count of the run)
+    unsigned long long* d_tot = d_n + 1;
+    TR_TRY(hipMemsetAsync(d_tot, 0, 8, st));
+    if (n_words) hipLaunchKernelGGL(k_sum_len, dim3(nblocks(n_words)), dim3(TB), 0, st, t->w_len, n_words, d_tot);
+    TR_TRY(hipGetLastError());
+    unsigned long long tot = 0;
+    TR_TRY(hipMemcpyAsync(&tot, d_tot, 8, hipMemcpyDeviceToHost, st));
+    TR_TRY(hipStreamSynchronize(st));
+    for (void* p : {(void*)tbuf, (void*)t_len, (void*)d_n, (void*)d_u, (void*)cs.key, (void*)cs.id, (void*)keys})
+        t->release(p);
+    t->n_alpha = (int32_t)n_keys;
+    t->c_dropped = (int64_t)dropped;
+    t->n_sym = (int64_t)tot;
+    return HUTK_OK;
+}
+
+int symbolise_once(hutk_trainer* t) {
+    TR_TRY(hipSetDevice(t->device));
+    hipStream_t st = t->st;
+    const int64_t n_words = t->n_unique, n_sym = t->arena_used;
+    t->n_sym = n_sym;
+    t->n_alpha = t->mode == HUTK_TRAIN_CHARS ? 0 : 256;
+    if (n_sym > INT32_MAX || n_words > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_trainer_run: more than 2^31 symbols or words");
+    // free the staging buffers of add()
+    t->release(t->d_bytes), t->d_bytes = nullptr, t->d_bytes_cap = 0;
+    t->release(t->d_dbm), t->d_dbm = nullptr;
+    t->release(t->d_wsb), t->d_wsb = nullptr, t->d_bm_cap = 0;
+    t->release(t->pend[0]), t->release(t->pend[1]), t->pend[0] = t->pend[1] = nullptr, t->pend_cap = 0;
+    t->release(t->d_offs), t->d_offs = nullptr, t->d_offs_cap = 0;
+
+    const int64_t nw1 = std::max<int64_t>(n_words, 1);
+    unsigned int* n_out = nullptr;
+    TR_TRY(t->alloc((void**)&t->sym, std::max<int64_t>(n_sym, 1) * 4));
+    TR_TRY(t->alloc((void**)&t->w_len, nw1 * 4));
+    TR_TRY(t->alloc((void**)&t->w_off, nw1 * 8));
+    TR_TRY(t->alloc((void**)&t->w_cnt, nw1 * 8));
+    TR_TRY(t->alloc((void**)&n_out, 4));
+    TR_TRY(hipMemsetAsync(n_out, 0, 4, st));
+    if (t->wt_cap)
+        hipLaunchKernelGGL(k_words_from_table, dim3(nblocks(t->wt_cap)), dim3(TB), 0, st, t->wt, t->wt_cap, t->w_off,
+                           t->w_len, t->w_cnt, n_out);
+    if (t->mode == HUTK_TRAIN_BYTES && n_sym)
+        hipLaunchKernelGGL(k_bytes_to_sym, dim3(1024), dim3(TB), 0, st, t->arena, n_sym, t->sym);
+    TR_TRY(hipGetLastError());
+    if (t->mode == HUTK_TRAIN_CHARS)
+        if (int rc = symbolise_chars(t, n_words)) return rc;
+    TR_TRY(hipStreamSynchronize(st));
+    t->release(n_out);
+    wordtab_free(t, &t->wt);
+    t->wt_cap = 0;
+    t->release(t->arena), t->arena = nullptr, t->arena_cap = 0;
+    return HUTK_OK;
+}
+
+// ends the adding phase: the unique words' initial symbols, the alphabet and its size (once; later calls give the same
+// answer)
+int symbolise(hutk_trainer* t) {
+    if (t->symbolised)
+        return t->sym_rc == HUTK_OK ? HUTK_OK : hutk::api_set_error(t->sym_rc, "hutk_trainer: symbolisation failed");
+    t->symbolised = true;
+    t->sym_rc = symbolise_once(t);
+    return t->sym_rc;
+}
+
 }  // namespace
 
 extern "C" {
 
-int hutk_trainer_create(hutk_trainer** out, int device) {
+int hutk_trainer_create(hutk_trainer** out, int device) { return hutk_trainer_create_mode(out, device, HUTK_TRAIN_BYTES); }
+
+int hutk_trainer_create_mode(hutk_trainer** out, int device, int mode) {
     if (!out) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_create: out is NULL");
     *out = nullptr;
+    if (mode != HUTK_TRAIN_BYTES && mode != HUTK_TRAIN_CHARS)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_create_mode: unknown mode");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return hutk::api_set_error(HUTK_E_DEVICE, "hutk_trainer_create: no HIP device");
@@ -619,6 +926,7 @@ int hutk_trainer_create(hutk_trainer** out, int device) {
     TR_TRY(hipSetDevice(device));
     hutk_trainer* t = new hutk_trainer();
     t->device = device;
+    t->mode = mode;
     hipError_t e = hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking);
     if (e == hipSuccess) e = t->alloc((void**)&t->ctl, sizeof(AddCtl));
     if (e == hipSuccess) e = hipMemsetAsync(t->ctl, 0, sizeof(AddCtl), t->st);
@@ -634,6 +942,7 @@ int hutk_trainer_create(hutk_trainer** out, int device) {
 int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs) {
     if (!t || n_docs < 0 || (n_docs > 0 && !offsets)) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: bad arguments");
     if (t->ran) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: the trainer has already run");
+    if (t->symbolised) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: the alphabet has been read");
     if (n_docs == 0) return HUTK_OK;
     for (int64_t i = 0; i < n_docs; i++)
         if (offsets[i + 1] < offsets[i] || offsets[i] < 0)
@@ -745,42 +1054,21 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     const char* e_cap = getenv("HUTK_TRAIN_PAIR_CAP_LOG2");
     const int cap_log2 = e_cap ? std::min(std::max(atoi(e_cap), 2), 30) : PAIR_CAP_LOG2;
     const uint64_t pair_floor = 1ull << cap_log2;
-    // every merge removes at least one symbol, so no more than n_sym merges can happen
-    n_merges = (int32_t)std::min<int64_t>(n_merges, t->arena_used);
+    if (int rc = symbolise(t)) return rc;
     TR_TRY(hipSetDevice(t->device));
+    // every merge removes at least one symbol, so no more than n_sym merges can happen; symbol ids stay below 2^31
+    n_merges = (int32_t)std::min<int64_t>({(int64_t)n_merges, t->n_sym, (int64_t)INT32_MAX - t->n_alpha});
     hipStream_t st = t->st;
-    const int64_t n_words = t->n_unique, n_sym = t->arena_used;
-    t->n_sym = n_sym;
-    if (n_sym > INT32_MAX || n_words > INT32_MAX)
-        return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_trainer_run: more than 2^31 symbols or words");
-    // free the staging buffers of add()
-    t->release(t->d_bytes), t->d_bytes = nullptr, t->d_bytes_cap = 0;
-    t->release(t->d_dbm), t->d_dbm = nullptr;
-    t->release(t->d_wsb), t->d_wsb = nullptr, t->d_bm_cap = 0;
-    t->release(t->pend[0]), t->release(t->pend[1]), t->pend[0] = t->pend[1] = nullptr, t->pend_cap = 0;
-    t->release(t->d_offs), t->d_offs = nullptr, t->d_offs_cap = 0;
-
-    int32_t *sym = nullptr, *w_len = nullptr, *act[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    int64_t *w_off = nullptr, *w_cnt = nullptr;
-    unsigned int* cnt2 = nullptr;  // [0..1] active short / long, [2] words out, [3] short before the long list
+    const int64_t n_words = t->n_unique, n_sym = t->n_sym;
+    const int base = t->n_alpha;
+    int32_t *sym = t->sym, *w_len = t->w_len, *act[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    int64_t *w_off = t->w_off, *w_cnt = t->w_cnt;
+    unsigned int* cnt2 = nullptr;  // [0..1] active short / long, [3] short before the long list
     const int64_t nw1 = std::max<int64_t>(n_words, 1);
-    TR_TRY(t->alloc((void**)&sym, std::max<int64_t>(n_sym, 1) * 4));
-    TR_TRY(t->alloc((void**)&w_len, nw1 * 4));
-    TR_TRY(t->alloc((void**)&w_off, nw1 * 8));
-    TR_TRY(t->alloc((void**)&w_cnt, nw1 * 8));
     for (int p = 0; p < 2; p++)
         for (int q = 0; q < 2; q++) TR_TRY(t->alloc((void**)&act[p][q], nw1 * 4));
     TR_TRY(t->alloc((void**)&cnt2, 16));
     TR_TRY(hipMemsetAsync(cnt2, 0, 16, st));
-    if (t->wt_cap)
-        hipLaunchKernelGGL(k_words_from_table, dim3(nblocks(t->wt_cap)), dim3(TB), 0, st, t->wt, t->wt_cap, w_off, w_len,
-                           w_cnt, cnt2 + 2);
-    if (n_sym) hipLaunchKernelGGL(k_bytes_to_sym, dim3(1024), dim3(TB), 0, st, t->arena, n_sym, sym);
-    TR_TRY(hipGetLastError());
-    TR_TRY(hipStreamSynchronize(st));
-    wordtab_free(t, &t->wt);
-    t->wt_cap = 0;
-    t->release(t->arena), t->arena = nullptr, t->arena_cap = 0;
 
     // active lists (cur = 0): words with >= 2 symbols
     unsigned n_act[2] = {0, 0};
@@ -816,8 +1104,8 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         p->full = d_full;
         return hipMemsetAsync(d_used, 0, 8, st);
     };
-    // initial keys: at most min(symbols, 65536) distinct byte pairs
-    pcap = pow2_at_least(std::max<uint64_t>(4 * std::min<int64_t>(n_sym, 65536), pair_floor));
+    // initial keys: at most min(symbols, A^2) distinct pairs (65536 in bytes mode)
+    pcap = pow2_at_least(std::max<uint64_t>(4 * std::min<int64_t>(n_sym, (int64_t)base * base), pair_floor));
     TR_TRY(pair_alloc(&pt, pcap));
     t->c_pcap_max = (int64_t)pcap;
     if (n_act[0])
@@ -889,14 +1177,14 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         const int end = (int)std::min<int64_t>(n_merges, k + sync_every);
         t->c_sel_blocks_max = std::max<int64_t>(t->c_sel_blocks_max, sel_blocks);
         for (int j = k; j < end; j++) {
-            hipLaunchKernelGGL(k_select, dim3(sel_blocks), dim3(TB), 0, st, pt, pcap, partial, lc, j, room, d_pairs,
-                               d_counts);
+            hipLaunchKernelGGL(k_select, dim3(sel_blocks), dim3(TB), 0, st, pt, pcap, partial, lc, base, j, room,
+                               d_pairs, d_counts);
             if (n_act[0])
                 hipLaunchKernelGGL(k_apply_short, dim3(nblocks(n_act[0])), dim3(TB), 0, st, sym, act[cur_list][0],
-                                   n_act[0], w_off, w_len, w_cnt, pt, lc, j);
+                                   n_act[0], w_off, w_len, w_cnt, pt, lc, base, j);
             if (n_act[1])
                 hipLaunchKernelGGL(k_apply_long, dim3(nblocks((uint64_t)n_act[1] * 64)), dim3(TB), 0, st, sym,
-                                   act[cur_list][1], n_act[1], w_off, w_len, w_cnt, pt, lc, j);
+                                   act[cur_list][1], n_act[1], w_off, w_len, w_cnt, pt, lc, base, j);
         }
         TR_TRY(hipGetLastError());
         TR_TRY(hipMemcpyAsync(&hl, lc, sizeof hl, hipMemcpyDeviceToHost, st));
@@ -935,7 +1223,7 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
             cur_list = nxt;
         }
         // the table: grow when a step paused, rebuild (dropping dead keys) when it is half used
-        const long long sym_room = 2LL * (256 + k) + 1;  // (the select kernel's bound; counts never grow)
+        const long long sym_room = 2LL * (base + k) + 1;  // (the select kernel's bound; counts never grow)
         const uint64_t step_room = (uint64_t)(hl.n_done ? std::min<long long>(2 * hl.best_cnt, sym_room) : sym_room);
         // (k_select scans the whole table every merge: room for one worst-case step is enough, a step that does not
         // fit pauses and comes back here)
@@ -964,12 +1252,14 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     // the workspace is returned now; stats stay readable
     for (auto& a : std::vector<std::pair<void*, int64_t>>(t->allocs))
         if (a.first != t->ctl) t->release(a.first);
+    t->sym = t->w_len = nullptr;
+    t->w_off = t->w_cnt = nullptr;
     return HUTK_OK;
 }
 
 int hutk_trainer_stats(const hutk_trainer* t, int64_t* out8) {
     if (!t || !out8) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_stats: bad arguments");
-    const int64_t v[8] = {t->n_docs, t->n_bytes, t->n_occ, t->n_unique, t->ran ? t->n_sym : t->arena_used,
+    const int64_t v[8] = {t->n_docs, t->n_bytes, t->n_occ, t->n_unique, t->symbolised ? t->n_sym : t->arena_used,
                           t->n_pairs0, t->peak, t->loop_us};
     memcpy(out8, v, sizeof v);
     return HUTK_OK;
@@ -979,9 +1269,35 @@ int hutk_trainer_debug_counters(const hutk_trainer* t, int64_t* out, int n) {
     if (!t || n < 0 || (n > 0 && !out)) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_debug_counters: bad arguments");
     const int64_t v[] = {t->c_pauses,        t->c_grows,         t->c_shrinks,      t->c_rebuilds,
                          t->c_syncs,         t->c_pcap_max,      t->c_sel_blocks_max, t->c_word_rehash,
-                         t->c_deferred,      t->c_insert_rounds_max, t->c_long_to_short};
+                         t->c_deferred,      t->c_insert_rounds_max, t->c_long_to_short, t->c_dropped,
+                         t->c_cset_grows};
     const int nv = (int)(sizeof v / sizeof v[0]);
     if (n > 0) memcpy(out, v, sizeof(int64_t) * std::min(n, nv));
+    return HUTK_OK;
+}
+
+int hutk_trainer_alphabet(hutk_trainer* t, uint8_t* bytes_out, int64_t bytes_cap, int64_t* offsets_out,
+                          int64_t offsets_cap, int64_t* n_symbols, int64_t* n_bytes) {
+    if (!t) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_alphabet: bad arguments");
+    if (int rc = symbolise(t)) return rc;
+    std::vector<uint8_t> b;
+    std::vector<int64_t> o{0};
+    for (int32_t i = 0; i < t->n_alpha; i++) {
+        if (t->mode == HUTK_TRAIN_BYTES) {
+            b.push_back((uint8_t)i);
+        } else {
+            for (int q = 3; q >= 0; q--)
+                if (const uint8_t c = (uint8_t)(t->alpha[i] >> (8 * q))) b.push_back(c);
+        }
+        o.push_back((int64_t)b.size());
+    }
+    if (n_symbols) *n_symbols = t->n_alpha;
+    if (n_bytes) *n_bytes = (int64_t)b.size();
+    if (!bytes_out || !offsets_out) return HUTK_OK;
+    if (bytes_cap < (int64_t)b.size() || offsets_cap < (int64_t)o.size())
+        return hutk::api_set_error(HUTK_E_CAPACITY, "hutk_trainer_alphabet: the buffers are too small");
+    if (!b.empty()) memcpy(bytes_out, b.data(), b.size());
+    memcpy(offsets_out, o.data(), o.size() * sizeof(int64_t));
     return HUTK_OK;
 }
 

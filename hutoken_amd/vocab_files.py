@@ -126,3 +126,48 @@ def raw_vocab_text(pairs, vocab_size):
     vocab_size lines at most (no 0x00 line: a document cannot hold one and the loader rejects it)."""
     toks = [bytes([b]) for b in range(1, 256)] + merge_tokens(pairs)
     return "".join(hex_line(tk, i) for i, tk in enumerate(toks[:vocab_size]))
+
+
+# ---- SentencePiece/Llama shape (VL, tools/make_vocab.py; the trainer's "chars" mode) ----------------------------
+LLAMA_FIXED_TOKENS = 259  # <unk>, <s>, </s> and the 256 byte-fallback tokens <0x00>..<0xFF>
+
+
+def char_merge_tokens(alphabet, pairs):
+    """Byte strings of the symbols A.. that merges (a, b) create over an alphabet of A characters."""
+    toks = list(alphabet)
+    for a, b in pairs:
+        toks.append(toks[int(a)] + toks[int(b)])
+    return toks[len(alphabet):]
+
+
+def llama_vocab_text(alphabet, pairs):
+    """A Llama-shaped vocab file (tools/make_vocab.py, VL): <unk>, <s>, </s>, <0x00>..<0xFF>, the alphabet, then the
+    merge tokens in order.  ids = line order."""
+    toks = [b"<unk>", b"<s>", b"</s>"] + [b"<0x%02X>" % b for b in range(256)]
+    toks += list(alphabet) + char_merge_tokens(alphabet, pairs)
+    return "".join(hex_line(tk, i) for i, tk in enumerate(toks))
+
+
+def llama_special_text():
+    return "".join("%d == %s\n" % (b, s) for b, s in sorted(llama_special_mapping().items()))
+
+
+def llama_merges_bytes(alphabet, pairs):
+    """merges.txt of a chars-mode run: "#version: 0.2", then one raw "left right" line per merge (no token holds a
+    space or a newline: spaces became U+2581 and words with control bytes were dropped)."""
+    toks = list(alphabet) + char_merge_tokens(alphabet, pairs)
+    return b"#version: 0.2\n" + b"".join(toks[int(a)] + b" " + toks[int(b)] + b"\n" for a, b in pairs)
+
+
+def write_llama_files(out_dir, name, alphabet, pairs):
+    """<name>_vocab.txt, <name>_special.txt, <name>_merges.txt under out_dir -> dict of the three paths."""
+    import os
+    paths = {"vocab_file": os.path.join(out_dir, name + "_vocab.txt"),
+             "special_file": os.path.join(out_dir, name + "_special.txt"),
+             "merges_file": os.path.join(out_dir, name + "_merges.txt")}
+    for key, data in (("vocab_file", llama_vocab_text(alphabet, pairs).encode("ascii")),
+                      ("special_file", llama_special_text().encode("utf-8")),
+                      ("merges_file", llama_merges_bytes(alphabet, pairs))):
+        with open(paths[key], "wb") as f:
+            f.write(data)
+    return paths

@@ -238,32 +238,50 @@ int hutk_debug_profile_raw(hutk_ctx* ctx, int64_t n_tiles, long long* out); /* t
 void hutk_set_timing(hutk_ctx* ctx, int enabled);
 
 /* ---- training ------------------------------------------------------------------------------------------
- * Byte-level BPE training on the GPU.  Replaces the reference's _hutoken.bpe_train / bbpe_train
- * (src/lib.c:76-126, src/bpe.c, src/bbpe.c) with the exact semantics of tools/train_vocab.cpp in "bytes" mode:
+ * BPE training on the GPU.  Replaces the reference's _hutoken.bpe_train / bbpe_train
+ * (src/lib.c:76-126, src/bpe.c, src/bbpe.c) with the exact semantics of tools/train_vocab.cpp in "bytes" mode
+ * (HUTK_TRAIN_BYTES) or "chars" mode (HUTK_TRAIN_CHARS):
  *   documents  bytes[offsets[i] .. offsets[i+1]); they may arrive over several hutk_trainer_add calls and the word
  *              counts accumulate.  A 0x00 byte inside a document fails the call with HUTK_E_NUL_BYTE and nothing
  *              of that call is counted.  Empty documents are allowed.
  *   words      the reference's splitter (src/parser.c, hutk_classify.h), never across documents, no length cap.
- *   symbols    byte values 0..255; merge k (0-based) creates symbol 256 + k = bytes(a) + bytes(b).
+ *   symbols    bytes mode: byte values 0..255, A = 256.  chars mode: a unique word holding a byte < 0x20 or 0x7F is
+ *              dropped; in the others each ' ' becomes E2 96 81 (U+2581), then the word is cut left to right into
+ *              characters whose length comes from the lead byte (< 0x80: 1, 110xxxxx: 2, 1110xxxx: 3, any other: 4,
+ *              cut short at the word's end; invalid UTF-8 is kept).  The distinct characters, sorted as byte strings,
+ *              are the symbols 0..A-1.  Merge k (0-based) creates symbol A + k = bytes(a) + bytes(b).
  *   counts     pair (a, b): sum over unique words of word count x adjacent (a, b) positions (overlaps count),
  *              64-bit, integer atomics only: the result does not depend on the schedule.
  *   selection  highest count; ties go to the smaller (uint64)a << 32 | b; training stops after n_merges merges or
  *              when no pair has a count >= 1.
  *   merge      in every word, left to right and non-overlapping (aaaa -> n n, aaa -> n a).
- * hutk_trainer_create: device = HIP ordinal, -1 for the current device.
+ * hutk_trainer_create: device = HIP ordinal, -1 for the current device; bytes mode.
+ * hutk_trainer_create_mode: the same with a mode (HUTK_TRAIN_BYTES or HUTK_TRAIN_CHARS; another value: HUTK_E_ARG).
+ * hutk_trainer_alphabet: ends the adding phase (a later hutk_trainer_add returns HUTK_E_ARG), turns the unique words
+ *   into symbols (once: later calls report the same) and writes the alphabet in id order: symbol i is
+ *   bytes_out[offsets_out[i] .. offsets_out[i+1]), n_symbols + 1 offsets.  *n_symbols and *n_bytes (either may be
+ *   NULL) receive the sizes; with bytes_out or offsets_out NULL only the sizes are reported; buffers too small for
+ *   them return HUTK_E_CAPACITY.  Bytes mode: the 256 single bytes.  hutk_trainer_run calls it if it was not called.
  * hutk_trainer_run: may be called once per trainer (a second call returns HUTK_E_ARG); writes
  *   pairs_out[2k], pairs_out[2k+1] = (a, b) of merge k and counts_out[k] (optional) for k < *n_done.
- * hutk_trainer_stats: out8 = documents, bytes, word occurrences, unique words, symbols in unique words,
- *   distinct pairs at the start, peak device workspace in bytes, microseconds of device time in the merge loop. */
+ * hutk_trainer_stats: out8 = documents, bytes, word occurrences, unique words, symbols in unique words (bytes before
+ *   the alphabet is made; characters of the kept words after that in chars mode), distinct pairs at the start, peak
+ *   device workspace in bytes, microseconds of device time in the merge loop. */
+#define HUTK_TRAIN_BYTES 0
+#define HUTK_TRAIN_CHARS 1
 typedef struct hutk_trainer hutk_trainer;
 int hutk_trainer_create(hutk_trainer** out, int device);
+int hutk_trainer_create_mode(hutk_trainer** out, int device, int mode);
+int hutk_trainer_alphabet(hutk_trainer* t, uint8_t* bytes_out, int64_t bytes_cap, int64_t* offsets_out,
+                          int64_t offsets_cap, int64_t* n_symbols, int64_t* n_bytes);
 int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs);
 int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int64_t* counts_out, int32_t* n_done);
 int hutk_trainer_stats(const hutk_trainer* t, int64_t* out8);
 /* Which internal paths the trainer took (for tests; host-side values, no added synchronisation).  Writes the first
- * min(n, 11) of: pauses, pair-table rebuilds that grew it, that shrank it, all rebuilds, host synchronisations of the
+ * min(n, 13) of: pauses, pair-table rebuilds that grew it, that shrank it, all rebuilds, host synchronisations of the
  * merge loop, largest pair-table capacity, largest k_select grid, word-table rehashes, deferred word insertions,
- * largest number of deferred-insertion rounds in one add, words that moved from the long to the short list. */
+ * largest number of deferred-insertion rounds in one add, words that moved from the long to the short list, unique
+ * words dropped for a control byte (chars mode), character-set regrowths (chars mode). */
 int hutk_trainer_debug_counters(const hutk_trainer* t, int64_t* out, int n);
 void hutk_trainer_destroy(hutk_trainer* t);
 

@@ -16,6 +16,10 @@ GPU every call raises.
 Also here (not in the reference): `encode_packed` / `encode_packed_device`, the
 zero-marshalling entry points for packed UTF-8 + offsets.
 
+Collation (not in the reference either): `collate_padded` / `batch_encode_padded` turn the device arrays of
+`encode_packed_device` into padded rows with attention mask and lengths, `SequencePacker` into packed rows of
+`seq_len` tokens with position and segment ids -- one HIP pass each (csrc/hutk_collate.hip).
+
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
 the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
@@ -28,7 +32,8 @@ import traceback
 from . import _capi
 
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
-           "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train"]
+           "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
+           "collate_padded", "batch_encode_padded", "SequencePacker"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -499,3 +504,236 @@ def bpe_train(*args, **kwargs):
 def bbpe_train(*args, **kwargs):
     """hutoken.bbpe_train (reference hutoken.py:168-171, lib.c:103-126): the same byte-level model as bpe_train."""
     return _native_bpe_train("bbpe_train", args, kwargs)
+
+
+# ---- collation ------------------------------------------------------------------------------------------------
+# The checks below run before any device call (and before torch is needed for anything but the tensors themselves).
+_INT32_MIN, _INT32_MAX = -2**31, 2**31 - 1
+
+
+def _token_arg(name, v, optional=True):
+    """bos_id / eos_id / pad_id -> int32 value; None -> the C ABI's "absent" (HUTK_NO_TOKEN)."""
+    if v is None and optional:
+        return _capi.NO_TOKEN
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError("%s must be an int%s, not %s" % (name, " or None" if optional else "", type(v).__name__))
+    if not (_INT32_MIN < v <= _INT32_MAX):
+        raise ValueError("%s must fit an int32 (and not be its lowest value)" % name)
+    return v
+
+
+def _length_arg(name, v, least):
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError("%s must be an int, not %s" % (name, type(v).__name__))
+    if v < least or v > _INT32_MAX:
+        raise ValueError("%s must be at least %d (1, and the bos/eos tokens must fit) and below 2**31" % (name, least))
+    return v
+
+
+def _out_width(dtype):
+    """torch.int32 / torch.int64 (or their names; None: int32) -> (4 | 8, name)."""
+    name = "int32" if dtype is None else dtype if isinstance(dtype, str) else str(dtype).rpartition(".")[2]
+    if name not in ("int32", "int64"):
+        raise ValueError("dtype must be torch.int32 or torch.int64, not %r" % (dtype,))
+    return (4 if name == "int32" else 8), name
+
+
+def _ragged_args(ids, offsets, n_ids):
+    """The (ids, offsets) pair of encode_packed_device: device tensors, int32 and int64[n_docs + 1]."""
+    for name, t, want in (("ids", ids, "int32"), ("offsets", offsets, "int64")):
+        if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")):
+            raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+        if str(t.dtype).rpartition(".")[2] != want:
+            raise TypeError("%s must have dtype %s, not %s" % (name, want, t.dtype))
+    for name, t in (("ids", ids), ("offsets", offsets)):
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be one-dimensional and contiguous" % name)
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU: the collation runs there and nowhere else" % name)
+    if offsets.numel() < 1:
+        raise ValueError("offsets must hold at least one entry")
+    if ids.device != offsets.device:
+        raise ValueError("ids and offsets must be on the same device")
+    if n_ids is not None:
+        if isinstance(n_ids, bool) or not isinstance(n_ids, int):
+            raise TypeError("n_ids must be an int or None")
+        if n_ids < 0 or n_ids > ids.numel():
+            raise ValueError("n_ids must be in 0 .. ids.numel()")
+
+
+def _n_ids(ids, offsets, n_ids):
+    if n_ids is None:
+        n_ids = int(offsets[-1].item())  # the one synchronisation; pass n_ids= to avoid it
+        if n_ids < 0 or n_ids > ids.numel():
+            raise ValueError("offsets[-1] = %d does not fit ids (%d elements)" % (n_ids, ids.numel()))
+    return n_ids
+
+
+def _raise_device_error(err, what):
+    code = int(err.item())
+    if code:
+        raise ValueError("hutoken_amd: %s: device-side error %d (offsets that do not describe ids)" % (what, code))
+
+
+_SIDES = ("right", "left")
+
+
+def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, pad_id=0, truncation="right",
+                   padding_side="right", dtype=None, n_ids=None, check=False):
+    """Device tensors of encode_packed_device in, a padded batch out, on the current torch stream:
+    -> (input_ids [n_docs, max_length] of `dtype` (torch.int32, the default, or torch.int64),
+        attention_mask uint8 [n_docs, max_length], lengths int32 [n_docs]).
+    Row i is [bos_id] + ids[offsets[i]:offsets[i+1]] + [eos_id] (those given); a longer one keeps bos/eos and the
+    first (truncation="right") or last ("left") max_length - s of the document's ids; pad_id fills the rest on
+    `padding_side`.  max_length=None pads to the longest sequence (one small synchronising read); a given one
+    synchronises only to read offsets[-1], and not at all with n_ids=.  check=True synchronises and raises ValueError
+    when the kernel found offsets that do not describe ids."""
+    bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
+    s = (bos != _capi.NO_TOKEN) + (eos != _capi.NO_TOKEN)
+    if max_length is not None:
+        _length_arg("max_length", max_length, max(1, s))
+    if truncation not in _SIDES:
+        raise ValueError("truncation must be 'right' or 'left', not %r" % (truncation,))
+    if padding_side not in _SIDES:
+        raise ValueError("padding_side must be 'right' or 'left', not %r" % (padding_side,))
+    width, dname = _out_width(dtype)
+    _ragged_args(ids, offsets, n_ids)
+    import torch
+    dev = ids.device
+    n_docs = offsets.numel() - 1
+    n_ids = _n_ids(ids, offsets, n_ids)
+    if max_length is None:
+        longest = int((offsets[1:] - offsets[:-1]).max().item()) if n_docs else 0
+        max_length = _length_arg("max_length", max(1, s, longest + s), 1)
+    out = torch.empty((n_docs, max_length), dtype=getattr(torch, dname), device=dev)
+    mask = torch.empty((n_docs, max_length), dtype=torch.uint8, device=dev)
+    lengths = torch.empty(n_docs, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = (_capi.COLLATE_TRUNC_LEFT if truncation == "left" else 0) | \
+            (_capi.COLLATE_PAD_LEFT if padding_side == "left" else 0)
+    with torch.cuda.device(dev):
+        _capi.collate_padded_device(ids.data_ptr(), offsets.data_ptr(), n_docs, n_ids, max_length, bos, eos, pad, flags,
+                                    width, out.data_ptr(), mask.data_ptr(), lengths.data_ptr(), err.data_ptr(),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    if check:
+        _raise_device_error(err, "collate_padded")
+    return out, mask, lengths
+
+
+_side_streams = {}
+
+
+def _texts_to_device(texts):
+    """list of str -> (ids, out_offsets) of encode_packed_device on the context's device."""
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    if not isinstance(texts, list):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    import torch
+    data, offs = _pack(texts)
+    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
+    d_bytes = torch.from_numpy(data.copy()).to(dev)  # (a copy: _pack's array is a read-only view of a bytes object)
+    d_offs = torch.from_numpy(offs).to(dev)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            return encode_packed_device(d_bytes, d_offs)
+        # The C ABI reads a NULL stream -- torch's default one -- as "the context's own stream", which no torch stream
+        # waits for.  So the encode goes to a stream of its own and the current stream waits for that.
+        side = _side_streams.get(dev.index)
+        if side is None:
+            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            ids, oo = encode_packed_device(d_bytes, d_offs)
+        cur.wait_stream(side)
+        ids.record_stream(cur)
+        oo.record_stream(cur)
+        return ids, oo
+
+
+def batch_encode_padded(texts, max_length=None, **collate_kwargs):
+    """A list of str -> collate_padded's (input_ids, attention_mask, lengths): encode_packed_device, then
+    collate_padded with `collate_kwargs`, both on the initialised context's GPU."""
+    ids, oo = _texts_to_device(texts)
+    return collate_padded(ids, oo, max_length, **collate_kwargs)
+
+
+class SequencePacker:
+    """Packs documents into rows of `seq_len` tokens for pretraining (hutk_packer_*, include/hutoken_amd.h).
+
+    The stream is the documents' sequences end to end, each [bos_id] + ids + [eos_id] with the ids given; add()
+    returns every complete row not yet returned as a dict of device tensors
+        input_ids [rows, seq_len] (dtype), position_ids int32 (0 at every document start and row start),
+        segment_ids int32 (1, 2, 3 .. per row, for masking attention at document boundaries)
+    and keeps the unfinished row on the device for the next call; flush() returns it padded with pad_id (position 0,
+    segment 0) and empties the stream.  The rows do not depend on how the documents are split over add() calls."""
+
+    def __init__(self, seq_len, *, eos_id=None, bos_id=None, pad_id=0, dtype=None, device=None):
+        bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
+        self.seq_len = _length_arg("seq_len", seq_len, 1)
+        self._width, self._dname = _out_width(dtype)
+        if device is not None and (isinstance(device, bool) or not isinstance(device, int)):
+            device = getattr(device, "index", device)  # a torch.device
+            if device is not None and not isinstance(device, int):
+                raise TypeError("device must be an int, a torch.device or None")
+        self._p = _capi.Packer(self.seq_len, bos, eos, pad, self._width, _default_device(device))
+        self._device = None
+
+    @property
+    def pending(self):
+        """Tokens held for the next row."""
+        return self._p.pending
+
+    def _rows(self, n, dev):
+        import torch
+        shape = (n, self.seq_len)
+        return {"input_ids": torch.empty(shape, dtype=getattr(torch, self._dname), device=dev),
+                "position_ids": torch.empty(shape, dtype=torch.int32, device=dev),
+                "segment_ids": torch.empty(shape, dtype=torch.int32, device=dev)}
+
+    def add(self, ids, offsets, n_ids=None, check=False):
+        """Device tensors of encode_packed_device -> the complete rows (possibly zero), on the current torch stream."""
+        _ragged_args(ids, offsets, n_ids)
+        import torch
+        dev = ids.device
+        n_docs = offsets.numel() - 1
+        n_ids = _n_ids(ids, offsets, n_ids)
+        n = self._p.rows(n_docs, n_ids)
+        out = self._rows(n, dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._device = dev
+        with torch.cuda.device(dev):
+            got = self._p.add(ids.data_ptr(), offsets.data_ptr(), n_docs, n_ids, out["input_ids"].data_ptr(),
+                              out["position_ids"].data_ptr(), out["segment_ids"].data_ptr(), n, err.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+        assert got == n
+        if check:
+            _raise_device_error(err, "SequencePacker.add")
+        return out
+
+    def add_texts(self, texts):
+        """A list of str: encoded with the initialised context (encode_packed_device), then add()."""
+        ids, oo = _texts_to_device(texts)
+        return self.add(ids, oo)
+
+    def flush(self):
+        """The unfinished row, padded (zero rows when nothing is pending); the stream starts anew."""
+        import torch
+        n = 1 if self._p.pending else 0
+        dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+        out = self._rows(n, dev)
+        if n:
+            with torch.cuda.device(dev):
+                self._p.flush(out["input_ids"].data_ptr(), out["position_ids"].data_ptr(),
+                              out["segment_ids"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def close(self):
+        self._p.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -25,8 +25,12 @@ EXPORTS = [
     "hutk_debug_seam", "hutk_debug_seam2_cut",
     "hutk_trainer_create", "hutk_trainer_add", "hutk_trainer_run", "hutk_trainer_stats", "hutk_trainer_destroy",
     "hutk_trainer_debug_counters", "hutk_trainer_create_mode", "hutk_trainer_alphabet",
+    "hutk_collate_padded_device", "hutk_packer_create", "hutk_packer_rows", "hutk_packer_add_device",
+    "hutk_packer_flush_device", "hutk_packer_pending", "hutk_packer_destroy",
 ]
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
+COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
+NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
 
 _lib = None
 
@@ -157,6 +161,22 @@ def load(build_if_missing=True):
         L.hutk_trainer_create_mode.argtypes = [C.POINTER(vp), i32, i32]
         L.hutk_trainer_alphabet.restype = i32
         L.hutk_trainer_alphabet.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    if hasattr(L, "hutk_collate_padded_device"):
+        L.hutk_collate_padded_device.restype = i32
+        L.hutk_collate_padded_device.argtypes = [vp, vp, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, i32, i32,
+                                                 vp, vp, vp, vp, vp]
+        L.hutk_packer_create.restype = i32
+        L.hutk_packer_create.argtypes = [C.POINTER(vp), i64, C.c_int32, C.c_int32, C.c_int32, i32, i32]
+        L.hutk_packer_rows.restype = i64
+        L.hutk_packer_rows.argtypes = [vp, i64, i64]
+        L.hutk_packer_add_device.restype = i32
+        L.hutk_packer_add_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
+        L.hutk_packer_flush_device.restype = i32
+        L.hutk_packer_flush_device.argtypes = [vp, vp, vp, vp, C.POINTER(i64), vp]
+        L.hutk_packer_pending.restype = i64
+        L.hutk_packer_pending.argtypes = [vp]
+        L.hutk_packer_destroy.restype = None
+        L.hutk_packer_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -478,6 +498,60 @@ class Trainer:
     def close(self):
         if getattr(self, "_h", None):
             load().hutk_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def collate_padded_device(d_ids, d_offsets, n_docs, n_ids, max_len, bos_id, eos_id, pad_id, flags, out_width,
+                          d_input_ids, d_mask=0, d_lengths=0, d_err=0, stream=0):
+    """hutk_collate_padded_device on raw device pointers (ints); asynchronous on `stream`.  bos_id / eos_id: NO_TOKEN
+    when absent."""
+    raise_for(load().hutk_collate_padded_device(d_ids or None, d_offsets or None, n_docs, n_ids, max_len, bos_id,
+                                                eos_id, pad_id, flags, out_width, d_input_ids or None,
+                                                d_mask or None, d_lengths or None, d_err or None, stream or None))
+
+
+class Packer:
+    """Owns one hutk_packer (include/hutoken_amd.h): raw device pointers (ints) in, rows written asynchronously."""
+
+    def __init__(self, seq_len, bos_id=NO_TOKEN, eos_id=NO_TOKEN, pad_id=0, out_width=4, device=-1):
+        h = C.c_void_p()
+        raise_for(load().hutk_packer_create(C.byref(h), int(seq_len), int(bos_id), int(eos_id), int(pad_id),
+                                            int(out_width), int(device)))
+        self._h = h
+
+    def rows(self, n_docs, n_ids):
+        """Rows the next add() with these sizes writes."""
+        return load().hutk_packer_rows(self._h, n_docs, n_ids)
+
+    @property
+    def pending(self):
+        return load().hutk_packer_pending(self._h)
+
+    def add(self, d_ids, d_offsets, n_docs, n_ids, d_input_ids, d_position_ids, d_segment_ids, rows_cap, d_err=0,
+            stream=0):
+        """-> the number of rows written."""
+        n = C.c_int64(0)
+        raise_for(load().hutk_packer_add_device(self._h, d_ids or None, d_offsets or None, n_docs, n_ids,
+                                                d_input_ids or None, d_position_ids or None, d_segment_ids or None,
+                                                rows_cap, C.byref(n), d_err or None, stream or None))
+        return n.value
+
+    def flush(self, d_input_ids, d_position_ids, d_segment_ids, stream=0):
+        """-> 0 or 1 rows written."""
+        n = C.c_int64(0)
+        raise_for(load().hutk_packer_flush_device(self._h, d_input_ids or None, d_position_ids or None,
+                                                  d_segment_ids or None, C.byref(n), stream or None))
+        return n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().hutk_packer_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,615 @@
+// hutk_collate.hip -- collation of encoded batches on the GPU: the ragged (ids, offsets) pair that hutk_encode_batch_device
+// writes becomes what a model reads.  Two layouts (include/hutoken_amd.h):
+//
+//   padded   one document per row of max_len elements: [bos] ids [eos], truncated, padded left or right, with the
+//            attention mask and the lengths                                            (k_collate_padded)
+//   packed   the sequences of all documents laid end to end and cut into rows of seq_len, with position and segment
+//            ids; the unfinished row is carried over to the next call                  (k_collate_packed, k_collate_flush)
+//
+// Both are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
+// length allows.  No element searches the offsets: a workgroup owns a contiguous span of output, finds the span's first
+// document with one search by a wavefront, marks the sequence starts of its span in LDS and turns the marks into "document
+// of this position", "where its sequence starts" and "starts since the row began" with one workgroup scan.
+#include <mutex>
+#include <string>
+
+#include "hutk_internal.h"
+
+namespace {
+
+constexpr int TB = 256;          // threads per workgroup
+constexpr int SPAN = 2048;       // packed: stream positions per workgroup (8 per thread)
+constexpr int PER = SPAN / TB;   // packed: positions a thread scans
+constexpr int PAD_TILE = 4096;   // padded: output elements per workgroup
+constexpr int PAD_ROWS = 256;    // padded: most rows per workgroup
+
+#define CL_TRY(expr)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e__ = (expr);                                                                            \
+        if (e__ != hipSuccess)                                                                              \
+            return hutk::api_set_error(HUTK_E_DEVICE, std::string("HIP error: ") + hipGetErrorString(e__) + \
+                                                          " at " #expr);                                    \
+    } while (0)
+
+__device__ __forceinline__ void note_error(int32_t* err, int code) {
+    if (err) atomicCAS(err, 0, code);
+}
+
+// four consecutive output elements of width W bytes, at element index i (16-byte aligned by the caller's choice of path)
+template <int W>
+__device__ __forceinline__ void store4(void* base, int64_t i, const int32_t (&v)[4]) {
+    if constexpr (W == 4) {
+        *reinterpret_cast<int4*>(static_cast<int32_t*>(base) + i) = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+        longlong2* p = reinterpret_cast<longlong2*>(static_cast<int64_t*>(base) + i);
+        p[0] = make_longlong2(v[0], v[1]);  // widened in registers
+        p[1] = make_longlong2(v[2], v[3]);
+    }
+}
+template <int W>
+__device__ __forceinline__ void store1(void* base, int64_t i, int32_t v) {
+    if constexpr (W == 4) static_cast<int32_t*>(base)[i] = v;
+    else static_cast<int64_t*>(base)[i] = v;
+}
+
+// ---- padded -------------------------------------------------------------------------------------------------------
+struct PadArgs {
+    const int32_t* ids;
+    const int64_t* offs;
+    int64_t n_docs, n_ids;
+    int32_t L, s;
+    int32_t bos, eos, pad;
+    int32_t has_bos, has_eos, trunc_left, pad_left;
+    void* out;
+    uint8_t* mask;
+    int32_t* lengths;
+    int32_t* err;
+    int32_t rows_per_block;  // > 1 only when rows_per_block * L <= PAD_TILE
+    int32_t col_chunks;      // pieces of PAD_TILE columns a row is cut into (1 unless rows_per_block == 1)
+};
+
+// A workgroup writes `rows_per_block` whole rows, or PAD_TILE columns of one long row.  The offsets of its rows are staged
+// in LDS once; an element is then a few integer operations and (inside the document) one dword read.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_padded(const PadArgs a) {
+    __shared__ int64_t s_off[PAD_ROWS + 1];
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids) {  // nothing is read through offsets that do not fit the ids
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
+        return;
+    }
+    const int64_t blk = blockIdx.x;
+    const int64_t rg = blk / a.col_chunks;
+    const int32_t cc = (int32_t)(blk - rg * a.col_chunks);
+    const int64_t row0 = rg * a.rows_per_block;
+    const int64_t left = a.n_docs - row0;
+    const int32_t nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
+    for (int32_t i = threadIdx.x; i <= nrows; i += TB) s_off[i] = a.offs[row0 + i];
+    __syncthreads();
+    const bool one_row = a.rows_per_block == 1;
+    const int32_t c0 = cc * PAD_TILE;
+    const int32_t ncols = one_row ? ((a.L - c0) < PAD_TILE ? (a.L - c0) : PAD_TILE) : a.L;
+    const int32_t total = nrows * ncols;
+    constexpr int V = VEC ? 4 : 1;
+    const int32_t room = a.L - a.s;
+    for (int32_t i = threadIdx.x * V; i < total; i += TB * V) {
+        const int32_t rl = one_row ? 0 : i / a.L;
+        const int32_t c = one_row ? c0 + i : i - rl * a.L;
+        const int64_t o0 = s_off[rl], o1 = s_off[rl + 1];
+        int64_t dl = o1 - o0;
+        if (dl < 0) {
+            dl = 0;
+            note_error(a.err, HUTK_E_ARG);
+        }
+        const int32_t n = dl > room ? room : (int32_t)dl;  // the document's own ids that stay
+        const int64_t src = a.trunc_left ? o1 - n : o0;
+        const int32_t sl = n + a.s;
+        const int32_t shift = a.pad_left ? a.L - sl : 0;
+        int32_t v[V];
+        uint8_t m[V];
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            const int32_t q = c + e - shift;
+            v[e] = a.pad;
+            m[e] = 0;
+            if (q >= 0 && q < sl) {
+                m[e] = 1;
+                if (a.has_bos && q == 0) v[e] = a.bos;
+                else if (a.has_eos && q == sl - 1) v[e] = a.eos;
+                else {
+                    const int64_t idx = src + q - a.has_bos;
+                    if (idx >= 0 && idx < a.n_ids) v[e] = a.ids[idx];
+                    else note_error(a.err, HUTK_E_ARG);
+                }
+            }
+        }
+        const int64_t at = (row0 + rl) * (int64_t)a.L + c;
+        if constexpr (VEC) {
+            store4<W>(a.out, at, v);
+            if (a.mask) *reinterpret_cast<uchar4*>(a.mask + at) = make_uchar4(m[0], m[1], m[2], m[3]);
+        } else {
+            store1<W>(a.out, at, v[0]);
+            if (a.mask) a.mask[at] = m[0];
+        }
+        if (c == 0 && a.lengths) a.lengths[row0 + rl] = sl;
+    }
+}
+
+// ---- packed -------------------------------------------------------------------------------------------------------
+// Stream positions of one add call: 0 .. P-1 are the tokens carried over (they end at a document end, so their position
+// and segment values are final), sequence j of the call begins at b_j = P + offsets[j] + j * s.  Rows are the stream cut
+// every L positions, so the flat index of an output element IS its stream position; what lies behind the last whole row
+// goes to the new carry instead.
+struct PackArgs {
+    const int32_t* ids;
+    const int64_t* offs;
+    int64_t n_docs, n_ids;
+    int64_t L, P, total, rows;
+    int32_t s, has_bos, has_eos;
+    int32_t bos, eos;
+    const int32_t *c_ids, *c_pos, *c_seg;  // the carry this call consumes (P entries)
+    int32_t *n_ids_out, *n_pos, *n_seg;    // the carry it leaves (total - rows * L entries)
+    void* out;
+    int32_t* pos;
+    int32_t* seg;
+    int32_t* err;
+    int32_t rows_per_block;  // L < SPAN: whole rows per workgroup
+    int32_t spans_per_row;   // L >= SPAN: workgroups per row
+};
+
+// last document whose sequence begins at or before stream position x; -1 when none does.  One wavefront searches: each
+// round its 64 lanes probe evenly spaced documents of the range and count the hits, so 2^20 documents take four dependent
+// loads where a binary search takes twenty.  All 64 lanes must call it; all get the answer.
+__device__ __forceinline__ int64_t last_doc_le(const PackArgs& a, int64_t x) {
+    int64_t lo = 0, hi = a.n_docs;  // documents below lo begin at or before x, those from hi on behind it
+    const int lane = threadIdx.x & 63;
+    while (lo < hi) {
+        const int64_t step = (hi - lo + 63) >> 6;
+        const int64_t at = lo + lane * step;
+        const int hits = __popcll(__ballot(at < hi && a.P + a.offs[at] + at * a.s <= x));
+        const int64_t top = lo + hits * step;  // the first probe that missed
+        if (hits) lo += (hits - 1) * step + 1;
+        hi = !hits ? lo : top < hi ? top : hi;
+    }
+    return lo - 1;
+}
+
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t s_d[SPAN + 4];  // marks (document - j0 at its sequence start), then their running maximum
+    __shared__ __attribute__((aligned(16))) int32_t s_c[SPAN];  // (1 + where the position's sequence starts in the span) << 16 | starts so far
+    __shared__ int32_t s_wmax[TB / 64], s_wcnt[TB / 64], s_wpos[TB / 64];
+    __shared__ int32_t s_pre;
+    __shared__ int64_t s_j[2];
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
+        return;
+    }
+    const int tid = threadIdx.x;
+    const int64_t blk = blockIdx.x;
+    int64_t k0, x0, x1;  // first row, first and one-past-last stream position of this workgroup
+    if (a.spans_per_row > 1) {
+        k0 = blk / a.spans_per_row;
+        x0 = k0 * a.L + (blk - k0 * a.spans_per_row) * SPAN;
+        x1 = x0 + SPAN < (k0 + 1) * a.L ? x0 + SPAN : (k0 + 1) * a.L;
+    } else {
+        k0 = blk * a.rows_per_block;
+        x0 = k0 * a.L;
+        x1 = x0 + a.rows_per_block * a.L;
+    }
+    if (x1 > a.total) x1 = a.total;
+    if (x0 >= x1) return;
+    const int32_t n = (int32_t)(x1 - x0);
+    const int64_t row_start0 = k0 * a.L;
+
+    for (int i = tid; i < SPAN + 4; i += TB) s_d[i] = 0;
+    if (tid == 0) s_pre = 0;
+    // the documents that hold the span's start and (when that is another place) the row's: a wavefront each, side by side
+    if (tid < 64) {
+        const int64_t j = last_doc_le(a, x0);
+        if (tid == 0) s_j[0] = j;
+    } else if (tid < 128 && x0 > row_start0) {
+        const int64_t j = last_doc_le(a, row_start0);
+        if (tid == 64) s_j[1] = j;
+    }
+    __syncthreads();
+    const int64_t j0 = s_j[0];
+    const int64_t b_j0 = j0 >= 0 ? a.P + a.offs[j0] + j0 * a.s : 0;
+
+    // the sequence starts inside the span.  Empty sequences (s == 0, no ids) start nothing, so several empty documents at
+    // one place cannot collide and the segment numbers stay dense.
+    for (int64_t j = j0 + 1 + tid; j < a.n_docs; j += TB) {
+        const int64_t o = a.offs[j];
+        const int64_t b = a.P + o + j * a.s;
+        if (b >= x1) break;
+        if (b > x0 && (a.s > 0 || a.offs[j + 1] > o)) s_d[b - x0] = (int32_t)(j - j0);
+    }
+    // starts between the row's start and the span's: in the carry, and in the documents up to j0
+    int32_t pre = 0;
+    if (k0 == 0 && a.P > 0) pre = a.c_seg[a.P - 1] - 1;
+    if (x0 > row_start0) {
+        const int64_t jk = s_j[1];
+        if (a.s > 0) pre += (int32_t)(j0 - jk);
+        else {
+            int32_t mine = 0;
+            for (int64_t j = jk + 1 + tid; j <= j0; j += TB) mine += a.offs[j + 1] > a.offs[j];
+            if (mine) atomicAdd(&s_pre, mine);
+        }
+    }
+    __syncthreads();
+    pre += s_pre;
+
+    // workgroup scan over the marks: the running maximum of the marks (they grow along the span) and of the places they
+    // stand at, and the running count
+    {
+        int32_t d[PER], c[PER];
+        const int4 lo = *reinterpret_cast<const int4*>(&s_d[tid * PER]);
+        const int4 hi = *reinterpret_cast<const int4*>(&s_d[tid * PER + 4]);
+        d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w;
+        d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
+        int32_t m = 0, cnt = 0, at = 0;  // at: 1 + the place of the last mark, 0 when there is none yet
+#pragma unroll
+        for (int e = 0; e < PER; e++) {
+            if (d[e] != 0) {
+                m = d[e];
+                at = tid * PER + e + 1;
+                cnt++;
+            }
+            d[e] = m;
+            c[e] = at << 16 | cnt;
+        }
+        const int lane = tid & 63, w = tid >> 6;
+        int32_t tm = m, tc = cnt, tp = at;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t pm = __shfl_up(tm, off), pc = __shfl_up(tc, off), pp = __shfl_up(tp, off);
+            if (lane >= off) {
+                tm = pm > tm ? pm : tm;
+                tp = pp > tp ? pp : tp;
+                tc += pc;
+            }
+        }
+        if (lane == 63) {
+            s_wmax[w] = tm;
+            s_wcnt[w] = tc;
+            s_wpos[w] = tp;
+        }
+        int32_t em = __shfl_up(tm, 1), ec = __shfl_up(tc, 1), ep = __shfl_up(tp, 1);
+        if (lane == 0) em = 0, ec = 0, ep = 0;
+        __syncthreads();
+        for (int u = 0; u < w; u++) {
+            em = s_wmax[u] > em ? s_wmax[u] : em;
+            ep = s_wpos[u] > ep ? s_wpos[u] : ep;
+            ec += s_wcnt[u];
+        }
+#pragma unroll
+        for (int e = 0; e < PER; e++) {
+            d[e] = d[e] > em ? d[e] : em;
+            const int32_t here = c[e] >> 16;
+            c[e] = (here > ep ? here : ep) << 16 | ((c[e] & 0xFFFF) + ec);
+        }
+        *reinterpret_cast<int4*>(&s_d[tid * PER]) = make_int4(d[0], d[1], d[2], d[3]);
+        *reinterpret_cast<int4*>(&s_d[tid * PER + 4]) = make_int4(d[4], d[5], d[6], d[7]);
+        *reinterpret_cast<int4*>(&s_c[tid * PER]) = make_int4(c[0], c[1], c[2], c[3]);
+        *reinterpret_cast<int4*>(&s_c[tid * PER + 4]) = make_int4(c[4], c[5], c[6], c[7]);
+    }
+    __syncthreads();
+
+    // the elements, V neighbours per thread and consecutive threads on consecutive groups (full-width coalesced stores)
+    constexpr int V = VEC ? 4 : 1;
+    const bool multi = a.spans_per_row <= 1 && a.rows_per_block > 1;
+    const int32_t Li = multi ? (int32_t)a.L : 0;
+    const int64_t out_end = a.rows * a.L;
+    for (int32_t i = tid * V; i < n; i += TB * V) {
+        const int32_t rl = multi ? i / Li : 0;  // row inside the workgroup (V neighbours share it: L % 4 == 0 on that path)
+        const int64_t row_start = row_start0 + (int64_t)rl * a.L;
+        const int32_t seg_base = rl == 0 ? 1 + pre : 1 - (s_c[rl * Li] & 0xFFFF);
+        int32_t vi[V], vp[V], vs[V];
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            const int64_t gp = x0 + i + e;
+            vi[e] = 0;
+            vp[e] = 0;
+            vs[e] = 0;
+            if (gp >= x1) continue;  // (only behind the stream's end: whole rows are multiples of V)
+            if (gp < a.P) {
+                vi[e] = a.c_ids[gp];
+                vp[e] = a.c_pos[gp];
+                vs[e] = a.c_seg[gp];
+                continue;
+            }
+            // No offsets are read here: the sequence's start is where its mark stood (or b_j0 for the one that reaches into
+            // the span), it ends where the next mark stands, and the id's place follows from the stream position.
+            const int32_t dd = s_d[i + e], cc = s_c[i + e];
+            const int64_t j = j0 + dd;
+            if (j < 0) {  // (offsets that do not describe the ids)
+                note_error(a.err, HUTK_E_ARG);
+                continue;
+            }
+            const int64_t b = dd ? x0 + (cc >> 16) - 1 : b_j0;
+            bool last = false;  // of its sequence (asked only with an eos, when every document is a sequence)
+            if (a.has_eos) {
+                if (i + e + 1 < n) last = s_d[i + e + 1] != dd;
+                else last = gp + 1 == (j + 1 < a.n_docs ? a.P + a.offs[j + 1] + (j + 1) * a.s : a.total);
+            }
+            if (a.has_bos && gp == b) vi[e] = a.bos;
+            else if (last) vi[e] = a.eos;
+            else {
+                const int64_t idx = gp - a.P - j * a.s - a.has_bos;
+                if (idx >= 0 && idx < a.n_ids) vi[e] = a.ids[idx];
+                else note_error(a.err, HUTK_E_ARG);
+            }
+            vp[e] = (int32_t)(gp - (b > row_start ? b : row_start));
+            vs[e] = seg_base + (cc & 0xFFFF);
+        }
+        const int64_t at = x0 + i;
+        if (at < out_end) {
+            if constexpr (VEC) {
+                store4<W>(a.out, at, vi);
+                if (a.pos) *reinterpret_cast<int4*>(a.pos + at) = make_int4(vp[0], vp[1], vp[2], vp[3]);
+                if (a.seg) *reinterpret_cast<int4*>(a.seg + at) = make_int4(vs[0], vs[1], vs[2], vs[3]);
+            } else {
+                store1<W>(a.out, at, vi[0]);
+                if (a.pos) a.pos[at] = vp[0];
+                if (a.seg) a.seg[at] = vs[0];
+            }
+        } else {  // behind the last whole row: the next call's carry
+#pragma unroll
+            for (int e = 0; e < V; e++) {
+                const int64_t t = at + e - out_end;
+                if (at + e < a.total) {
+                    a.n_ids_out[t] = vi[e];
+                    a.n_pos[t] = vp[e];
+                    a.n_seg[t] = vs[e];
+                }
+            }
+        }
+    }
+}
+
+// the carry as one padded row
+template <int W>
+__global__ __launch_bounds__(TB) void k_collate_flush(const int32_t* c_ids, const int32_t* c_pos, const int32_t* c_seg,
+                                                      int64_t P, int64_t L, int32_t pad, void* out, int32_t* pos, int32_t* seg) {
+    for (int64_t c = (int64_t)blockIdx.x * TB + threadIdx.x; c < L; c += (int64_t)gridDim.x * TB) {
+        const bool in = c < P;
+        store1<W>(out, c, in ? c_ids[c] : pad);
+        if (pos) pos[c] = in ? c_pos[c] : 0;
+        if (seg) seg[c] = in ? c_seg[c] : 0;
+    }
+}
+
+bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
+int device_present(const char* who) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return hutk::api_set_error(HUTK_E_DEVICE, std::string(who) + ": no HIP device");
+    return HUTK_OK;
+}
+
+}  // namespace
+
+struct hutk_packer {
+    int device = 0;
+    int64_t L = 0;
+    int32_t bos = HUTK_NO_TOKEN, eos = HUTK_NO_TOKEN, pad = 0;
+    int width = 4;
+    int64_t pending = 0;
+    int cur = 0;                 // which half of the carry holds the pending tokens
+    int32_t* carry = nullptr;    // [2][3][L]: ids, positions, segments
+    hipEvent_t ev = nullptr;     // behind the last kernel of the last call
+    bool ev_recorded = false;
+    std::mutex mu;
+    int s() const { return (bos != HUTK_NO_TOKEN) + (eos != HUTK_NO_TOKEN); }
+    int32_t* half(int h, int which) const { return carry + ((int64_t)h * 3 + which) * L; }
+};
+
+extern "C" {
+
+int hutk_collate_padded_device(const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs, int64_t n_ids,
+                               int64_t max_len, int32_t bos_id, int32_t eos_id, int32_t pad_id, int flags,
+                               int out_width, void* d_input_ids, uint8_t* d_mask, int32_t* d_lengths, int32_t* d_err,
+                               void* hip_stream) {
+    const int s = (bos_id != HUTK_NO_TOKEN) + (eos_id != HUTK_NO_TOKEN);
+    if (n_docs < 0 || n_ids < 0 || (out_width != 4 && out_width != 8) ||
+        (flags & ~(HUTK_COLLATE_TRUNC_LEFT | HUTK_COLLATE_PAD_LEFT)))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_padded_device: bad arguments");
+    if (max_len < 1 || max_len < s || max_len > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_padded_device: max_len must be at least 1 and the number of "
+                                               "bos/eos tokens, and below 2^31");
+    if (int rc = device_present("hutk_collate_padded_device")) return rc;
+    if (n_docs == 0) return HUTK_OK;
+    if (!d_offsets || !d_input_ids || (n_ids > 0 && !d_ids))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_padded_device: a buffer is NULL");
+    PadArgs a;
+    a.ids = d_ids;
+    a.offs = d_offsets;
+    a.n_docs = n_docs;
+    a.n_ids = n_ids;
+    a.L = (int32_t)max_len;
+    a.s = s;
+    a.bos = bos_id;
+    a.eos = eos_id;
+    a.pad = pad_id;
+    a.has_bos = bos_id != HUTK_NO_TOKEN;
+    a.has_eos = eos_id != HUTK_NO_TOKEN;
+    a.trunc_left = (flags & HUTK_COLLATE_TRUNC_LEFT) != 0;
+    a.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
+    a.out = d_input_ids;
+    a.mask = d_mask;
+    a.lengths = d_lengths;
+    a.err = d_err;
+    int64_t rpb = PAD_TILE / max_len;
+    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
+    a.rows_per_block = (int32_t)rpb;
+    a.col_chunks = rpb == 1 ? (int32_t)((max_len + PAD_TILE - 1) / PAD_TILE) : 1;
+    const int64_t blocks = (n_docs + rpb - 1) / rpb * a.col_chunks;
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_padded_device: the batch is too large for one launch");
+    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) CL_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    const dim3 grid((unsigned)blocks), block(TB);
+    if (out_width == 4) {
+        if (vec) hipLaunchKernelGGL((k_collate_padded<4, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_collate_padded<4, false>), grid, block, 0, st, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_collate_padded<8, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_collate_padded<8, false>), grid, block, 0, st, a);
+    }
+    CL_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_packer_create(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32_t eos_id, int32_t pad_id,
+                       int out_width, int device) {
+    if (!out) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_create: out is NULL");
+    *out = nullptr;
+    if (seq_len < 1 || seq_len > INT32_MAX || (out_width != 4 && out_width != 8))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_create: seq_len must be in 1 .. 2^31 - 1 and out_width 4 or 8");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no HIP device");
+    if (device < 0) CL_TRY(hipGetDevice(&device));
+    if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no such device");
+    CL_TRY(hipSetDevice(device));
+    hutk_packer* p = new hutk_packer();
+    p->device = device;
+    p->L = seq_len;
+    p->bos = bos_id;
+    p->eos = eos_id;
+    p->pad = pad_id;
+    p->width = out_width;
+    hipError_t e = hipMalloc((void**)&p->carry, (size_t)seq_len * 6 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        hutk_packer_destroy(p);
+        return hutk::api_set_error(e == hipErrorOutOfMemory ? HUTK_E_MEMORY : HUTK_E_DEVICE,
+                                   std::string("hutk_packer_create: ") + hipGetErrorString(e));
+    }
+    *out = p;
+    return HUTK_OK;
+}
+
+int64_t hutk_packer_rows(const hutk_packer* p, int64_t n_docs, int64_t n_ids) {
+    if (!p || n_docs < 0 || n_ids < 0) return -1;
+    return (p->pending + n_ids + n_docs * p->s()) / p->L;
+}
+
+int64_t hutk_packer_pending(const hutk_packer* p) { return p ? p->pending : -1; }
+
+int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs,
+                           int64_t n_ids, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                           int64_t rows_cap, int64_t* n_rows, int32_t* d_err, void* hip_stream) {
+    if (!p || n_docs < 0 || n_ids < 0 || rows_cap < 0 || n_docs > INT32_MAX - 1)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_add_device: bad arguments");
+    std::lock_guard<std::mutex> lock(p->mu);
+    const int s = p->s();
+    const int64_t total = p->pending + n_ids + n_docs * s;
+    const int64_t rows = total / p->L;
+    if (rows > rows_cap)
+        return hutk::api_set_error(HUTK_E_CAPACITY, "hutk_packer_add_device: rows_cap is below hutk_packer_rows()");
+    if ((n_docs > 0 && !d_offsets) || (n_ids > 0 && !d_ids) || (rows > 0 && !d_input_ids))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_add_device: a buffer is NULL");
+    hipStream_t st = (hipStream_t)hip_stream;
+    CL_TRY(hipSetDevice(p->device));
+    if (d_err) CL_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_rows) *n_rows = rows;
+    if (n_docs == 0) return HUTK_OK;  // nothing joins the stream (n_ids must then be 0)
+    const int64_t rows_all = rows + (total > rows * p->L);
+    PackArgs a;
+    a.ids = d_ids;
+    a.offs = d_offsets;
+    a.n_docs = n_docs;
+    a.n_ids = n_ids;
+    a.L = p->L;
+    a.P = p->pending;
+    a.total = total;
+    a.rows = rows;
+    a.s = s;
+    a.has_bos = p->bos != HUTK_NO_TOKEN;
+    a.has_eos = p->eos != HUTK_NO_TOKEN;
+    a.bos = p->bos;
+    a.eos = p->eos;
+    a.c_ids = p->half(p->cur, 0);
+    a.c_pos = p->half(p->cur, 1);
+    a.c_seg = p->half(p->cur, 2);
+    a.n_ids_out = p->half(p->cur ^ 1, 0);
+    a.n_pos = p->half(p->cur ^ 1, 1);
+    a.n_seg = p->half(p->cur ^ 1, 2);
+    a.out = d_input_ids;
+    a.pos = d_position_ids;
+    a.seg = d_segment_ids;
+    a.err = d_err;
+    int64_t blocks;
+    if (p->L >= SPAN) {
+        a.rows_per_block = 1;
+        a.spans_per_row = (int32_t)((p->L + SPAN - 1) / SPAN);
+        blocks = rows_all * a.spans_per_row;
+    } else {
+        a.rows_per_block = (int32_t)(SPAN / p->L);
+        a.spans_per_row = 1;
+        blocks = (rows_all + a.rows_per_block - 1) / a.rows_per_block;
+    }
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_packer_add_device: the batch is too large for one launch");
+    if (blocks > 0) {
+        if (p->ev_recorded) CL_TRY(hipStreamWaitEvent(st, p->ev, 0));
+        const bool vec = p->L % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_position_ids, 16) &&
+                         aligned_to(d_segment_ids, 16);
+        const dim3 grid((unsigned)blocks), block(TB);
+        if (p->width == 4) {
+            if (vec) hipLaunchKernelGGL((k_collate_packed<4, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_collate_packed<4, false>), grid, block, 0, st, a);
+        } else {
+            if (vec) hipLaunchKernelGGL((k_collate_packed<8, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((k_collate_packed<8, false>), grid, block, 0, st, a);
+        }
+        CL_TRY(hipGetLastError());
+        CL_TRY(hipEventRecord(p->ev, st));
+        p->ev_recorded = true;
+        p->cur ^= 1;
+    }
+    p->pending = total - rows * p->L;
+    return HUTK_OK;
+}
+
+int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                             int64_t* n_rows, void* hip_stream) {
+    if (!p) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_flush_device: bad arguments");
+    std::lock_guard<std::mutex> lock(p->mu);
+    if (p->pending == 0) {
+        if (n_rows) *n_rows = 0;
+        return HUTK_OK;
+    }
+    if (!d_input_ids) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_flush_device: d_input_ids is NULL");
+    hipStream_t st = (hipStream_t)hip_stream;
+    CL_TRY(hipSetDevice(p->device));
+    if (p->ev_recorded) CL_TRY(hipStreamWaitEvent(st, p->ev, 0));
+    int64_t blocks = (p->L + TB - 1) / TB;
+    if (blocks > 4096) blocks = 4096;
+    const dim3 grid((unsigned)blocks), block(TB);
+    if (p->width == 4)
+        hipLaunchKernelGGL((k_collate_flush<4>), grid, block, 0, st, p->half(p->cur, 0), p->half(p->cur, 1),
+                           p->half(p->cur, 2), p->pending, p->L, p->pad, d_input_ids, d_position_ids, d_segment_ids);
+    else
+        hipLaunchKernelGGL((k_collate_flush<8>), grid, block, 0, st, p->half(p->cur, 0), p->half(p->cur, 1),
+                           p->half(p->cur, 2), p->pending, p->L, p->pad, d_input_ids, d_position_ids, d_segment_ids);
+    CL_TRY(hipGetLastError());
+    CL_TRY(hipEventRecord(p->ev, st));
+    p->ev_recorded = true;
+    p->pending = 0;
+    if (n_rows) *n_rows = 1;
+    return HUTK_OK;
+}
+
+void hutk_packer_destroy(hutk_packer* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (p->ev) {
+        if (p->ev_recorded) (void)hipEventSynchronize(p->ev);  // nothing is freed under a running kernel
+        (void)hipEventDestroy(p->ev);
+    }
+    if (p->carry) (void)hipFree(p->carry);
+    delete p;
+}
+
+}  // extern "C"

@@ -285,6 +285,57 @@ int hutk_trainer_stats(const hutk_trainer* t, int64_t* out8);
 int hutk_trainer_debug_counters(const hutk_trainer* t, int64_t* out, int n);
 void hutk_trainer_destroy(hutk_trainer* t);
 
+/* ---- collation -----------------------------------------------------------------------------------------
+ * From the ragged pair hutk_encode_batch_device writes (d_ids int32, d_offsets int64[n_docs + 1], offsets[0] == 0,
+ * non-decreasing, offsets[n_docs] == n_ids) to what a model reads, on the GPU in one pass.  The reference has no
+ * counterpart.  Ids are copied as they are, negative ones included.  bos_id / eos_id: HUTK_NO_TOKEN = not inserted; s is
+ * the number of them present; the SEQUENCE of document i is [bos] ids_i [eos].  out_width 4 or 8: d_input_ids is int32
+ * or int64.  All calls are asynchronous on hip_stream and never synchronise; *d_err (may be NULL) is cleared by the call and
+ * receives HUTK_E_ARG when the kernel finds offsets[0] != 0, offsets[n_docs] != n_ids or offsets that point outside
+ * the ids (nothing is read out of bounds; the outputs are then undefined).  No HIP device: HUTK_E_DEVICE, there is no CPU
+ * fallback.  Sizes: n_docs < 2^31 - 1, max_len and seq_len < 2^31; element counts (n_docs x max_len, the stream) are 64-bit.
+ *
+ * PADDED.  Row i of d_input_ids[n_docs][max_len] is the sequence of document i; when it is longer than max_len the
+ * document's own ids are cut to max_len - s (the first ones, or with HUTK_COLLATE_TRUNC_LEFT the last ones) and bos/eos
+ * stay.  d_lengths[i] (may be NULL) is the sequence length after that; pad_id fills the rest of the row behind the
+ * sequence, or with HUTK_COLLATE_PAD_LEFT in front of it; d_mask[n_docs][max_len] (may be NULL) is 1 on the sequence
+ * and 0 on padding.  max_len < 1 or < s: HUTK_E_ARG.  n_docs == 0 writes nothing and succeeds.
+ *
+ * PACKED.  A packer holds a stream: the sequences of all documents added since it was created or last flushed, end to
+ * end (an empty sequence -- no ids, s == 0 -- contributes nothing).  Row k is stream[k * seq_len .. (k + 1) * seq_len).
+ * For the stream index p = k * seq_len + c inside the sequence that begins at b: position_ids[k][c] = p - max(b, k * seq_len)
+ * (from 0 at every sequence start and every row start), segment_ids[k][c] = 1 + the number of sequences that begin in
+ * (k * seq_len, p] (1, 2, 3 .. within a row; a sequence continued from the previous row is 1).  The rows depend on the
+ * order of the documents only, not on how they were split over the add calls.
+ *   the rows query  returns the number of rows the next add call with these sizes will write (-1: bad arguments).
+ *   the add call    writes every complete row (n_rows receives their number, possibly 0) and keeps the remaining
+ *                   < seq_len tokens, with their final position and segment values, in a device buffer of the packer.
+ *                   rows_cap below the rows query: HUTK_E_CAPACITY, nothing is enqueued or consumed.
+ *                   d_position_ids / d_segment_ids (int32) may be NULL.  After a call whose *d_err turned out non-zero
+ *                   the packer's contents are undefined until it is flushed.
+ *   the flush call  writes the kept tokens as one row padded with pad_id, position 0, segment 0 (*n_rows = 1), or
+ *                   nothing when none are kept (*n_rows = 0), and empties the stream.
+ *   pending         the number of tokens kept.
+ * Calls on one packer are serialised like calls on one context: a mutex on the host, an event on the device. */
+#define HUTK_COLLATE_TRUNC_LEFT 1
+#define HUTK_COLLATE_PAD_LEFT 2
+#define HUTK_NO_TOKEN INT32_MIN
+int hutk_collate_padded_device(const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs, int64_t n_ids,
+                               int64_t max_len, int32_t bos_id, int32_t eos_id, int32_t pad_id, int flags,
+                               int out_width, void* d_input_ids, uint8_t* d_mask, int32_t* d_lengths, int32_t* d_err,
+                               void* hip_stream);
+typedef struct hutk_packer hutk_packer;
+int hutk_packer_create(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32_t eos_id, int32_t pad_id,
+                       int out_width, int device);
+int64_t hutk_packer_rows(const hutk_packer* p, int64_t n_docs, int64_t n_ids);
+int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs,
+                           int64_t n_ids, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                           int64_t rows_cap, int64_t* n_rows, int32_t* d_err, void* hip_stream);
+int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                             int64_t* n_rows, void* hip_stream);
+int64_t hutk_packer_pending(const hutk_packer* p);
+void hutk_packer_destroy(hutk_packer* p);
+
 #ifdef __cplusplus
 }
 #endif

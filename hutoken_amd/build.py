@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
 HIP_SOURCES = ["hutk_loader.cpp", "hutk_api.cpp", "hutk_kernels.hip", "hutk_ptiles.hip", "hutk_decode.hip", "hutk_train.hip", "hutk_collate.hip"]
-HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_classify.h", "hutk_lab.h", os.path.join(INCLUDE, "hutoken_amd.h")]
+HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_classify.h", "hutk_lab.h", "hutk_exc.h", os.path.join(INCLUDE, "hutoken_amd.h")]
 
 LIB_HIP = os.path.join(LIBDIR, "libhutoken_amd.so")
 LIB_SYNTH = os.path.join(LIBDIR, "libhutk_synth.so")
@@ -79,17 +79,18 @@ def build_synth(force=False):
     return LIB_SYNTH
 
 
-def build_hip(force=False, extra_flags=()):
+def build_hip(force=False, extra_flags=(), out=LIB_HIP):
+    """out: another path for a variant build (tools/build_variant.sh: these sources and flags plus extra_flags)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     deps = srcs + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HIP_HEADERS]
-    if force or _stale(LIB_HIP, deps):
-        with _BuildLock(LIB_HIP):
-            if force or _stale(LIB_HIP, deps):
+    if force or _stale(out, deps):
+        with _BuildLock(out):
+            if force or _stale(out, deps):
                 cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                        "-Wall", "-Wno-unused-result", "-I" + INCLUDE, "-I" + CSRC,
-                       *extra_flags, "-o", LIB_HIP, *srcs, "-lpthread"]
-                _compile(cmd, LIB_HIP)
-    return LIB_HIP
+                       *extra_flags, "-o", out, *srcs, "-lpthread"]
+                _compile(cmd, out)
+    return out
 
 
 def build_pyshim(force=False):

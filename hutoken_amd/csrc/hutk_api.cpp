@@ -26,9 +26,7 @@
 
 #include "hutk_classify.h"
 #include "hutk_device.h"
-#ifndef HUTK_PTILES_DEFAULT
-#define HUTK_PTILES_DEFAULT 2  // 0: k_tiles; 1: k_ptiles; 2: auto
-#endif
+constexpr int PTILES_DEFAULT = 2;  // 0: k_tiles; 1: k_ptiles; 2: auto
 
 using namespace hutk;
 
@@ -355,9 +353,9 @@ int ensure_workspace(hutk_ctx* c, int64_t n_bytes, int64_t n_docs, int64_t n_til
     HIP_TRY(c->w_tile_u32.reserve((size_t)n_tiles * 8 + n_tiles / 32 + 16));
     HIP_TRY(c->w_tile_i64.reserve((size_t)n_tiles * 2 + n_tiles / 2048 + 16));
     HIP_TRY(c->w_doc_pos.reserve((size_t)n_docs + 2));
-    if (!c->w_counters.p) {  // (zeroed once: counters[10], k_pre's sample, is zeroed for the NEXT call by k_scan / k_tail_small)
-        HIP_TRY(c->w_counters.reserve(16));
-        HIP_TRY(hipMemset(c->w_counters.p, 0, 16 * sizeof(uint32_t)));
+    if (!c->w_counters.p) {  // (zeroed once: counters[CTR_SELECT_HI], k_pre's sample, is zeroed for the NEXT call by k_scan / k_tail_small)
+        HIP_TRY(c->w_counters.reserve(N_COUNTERS));
+        HIP_TRY(hipMemset(c->w_counters.p, 0, N_COUNTERS * sizeof(uint32_t)));
     }
     HIP_TRY(c->w_err.reserve(1));
     // exception words: longer than a lane takes (more than LANE_MAX_UNITS bytes), first of their document, or cut off by
@@ -780,7 +778,7 @@ int hutk_encode_batch_device(hutk_ctx* c, const uint8_t* d_bytes, const int64_t*
 // kernel for text dense in three- and four-byte characters (2.4x on CJK paragraphs), k_tiles for everything else.
 static int ptiles_mode() {
     const char* e = getenv("HUTK_PTILES");
-    return e ? (atoi(e) != 0 ? 1 : 0) : HUTK_PTILES_DEFAULT;
+    return e ? (atoi(e) != 0 ? 1 : 0) : PTILES_DEFAULT;
 }
 
 static int encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,

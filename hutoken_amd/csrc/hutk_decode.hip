@@ -38,10 +38,7 @@ __device__ __forceinline__ int64_t dec_doc_of(const DecArgs& D, int64_t i) {
     return lo;
 }
 
-#ifndef HUTK_DEC_PER_THREAD
-#define HUTK_DEC_PER_THREAD 8
-#endif
-constexpr int DEC_THREADS = 256, DEC_PER_THREAD = HUTK_DEC_PER_THREAD, DEC_TILE = DEC_THREADS * DEC_PER_THREAD;
+constexpr int DEC_THREADS = 256, DEC_PER_THREAD = 8, DEC_TILE = DEC_THREADS * DEC_PER_THREAD;
 static_assert(DEC_PER_THREAD % 4 == 0 && 32 % DEC_PER_THREAD == 0, "16-byte id loads; a thread's first-token bits sit in one word");
 
 // first document whose first token is at or after the tile's first token (binary search, once per tile)

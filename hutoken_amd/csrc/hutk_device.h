@@ -101,8 +101,32 @@ struct ExcRec {
     uint32_t tile;
 };
 
+// Workspace::counters: the batch's device-side counts and work cursors, zeroed by k_pre (CTR_SELECT_HI: see there).
+// The exception words are on five lists by length (exc_list_of): *_COUNT their entries, *_CURSOR the next lot of 64 lanes
+// that a wavefront of the kernel that walks the list takes.
+enum : int {
+    CTR_EXC = 0,        // exception records ...
+    CTR_EXC_TILES = 1,  // ... and tiles that have some: the two are claimed together by ONE 64-bit atomic (k_tiles, k_ptiles)
+    CTR_WAVE_CURSOR,    // d_exc
+    CTR_LANE_CURSOR,    // d_exc_lane (k_exc_a)
+    CTR_G2_COUNT,       // exc_quad from the front: words of up to 128 units
+    CTR_WAVE_COUNT,     // exc_wave
+    CTR_NOREAL_TILES,   // tiles without a word start of the reference's own (k_cut)
+    CTR_SCAN_TICKET,    // k_scan
+    CTR_G2_CURSOR,      // d_exc_group_fast<2> (k_exc_b)
+    CTR_G4_CURSOR,      // d_exc_group_fast<4>
+    CTR_SELECT_HI,      // k_pre's sample of the batch's bytes (Workspace::select)
+    CTR_G4_COUNT,       // exc_quad from the back: 129..256 units
+    CTR_G8_COUNT,       // exc_mid from the front: 257..512 units
+    CTR_G16_COUNT,      // exc_mid from the back: 513..1024 units
+    CTR_G8_CURSOR,      // d_exc_group_fast<8>
+    CTR_G16_CURSOR,     // d_exc_group_fast<16>
+    N_COUNTERS
+};
+static_assert(CTR_EXC == 0 && CTR_EXC_TILES == 1 && N_COUNTERS == 16, "one 64-bit atomic claims records and tiles");
+
 struct Workspace {
-    uint32_t* run;        // SYMBOLS of tile t's lane-path words at run[t*RUN_STRIDE + first_word + k]; k_gather maps to ids
+    uint32_t* run;        // SYMBOLS of tile t's lane-path words at run[t*RUN_STRIDE + first_word + k]; k_finish maps to ids
     int32_t* exc_tok;     // [cap_bytes + pad] ids of exception words at their own byte offset (+ doc padding)
     uint32_t* exc_sym;    // [cap_bytes + pad] symbol array of exception words too long for LDS
     uint32_t* exc_mrg;    // [cap_bytes + pad] their pair array
@@ -117,10 +141,10 @@ struct Workspace {
     int64_t n_scan_blocks;
     uint32_t* doc_tile_pos;    // [n_docs + 1] ids the owning tile emits before the document start
     ExcRec* exc;               // [cap_exc]
-    uint32_t* exc_quad;        // [cap_exc] exception words of at most 128 units from the front (count: counters[4]), of 129..256 from the back (counters[11]): d_exc_group_fast<2>, <4> (or d_exc_quad, both as one list)
-    uint32_t* exc_mid;         // [cap_exc] ... of 257..512 units from the front (counters[12]), of 513..1024 from the back (counters[13]): d_exc_group_fast<8>, <16>
-    uint32_t* exc_wave;        // [cap_exc] ... the rest, one wavefront each in d_exc (count: counters[5])
-    uint32_t* counters;        // [0] exception total, [1] tiles with exceptions (one 64-bit atomic claims both), [2] d_exc's work cursor, [3] d_exc_lane_fast<1>'s (k_exc_a), [8] [9] [14] [15] d_exc_group_fast<2>'s .. <16>'s (k_exc_b), [4] / [5] entries of exc_quad / exc_wave, [6] tiles without a start of the reference's own, [7] k_scan's ticket
+    uint32_t* exc_quad;        // [cap_exc] exception words of at most 128 units from the front (CTR_G2_COUNT), of 129..256 from the back (CTR_G4_COUNT): d_exc_group_fast<2>, <4> (or d_exc_quad, both as one list)
+    uint32_t* exc_mid;         // [cap_exc] ... of 257..512 units from the front (CTR_G8_COUNT), of 513..1024 from the back (CTR_G16_COUNT): d_exc_group_fast<8>, <16>
+    uint32_t* exc_wave;        // [cap_exc] ... the rest, one wavefront each in d_exc (CTR_WAVE_COUNT)
+    uint32_t* counters;        // [N_COUNTERS], the CTR_* slots above
     uint32_t* exc_tiles;       // [n_tiles] those tiles, in no particular order
     uint32_t* noreal_bits;     // [n_tiles / 32 + 1] bit t: tile t holds no word start of the reference's own (k_cut)
     uint32_t* tile_first_start;  // [n_tiles] first word start (seams and document starts included) among the tile's 1024 classified positions, 0xFFFF: none -- d_exc_ends finds the end of a word its tile could not see here
@@ -129,7 +153,7 @@ struct Workspace {
     int32_t pad_per_doc;       // extra exc_* slots per document (prefix units + prefix-alone ids)
     long long* prof;           // diagnostic: [n_tiles][10] clock64 stamps of k_tiles, or null
     // Which tile kernel encodes the batch when BOTH are enqueued (hutk_api.cpp, "auto"): k_pre samples the batch's bytes
-    // (counters[10] = bytes >= 0xE0 among the SELECT_SAMPLE bytes it looks at in one tile of SELECT_BLOCK_STRIDE); a batch in which they are at
+    // (CTR_SELECT_HI = bytes >= 0xE0 among the SELECT_SAMPLE bytes it looks at in one tile of SELECT_BLOCK_STRIDE); a batch in which they are at
     // least one byte in SELECT_DENSE_DIV is "dense".  select: 0 = run; 1 = run only for a dense batch (k_ptiles); 2 = run
     // only for one that is not (k_tiles).  The kernel that is not chosen returns at once.
     int32_t select;
@@ -140,7 +164,7 @@ constexpr int SELECT_SAMPLE = 16, SELECT_DENSE_DIV = 8, SELECT_BLOCK_STRIDE = 8;
 __device__ __forceinline__ bool select_skips(const Workspace& W, int64_t n_tiles) {
     if (W.select == 0) return false;
     // (about one tile in SELECT_BLOCK_STRIDE is sampled; the batches both kernels take have thousands of tiles)
-    const bool dense = (int64_t)W.counters[10] * SELECT_DENSE_DIV * SELECT_BLOCK_STRIDE >= n_tiles * SELECT_SAMPLE;
+    const bool dense = (int64_t)W.counters[CTR_SELECT_HI] * SELECT_DENSE_DIV * SELECT_BLOCK_STRIDE >= n_tiles * SELECT_SAMPLE;
     return (W.select == 1) != dense;
 }
 

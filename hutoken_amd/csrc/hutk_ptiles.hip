@@ -26,51 +26,21 @@
 #include <cstdlib>
 
 #include "hutk_kdev.h"
+#include "hutk_lab.h"
 
 namespace hutk {
 
-#ifndef HUTK_PT_WAVES
-#define HUTK_PT_WAVES 16
-#endif
-#ifndef HUTK_PT_PROF
-#define HUTK_PT_PROF 0
-#endif
-#ifndef HUTK_PT_PERTURB_VALU
-#define HUTK_PT_PERTURB_VALU 0
-#endif
-#ifndef HUTK_PT_PERTURB_SLEEP
-#define HUTK_PT_PERTURB_SLEEP 0
-#endif
-#ifndef HUTK_PT_MARKS
-#define HUTK_PT_MARKS 0
-#endif
-#ifndef HUTK_PT_SWAR
-#define HUTK_PT_SWAR 0
-#endif
-#ifndef HUTK_PT_REFILL
-#define HUTK_PT_REFILL 48
-#endif
-#if HUTK_PT_MARKS  // (tools/ptiles_isa.py builds with -DHUTK_PT_MARKS=1: comments in the ISA between which it counts instructions)
+#if HUTK_PT_MARKS  // (hutk_lab.h; tools/ptiles_isa.py)
 #define PT_MARK(name) asm volatile("; PTMARK " name)
 #else
 #define PT_MARK(name) do {} while (0)
 #endif
-constexpr int PT_WAVES = HUTK_PT_WAVES;       // wavefronts of the one workgroup a compute unit holds
-#ifndef HUTK_PT_WGS
-#define HUTK_PT_WGS 1  // workgroups per compute unit (2: eight wavefronts per SIMD, 64 VGPRs, half the LDS each)
-#endif
-#ifndef HUTK_PT_SLOTS
-#define HUTK_PT_SLOTS (HUTK_PT_WGS == 1 ? 30 : 13)
-#endif
-#ifndef HUTK_PT_ARENAS
-#define HUTK_PT_ARENAS (HUTK_PT_WGS == 1 ? 5 : 3)
-#endif
-constexpr int PT_WGS = HUTK_PT_WGS;
-constexpr int PT_SLOTS = HUTK_PT_SLOTS;       // tiles in flight per workgroup (one bit each in the control masks)
-constexpr int PT_QCAP = HUTK_PT_WGS == 1 ? 2048 : 1024;  // entries of the merge-word queue (a power of two)
-constexpr int PT_ARENAS = HUTK_PT_ARENAS;     // wavefronts that can merge at the same time
+constexpr int PT_WAVES = 16;                  // wavefronts of the one workgroup a compute unit holds (two workgroups of eight, 64 VGPRs and half the LDS each: 3.50 ms)
+constexpr int PT_SLOTS = 30;                  // tiles in flight per workgroup (one bit each in the control masks)
+constexpr int PT_QCAP = 2048;                 // entries of the merge-word queue (a power of two)
+constexpr int PT_ARENAS = 5;                  // wavefronts that can merge at the same time
 constexpr int PT_ROW = 34;                    // 16-bit entries of one lane's row of pair results: 32 units + one dword, so that lane l's row begins one bank behind lane l - 1's
-constexpr int PT_REFILL_MIN = HUTK_PT_REFILL;  // a merging wavefront takes new words when that many of its lanes are without one
+constexpr int PT_REFILL_MIN = 48;  // a merging wavefront takes new words when that many of its lanes are without one
 constexpr int PT_STAGE = 256;                 // word starts a front end stages at a time (a tile has ~180 words of 2..14 bytes)
 constexpr int PT_ROOM_AHEAD = 64;             // queue entries a front end reserves before it knows its words (a tile has ~11)
 constexpr uint32_t PT_Q_VALID = 0x80000000u;
@@ -111,7 +81,7 @@ struct PtCtl {
     int32_t q_room;       // ring entries that no producer has reserved and every consumer has read
 };
 
-__global__ __launch_bounds__(64 * PT_WAVES) __attribute__((amdgpu_waves_per_eu(PT_WAVES * PT_WGS / 4, PT_WAVES * PT_WGS / 4))) void k_ptiles(DevTables T, BatchArgs A, Workspace W) {
+__global__ __launch_bounds__(64 * PT_WAVES) __attribute__((amdgpu_waves_per_eu(PT_WAVES / 4, PT_WAVES / 4))) void k_ptiles(DevTables T, BatchArgs A, Workspace W) {
     typedef uint16_t SymT;
     __shared__ PtSlot slots[PT_SLOTS];
     __shared__ __attribute__((aligned(16))) uint8_t s_dfa[dfa::TABLE_BYTES + 256];  // transition table (seam map in its rows' padding), then byte classes
@@ -431,11 +401,7 @@ __global__ __launch_bounds__(64 * PT_WAVES) __attribute__((amdgpu_waves_per_eu(P
             const uint32_t dw[8] = {(uint32_t)w.a, (uint32_t)(w.a >> 32), (uint32_t)w.b, (uint32_t)(w.b >> 32),
                                     (uint32_t)w.c, (uint32_t)(w.c >> 32), (uint32_t)w.d, (uint32_t)(w.d >> 32)};
             bool exotic;
-#if HUTK_PT_SWAR
-            flags = classify16(dw, dbits, &exotic);  // byte-parallel mask algebra: ~650 integer instructions, NO LDS lookup
-#else
             flags = classify16_dfa2(dw, dbits, reinterpret_cast<const uint16_t*>(s_dfa), s_dfa + dfa::TABLE_BYTES, &exotic);  // (two walks side by side: a shorter chain)
-#endif
             if (exotic) {
                 // overlong encodings: per-position decode.  Its window lives in LDS meanwhile (the slot's symbols are not written
                 // yet): the decode indexes it dynamically, which in registers means scratch memory -- and a launch whose scratch
@@ -563,7 +529,7 @@ __global__ __launch_bounds__(64 * PT_WAVES) __attribute__((amdgpu_waves_per_eu(P
                 if (lane == 0) {
                     if (minel == 0) {
                         atomicOr(&W.noreal_bits[tile >> 5], 1u << (tile & 31));
-                        atomicAdd(&W.counters[6], 1u);
+                        atomicAdd(&W.counters[CTR_NOREAL_TILES], 1u);
                     } else {  // last_real16: the starts (without seams) of the tile's last lane that has one
                         me.cutpos = 1u + (uint32_t)(16 * (63 - __builtin_clzll(minel)) + 31 - __builtin_clz(last_real16 & 0xFFFFu));
                     }
@@ -1095,7 +1061,7 @@ static int pt_grid() {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
             cus = 256;
-        g = cus / 8 * 8 * PT_WGS;
+        g = cus / 8 * 8;
     }
     return g;
 }

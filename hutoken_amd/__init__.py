@@ -20,6 +20,10 @@ Collation (not in the reference either): `collate_padded` / `batch_encode_padded
 `encode_packed_device` into padded rows with attention mask and lengths, `SequencePacker` into packed rows of
 `seq_len` tokens with position and segment ids -- one HIP pass each (csrc/hutk_collate.hip).
 
+Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
+[start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
+`encode_with_offsets` are the list forms (csrc/hutk_spans.hip).
+
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
 the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
@@ -33,7 +37,8 @@ from . import _capi
 
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
-           "collate_padded", "batch_encode_padded", "SequencePacker"]
+           "collate_padded", "batch_encode_padded", "SequencePacker",
+           "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -623,8 +628,9 @@ def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, p
 _side_streams = {}
 
 
-def _texts_to_device(texts):
-    """list of str -> (ids, out_offsets) of encode_packed_device on the context's device."""
+def _texts_to_device(texts, with_text=False):
+    """list of str -> (ids, out_offsets) of encode_packed_device on the context's device; with_text: and the packed
+    text they were made from, (ids, out_offsets, d_bytes, d_offs)."""
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
     if not isinstance(texts, list):
@@ -637,7 +643,8 @@ def _texts_to_device(texts):
     with torch.cuda.device(dev):
         cur = torch.cuda.current_stream(dev)
         if cur.cuda_stream:
-            return encode_packed_device(d_bytes, d_offs)
+            ids, oo = encode_packed_device(d_bytes, d_offs)
+            return (ids, oo, d_bytes, d_offs) if with_text else (ids, oo)
         # The C ABI reads a NULL stream -- torch's default one -- as "the context's own stream", which no torch stream
         # waits for.  So the encode goes to a stream of its own and the current stream waits for that.
         side = _side_streams.get(dev.index)
@@ -649,7 +656,7 @@ def _texts_to_device(texts):
         cur.wait_stream(side)
         ids.record_stream(cur)
         oo.record_stream(cur)
-        return ids, oo
+        return (ids, oo, d_bytes, d_offs) if with_text else (ids, oo)
 
 
 def batch_encode_padded(texts, max_length=None, **collate_kwargs):
@@ -737,3 +744,99 @@ class SequencePacker:
 
     def __exit__(self, *exc):
         self.close()
+
+
+# ---- token spans (offset mapping) ------------------------------------------------------------------------------------
+_UNITS = {"char": _capi.SPANS_CHARS, "byte": _capi.SPANS_BYTES}
+
+
+def _span_unit(unit):
+    if unit not in _UNITS:
+        raise ValueError("unit must be 'char' or 'byte', not %r" % (unit,))
+    return _UNITS[unit]
+
+
+def token_spans_device(d_bytes, d_offsets, ids, out_offsets, unit="char", dtype=None, n_ids=None, check=True):
+    """The packed text (device tensors: uint8 bytes, int64 offsets[n_docs + 1]) and what encode_packed_device made of it
+    (ids int32, out_offsets int64[n_docs + 1]) -> a device tensor [n_ids, 2] of `dtype` (torch.int32, the default, or
+    torch.int64): token k of document i covers text_i[start:end] with (start, end) = spans[out_offsets[i] + k], counted in
+    characters (unit="char", what str slicing takes) or bytes (unit="byte") from the document's start.  An id of -1 covers
+    the one character (byte, with is_byte_encoder) at its place; the tokens of a prefix encoded on its own get (0, 0).
+    On the current torch stream; synchronises only to read out_offsets[-1] (not with n_ids=) and for check=True, which
+    raises ValueError naming the first document whose text does not hold its tokens' bytes, or TypeError for offsets
+    that do not describe the tensors."""
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    code = _span_unit(unit)
+    width, dname = _out_width(dtype)
+    _ragged_args(ids, out_offsets, n_ids)
+    for name, t, want in (("d_bytes", d_bytes, "uint8"), ("d_offsets", d_offsets, "int64")):
+        if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")):
+            raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+        if str(t.dtype).rpartition(".")[2] != want:
+            raise TypeError("%s must have dtype %s, not %s" % (name, want, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous() or t.device != ids.device:
+            raise ValueError("%s must be one-dimensional, contiguous and on the device of ids" % name)
+    if d_offsets.numel() != out_offsets.numel():
+        raise ValueError("d_offsets and out_offsets must describe the same documents")
+    import torch
+    dev = ids.device
+    if dev.index != _capi.load().hutk_device_ordinal(_ctx.handle):
+        raise ValueError("the tensors must be on the context's device: spans are computed there")
+    n_docs = d_offsets.numel() - 1
+    n_ids = _n_ids(ids, out_offsets, n_ids)
+    spans = torch.empty((n_ids, 2), dtype=getattr(torch, dname), device=dev)
+    status = torch.empty(max(n_docs, 1), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _ctx.token_spans_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, d_bytes.numel(), ids.data_ptr(),
+                                out_offsets.data_ptr(), n_ids, code, width, spans.data_ptr(), status.data_ptr(),
+                                err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            call()
+        else:  # (a NULL stream would mean the context's own stream to the C ABI: see _texts_to_device)
+            side = _side_streams.get(dev.index)
+            if side is None:
+                side = _side_streams[dev.index] = torch.cuda.Stream(dev)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                call()
+            cur.wait_stream(side)
+            for t in (d_bytes, d_offsets, ids, out_offsets, spans, status, err):
+                t.record_stream(side)
+    if check:
+        rc = int(err.item())
+        if rc == _capi.E_ARG:
+            raise TypeError("hutoken_amd: token_spans_device: offsets that do not describe the tensors (or a document of "
+                            "2**31 bytes or more with int32 spans)")
+        if rc:
+            bad = torch.nonzero(status[:n_docs]).flatten()
+            which = int(bad[0].item()) if bad.numel() else -1
+            raise ValueError("hutoken_amd: token_spans_device: document %d: the text does not hold the decoded bytes of its "
+                             "tokens where their spans lie (status %d, device-side error %d)"
+                             % (which, int(status[which].item()) if which >= 0 else 0, rc))
+    return spans
+
+
+def batch_encode_with_offsets(texts, unit="char"):
+    """A list of str -> (ids, offsets): ids as batch_encode returns them, offsets[i][k] = (start, end) of token k in
+    texts[i], so that texts[i][start:end] is the text the token covers (unit="char"; "byte": in the UTF-8 bytes)."""
+    _span_unit(unit)
+    ids, oo, d_bytes, d_offs = _texts_to_device(texts, with_text=True)
+    bounds = oo.cpu().tolist()
+    spans = token_spans_device(d_bytes, d_offs, ids, oo, unit=unit, n_ids=bounds[-1])
+    flat = ids[:bounds[-1]].cpu().tolist()
+    sp = spans.cpu().tolist()
+    return ([flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))],
+            [[(a, b) for a, b in sp[bounds[i]:bounds[i + 1]]] for i in range(len(texts))])
+
+
+def encode_with_offsets(text, unit="char"):
+    """One str -> (ids, [(start, end), ...]); see batch_encode_with_offsets."""
+    if not isinstance(text, str):
+        raise TypeError(f"argument 1 must be str, not {type(text).__name__}")
+    ids, spans = batch_encode_with_offsets([text], unit)
+    return ids[0], spans[0]

@@ -14,6 +14,7 @@ OK = 0
 E_FILE_NOT_FOUND, E_VALUE, E_MEMORY, E_ARG, E_DEVICE, E_UNSUPPORTED = 1, 2, 3, 4, 5, 6
 E_CAPACITY, E_NUL_BYTE, E_WORD_TOO_LARGE, E_INVALID_UTF8 = 7, 8, 9, 10
 DOC_OK, DOC_WORD_TOO_LARGE, DOC_INVALID_UTF8 = 0, 1, 2
+DOC_ID_OUT_OF_RANGE, DOC_ID_UNDECODABLE, DOC_SPAN_MISMATCH = 3, 4, 5
 
 # every symbol include/hutoken_amd.h declares
 EXPORTS = [
@@ -27,10 +28,12 @@ EXPORTS = [
     "hutk_trainer_debug_counters", "hutk_trainer_create_mode", "hutk_trainer_alphabet",
     "hutk_collate_padded_device", "hutk_packer_create", "hutk_packer_rows", "hutk_packer_add_device",
     "hutk_packer_flush_device", "hutk_packer_pending", "hutk_packer_destroy",
+    "hutk_token_spans_device", "hutk_token_spans",
 ]
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
 NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
+SPANS_BYTES, SPANS_CHARS = 0, 1
 
 _lib = None
 
@@ -177,6 +180,11 @@ def load(build_if_missing=True):
         L.hutk_packer_pending.argtypes = [vp]
         L.hutk_packer_destroy.restype = None
         L.hutk_packer_destroy.argtypes = [vp]
+    if hasattr(L, "hutk_token_spans_device"):
+        L.hutk_token_spans_device.restype = i32
+        L.hutk_token_spans_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp]
+        L.hutk_token_spans.restype = i32
+        L.hutk_token_spans.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
     _lib = L
     return L
 
@@ -406,6 +414,36 @@ class Context:
         rc = load().hutk_encode_batch_device(self._h, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap,
                                              d_out_offsets, d_status or None, d_err or None, stream or None)
         raise_for(rc)
+
+    def token_spans_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, d_id_offsets, n_ids, unit, out_width,
+                           d_spans, d_status=0, d_err=0, stream=0):
+        """hutk_token_spans_device on raw device pointers (ints); asynchronous on `stream`."""
+        raise_for(load().hutk_token_spans_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                 d_ids or None, d_id_offsets or None, n_ids, unit, out_width,
+                                                 d_spans or None, d_status or None, d_err or None, stream or None))
+
+    def token_spans_packed(self, data, offsets, ids, id_offsets, unit=SPANS_CHARS, out_width=4):
+        """Host numpy buffers in and out (hutk_token_spans): -> (spans [n_ids, 2], status int32[n_docs], return code).
+        A span mismatch (return code E_UNSUPPORTED) is reported through the status, anything else raises."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if n < 0 or len(id_offsets) != n + 1:
+            raise TypeError("offsets and id_offsets must hold n_docs + 1 entries each")
+        if n and (int(offsets[n]) > len(data) or int(id_offsets[n]) > len(ids)):
+            raise TypeError("offsets point outside the buffers")
+        n_ids = int(id_offsets[n])
+        spans = np.zeros((n_ids, 2), dtype=np.int32 if out_width == 4 else np.int64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        rc = load().hutk_token_spans(self._h, data.ctypes.data if len(data) else None, offsets.ctypes.data, n,
+                                     ids.ctypes.data if len(ids) else None, id_offsets.ctypes.data, unit, out_width,
+                                     spans.ctypes.data if n_ids else None, st.ctypes.data)
+        if rc != OK and not (rc == E_UNSUPPORTED and (st[:n] == DOC_SPAN_MISMATCH).any()):
+            raise_for(rc)
+        return spans, st[:n], rc
 
     def profile(self, enable):
         load().hutk_debug_profile(self._h, 1 if enable else 0)

@@ -117,6 +117,12 @@ struct hutk_ctx {
     DevBuf<int64_t> ds_offs, ds_oo;
     DevBuf<uint8_t> ds_bytes;
     DevBuf<int32_t> w_err;
+    // token spans: the rank / select structure over the batch's character starts, staging of the host-buffer form
+    DevBuf<uint64_t> sp_bits;
+    DevBuf<uint32_t> sp_in_chunk;
+    DevBuf<int64_t> sp_chunk, sp_sel, ss_spans;
+    DevBuf<int32_t> sp_ok;
+    uint32_t dec_max_len = 0;  // the longest decoded token, in bytes
 
     // staging for the host-buffer entry point
     DevBuf<uint8_t> s_bytes;
@@ -304,8 +310,10 @@ int upload_tables(hutk_ctx* c) {
     {
         const size_t N = (size_t)T.dec_n;
         std::vector<uint2> ent(N ? N : 1), sent;
+        c->dec_max_len = 0;
         auto pack = [&](uint32_t off, uint32_t len, bool bad) {
             if (bad) return make_uint2(DEC_TAG_BAD, 0u);
+            if (len > c->dec_max_len) c->dec_max_len = len;
             if (len > DEC_INLINE_MAX) return make_uint2(DEC_TAG_LONG | (len << 8), off);
             uint64_t v = len;
             for (uint32_t j = 0; j < len; j++) v |= (uint64_t)T.dec_blob[off + j] << (8 * (j + 1));
@@ -418,6 +426,8 @@ void destroy(hutk_ctx* c) {
         c->d_dec_ent.release(); c->d_dec_sent.release(); c->d_dec_blob.release(); c->dw_first.release();
         c->dw_state.release(); c->dw_tfd.release(); c->ds_ids.release(); c->ds_status.release();
         c->ds_offs.release(); c->ds_oo.release(); c->ds_bytes.release(); c->w_err.release();
+        c->sp_bits.release(); c->sp_in_chunk.release(); c->sp_chunk.release(); c->sp_sel.release(); c->ss_spans.release();
+        c->sp_ok.release();
         c->s_bytes.release(); c->s_offsets.release(); c->s_out_offsets.release(); c->s_ids.release();
         c->s_status.release(); c->s_small_in.release(); c->s_small_out.release();
         if (c->small_host) (void)hipHostFree(c->small_host);
@@ -1253,6 +1263,142 @@ int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets
             return set_err(err, "a token cannot be decoded on its own (id without a unique key, or a token that ends "
                                 "inside a special value or a character)");
         case HUTK_E_CAPACITY: return set_err(err, "bytes_cap too small");
+        default: return set_err(err, "device-side failure");
+    }
+}
+
+int hutk_token_spans_device(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                            const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_ids, int unit, int out_width,
+                            void* d_spans, int32_t* d_status, int32_t* d_err, void* hip_stream) {
+    if (!c) return set_err(HUTK_E_ARG, "ctx is NULL");
+    if (c->host_only) return set_err(HUTK_E_DEVICE, "host-only context: no device to compute spans on");
+    if (n_docs < 0 || n_bytes < 0 || n_ids < 0 || n_docs > INT32_MAX - 1 || (out_width != 4 && out_width != 8) ||
+        (unit != HUTK_SPANS_BYTES && unit != HUTK_SPANS_CHARS))
+        return set_err(HUTK_E_ARG, "hutk_token_spans_device: bad arguments");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    // contexts whose tokens do not tile the document, or whose items are not what the span kernels assume
+    if (!c->pattern.empty())
+        return set_err(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a regex pattern drops the text between its matches; "
+                                           "the tokens do not tile the document");
+    if (c->tab.has_multi)
+        return set_err(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a special-character replacement of several units");
+    if (!c->tab.is_byte_encoder)
+        for (int b = 0x80; b < 256; b++)
+            if (c->tab.item_direct[b])
+                return set_err(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a special-character entry for a byte >= 0x80 "
+                                                   "without is_byte_encoder");
+    // k_sp_tiles adds a tile's units up in 32 bits
+    if ((uint64_t)c->dec_max_len * (uint64_t)span_tile_ids() > 0xFFFFFFFFull)
+        return set_err(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a token of this vocabulary is too long");
+    if (n_docs == 0) {
+        if (n_ids != 0) return set_err(HUTK_E_ARG, "hutk_token_spans_device: ids without documents");
+        HIP_TRY(hipSetDevice(c->device));
+        if (d_err) HIP_TRY(hipMemsetAsync(d_err, 0, 4, hip_stream ? (hipStream_t)hip_stream : c->stream));
+        return HUTK_OK;
+    }
+    // (documents without ids: the offsets are still checked, nothing else is read or written)
+    if (!d_offsets || !d_id_offsets || (n_ids > 0 && (!d_ids || !d_spans)) || (n_bytes > 0 && !d_bytes))
+        return set_err(HUTK_E_ARG, "hutk_token_spans_device: a buffer is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int64_t tile = span_tile_ids();
+    const int64_t n_tiles = (n_ids + tile - 1) / tile;
+    const int64_t n_chunks = n_bytes / SPAN_CHUNK_BYTES + 1;
+    if (n_tiles > 0x7FFFFFFFll || n_chunks > 0x7FFFFFFFll / 256) return set_err(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: the batch is too large for one launch");
+    const bool byte_mode = c->tab.is_byte_encoder;
+    const bool sel_wide = n_bytes > 0xFFFFFFFFll;
+    // HUTK_SPANS_SELECT=search: no scattered select array; select searches the rank structure (the slower form)
+    const char* sel_form = getenv("HUTK_SPANS_SELECT");
+    const bool scatter = !byte_mode && n_ids > 0 && !(sel_form && strcmp(sel_form, "search") == 0);
+    HIP_TRY(c->dw_first.reserve((size_t)(n_ids / 32 + 4)));
+    HIP_TRY(c->dw_state.reserve((size_t)n_tiles + 8));
+    HIP_TRY(c->dw_tfd.reserve((size_t)n_tiles + 1));
+    HIP_TRY(c->w_err.reserve(1));
+    HIP_TRY(c->sp_ok.reserve(4));
+    HIP_TRY(c->sp_bits.reserve((size_t)n_chunks * 256));
+    HIP_TRY(c->sp_in_chunk.reserve((size_t)n_chunks * 256));
+    HIP_TRY(c->sp_chunk.reserve((size_t)n_chunks + 1));
+    if (scatter) HIP_TRY(c->sp_sel.reserve(sel_wide ? (size_t)n_bytes + 1 : (size_t)n_bytes / 2 + 1));
+    if (c->busy_valid) HIP_TRY(hipStreamWaitEvent(s, c->ev_busy, 0));
+    struct BusyMark {
+        hutk_ctx* c; hipStream_t s;
+        ~BusyMark() { if (hipEventRecord(c->ev_busy, s) == hipSuccess) c->busy_valid = true; }
+    } busy_mark{c, s};
+    SpanArgs A{};
+    A.bytes = d_bytes;
+    A.doc_offs = d_offsets;
+    A.n_docs = n_docs;
+    A.n_bytes = n_bytes;
+    A.ids = d_ids;
+    A.id_offs = d_id_offsets;
+    A.n_ids = n_ids;
+    A.n_tiles = n_tiles;
+    A.chars = unit == HUTK_SPANS_CHARS;
+    A.byte_mode = byte_mode;
+    A.out = d_spans;
+    A.status = d_status;
+    A.err = d_err ? d_err : c->w_err.p;
+    A.ok = c->sp_ok.p;
+    A.first_bits = c->dw_first.p;
+    A.tile_state = c->dw_state.p;
+    A.tile_first_doc = c->dw_tfd.p;
+    A.rk_bits = c->sp_bits.p;
+    A.rk_in_chunk = c->sp_in_chunk.p;
+    A.rk_chunk = c->sp_chunk.p;
+    A.n_chunks = n_chunks;
+    A.sel = scatter ? c->sp_sel.p : nullptr;
+    A.sel_wide = sel_wide;
+    A.help_after = getenv("HUTK_SPANS_HELP_AFTER") ? (uint32_t)atol(getenv("HUTK_SPANS_HELP_AFTER")) : (1u << 14);  // (0: tests of the fallback)
+    HIP_TRY(hipMemsetAsync(A.err, 0, 4, s));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A.ok, 1, 1, s));
+    HIP_TRY(hipMemsetAsync(A.first_bits, 0, (size_t)(n_ids / 32 + 4) * 4, s));
+    if (n_tiles) HIP_TRY(hipMemsetAsync(A.tile_state, 0, (size_t)n_tiles * 8, s));
+    if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n_docs * 4, s));
+    launch_spans(c->dec, A, out_width, s);
+    HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_token_spans(hutk_ctx* c, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, const int32_t* ids,
+                     const int64_t* id_offsets, int unit, int out_width, void* spans, int32_t* status) {
+    if (!c) return set_err(HUTK_E_ARG, "ctx is NULL");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (c->host_only) return set_err(HUTK_E_DEVICE, "host-only context: no device to compute spans on");
+    if (n_docs < 0 || !offsets || !id_offsets || (out_width != 4 && out_width != 8))
+        return set_err(HUTK_E_ARG, "hutk_token_spans: bad arguments");
+    if (offsets[0] < 0 || id_offsets[0] != 0) return set_err(HUTK_E_ARG, "offsets[0] must not be negative, id_offsets[0] must be 0");
+    for (int64_t i = 0; i < n_docs; i++)
+        if (offsets[i + 1] < offsets[i] || id_offsets[i + 1] < id_offsets[i])
+            return set_err(HUTK_E_ARG, "offsets must not decrease");
+    const int64_t n_bytes = offsets[n_docs], n_ids = id_offsets[n_docs];
+    if ((n_bytes > 0 && !bytes) || (n_ids > 0 && (!ids || !spans))) return set_err(HUTK_E_ARG, "hutk_token_spans: a buffer is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIP_TRY(c->s_bytes.reserve((size_t)n_bytes + 16));
+    HIP_TRY(c->s_offsets.reserve((size_t)n_docs + 1));
+    HIP_TRY(c->ds_ids.reserve((size_t)n_ids + 16));
+    HIP_TRY(c->ds_offs.reserve((size_t)n_docs + 1));
+    HIP_TRY(c->ds_status.reserve((size_t)n_docs + 1));
+    HIP_TRY(c->ss_spans.reserve((size_t)n_ids * 2 + 2));
+    HIP_TRY(c->w_err.reserve(1));
+    if (n_bytes) HIP_TRY(hipMemcpyAsync(c->s_bytes.p, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+    if (n_ids) HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->s_offsets.p, offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    int rc = hutk_token_spans_device(c, c->s_bytes.p, c->s_offsets.p, n_docs, n_bytes, c->ds_ids.p, c->ds_offs.p, n_ids, unit,
+                                     out_width, c->ss_spans.p, c->ds_status.p, c->w_err.p, s);
+    if (rc) return rc;
+    int32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
+    if (n_ids) HIP_TRY(hipMemcpyAsync(spans, c->ss_spans.p, (size_t)n_ids * 2 * out_width, hipMemcpyDeviceToHost, s));
+    if (status && n_docs) HIP_TRY(hipMemcpyAsync(status, c->ds_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    switch (err) {
+        case HUTK_OK: return HUTK_OK;
+        case HUTK_E_ARG: return set_err(err, "offsets that do not describe the buffers, or a document of 2^31 bytes or more with 32-bit spans");
+        case HUTK_E_UNSUPPORTED:
+            return set_err(err, "the source text does not hold a token's decoded bytes where its span lies (see status: "
+                                "HUTK_DOC_SPAN_MISMATCH)");
         default: return set_err(err, "device-side failure");
     }
 }

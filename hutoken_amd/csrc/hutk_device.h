@@ -219,6 +219,40 @@ int64_t dec_tile_ids();
 void launch_dec_mark(const DecArgs& d, hipStream_t s);
 void launch_dec(const DecTables& t, const DecArgs& d, hipStream_t s);
 
+// ---- token spans (hutk_spans.hip): which stretch of its document each id covers ----
+// Rank structure over the batch's character starts (bytes b with (b & 0xC0) != 0x80), built per call: one 64-bit word
+// of start bits per 64 source bytes, the starts before the word inside its chunk of SPAN_CHUNK_BYTES, and the starts
+// before every chunk.  rank(p) = starts in bytes[0, p) = three loads and a population count.  Character mode also
+// gets the scattered form, sel[k] = byte position of the k-th start (sel[number of starts] = n_bytes), unless
+// HUTK_SPANS_SELECT=search asks for select by search over the counts.
+constexpr int SPAN_CHUNK_BYTES = 16384;
+struct SpanArgs {
+    const uint8_t* bytes;
+    const int64_t* doc_offs;     // [n_docs + 1] into bytes
+    int64_t n_docs, n_bytes;
+    const int32_t* ids;
+    const int64_t* id_offs;      // [n_docs + 1] into ids
+    int64_t n_ids, n_tiles;
+    int32_t chars;               // unit of the output: 0 bytes, 1 characters
+    int32_t byte_mode;           // is_byte_encoder
+    void* out;                   // [n_ids][2] of int32 or int64
+    int32_t* status;             // may be null
+    int32_t* err;
+    int32_t* ok;                 // workspace: cleared by k_sp_check when the offsets do not describe the buffers
+    uint32_t* first_bits;        // [n_ids / 32 + 2] bit i: token i is the first of a document
+    unsigned long long* tile_state;  // [n_tiles] decoupled look-back: flag (2 bits) | units since the last document start
+    int64_t* tile_first_doc;     // [n_tiles] first document whose first token is at or after the tile's
+    uint64_t* rk_bits;           // [n_chunks * 256]
+    uint32_t* rk_in_chunk;       // [n_chunks * 256]
+    int64_t* rk_chunk;           // [n_chunks + 1]; the last entry is the number of starts in the batch
+    int64_t n_chunks;
+    void* sel;                   // character mode: [n_bytes + 1] of uint32 (n_bytes < 2^32) or int64; null: select searches
+    int32_t sel_wide;
+    uint32_t help_after;         // as DecArgs::help_after
+};
+int64_t span_tile_ids();
+void launch_spans(const DecTables& t, const SpanArgs& a, int out_width, hipStream_t s);
+
 // hutk_kernels.hip
 void launch_pre(const BatchArgs& a, const Workspace& w, hipStream_t s);
 void launch_rebase_offsets(const int64_t* in, int64_t* out, int64_t n, hipStream_t s);

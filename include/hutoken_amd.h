@@ -50,8 +50,11 @@ enum {
     HUTK_DOC_INVALID_UTF8 = 2,
     /* decode direction */
     HUTK_DOC_ID_OUT_OF_RANGE = 3, /* an id < 0 or >= the number of vocabulary lines (src/core.c:523-531) */
-    HUTK_DOC_ID_UNDECODABLE = 4   /* an id without a unique key, or a token whose decoding depends on its
+    HUTK_DOC_ID_UNDECODABLE = 4,  /* an id without a unique key, or a token whose decoding depends on its
                                      neighbours (see hutk_decode_batch) */
+    /* token spans */
+    HUTK_DOC_SPAN_MISMATCH = 5    /* the document's text does not hold a token's decoded bytes where the token's
+                                     span lies (see hutk_token_spans_device): its spans are unspecified */
 };
 
 /* Replaces _hutoken.initialize(vocab_file_path, special_file_path, prefix,
@@ -335,6 +338,47 @@ int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_posit
                              int64_t* n_rows, void* hip_stream);
 int64_t hutk_packer_pending(const hutk_packer* p);
 void hutk_packer_destroy(hutk_packer* p);
+
+/* ---- token spans (offset mapping) ----------------------------------------------------------------------
+ * Which stretch of its document each id covers: from the packed text (d_bytes, d_offsets) and the ragged pair that
+ * hutk_encode_batch_device wrote for it (d_ids, d_id_offsets; n_ids as in the collation calls: d_id_offsets[n_docs] ==
+ * n_ids) to d_spans[n_ids][2] = {start, end}, half open, relative to the document's first byte; out_width 4 or 8: int32
+ * or int64.  The reference has no counterpart.  An ITEM is what the pretokenizer consumes in one step
+ * (src/pretokenizer.c:102-168): a byte with is_byte_encoder, otherwise a UTF-8 character whose length its lead byte
+ * gives, cut short at the document's end.  Every id covers a whole number of consecutive items and the ids of a
+ * document tile its encoded part from byte 0 on: a known id covers the items of its decoded text (what
+ * hutk_decode_batch writes for it; for a document's first token the prefix-stripped form, so the tokens of a prefix that
+ * was encoded as a word of its own get the empty span {0, 0}), an id of -1 (a unit the vocabulary does not hold,
+ * core.c:205-207) covers the ONE item at the cursor.  A document cut at an over-long word has spans for the ids it has.
+ *   unit  HUTK_SPANS_BYTES  start and end in bytes
+ *         HUTK_SPANS_CHARS  in characters; a character starts at every byte b with (b & 0xC0) != 0x80.  end = the number
+ *                           of character starts in doc[0, byte end); start of a non-empty span = the index of the
+ *                           character that holds byte `byte start` (two byte-level tokens that split one character
+ *                           both report it); an empty span is {c, c}, c = the character starts in front of it.
+ * Nothing is taken on trust: the decoded bytes of every known id are compared with the source bytes of its span (and
+ * the length of every -1 item with the pretokenizer's rule).  A difference -- ids that are not this text's, a special
+ * value that equals an ordinary character, an id that cannot be decoded on its own -- sets status[doc] =
+ * HUTK_DOC_SPAN_MISMATCH and *d_err = HUTK_E_UNSUPPORTED; that document's spans are then unspecified, every write stays
+ * inside d_spans and the other documents are exact.
+ * Refused at the call with HUTK_E_UNSUPPORTED: a context with a regex pattern (the text between matches is dropped),
+ * a special-character replacement of several units, a special-character entry for a byte >= 0x80 without
+ * is_byte_encoder.  Offsets that do not describe the buffers (negative, decreasing, beyond n_bytes or n_ids,
+ * d_id_offsets[0] != 0, d_id_offsets[n_docs] != n_ids), or a document of 2^31 bytes or more with out_width 4: *d_err =
+ * HUTK_E_ARG, nothing is read out of bounds, d_spans is not written.  n_docs == 0 or n_ids == 0 writes no span and
+ * succeeds (with documents and no ids the offsets are still checked; d_ids and d_spans may then be NULL).  d_spans
+ * need only be aligned to its element; 16-byte alignment gets 16-byte stores.  Also HUTK_E_UNSUPPORTED at the call: a
+ * vocabulary with a token of 2 MiB or more.  Asynchronous on hip_stream (NULL: the context's stream), never synchronises once the context's workspace
+ * has grown to the batch's size; serialised with the other calls on the context; runs on the context's first device.
+ * d_status int32[n_docs] and d_err int32[1] may be NULL; both are cleared by the call.
+ * hutk_token_spans: the same from host buffers (copies, calls the device form, waits); returns what *d_err held.
+ * There is no CPU fallback. */
+#define HUTK_SPANS_BYTES 0
+#define HUTK_SPANS_CHARS 1
+int hutk_token_spans_device(hutk_ctx* ctx, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                            int64_t n_bytes, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_ids, int unit,
+                            int out_width, void* d_spans, int32_t* d_status, int32_t* d_err, void* hip_stream);
+int hutk_token_spans(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, const int32_t* ids,
+                     const int64_t* id_offsets, int unit, int out_width, void* spans, int32_t* status);
 
 #ifdef __cplusplus
 }

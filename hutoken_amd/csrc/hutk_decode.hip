@@ -67,6 +67,13 @@ __device__ __forceinline__ uint32_t dec_wave_incl(uint32_t v) {
 constexpr unsigned long long DEC_ST_MASK = 3ull << 62, DEC_ST_TOTAL = 1ull << 62, DEC_ST_PREFIX = 2ull << 62;
 constexpr int DEC_LOOK = 1;  // look-back window = 64 * DEC_LOOK tiles per round trip (4: measured 9 % slower)
 constexpr int DEC_LDS_BYTES = 3 * 1024 * DEC_PER_THREAD;  // text of one tile staged for coalesced stores (mean a third of it)
+// Bytes of the tile before each of its tokens (what out_offsets are made of) are kept as 16-bit positions while the
+// tile's text is below 64 KiB.  A tile of longer text (a mean of 32 bytes per token: run tokens of a real GPT-2
+// vocabulary) is never staged, so its 32-bit positions go where the staged text would have been.  32-bit positions
+// of their own would be 4 KiB more: 32.7 KiB per workgroup, and five workgroups no longer fit a CU's 160 KiB of LDS.
+constexpr uint32_t DEC_PREF16_MAX = 0xFFFFu;
+static_assert(DEC_LDS_BYTES <= (int)DEC_PREF16_MAX, "a staged tile has 16-bit positions");
+static_assert(DEC_LDS_BYTES + 16 >= DEC_TILE * 4, "the 32-bit positions of an unstaged tile fit the staging area");
 
 // token i of the batch: its table entry (see DecTables); errors are reported here and leave an empty token
 __device__ __forceinline__ uint2 dec_entry(const DecTables& T, const DecArgs& D, int64_t i, int32_t id, bool first) {
@@ -101,8 +108,9 @@ __device__ __forceinline__ uint64_t dec_tile_total(const DecTables& T, const Dec
 template <bool WRITE>
 __global__ __launch_bounds__(DEC_THREADS) __attribute__((amdgpu_waves_per_eu(5))) void k_dec_tiles(DecTables T, DecArgs D) {  // (96 VGPRs: with the look-back's fallback inlined the compiler takes 98 and loses a wavefront per SIMD)
     __shared__ uint32_t s_part[DEC_THREADS / 64];
-    __shared__ uint16_t s_pref[DEC_TILE];  // bytes of the tile before each of its tokens
-    __shared__ __attribute__((aligned(16))) uint8_t s_text[WRITE ? DEC_LDS_BYTES + 16 : 16];
+    __shared__ uint16_t s_pref[WRITE ? DEC_TILE : 1];  // bytes of the tile before each of its tokens, tile text <= DEC_PREF16_MAX
+    __shared__ __attribute__((aligned(16))) uint8_t s_text[WRITE ? DEC_LDS_BYTES + 16 : DEC_TILE * 4];  // or s_pref32
+    uint32_t* const s_pref32 = reinterpret_cast<uint32_t*>(s_text);  // the same for a longer text, and without WRITE
     const int tid = threadIdx.x;
     const int64_t tile = blockIdx.x;
     const int64_t i0 = tile * DEC_TILE + (int64_t)tid * DEC_PER_THREAD;
@@ -161,7 +169,15 @@ __global__ __launch_bounds__(DEC_THREADS) __attribute__((amdgpu_waves_per_eu(5))
                            __HIP_MEMORY_SCOPE_AGENT);
     // While the predecessors get there: bytes before each token of the tile, and the tile's text staged in LDS
     // from index 0 (its alignment in the output is not known yet).
-    {
+    const bool wide = !WRITE || total > DEC_PREF16_MAX;  // (the same for the whole workgroup)
+    if (wide) {
+        uint32_t pos = before;
+#pragma unroll
+        for (int k = 0; k < DEC_PER_THREAD; k++) {
+            s_pref32[tid * DEC_PER_THREAD + k] = pos;
+            pos += len[k];
+        }
+    } else {
         uint32_t pos = before;
 #pragma unroll
         for (int k = 0; k < DEC_PER_THREAD; k++) {
@@ -170,7 +186,7 @@ __global__ __launch_bounds__(DEC_THREADS) __attribute__((amdgpu_waves_per_eu(5))
         }
     }
     const bool write = WRITE && D.bytes_out != nullptr;
-    const bool staged = write && total <= (uint32_t)DEC_LDS_BYTES;  // (always < 65536: s_pref holds 16-bit positions)
+    const bool staged = write && total <= (uint32_t)DEC_LDS_BYTES;  // (never together with `wide`)
     if (staged) {
         // short tokens (almost all) carry their bytes in the entry; long ones are copied from the blob
         // (OR-ing shifted dwords into a zeroed area with LDS atomics instead of plain stores: measured 5 % slower)
@@ -266,7 +282,7 @@ __global__ __launch_bounds__(DEC_THREADS) __attribute__((amdgpu_waves_per_eu(5))
         for (int64_t d = D.tile_first_doc[tile] + tid; d < D.n_docs; d += DEC_THREADS) {
             const int64_t i = D.id_offsets[d];
             if (i >= t1 || i >= D.n_ids) break;
-            D.out_offsets[d] = g0 + s_pref[i - t0];
+            D.out_offsets[d] = g0 + (wide ? s_pref32[i - t0] : (uint32_t)s_pref[i - t0]);
         }
     }
     if (!write) return;
@@ -276,9 +292,9 @@ __global__ __launch_bounds__(DEC_THREADS) __attribute__((amdgpu_waves_per_eu(5))
     }
     if (staged) {
         // 16-byte aligned stores: chunk c of the output holds text bytes [c - shift, c - shift + 16), read from
-        // LDS as five dwords and realigned
-        const uint32_t shift = (uint32_t)(g0 & 15);
-        uint8_t* gbase = D.bytes_out + (g0 - shift);  // 16-byte aligned
+        // LDS as five dwords and realigned.  Chunks are those of the ADDRESS, so bytes_out itself may start anywhere.
+        const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(D.bytes_out + g0) & 15);
+        uint8_t* gbase = D.bytes_out + g0 - shift;  // 16-byte aligned
         const uint32_t end = total + shift;
         const uint32_t* text32 = reinterpret_cast<const uint32_t*>(s_text);
         for (uint32_t c = (uint32_t)tid * 16; c < end; c += DEC_THREADS * 16) {

@@ -188,7 +188,15 @@ int hutk_encode(hutk_ctx* ctx, const uint8_t* text, int64_t len, int32_t* ids_ou
  * on the next token).  status[] names the documents. */
 int hutk_decode_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
                       uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
-/* The same on device-resident buffers, asynchronously on `hip_stream`; *d_err receives the error code. */
+/* The same on device-resident buffers, asynchronously on `hip_stream`; *d_err receives the error code
+ * (HUTK_E_VALUE, HUTK_E_UNSUPPORTED, or HUTK_E_CAPACITY when the text does not fit bytes_cap: nothing is written at or
+ * beyond d_bytes_out + bytes_cap, out_offsets and status are complete all the same), d_status[] (may be NULL) the
+ * documents with a bad id.  A bad id contributes no bytes; the other tokens and documents are decoded as ever.
+ * Alignment: that of the element types is enough.  d_bytes_out may start at ANY byte address (the 16-byte stores are
+ * aligned on the address written to, the bytes around the output are left alone); d_ids needs 4 bytes (16 take the
+ * faster loads).  d_ids may be NULL when n_ids == 0, d_bytes_out == NULL asks for out_offsets and status only.
+ * Token length: every decoded length the loader accepts (vocabulary keys of up to 2047 bytes) is decoded exactly,
+ * whatever a tile of 2048 tokens adds up to. */
 int hutk_decode_batch_device(hutk_ctx* ctx, const int32_t* d_ids, const int64_t* d_id_offsets,
                              int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap,
                              int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err, void* hip_stream);

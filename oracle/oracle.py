@@ -167,7 +167,7 @@ class Oracle:
         p = C.POINTER(C.c_uint8)()
         n = C.c_size_t(0)
         st = L.hto_decode(self._h, arr.ctypes.data, len(arr), C.byref(p), C.byref(n))
-        out = bytes(bytearray(p[i] for i in range(n.value))) if st == 0 else b""
+        out = C.string_at(p, n.value) if st == 0 else b""
         if st == 0:
             L.hto_free(p)
         return out, st

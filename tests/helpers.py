@@ -226,3 +226,41 @@ def giant_word_docs():
         return b"".join(parts)[:n]
     docs = [b"a " + blob(1100) + b" b", blob(5000), b"x " + blob(30000), blob(2047) + b" " + blob(1025)]
     return docs, b"q " + blob(262143)
+
+
+LONG_BYTE_RUNS = list(range(13, 41)) + [48, 63, 64, 65, 100, 127, 128, 129, 200, 255, 256, 257, 300]
+LONG_CHAR_RUNS = [5, 11, 12, 13, 20, 21, 22, 40, 64, 100]
+
+
+def long_token_byte_vocab(seed):
+    """random_byte_vocab(seed, n_merges=300) plus run tokens of 13 .. 300 characters ("-", " ", "é" and "abab.." runs;
+    an "é" run is twice as many bytes): what the decode direction meets in a real GPT-2 vocabulary and the small
+    builders never make.  -> (entries, special mapping, raw token bytes by id); the added ids are 556 and up."""
+    entries, special = random_byte_vocab(seed, n_merges=300)
+    t = vf.bytes_to_unicode()
+    back = {c: b for b, c in t.items()}
+    raw = [bytes(back[c] for c in key.decode("utf-8")) for key, _i in entries]
+    seen = set(raw)
+    for k in LONG_BYTE_RUNS:
+        for tok in (b"-" * k, b" " * k, ("é" * k).encode("utf-8"), (b"ab" * k)[:k]):
+            assert tok not in seen
+            seen.add(tok)
+            entries.append((vf.encode_visible(tok, t), len(raw)))
+            raw.append(tok)
+    return entries, special, raw
+
+
+def long_token_char_vocab(seed):
+    """random_char_vocab(seed, n_merges=300) plus run tokens of 5 .. 100 characters (prefix runs, "a" runs, three-byte
+    "漢" runs, the prefix and an "e" run).  -> (entries, special mapping, token strings by id)."""
+    entries, special = random_char_vocab(seed, n_merges=300)
+    toks = [key.decode("utf-8") for key, _i in entries]
+    seen = set(toks)
+    for k in LONG_CHAR_RUNS:
+        for tok in ("▁" * k, "a" * k, "漢" * k, "▁" + "e" * k):
+            if tok in seen:  # (a five-character run the merges happened to make already)
+                continue
+            seen.add(tok)
+            entries.append((tok.encode("utf-8"), len(toks)))
+            toks.append(tok)
+    return entries, special, toks

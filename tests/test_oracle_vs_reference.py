@@ -184,6 +184,27 @@ def test_decode_direction(tmp_path, oracle_mod, reference):
             _same_decode(orc, r, [rng.randrange(0, len(ents)) for _ in range(rng.randint(0, 10))])
 
 
+def test_decode_long_tokens(tmp_path, oracle_mod, reference):
+    """Tokens of 13 .. 300 characters (helpers.long_token_*_vocab; the small builders stop at 12 bytes): each added id
+    alone (at the front of a document: the prefix stripped), behind another token, and random lists."""
+    for kind in ("byte", "char"):
+        if kind == "byte":
+            ents, sp, toks = H.long_token_byte_vocab(1)
+            prefix, is_byte, first_added = None, True, 556
+        else:
+            ents, sp, toks = H.long_token_char_vocab(1)
+            prefix, is_byte, first_added = "▁", False, len(toks) - 4 * len(H.LONG_CHAR_RUNS)
+        vp, spath = H.write_vocab(tmp_path, "long" + kind, ents, sp)
+        orc = oracle_mod.Oracle(vp, spath, prefix, is_byte)
+        r = reference(vp, spath, prefix, is_byte)
+        rng = random.Random(len(ents))
+        for i in range(first_added, len(ents)):
+            _same_decode(orc, r, [i])
+            _same_decode(orc, r, [rng.randrange(0, len(ents)), i])
+        for _ in range(300):
+            _same_decode(orc, r, [rng.randrange(0, len(ents)) for _ in range(rng.randint(0, 10))])
+
+
 def test_batch_threads_and_word_too_large(tmp_path, oracle_mod, reference):
     ents, sp = H.random_byte_vocab(9, n_merges=100)
     vp, spath = H.write_vocab(tmp_path, "t", ents, sp)

@@ -10,6 +10,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--docs", type=int, default=1_000_000)
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--events", action="store_true", help="also time every step with device events: step_ms, step_ms_median")
 args = ap.parse_args()
 vp, sp, kw = data.vocab_files("VG")
 ctx = _capi.Context(vp, sp, kw["prefix"], kw["is_byte_encoder"])
@@ -38,14 +39,21 @@ for _ in range(args.warmup):
 torch.cuda.synchronize()
 assert int(err.item()) == 0
 assert torch.equal(text[: len(d)], db) and torch.equal(boff, do), "decode(encode(text)) != text"
+ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps if args.events else 0)]
 t = time.perf_counter()
-for _ in range(args.steps):
+for k in range(args.steps):
+    if ev:
+        ev[k][0].record()
     step()
+    if ev:
+        ev[k][1].record()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t) / args.steps
+step_ms = sorted(round(a.elapsed_time(b), 4) for a, b in ev)
 b_alg = 4 * n_ids + 8 * (args.docs + 1) + len(d) + 8 * (args.docs + 1)
 print(json.dumps({"metric": "GB/s of text decoded (GPT-2-shaped vocab), bit-exact round trip", "value": round(len(d) / dt / 1e9, 2),
                   "unit": "GB/s", "ms_per_step": round(dt * 1e3, 4), "n_gpus": 1, "steps": args.steps,
+                  **({"step_ms_median": step_ms[len(step_ms) // 2], "step_ms_min": step_ms[0], "step_ms_max": step_ms[-1]} if ev else {}),
                   "config": {"workload": f"C3 {args.docs} docs, {len(d)/1e6:.1f} MB of text, {n_ids} ids, device-resident"},
                   "roofline": {"bound": "hbm", "achieved": round(b_alg / dt / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                                "frac": round(b_alg / dt / 8e12, 4), "algorithmic_bytes": b_alg,

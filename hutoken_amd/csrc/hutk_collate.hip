@@ -13,7 +13,7 @@
 #include <mutex>
 #include <string>
 
-#include "hutk_internal.h"
+#include "hutk_host.h"
 
 namespace {
 
@@ -22,14 +22,6 @@ constexpr int SPAN = 2048;       // packed: stream positions per workgroup (8 pe
 constexpr int PER = SPAN / TB;   // packed: positions a thread scans
 constexpr int PAD_TILE = 4096;   // padded: output elements per workgroup
 constexpr int PAD_ROWS = 256;    // padded: most rows per workgroup
-
-#define CL_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess)                                                                              \
-            return hutk::api_set_error(HUTK_E_DEVICE, std::string("HIP error: ") + hipGetErrorString(e__) + \
-                                                          " at " #expr);                                    \
-    } while (0)
 
 __device__ __forceinline__ void note_error(int32_t* err, int code) {
     if (err) atomicCAS(err, 0, code);
@@ -447,7 +439,7 @@ int hutk_collate_padded_device(const int32_t* d_ids, const int64_t* d_offsets, i
     if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_padded_device: the batch is too large for one launch");
     const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4);
     hipStream_t st = (hipStream_t)hip_stream;
-    if (d_err) CL_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
     const dim3 grid((unsigned)blocks), block(TB);
     if (out_width == 4) {
         if (vec) hipLaunchKernelGGL((k_collate_padded<4, true>), grid, block, 0, st, a);
@@ -456,7 +448,7 @@ int hutk_collate_padded_device(const int32_t* d_ids, const int64_t* d_offsets, i
         if (vec) hipLaunchKernelGGL((k_collate_padded<8, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_collate_padded<8, false>), grid, block, 0, st, a);
     }
-    CL_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }
 
@@ -469,9 +461,9 @@ int hutk_packer_create(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no HIP device");
-    if (device < 0) CL_TRY(hipGetDevice(&device));
+    if (device < 0) HUTK_HIP_TRY(hipGetDevice(&device));
     if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no such device");
-    CL_TRY(hipSetDevice(device));
+    HUTK_HIP_TRY(hipSetDevice(device));
     hutk_packer* p = new hutk_packer();
     p->device = device;
     p->L = seq_len;
@@ -511,8 +503,8 @@ int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* 
     if ((n_docs > 0 && !d_offsets) || (n_ids > 0 && !d_ids) || (rows > 0 && !d_input_ids))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_add_device: a buffer is NULL");
     hipStream_t st = (hipStream_t)hip_stream;
-    CL_TRY(hipSetDevice(p->device));
-    if (d_err) CL_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    HUTK_HIP_TRY(hipSetDevice(p->device));
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
     if (n_rows) *n_rows = rows;
     if (n_docs == 0) return HUTK_OK;  // nothing joins the stream (n_ids must then be 0)
     const int64_t rows_all = rows + (total > rows * p->L);
@@ -552,7 +544,7 @@ int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* 
     }
     if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_packer_add_device: the batch is too large for one launch");
     if (blocks > 0) {
-        if (p->ev_recorded) CL_TRY(hipStreamWaitEvent(st, p->ev, 0));
+        if (p->ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, p->ev, 0));
         const bool vec = p->L % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_position_ids, 16) &&
                          aligned_to(d_segment_ids, 16);
         const dim3 grid((unsigned)blocks), block(TB);
@@ -563,8 +555,8 @@ int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* 
             if (vec) hipLaunchKernelGGL((k_collate_packed<8, true>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((k_collate_packed<8, false>), grid, block, 0, st, a);
         }
-        CL_TRY(hipGetLastError());
-        CL_TRY(hipEventRecord(p->ev, st));
+        HUTK_HIP_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipEventRecord(p->ev, st));
         p->ev_recorded = true;
         p->cur ^= 1;
     }
@@ -582,8 +574,8 @@ int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_posit
     }
     if (!d_input_ids) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_flush_device: d_input_ids is NULL");
     hipStream_t st = (hipStream_t)hip_stream;
-    CL_TRY(hipSetDevice(p->device));
-    if (p->ev_recorded) CL_TRY(hipStreamWaitEvent(st, p->ev, 0));
+    HUTK_HIP_TRY(hipSetDevice(p->device));
+    if (p->ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, p->ev, 0));
     int64_t blocks = (p->L + TB - 1) / TB;
     if (blocks > 4096) blocks = 4096;
     const dim3 grid((unsigned)blocks), block(TB);
@@ -593,8 +585,8 @@ int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_posit
     else
         hipLaunchKernelGGL((k_collate_flush<8>), grid, block, 0, st, p->half(p->cur, 0), p->half(p->cur, 1),
                            p->half(p->cur, 2), p->pending, p->L, p->pad, d_input_ids, d_position_ids, d_segment_ids);
-    CL_TRY(hipGetLastError());
-    CL_TRY(hipEventRecord(p->ev, st));
+    HUTK_HIP_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipEventRecord(p->ev, st));
     p->ev_recorded = true;
     p->pending = 0;
     if (n_rows) *n_rows = 1;

@@ -13,9 +13,14 @@
 //                 decoupled look-back over the earlier tiles' totals, the text staged in LDS and stored in
 //                 16-byte chunks, out_offsets of the documents that start in the tile
 //   k_dec_tail    out_offsets of the (empty) documents at the very end
+//
+// The direction's C entry points are at the end of the file: hutk_decode_batch_device (device buffers, asynchronous) and
+// hutk_decode_batch (host buffers, staged through the context's).
 #include <hip/hip_runtime.h>
 
-#include "hutk_device.h"
+#include <cstdlib>
+
+#include "hutk_host.h"
 
 namespace hutk {
 
@@ -350,3 +355,90 @@ void launch_dec(const DecTables& t, const DecArgs& d, hipStream_t s) {
 }
 
 }  // namespace hutk
+
+using namespace hutk;
+
+extern "C" {
+
+int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
+                             int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
+                             int32_t* d_status, int32_t* d_err, void* hip_stream) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
+    if (n_docs < 0 || n_ids < 0 || !d_id_offsets || !d_out_offsets || (n_ids > 0 && !d_ids))
+        return api_set_error(HUTK_E_ARG, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    StreamScope scope(c, hip_stream);
+    if (scope.rc) return scope.rc;
+    hipStream_t s = scope.s;
+    const int64_t tile = dec_tile_ids();
+    const int64_t n_tiles = (n_ids + tile - 1) / tile;
+    if (n_tiles > 0x7FFFFFFFll) return api_set_error(HUTK_E_ARG, "batch too large");
+    HUTK_HIP_TRY(c->dw_first.reserve((size_t)(n_ids / 32 + 4)));
+    HUTK_HIP_TRY(c->dw_state.reserve((size_t)n_tiles + 8));
+    HUTK_HIP_TRY(c->dw_tfd.reserve((size_t)n_tiles + 1));
+    HUTK_HIP_TRY(c->w_err.reserve(1));
+    DecArgs D{};
+    D.ids = d_ids;
+    D.id_offsets = d_id_offsets;
+    D.n_docs = n_docs;
+    D.n_ids = n_ids;
+    D.n_tiles = n_tiles;
+    D.bytes_out = d_bytes_out;
+    D.bytes_cap = bytes_cap;
+    D.out_offsets = d_out_offsets;
+    D.status = d_status;
+    D.err = d_err ? d_err : c->w_err.p;
+    D.first_bits = c->dw_first.p;
+    D.tile_state = c->dw_state.p;
+    D.tile_first_doc = c->dw_tfd.p;
+    D.help_after = getenv("HUTK_DEC_HELP_AFTER") ? (uint32_t)atol(getenv("HUTK_DEC_HELP_AFTER")) : (1u << 14);  // (0: tests of the fallback)
+    HUTK_HIP_TRY(hipMemsetAsync(D.err, 0, 4, s));
+    const bool strip = c->dec.sent != nullptr;  // the first-token bitmap is only needed to strip a prefix
+    if (strip) HUTK_HIP_TRY(hipMemsetAsync(D.first_bits, 0, (size_t)(n_ids / 32 + 4) * 4, s));
+    else D.first_bits = nullptr;
+    if (d_status && n_docs) HUTK_HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n_docs * 4, s));
+    if (n_tiles == 0) {
+        HUTK_HIP_TRY(hipMemsetAsync(d_out_offsets, 0, (size_t)(n_docs + 1) * 8, s));
+        return HUTK_OK;
+    }
+    if (strip) launch_dec_mark(D, s);
+    HUTK_HIP_TRY(hipMemsetAsync(D.tile_state, 0, (size_t)n_tiles * 8, s));
+    launch_dec(c->dec, D, s);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* bytes_out,
+                      int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
+    if (n_docs < 0 || !id_offsets || !out_offsets) return api_set_error(HUTK_E_ARG, "bad argument");
+    if (int rc = check_offsets(id_offsets, n_docs, true, "id_offsets")) return rc;
+    const int64_t n_ids = id_offsets[n_docs];
+    if (n_ids > 0 && !ids) return api_set_error(HUTK_E_ARG, "bad argument");
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HUTK_HIP_TRY(c->ds_ids.reserve((size_t)n_ids + 16));
+    HUTK_HIP_TRY(c->ds_offs.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ds_oo.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ds_status.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->w_err.reserve(1));
+    if (bytes_out && bytes_cap > 0) HUTK_HIP_TRY(c->ds_bytes.reserve((size_t)bytes_cap + 16));
+    if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    int rc = hutk_decode_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, bytes_out ? c->ds_bytes.p : nullptr,
+                                      bytes_cap, c->ds_oo.p, c->ds_status.p, c->w_err.p, s);
+    if (rc) return rc;
+    int32_t err = 0;
+    HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->ds_oo.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
+    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->ds_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipStreamSynchronize(s));
+    if (bytes_out && err == HUTK_OK && out_offsets[n_docs] > 0)
+        HUTK_HIP_TRY(hipMemcpy(bytes_out, c->ds_bytes.p, (size_t)out_offsets[n_docs], hipMemcpyDeviceToHost));
+    return err == HUTK_OK ? HUTK_OK : api_set_error(err, device_error_message(Direction::Decode, err));
+}
+
+}  // extern "C"

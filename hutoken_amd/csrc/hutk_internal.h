@@ -237,7 +237,7 @@ struct LoadError {
 LoadError load_tables(const char* vocab_path, const char* special_path, const char* prefix,
                       bool is_byte_encoder, const char* merges_path, Tables& out);
 
-// hutk_api.cpp: set the message hutk_last_error() returns; returns `code` (used by hutk_train.hip)
+// hutk_api.cpp: set the message hutk_last_error() returns; returns `code` (every file with entry points reports through it)
 int api_set_error(int code, const std::string& msg);
 
 }  // namespace hutk

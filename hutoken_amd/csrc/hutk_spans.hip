@@ -20,9 +20,15 @@
 //   k_sp_tiles    ONE pass over the ids: units per token, segmented workgroup scan, the units since the document's start
 //                 in front of the tile by decoupled look-back (as k_dec_tiles: flag and value in one 64-bit word, relaxed
 //                 agent-scope atomics, and a tile that waits too long adds its predecessor up itself), verify, write
+//
+// The direction's C entry points are at the end of the file: hutk_token_spans_device (device buffers, asynchronous) and
+// hutk_token_spans (host buffers, staged through the context's).
 #include <hip/hip_runtime.h>
 
-#include "hutk_device.h"
+#include <cstdlib>
+#include <cstring>
+
+#include "hutk_host.h"
 
 namespace hutk {
 
@@ -578,3 +584,134 @@ void launch_spans(const DecTables& t, const SpanArgs& a, int out_width, hipStrea
 }
 
 }  // namespace hutk
+
+using namespace hutk;
+
+extern "C" {
+
+int hutk_token_spans_device(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                            const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_ids, int unit, int out_width,
+                            void* d_spans, int32_t* d_status, int32_t* d_err, void* hip_stream) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to compute spans on");
+    if (n_docs < 0 || n_bytes < 0 || n_ids < 0 || n_docs > INT32_MAX - 1 || (out_width != 4 && out_width != 8) ||
+        (unit != HUTK_SPANS_BYTES && unit != HUTK_SPANS_CHARS))
+        return api_set_error(HUTK_E_ARG, "hutk_token_spans_device: bad arguments");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    // contexts whose tokens do not tile the document, or whose items are not what the span kernels assume
+    if (!c->pattern.empty())
+        return api_set_error(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a regex pattern drops the text between its matches; "
+                                           "the tokens do not tile the document");
+    if (c->tab.has_multi)
+        return api_set_error(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a special-character replacement of several units");
+    if (!c->tab.is_byte_encoder)
+        for (int b = 0x80; b < 256; b++)
+            if (c->tab.item_direct[b])
+                return api_set_error(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a special-character entry for a byte >= 0x80 "
+                                                   "without is_byte_encoder");
+    // k_sp_tiles adds a tile's units up in 32 bits
+    if ((uint64_t)c->dec_max_len * (uint64_t)span_tile_ids() > 0xFFFFFFFFull)
+        return api_set_error(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: a token of this vocabulary is too long");
+    if (n_docs == 0) {
+        if (n_ids != 0) return api_set_error(HUTK_E_ARG, "hutk_token_spans_device: ids without documents");
+        HUTK_HIP_TRY(hipSetDevice(c->device));
+        if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, 4, hip_stream ? (hipStream_t)hip_stream : c->stream));
+        return HUTK_OK;
+    }
+    // (documents without ids: the offsets are still checked, nothing else is read or written)
+    if (!d_offsets || !d_id_offsets || (n_ids > 0 && (!d_ids || !d_spans)) || (n_bytes > 0 && !d_bytes))
+        return api_set_error(HUTK_E_ARG, "hutk_token_spans_device: a buffer is NULL");
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    const int64_t tile = span_tile_ids();
+    const int64_t n_tiles = (n_ids + tile - 1) / tile;
+    const int64_t n_chunks = n_bytes / SPAN_CHUNK_BYTES + 1;
+    if (n_tiles > 0x7FFFFFFFll || n_chunks > 0x7FFFFFFFll / 256) return api_set_error(HUTK_E_UNSUPPORTED, "hutk_token_spans_device: the batch is too large for one launch");
+    const bool byte_mode = c->tab.is_byte_encoder;
+    const bool sel_wide = n_bytes > 0xFFFFFFFFll;
+    // HUTK_SPANS_SELECT=search: no scattered select array; select searches the rank structure (the slower form)
+    const char* sel_form = getenv("HUTK_SPANS_SELECT");
+    const bool scatter = !byte_mode && n_ids > 0 && !(sel_form && strcmp(sel_form, "search") == 0);
+    HUTK_HIP_TRY(c->dw_first.reserve((size_t)(n_ids / 32 + 4)));
+    HUTK_HIP_TRY(c->dw_state.reserve((size_t)n_tiles + 8));
+    HUTK_HIP_TRY(c->dw_tfd.reserve((size_t)n_tiles + 1));
+    HUTK_HIP_TRY(c->w_err.reserve(1));
+    HUTK_HIP_TRY(c->sp_ok.reserve(4));
+    HUTK_HIP_TRY(c->sp_bits.reserve((size_t)n_chunks * 256));
+    HUTK_HIP_TRY(c->sp_in_chunk.reserve((size_t)n_chunks * 256));
+    HUTK_HIP_TRY(c->sp_chunk.reserve((size_t)n_chunks + 1));
+    if (scatter) HUTK_HIP_TRY(c->sp_sel.reserve(sel_wide ? (size_t)n_bytes + 1 : (size_t)n_bytes / 2 + 1));
+    StreamScope scope(c, hip_stream, false);  // (the device was selected in front of the allocations)
+    if (scope.rc) return scope.rc;
+    hipStream_t s = scope.s;
+    SpanArgs A{};
+    A.bytes = d_bytes;
+    A.doc_offs = d_offsets;
+    A.n_docs = n_docs;
+    A.n_bytes = n_bytes;
+    A.ids = d_ids;
+    A.id_offs = d_id_offsets;
+    A.n_ids = n_ids;
+    A.n_tiles = n_tiles;
+    A.chars = unit == HUTK_SPANS_CHARS;
+    A.byte_mode = byte_mode;
+    A.out = d_spans;
+    A.status = d_status;
+    A.err = d_err ? d_err : c->w_err.p;
+    A.ok = c->sp_ok.p;
+    A.first_bits = c->dw_first.p;
+    A.tile_state = c->dw_state.p;
+    A.tile_first_doc = c->dw_tfd.p;
+    A.rk_bits = c->sp_bits.p;
+    A.rk_in_chunk = c->sp_in_chunk.p;
+    A.rk_chunk = c->sp_chunk.p;
+    A.n_chunks = n_chunks;
+    A.sel = scatter ? c->sp_sel.p : nullptr;
+    A.sel_wide = sel_wide;
+    A.help_after = getenv("HUTK_SPANS_HELP_AFTER") ? (uint32_t)atol(getenv("HUTK_SPANS_HELP_AFTER")) : (1u << 14);  // (0: tests of the fallback)
+    HUTK_HIP_TRY(hipMemsetAsync(A.err, 0, 4, s));
+    HUTK_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A.ok, 1, 1, s));
+    HUTK_HIP_TRY(hipMemsetAsync(A.first_bits, 0, (size_t)(n_ids / 32 + 4) * 4, s));
+    if (n_tiles) HUTK_HIP_TRY(hipMemsetAsync(A.tile_state, 0, (size_t)n_tiles * 8, s));
+    if (d_status) HUTK_HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n_docs * 4, s));
+    launch_spans(c->dec, A, out_width, s);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_token_spans(hutk_ctx* c, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, const int32_t* ids,
+                     const int64_t* id_offsets, int unit, int out_width, void* spans, int32_t* status) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to compute spans on");
+    if (n_docs < 0 || !offsets || !id_offsets || (out_width != 4 && out_width != 8))
+        return api_set_error(HUTK_E_ARG, "hutk_token_spans: bad arguments");
+    if (offsets[0] < 0 || id_offsets[0] != 0) return api_set_error(HUTK_E_ARG, "offsets[0] must not be negative, id_offsets[0] must be 0");
+    if (int rc = check_offsets(offsets, n_docs, false, "offsets")) return rc;
+    if (int rc = check_offsets(id_offsets, n_docs, false, "offsets")) return rc;  // (one text for both arrays)
+    const int64_t n_bytes = offsets[n_docs], n_ids = id_offsets[n_docs];
+    if ((n_bytes > 0 && !bytes) || (n_ids > 0 && (!ids || !spans))) return api_set_error(HUTK_E_ARG, "hutk_token_spans: a buffer is NULL");
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HUTK_HIP_TRY(c->s_bytes.reserve((size_t)n_bytes + 16));
+    HUTK_HIP_TRY(c->s_offsets.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ds_ids.reserve((size_t)n_ids + 16));
+    HUTK_HIP_TRY(c->ds_offs.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ds_status.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ss_spans.reserve((size_t)n_ids * 2 + 2));
+    HUTK_HIP_TRY(c->w_err.reserve(1));
+    if (n_bytes) HUTK_HIP_TRY(hipMemcpyAsync(c->s_bytes.p, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+    if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(c->s_offsets.p, offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    int rc = hutk_token_spans_device(c, c->s_bytes.p, c->s_offsets.p, n_docs, n_bytes, c->ds_ids.p, c->ds_offs.p, n_ids, unit,
+                                     out_width, c->ss_spans.p, c->ds_status.p, c->w_err.p, s);
+    if (rc) return rc;
+    int32_t err = 0;
+    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
+    if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(spans, c->ss_spans.p, (size_t)n_ids * 2 * out_width, hipMemcpyDeviceToHost, s));
+    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->ds_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipStreamSynchronize(s));
+    return err == HUTK_OK ? HUTK_OK : api_set_error(err, device_error_message(Direction::Spans, err));
+}
+
+}  // extern "C"

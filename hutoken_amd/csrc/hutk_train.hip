@@ -52,7 +52,7 @@
 #include <string>
 #include <vector>
 
-#include "hutk_internal.h"
+#include "hutk_host.h"
 #include "hutk_classify.h"
 
 namespace {
@@ -62,14 +62,6 @@ constexpr int LONG_WORD = 64;        // words with more symbols take the wavefro
 constexpr uint64_t PK_EMPTY = ~0ull; // pair table: empty key (a = b = -1 is no pair)
 constexpr int SYNC_EVERY = 64;       // merges enqueued between host synchronisations
 constexpr int PAIR_CAP_LOG2 = 16;    // the pair table's floor: 2^16 slots
-
-#define TR_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess)                                                                              \
-            return hutk::api_set_error(HUTK_E_DEVICE, std::string("HIP error: ") + hipGetErrorString(e__) + \
-                                                          " at " #expr);                                    \
-    } while (0)
 
 __host__ __device__ inline uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
     x ^= x >> 30;
@@ -787,36 +779,36 @@ int symbolise_chars(hutk_trainer* t, int64_t n_words) {
     int64_t* t_len = nullptr;
     unsigned long long* d_n = nullptr;  // [0] dropped words, [1] set slots used
     unsigned int* d_u = nullptr;        // [0] set full, [1] compacted keys
-    TR_TRY(t->alloc((void**)&tbuf, std::max<int64_t>(3 * n_sym, 1)));
-    TR_TRY(t->alloc((void**)&t_len, std::max<int64_t>(n_words, 1) * 8));
-    TR_TRY(t->alloc((void**)&d_n, 16));
-    TR_TRY(t->alloc((void**)&d_u, 8));
-    TR_TRY(hipMemsetAsync(d_n, 0, 16, st));
+    HUTK_HIP_TRY(t->alloc((void**)&tbuf, std::max<int64_t>(3 * n_sym, 1)));
+    HUTK_HIP_TRY(t->alloc((void**)&t_len, std::max<int64_t>(n_words, 1) * 8));
+    HUTK_HIP_TRY(t->alloc((void**)&d_n, 16));
+    HUTK_HIP_TRY(t->alloc((void**)&d_u, 8));
+    HUTK_HIP_TRY(hipMemsetAsync(d_n, 0, 16, st));
     if (n_words)
         hipLaunchKernelGGL(k_chars_xform, dim3(grid), dim3(TB), 0, st, t->arena, t->w_off, t->w_len, n_words, tbuf,
                            t_len, d_n);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     CharSet cs{};
     // (HUTK_TRAIN_CHARSET_CAP_LOG2, test only: the set's first size, so that a test can make it grow)
     const char* e_cs = getenv("HUTK_TRAIN_CHARSET_CAP_LOG2");
     uint64_t cap = e_cs ? 1ull << std::min(std::max(atoi(e_cs), 2), 30)
                         : pow2_at_least(std::max<uint64_t>(2 * std::min<int64_t>(n_sym, 1 << 20), 1 << 12));
     for (;;) {
-        TR_TRY(t->alloc((void**)&cs.key, cap * 4));
-        TR_TRY(t->alloc((void**)&cs.id, cap * 4));
-        TR_TRY(hipMemsetAsync(cs.key, 0, cap * 4, st));
-        TR_TRY(hipMemsetAsync(d_n + 1, 0, 8, st));
-        TR_TRY(hipMemsetAsync(d_u, 0, 8, st));
+        HUTK_HIP_TRY(t->alloc((void**)&cs.key, cap * 4));
+        HUTK_HIP_TRY(t->alloc((void**)&cs.id, cap * 4));
+        HUTK_HIP_TRY(hipMemsetAsync(cs.key, 0, cap * 4, st));
+        HUTK_HIP_TRY(hipMemsetAsync(d_n + 1, 0, 8, st));
+        HUTK_HIP_TRY(hipMemsetAsync(d_u, 0, 8, st));
         cs.mask = cap - 1;
         cs.used = d_n + 1;
         cs.full = d_u;
         if (n_words)
             hipLaunchKernelGGL(k_chars_walk<false>, dim3(grid), dim3(TB), 0, st, tbuf, t->w_off, t_len, n_words, cs,
                                t->w_len, t->sym);
-        TR_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipGetLastError());
         unsigned full = 0;
-        TR_TRY(hipMemcpyAsync(&full, d_u, 4, hipMemcpyDeviceToHost, st));
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(hipMemcpyAsync(&full, d_u, 4, hipMemcpyDeviceToHost, st));
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         if (!full) break;
         t->release(cs.key);
         t->release(cs.id);
@@ -824,32 +816,32 @@ int symbolise_chars(hutk_trainer* t, int64_t n_words) {
         t->c_cset_grows++;
     }
     uint32_t* keys = nullptr;
-    TR_TRY(t->alloc((void**)&keys, cap / 2 * 4 + 4));
+    HUTK_HIP_TRY(t->alloc((void**)&keys, cap / 2 * 4 + 4));
     hipLaunchKernelGGL(k_cset_compact, dim3(nblocks(cap)), dim3(TB), 0, st, cs, cap, keys, d_u + 1);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     unsigned n_keys = 0;
     unsigned long long dropped = 0;
-    TR_TRY(hipMemcpyAsync(&n_keys, d_u + 1, 4, hipMemcpyDeviceToHost, st));
-    TR_TRY(hipMemcpyAsync(&dropped, d_n, 8, hipMemcpyDeviceToHost, st));
-    TR_TRY(hipStreamSynchronize(st));
+    HUTK_HIP_TRY(hipMemcpyAsync(&n_keys, d_u + 1, 4, hipMemcpyDeviceToHost, st));
+    HUTK_HIP_TRY(hipMemcpyAsync(&dropped, d_n, 8, hipMemcpyDeviceToHost, st));
+    HUTK_HIP_TRY(hipStreamSynchronize(st));
     t->alpha.resize(n_keys);
-    if (n_keys) TR_TRY(hipMemcpy(t->alpha.data(), keys, (size_t)n_keys * 4, hipMemcpyDeviceToHost));
+    if (n_keys) HUTK_HIP_TRY(hipMemcpy(t->alpha.data(), keys, (size_t)n_keys * 4, hipMemcpyDeviceToHost));
     std::sort(t->alpha.begin(), t->alpha.end());  // memcmp order of the characters: no byte is 0x00
     if (n_keys) {
-        TR_TRY(hipMemcpyAsync(keys, t->alpha.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, st));
+        HUTK_HIP_TRY(hipMemcpyAsync(keys, t->alpha.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_cset_number, dim3(nblocks(n_keys)), dim3(TB), 0, st, cs, keys, n_keys);
         hipLaunchKernelGGL(k_chars_walk<true>, dim3(grid), dim3(TB), 0, st, tbuf, t->w_off, t_len, n_words, cs,
                            t->w_len, t->sym);
-        TR_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipGetLastError());
     }
     // characters in all words (the symbol count of the run)
     unsigned long long* d_tot = d_n + 1;
-    TR_TRY(hipMemsetAsync(d_tot, 0, 8, st));
+    HUTK_HIP_TRY(hipMemsetAsync(d_tot, 0, 8, st));
     if (n_words) hipLaunchKernelGGL(k_sum_len, dim3(nblocks(n_words)), dim3(TB), 0, st, t->w_len, n_words, d_tot);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     unsigned long long tot = 0;
-    TR_TRY(hipMemcpyAsync(&tot, d_tot, 8, hipMemcpyDeviceToHost, st));
-    TR_TRY(hipStreamSynchronize(st));
+    HUTK_HIP_TRY(hipMemcpyAsync(&tot, d_tot, 8, hipMemcpyDeviceToHost, st));
+    HUTK_HIP_TRY(hipStreamSynchronize(st));
     for (void* p : {(void*)tbuf, (void*)t_len, (void*)d_n, (void*)d_u, (void*)cs.key, (void*)cs.id, (void*)keys})
         t->release(p);
     t->n_alpha = (int32_t)n_keys;
@@ -859,7 +851,7 @@ int symbolise_chars(hutk_trainer* t, int64_t n_words) {
 }
 
 int symbolise_once(hutk_trainer* t) {
-    TR_TRY(hipSetDevice(t->device));
+    HUTK_HIP_TRY(hipSetDevice(t->device));
     hipStream_t st = t->st;
     const int64_t n_words = t->n_unique, n_sym = t->arena_used;
     t->n_sym = n_sym;
@@ -875,21 +867,21 @@ int symbolise_once(hutk_trainer* t) {
 
     const int64_t nw1 = std::max<int64_t>(n_words, 1);
     unsigned int* n_out = nullptr;
-    TR_TRY(t->alloc((void**)&t->sym, std::max<int64_t>(n_sym, 1) * 4));
-    TR_TRY(t->alloc((void**)&t->w_len, nw1 * 4));
-    TR_TRY(t->alloc((void**)&t->w_off, nw1 * 8));
-    TR_TRY(t->alloc((void**)&t->w_cnt, nw1 * 8));
-    TR_TRY(t->alloc((void**)&n_out, 4));
-    TR_TRY(hipMemsetAsync(n_out, 0, 4, st));
+    HUTK_HIP_TRY(t->alloc((void**)&t->sym, std::max<int64_t>(n_sym, 1) * 4));
+    HUTK_HIP_TRY(t->alloc((void**)&t->w_len, nw1 * 4));
+    HUTK_HIP_TRY(t->alloc((void**)&t->w_off, nw1 * 8));
+    HUTK_HIP_TRY(t->alloc((void**)&t->w_cnt, nw1 * 8));
+    HUTK_HIP_TRY(t->alloc((void**)&n_out, 4));
+    HUTK_HIP_TRY(hipMemsetAsync(n_out, 0, 4, st));
     if (t->wt_cap)
         hipLaunchKernelGGL(k_words_from_table, dim3(nblocks(t->wt_cap)), dim3(TB), 0, st, t->wt, t->wt_cap, t->w_off,
                            t->w_len, t->w_cnt, n_out);
     if (t->mode == HUTK_TRAIN_BYTES && n_sym)
         hipLaunchKernelGGL(k_bytes_to_sym, dim3(1024), dim3(TB), 0, st, t->arena, n_sym, t->sym);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     if (t->mode == HUTK_TRAIN_CHARS)
         if (int rc = symbolise_chars(t, n_words)) return rc;
-    TR_TRY(hipStreamSynchronize(st));
+    HUTK_HIP_TRY(hipStreamSynchronize(st));
     t->release(n_out);
     wordtab_free(t, &t->wt);
     t->wt_cap = 0;
@@ -921,9 +913,9 @@ int hutk_trainer_create_mode(hutk_trainer** out, int device, int mode) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return hutk::api_set_error(HUTK_E_DEVICE, "hutk_trainer_create: no HIP device");
-    if (device < 0) TR_TRY(hipGetDevice(&device));
+    if (device < 0) HUTK_HIP_TRY(hipGetDevice(&device));
     if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_trainer_create: no such device");
-    TR_TRY(hipSetDevice(device));
+    HUTK_HIP_TRY(hipSetDevice(device));
     hutk_trainer* t = new hutk_trainer();
     t->device = device;
     t->mode = mode;
@@ -944,38 +936,38 @@ int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offse
     if (t->ran) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: the trainer has already run");
     if (t->symbolised) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: the alphabet has been read");
     if (n_docs == 0) return HUTK_OK;
-    for (int64_t i = 0; i < n_docs; i++)
-        if (offsets[i + 1] < offsets[i] || offsets[i] < 0)
-            return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: offsets must not decrease");
+    // (a negative offset is reported as a decreasing one: behind a first offset of 0 or more, none can be negative)
+    if (offsets[0] < 0) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: offsets must not decrease");
+    if (int rc = hutk::check_offsets(offsets, n_docs, false, "hutk_trainer_add: offsets")) return rc;
     const int64_t base = offsets[0], n = offsets[n_docs] - base;
     if (n > 0 && !bytes) return hutk::api_set_error(HUTK_E_ARG, "hutk_trainer_add: bytes is NULL");
     if (n == 0) {
         t->n_docs += n_docs;
         return HUTK_OK;
     }
-    TR_TRY(hipSetDevice(t->device));
+    HUTK_HIP_TRY(hipSetDevice(t->device));
     hipStream_t st = t->st;
     const int64_t n_groups = (n + 15) / 16, n_bm = (n + 31) / 32;
-    TR_TRY(t->grow(&t->d_bytes, &t->d_bytes_cap, n + 64));
-    TR_TRY(t->grow(&t->d_offs, &t->d_offs_cap, n_docs + 1));
-    TR_TRY(t->grow(&t->d_wsb, &t->d_bm_cap, std::max(n_groups, n_bm) + 1));
+    HUTK_HIP_TRY(t->grow(&t->d_bytes, &t->d_bytes_cap, n + 64));
+    HUTK_HIP_TRY(t->grow(&t->d_offs, &t->d_offs_cap, n_docs + 1));
+    HUTK_HIP_TRY(t->grow(&t->d_wsb, &t->d_bm_cap, std::max(n_groups, n_bm) + 1));
     {
         int64_t c2 = 0;
         t->release(t->d_dbm);
         t->d_dbm = nullptr;
-        TR_TRY(t->grow(&t->d_dbm, &c2, n_bm + 1));
+        HUTK_HIP_TRY(t->grow(&t->d_dbm, &c2, n_bm + 1));
     }
-    TR_TRY(hipMemcpyAsync(t->d_bytes, bytes + base, n, hipMemcpyHostToDevice, st));
-    TR_TRY(hipMemsetAsync(t->d_bytes + n, 0, 64, st));
-    TR_TRY(hipMemcpyAsync(t->d_offs, offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, st));
-    TR_TRY(hipMemsetAsync(t->d_dbm, 0, (n_bm + 1) * 4, st));
-    TR_TRY(hipMemsetAsync(t->ctl, 0, sizeof(AddCtl), st));
+    HUTK_HIP_TRY(hipMemcpyAsync(t->d_bytes, bytes + base, n, hipMemcpyHostToDevice, st));
+    HUTK_HIP_TRY(hipMemsetAsync(t->d_bytes + n, 0, 64, st));
+    HUTK_HIP_TRY(hipMemcpyAsync(t->d_offs, offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, st));
+    HUTK_HIP_TRY(hipMemsetAsync(t->d_dbm, 0, (n_bm + 1) * 4, st));
+    HUTK_HIP_TRY(hipMemsetAsync(t->ctl, 0, sizeof(AddCtl), st));
     hipLaunchKernelGGL(k_docmark, dim3(nblocks(n_docs)), dim3(TB), 0, st, t->d_offs, n_docs, base, n, t->d_dbm);
     hipLaunchKernelGGL(k_split, dim3(nblocks(n_groups)), dim3(TB), 0, st, t->d_bytes, n, t->d_dbm, t->d_wsb, t->ctl);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     AddCtl h;
-    TR_TRY(hipMemcpyAsync(&h, t->ctl, sizeof h, hipMemcpyDeviceToHost, st));
-    TR_TRY(hipStreamSynchronize(st));
+    HUTK_HIP_TRY(hipMemcpyAsync(&h, t->ctl, sizeof h, hipMemcpyDeviceToHost, st));
+    HUTK_HIP_TRY(hipStreamSynchronize(st));
     if (h.nul) return hutk::api_set_error(HUTK_E_NUL_BYTE, "hutk_trainer_add: a document holds a 0x00 byte");
     const int64_t nw = (int64_t)h.n_words;
 
@@ -983,9 +975,9 @@ int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offse
     if (t->arena_used + n > t->arena_cap) {
         const int64_t cap = std::max<int64_t>(t->arena_used + n, 2 * t->arena_cap);
         uint8_t* p = nullptr;
-        TR_TRY(t->alloc((void**)&p, cap));
-        if (t->arena_used) TR_TRY(hipMemcpyAsync(p, t->arena, t->arena_used, hipMemcpyDeviceToDevice, st));
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(t->alloc((void**)&p, cap));
+        if (t->arena_used) HUTK_HIP_TRY(hipMemcpyAsync(p, t->arena, t->arena_used, hipMemcpyDeviceToDevice, st));
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         t->release(t->arena);
         t->arena = p;
         t->arena_cap = cap;
@@ -993,45 +985,45 @@ int hutk_trainer_add(hutk_trainer* t, const uint8_t* bytes, const int64_t* offse
     const uint64_t need = pow2_at_least((uint64_t)std::max<int64_t>(2 * (t->n_unique + nw), 1024));
     if (need > t->wt_cap) {
         WordTab nt{};
-        TR_TRY(wordtab_alloc(t, &nt, need));
+        HUTK_HIP_TRY(wordtab_alloc(t, &nt, need));
         if (t->wt_cap) {
             hipLaunchKernelGGL(k_word_rehash, dim3(nblocks(t->wt_cap)), dim3(TB), 0, st, t->wt, t->wt_cap, nt, t->ctl);
             t->c_word_rehash++;
         }
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         wordtab_free(t, &t->wt);
         t->wt = nt;
         t->wt_cap = need;
     }
-    TR_TRY(t->grow(&t->pend[0], &t->pend_cap, nw));
+    HUTK_HIP_TRY(t->grow(&t->pend[0], &t->pend_cap, nw));
     {
         int64_t c1 = 0;
         t->release(t->pend[1]);
         t->pend[1] = nullptr;
-        TR_TRY(t->grow(&t->pend[1], &c1, t->pend_cap));
+        HUTK_HIP_TRY(t->grow(&t->pend[1], &c1, t->pend_cap));
     }
     // arena_used / n_unique continue from the earlier batches
     h = AddCtl{};
     h.arena_used = (unsigned long long)t->arena_used;
     h.n_unique = (unsigned long long)t->n_unique;
-    TR_TRY(hipMemcpy(t->ctl, &h, sizeof h, hipMemcpyHostToDevice));
+    HUTK_HIP_TRY(hipMemcpy(t->ctl, &h, sizeof h, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_insert, dim3(nblocks(n_groups)), dim3(TB), 0, st, t->d_bytes, n, t->d_wsb, t->wt, t->arena,
                        t->ctl, t->pend[0]);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     int which = 0;
     for (int round = 0;; round++) {
-        TR_TRY(hipMemcpyAsync(&h, t->ctl, sizeof h, hipMemcpyDeviceToHost, st));
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(hipMemcpyAsync(&h, t->ctl, sizeof h, hipMemcpyDeviceToHost, st));
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         if (h.full) return hutk::api_set_error(HUTK_E_CAPACITY, "hutk_trainer_add: word table full");
         if (h.pend_n[which] == 0) break;
         if (round > 64) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_trainer_add: word insertion does not settle");
         t->c_deferred += h.pend_n[which];
         t->c_insert_rounds_max = std::max<int64_t>(t->c_insert_rounds_max, round + 1);
-        TR_TRY(hipMemsetAsync(&t->ctl->pend_n[which ^ 1], 0, 4, st));
+        HUTK_HIP_TRY(hipMemsetAsync(&t->ctl->pend_n[which ^ 1], 0, 4, st));
         hipLaunchKernelGGL(k_insert_pending, dim3(nblocks(h.pend_n[which])), dim3(TB), 0, st, t->d_bytes, t->wt,
                            t->arena, t->ctl, t->pend[which], which, t->pend[which ^ 1]);
-        TR_TRY(hipGetLastError());
-        TR_TRY(hipMemsetAsync(&t->ctl->pend_n[which], 0, 4, st));
+        HUTK_HIP_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipMemsetAsync(&t->ctl->pend_n[which], 0, 4, st));
         which ^= 1;
     }
     t->arena_used = (int64_t)h.arena_used;
@@ -1055,7 +1047,7 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     const int cap_log2 = e_cap ? std::min(std::max(atoi(e_cap), 2), 30) : PAIR_CAP_LOG2;
     const uint64_t pair_floor = 1ull << cap_log2;
     if (int rc = symbolise(t)) return rc;
-    TR_TRY(hipSetDevice(t->device));
+    HUTK_HIP_TRY(hipSetDevice(t->device));
     // every merge removes at least one symbol, so no more than n_sym merges can happen; symbol ids stay below 2^31
     n_merges = (int32_t)std::min<int64_t>({(int64_t)n_merges, t->n_sym, (int64_t)INT32_MAX - t->n_alpha});
     hipStream_t st = t->st;
@@ -1066,21 +1058,21 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     unsigned int* cnt2 = nullptr;  // [0..1] active short / long, [3] short before the long list
     const int64_t nw1 = std::max<int64_t>(n_words, 1);
     for (int p = 0; p < 2; p++)
-        for (int q = 0; q < 2; q++) TR_TRY(t->alloc((void**)&act[p][q], nw1 * 4));
-    TR_TRY(t->alloc((void**)&cnt2, 16));
-    TR_TRY(hipMemsetAsync(cnt2, 0, 16, st));
+        for (int q = 0; q < 2; q++) HUTK_HIP_TRY(t->alloc((void**)&act[p][q], nw1 * 4));
+    HUTK_HIP_TRY(t->alloc((void**)&cnt2, 16));
+    HUTK_HIP_TRY(hipMemsetAsync(cnt2, 0, 16, st));
 
     // active lists (cur = 0): words with >= 2 symbols
     unsigned n_act[2] = {0, 0};
     int cur_list = 0;
     auto partition = [&](const int32_t* in, unsigned n_in, int dst) -> int {
-        TR_TRY(hipMemsetAsync(cnt2, 0, 8, st));
+        HUTK_HIP_TRY(hipMemsetAsync(cnt2, 0, 8, st));
         if (n_in)
             hipLaunchKernelGGL(k_partition, dim3(nblocks(n_in)), dim3(TB), 0, st, in, n_in, w_len, act[dst][0],
                                act[dst][1], cnt2);
-        TR_TRY(hipGetLastError());
-        TR_TRY(hipMemcpyAsync(n_act, cnt2, 8, hipMemcpyDeviceToHost, st));
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipMemcpyAsync(n_act, cnt2, 8, hipMemcpyDeviceToHost, st));
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         return HUTK_OK;
     };
     if (int rc = partition(nullptr, (unsigned)n_words, 0)) return rc;
@@ -1090,9 +1082,9 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     uint64_t pcap = 0;
     unsigned long long* d_used = nullptr;
     unsigned int* d_full = nullptr;
-    TR_TRY(t->alloc((void**)&d_used, 8));
-    TR_TRY(t->alloc((void**)&d_full, 4));
-    TR_TRY(hipMemsetAsync(d_full, 0, 4, st));
+    HUTK_HIP_TRY(t->alloc((void**)&d_used, 8));
+    HUTK_HIP_TRY(t->alloc((void**)&d_full, 4));
+    HUTK_HIP_TRY(hipMemsetAsync(d_full, 0, 4, st));
     auto pair_alloc = [&](PairTab* p, uint64_t cap) -> hipError_t {
         hipError_t e;
         if ((e = t->alloc((void**)&p->key, cap * 8)) != hipSuccess) return e;
@@ -1106,7 +1098,7 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     };
     // initial keys: at most min(symbols, A^2) distinct pairs (65536 in bytes mode)
     pcap = pow2_at_least(std::max<uint64_t>(4 * std::min<int64_t>(n_sym, (int64_t)base * base), pair_floor));
-    TR_TRY(pair_alloc(&pt, pcap));
+    HUTK_HIP_TRY(pair_alloc(&pt, pcap));
     t->c_pcap_max = (int64_t)pcap;
     if (n_act[0])
         hipLaunchKernelGGL(k_init_short, dim3(nblocks(n_act[0])), dim3(TB), 0, st, sym, act[0][0], n_act[0], w_off, w_len,
@@ -1114,10 +1106,10 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     if (n_act[1])
         hipLaunchKernelGGL(k_init_long, dim3(nblocks((uint64_t)n_act[1] * 64)), dim3(TB), 0, st, sym, act[0][1], n_act[1],
                            w_off, w_len, w_cnt, pt);
-    TR_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipGetLastError());
     unsigned long long used = 0;
-    TR_TRY(hipMemcpyAsync(&used, d_used, 8, hipMemcpyDeviceToHost, st));
-    TR_TRY(hipStreamSynchronize(st));
+    HUTK_HIP_TRY(hipMemcpyAsync(&used, d_used, 8, hipMemcpyDeviceToHost, st));
+    HUTK_HIP_TRY(hipStreamSynchronize(st));
     t->n_pairs0 = (int64_t)used;
 
     int32_t* d_pairs = nullptr;
@@ -1125,11 +1117,11 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     LoopCtl* lc = nullptr;
     Best* partial = nullptr;
     constexpr unsigned SEL_BLOCKS_MAX = 1024;
-    TR_TRY(t->alloc((void**)&d_pairs, std::max<int64_t>(2LL * n_merges, 2) * 4));
-    TR_TRY(t->alloc((void**)&d_counts, std::max<int64_t>(n_merges, 1) * 8));
-    TR_TRY(t->alloc((void**)&lc, sizeof(LoopCtl)));
-    TR_TRY(t->alloc((void**)&partial, SEL_BLOCKS_MAX * sizeof(Best)));
-    TR_TRY(hipMemsetAsync(lc, 0, sizeof(LoopCtl), st));
+    HUTK_HIP_TRY(t->alloc((void**)&d_pairs, std::max<int64_t>(2LL * n_merges, 2) * 4));
+    HUTK_HIP_TRY(t->alloc((void**)&d_counts, std::max<int64_t>(n_merges, 1) * 8));
+    HUTK_HIP_TRY(t->alloc((void**)&lc, sizeof(LoopCtl)));
+    HUTK_HIP_TRY(t->alloc((void**)&partial, SEL_BLOCKS_MAX * sizeof(Best)));
+    HUTK_HIP_TRY(hipMemsetAsync(lc, 0, sizeof(LoopCtl), st));
 
     auto rebuild = [&](uint64_t live_hint, uint64_t room_hint) -> int {
         uint64_t cap = pow2_at_least(std::max<uint64_t>(4 * (live_hint + room_hint), pair_floor));
@@ -1138,19 +1130,19 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         const uint64_t old_cap = pcap;
         // the new table's `used` counter is the same device word: reset after the old table is no longer read
         unsigned long long* used_new = nullptr;
-        TR_TRY(t->alloc((void**)&used_new, 8));
+        HUTK_HIP_TRY(t->alloc((void**)&used_new, 8));
         hipError_t e;
-        if ((e = t->alloc((void**)&nt.key, cap * 8)) != hipSuccess) TR_TRY(e);
-        if ((e = t->alloc((void**)&nt.cnt, cap * 8)) != hipSuccess) TR_TRY(e);
-        TR_TRY(hipMemsetAsync(nt.key, 0xFF, cap * 8, st));
-        TR_TRY(hipMemsetAsync(nt.cnt, 0, cap * 8, st));
-        TR_TRY(hipMemsetAsync(used_new, 0, 8, st));
+        if ((e = t->alloc((void**)&nt.key, cap * 8)) != hipSuccess) HUTK_HIP_TRY(e);
+        if ((e = t->alloc((void**)&nt.cnt, cap * 8)) != hipSuccess) HUTK_HIP_TRY(e);
+        HUTK_HIP_TRY(hipMemsetAsync(nt.key, 0xFF, cap * 8, st));
+        HUTK_HIP_TRY(hipMemsetAsync(nt.cnt, 0, cap * 8, st));
+        HUTK_HIP_TRY(hipMemsetAsync(used_new, 0, 8, st));
         nt.mask = cap - 1;
         nt.used = used_new;
         nt.full = d_full;
         hipLaunchKernelGGL(k_pair_rehash, dim3(nblocks(old_cap)), dim3(TB), 0, st, old, old_cap, nt);
-        TR_TRY(hipGetLastError());
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         t->release(old.key);
         t->release(old.cnt);
         t->release(d_used);
@@ -1165,9 +1157,9 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
     };
 
     hipEvent_t ev0, ev1;
-    TR_TRY(hipEventCreate(&ev0));
-    TR_TRY(hipEventCreate(&ev1));
-    TR_TRY(hipEventRecord(ev0, st));
+    HUTK_HIP_TRY(hipEventCreate(&ev0));
+    HUTK_HIP_TRY(hipEventCreate(&ev1));
+    HUTK_HIP_TRY(hipEventRecord(ev0, st));
     int k = 0;
     LoopCtl hl{};
     int rc = HUTK_OK;
@@ -1186,12 +1178,12 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
                 hipLaunchKernelGGL(k_apply_long, dim3(nblocks((uint64_t)n_act[1] * 64)), dim3(TB), 0, st, sym,
                                    act[cur_list][1], n_act[1], w_off, w_len, w_cnt, pt, lc, base, j);
         }
-        TR_TRY(hipGetLastError());
-        TR_TRY(hipMemcpyAsync(&hl, lc, sizeof hl, hipMemcpyDeviceToHost, st));
+        HUTK_HIP_TRY(hipGetLastError());
+        HUTK_HIP_TRY(hipMemcpyAsync(&hl, lc, sizeof hl, hipMemcpyDeviceToHost, st));
         unsigned full = 0;
-        TR_TRY(hipMemcpyAsync(&full, d_full, 4, hipMemcpyDeviceToHost, st));
-        TR_TRY(hipMemcpyAsync(&used, d_used, 8, hipMemcpyDeviceToHost, st));
-        TR_TRY(hipStreamSynchronize(st));
+        HUTK_HIP_TRY(hipMemcpyAsync(&full, d_full, 4, hipMemcpyDeviceToHost, st));
+        HUTK_HIP_TRY(hipMemcpyAsync(&used, d_used, 8, hipMemcpyDeviceToHost, st));
+        HUTK_HIP_TRY(hipStreamSynchronize(st));
         t->c_syncs++;
         t->c_pauses += hl.pause != 0;
         if (full) {
@@ -1204,20 +1196,20 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         const unsigned na0 = n_act[0], na1 = n_act[1];
         const int nxt = cur_list ^ 1;
         {
-            TR_TRY(hipMemsetAsync(cnt2, 0, 8, st));
+            HUTK_HIP_TRY(hipMemsetAsync(cnt2, 0, 8, st));
             if (na0)
                 hipLaunchKernelGGL(k_partition, dim3(nblocks(na0)), dim3(TB), 0, st, act[cur_list][0], na0, w_len,
                                    act[nxt][0], act[nxt][1], cnt2);
             // (the short count before the long list goes in: cnt2[3], so that the host learns how many long words
             // became short from the same copy; short words never become long)
-            if (na1) TR_TRY(hipMemcpyAsync(cnt2 + 3, cnt2, 4, hipMemcpyDeviceToDevice, st));
+            if (na1) HUTK_HIP_TRY(hipMemcpyAsync(cnt2 + 3, cnt2, 4, hipMemcpyDeviceToDevice, st));
             if (na1)
                 hipLaunchKernelGGL(k_partition, dim3(nblocks(na1)), dim3(TB), 0, st, act[cur_list][1], na1, w_len,
                                    act[nxt][0], act[nxt][1], cnt2);
-            TR_TRY(hipGetLastError());
+            HUTK_HIP_TRY(hipGetLastError());
             unsigned n4[4] = {0, 0, 0, 0};
-            TR_TRY(hipMemcpyAsync(n4, cnt2, na1 ? 16 : 8, hipMemcpyDeviceToHost, st));
-            TR_TRY(hipStreamSynchronize(st));
+            HUTK_HIP_TRY(hipMemcpyAsync(n4, cnt2, na1 ? 16 : 8, hipMemcpyDeviceToHost, st));
+            HUTK_HIP_TRY(hipStreamSynchronize(st));
             n_act[0] = n4[0], n_act[1] = n4[1];
             if (na1) t->c_long_to_short += n4[0] - n4[3];
             cur_list = nxt;
@@ -1230,23 +1222,23 @@ int hutk_trainer_run(hutk_trainer* t, int32_t n_merges, int32_t* pairs_out, int6
         if (hl.pause || used + 2 * step_room > pcap / 2 ||
             pcap > 16 * std::max<uint64_t>(used + step_room, pair_floor >> 2)) {
             if ((rc = rebuild(used, step_room))) break;
-            TR_TRY(hipMemsetAsync(&lc->pause, 0, 4, st));
+            HUTK_HIP_TRY(hipMemsetAsync(&lc->pause, 0, 4, st));
         }
     }
-    TR_TRY(hipEventRecord(ev1, st));
-    TR_TRY(hipEventSynchronize(ev1));
+    HUTK_HIP_TRY(hipEventRecord(ev1, st));
+    HUTK_HIP_TRY(hipEventSynchronize(ev1));
     float ms = 0;
-    TR_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    HUTK_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
     t->loop_us = (int64_t)(ms * 1000.0f);
     if (rc) return rc;
-    TR_TRY(hipMemcpyAsync(&hl, lc, sizeof hl, hipMemcpyDeviceToHost, st));
-    TR_TRY(hipStreamSynchronize(st));
+    HUTK_HIP_TRY(hipMemcpyAsync(&hl, lc, sizeof hl, hipMemcpyDeviceToHost, st));
+    HUTK_HIP_TRY(hipStreamSynchronize(st));
     const int done = hl.n_done;
     if (done) {
-        TR_TRY(hipMemcpy(pairs_out, d_pairs, (size_t)done * 8, hipMemcpyDeviceToHost));
-        if (counts_out) TR_TRY(hipMemcpy(counts_out, d_counts, (size_t)done * 8, hipMemcpyDeviceToHost));
+        HUTK_HIP_TRY(hipMemcpy(pairs_out, d_pairs, (size_t)done * 8, hipMemcpyDeviceToHost));
+        if (counts_out) HUTK_HIP_TRY(hipMemcpy(counts_out, d_counts, (size_t)done * 8, hipMemcpyDeviceToHost));
     }
     *n_done = done;
     // the workspace is returned now; stats stay readable

@@ -24,6 +24,10 @@ Offset mapping (not in the reference): `token_spans_device` turns the same devic
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
 `encode_with_offsets` are the list forms (csrc/hutk_spans.hip).
 
+Special tokens (not in the reference, which cuts "<|endoftext|>" into eight ids): `set_special_tokens` installs
+{string: id}; `encode_special`, `batch_encode_special` and `encode_special_packed_device` match them on the GPU and give
+each ONE id, the text between them encoded as ever (csrc/hutk_special.hip).  `encode` / `batch_encode` never look at them.
+
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
 the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
@@ -38,7 +42,8 @@ from . import _capi
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker",
-           "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets"]
+           "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
+           "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -840,3 +845,111 @@ def encode_with_offsets(text, unit="char"):
         raise TypeError(f"argument 1 must be str, not {type(text).__name__}")
     ids, spans = batch_encode_with_offsets([text], unit)
     return ids[0], spans[0]
+
+
+# ---- special tokens ----------------------------------------------------------------------------------------------
+def _special_pairs(mapping):
+    """{str: int} -> [(utf-8 bytes, id)]; TypeError / ValueError before anything reaches the library."""
+    if mapping is None:
+        return []
+    if not isinstance(mapping, dict):
+        raise TypeError("special tokens must be a dict {str: int} or None, not %s" % type(mapping).__name__)
+    pairs = []
+    for k, v in mapping.items():
+        if not isinstance(k, str):
+            raise TypeError("a special token must be a str, not %s" % type(k).__name__)
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("the id of special token %r must be an int, not %s" % (k, type(v).__name__))
+        raw = k.encode("utf-8")  # (a lone surrogate: UnicodeEncodeError, a ValueError)
+        if not raw:
+            raise ValueError("a special token must not be empty")
+        if len(raw) > 255:
+            raise ValueError("special token %r is longer than 255 bytes" % (k,))
+        if b"\0" in raw:
+            raise ValueError("special token %r holds a NUL character" % (k,))
+        if not 0 <= v < 2**31:
+            raise ValueError("the id of special token %r must be in [0, 2**31)" % (k,))
+        pairs.append((raw, v))
+    if len(pairs) > 1024:
+        raise ValueError("at most 1024 special tokens")
+    return pairs
+
+
+def set_special_tokens(mapping):
+    """Install special tokens on the initialised context: {str: int}, the strings as UTF-8; None or {} removes them.
+    At most 1024 strings of 1..255 bytes without NUL, ids in [0, 2**31) that need not be vocabulary lines.  A new
+    initialize() starts without any.  Only the *_special functions look at them."""
+    pairs = _special_pairs(mapping)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    _ctx.set_special_tokens(pairs)
+
+
+def encode_special_packed_device(d_bytes, d_offsets, check=True):
+    """encode_packed_device with the special tokens of set_special_tokens: every match (leftmost first, then longest,
+    inside one document) becomes its one id, the text between the matches is encoded as documents of its own.  Same
+    tensors in, the same pair out -- (ids int32[capacity], out_offsets int64[n+1]) -- so collate_padded,
+    SequencePacker.add and the spans' callers take it unchanged (spans over special ids are not defined).  Synchronises
+    the current torch stream once, after the scan for matches."""
+    import torch
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    n_docs = d_offsets.numel() - 1
+    n_bytes = d_bytes.numel()
+    cap = _ctx.special_ids_capacity(n_bytes, n_docs)
+    dev = d_bytes.device
+    ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _ctx.encode_special_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap,
+                               oo.data_ptr(), 0, err.data_ptr(), stream)
+    if check:
+        code = int(err.item())
+        if code not in (0, _capi.E_WORD_TOO_LARGE):
+            raise RuntimeError(f"hutoken_amd: device-side error {code}")
+    return ids, oo
+
+
+def _special_texts_to_device(texts):
+    """_texts_to_device for the special-token encode (the same handling of torch's NULL stream)."""
+    if not isinstance(texts, list):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    import torch
+    data, offs = _pack(texts)
+    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
+    d_bytes = torch.from_numpy(data.copy()).to(dev)
+    d_offs = torch.from_numpy(offs).to(dev)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            return encode_special_packed_device(d_bytes, d_offs)
+        side = _side_streams.get(dev.index)
+        if side is None:
+            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            ids, oo = encode_special_packed_device(d_bytes, d_offs)
+        cur.wait_stream(side)
+        ids.record_stream(cur)
+        oo.record_stream(cur)
+        return ids, oo
+
+
+def batch_encode_special(texts):
+    """batch_encode with the special tokens of set_special_tokens -> list[list[int]]."""
+    ids, oo = _special_texts_to_device(texts)
+    bounds = oo.tolist()
+    flat = ids[:bounds[-1]].tolist()
+    return [flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))]
+
+
+def encode_special(text):
+    """encode with the special tokens of set_special_tokens -> list[int]."""
+    if not isinstance(text, str):
+        raise TypeError(f"argument 1 must be str, not {type(text).__name__}")
+    if "\0" in text:
+        raise ValueError("embedded null character")
+    return batch_encode_special([text])[0]

@@ -29,6 +29,9 @@ EXPORTS = [
     "hutk_collate_padded_device", "hutk_packer_create", "hutk_packer_rows", "hutk_packer_add_device",
     "hutk_packer_flush_device", "hutk_packer_pending", "hutk_packer_destroy",
     "hutk_token_spans_device", "hutk_token_spans",
+    "hutk_ctx_set_special_tokens", "hutk_ctx_special_token_count", "hutk_special_ids_capacity",
+    "hutk_encode_special_batch_device", "hutk_encode_special_batch", "hutk_special_last_matches",
+    "hutk_debug_special_tile_bytes",
 ]
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
@@ -185,6 +188,21 @@ def load(build_if_missing=True):
         L.hutk_token_spans_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp]
         L.hutk_token_spans.restype = i32
         L.hutk_token_spans.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
+    if hasattr(L, "hutk_ctx_set_special_tokens"):
+        L.hutk_ctx_set_special_tokens.restype = i32
+        L.hutk_ctx_set_special_tokens.argtypes = [vp, vp, vp, vp, i64]
+        L.hutk_ctx_special_token_count.restype = i64
+        L.hutk_ctx_special_token_count.argtypes = [vp]
+        L.hutk_special_ids_capacity.restype = i64
+        L.hutk_special_ids_capacity.argtypes = [vp, i64, i64]
+        L.hutk_encode_special_batch_device.restype = i32
+        L.hutk_encode_special_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]
+        L.hutk_encode_special_batch.restype = i32
+        L.hutk_encode_special_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
+        L.hutk_special_last_matches.restype = i64
+        L.hutk_special_last_matches.argtypes = [vp]
+        L.hutk_debug_special_tile_bytes.restype = i32
+        L.hutk_debug_special_tile_bytes.argtypes = []
     _lib = L
     return L
 
@@ -444,6 +462,62 @@ class Context:
         if rc != OK and not (rc == E_UNSUPPORTED and (st[:n] == DOC_SPAN_MISMATCH).any()):
             raise_for(rc)
         return spans, st[:n], rc
+
+    def set_special_tokens(self, pairs):
+        """Install special tokens (hutk_ctx_set_special_tokens): `pairs` is a sequence of (bytes, id); an empty one
+        removes the set.  ValueError for a set the library refuses."""
+        import numpy as np
+        pairs = list(pairs)
+        n = len(pairs)
+        if n == 0:
+            raise_for(load().hutk_ctx_set_special_tokens(self._h, None, None, None, 0))
+            return
+        blob = b"".join(bytes(k) for k, _i in pairs)
+        data = np.frombuffer(blob + b"\0", dtype=np.uint8)  # (never empty: an empty string is the library's to refuse)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(k) for k, _i in pairs], out=offs[1:])
+        for _k, i in pairs:
+            if not -2**31 <= int(i) < 2**31:
+                raise ValueError("the id of a special token must fit an int32")
+        ids = np.array([int(i) for _k, i in pairs], dtype=np.int32)
+        raise_for(load().hutk_ctx_set_special_tokens(self._h, data.ctypes.data, offs.ctypes.data, ids.ctypes.data, n))
+
+    @property
+    def special_token_count(self):
+        return int(load().hutk_ctx_special_token_count(self._h))
+
+    @property
+    def special_last_matches(self):
+        """Matches the last encode_special_* call on this context found."""
+        return int(load().hutk_special_last_matches(self._h))
+
+    def special_ids_capacity(self, n_bytes, n_docs):
+        return load().hutk_special_ids_capacity(self._h, n_bytes, n_docs)
+
+    def encode_special_packed(self, data, offsets):
+        """encode_packed with the context's special tokens (hutk_encode_special_batch): host numpy buffers in and out.
+        -> (ids int32, out_offsets int64, status int32, return code)"""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        nbytes = int(offsets[n]) if n >= 0 else 0
+        cap = self.special_ids_capacity(nbytes, n)
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        oo = np.zeros(n + 1, dtype=np.int64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        rc = load().hutk_encode_special_batch(self._h, data.ctypes.data if nbytes else None, offsets.ctypes.data, n,
+                                              ids.ctypes.data, cap, oo.ctypes.data, st.ctypes.data)
+        if rc not in (OK, E_WORD_TOO_LARGE):
+            raise_for(rc)
+        return ids[: int(oo[n])], oo, st[:n], rc
+
+    def encode_special_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets,
+                              d_status=0, d_err=0, stream=0):
+        """hutk_encode_special_batch_device on raw device pointers (ints): synchronises `stream` once, after the scan."""
+        raise_for(load().hutk_encode_special_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                          d_ids or None, ids_cap, d_out_offsets or None,
+                                                          d_status or None, d_err or None, stream or None))
 
     def profile(self, enable):
         load().hutk_debug_profile(self._h, 1 if enable else 0)

@@ -304,6 +304,7 @@ void destroy(hutk_ctx* c) {
         c->ds_offs.release(); c->ds_oo.release(); c->ds_bytes.release(); c->w_err.release();
         c->sp_bits.release(); c->sp_in_chunk.release(); c->sp_chunk.release(); c->sp_sel.release(); c->ss_spans.release();
         c->sp_ok.release();
+        c->sx.release();
         c->s_bytes.release(); c->s_offsets.release(); c->s_out_offsets.release(); c->s_ids.release();
         c->s_status.release(); c->s_small_in.release(); c->s_small_out.release();
         if (c->small_host) (void)hipHostFree(c->small_host);
@@ -631,11 +632,12 @@ static int ptiles_mode() {
     return e ? (atoi(e) != 0 ? 1 : 0) : PTILES_DEFAULT;
 }
 
-static int encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
-                              int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets,
-                              int32_t* d_status, int32_t* d_err, void* hip_stream, const uint32_t* d_word_bits,
-                              const uint32_t* d_gap_bits, const uint32_t* d_first_bits = nullptr,
-                              const uint32_t* d_alone_bits = nullptr) {
+// (declared in hutk_internal.h: hutk_special.hip encodes the pieces between special tokens with it)
+extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                                          int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets,
+                                          int32_t* d_status, int32_t* d_err, void* hip_stream, const uint32_t* d_word_bits,
+                                          const uint32_t* d_gap_bits, const uint32_t* d_first_bits,
+                                          const uint32_t* d_alone_bits) {
     if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to encode on");
     if (n_docs < 0 || n_bytes < 0 || !d_offsets || !d_out_offsets || (n_bytes > 0 && (!d_bytes || !d_ids_out)))

@@ -1,5 +1,5 @@
 // hutk_host.h -- what the C entry points of every direction share (hutk_api.cpp, hutk_decode.hip, hutk_spans.hip,
-// hutk_collate.hip, hutk_train.hip; DESIGN.md section 1, "Host layer").  Host code only: no kernel uses any of it.
+// hutk_special.hip, hutk_collate.hip, hutk_train.hip; DESIGN.md section 1, "Host layer").  Host code only: no kernel uses any of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,6 +95,29 @@ struct hutk_ctx {
     DevBuf<int64_t> sp_chunk, sp_sel, ss_spans;
     DevBuf<int32_t> sp_ok;
     uint32_t dec_max_len = 0;  // the longest decoded token, in bytes
+
+    // special tokens (hutk_special.hip): the set as hutk_ctx_set_special_tokens validated it, its tables on the host and
+    // on the device, and the workspace of hutk_encode_special_batch_device
+    struct Specials {
+        int64_t n = 0;                 // pairs in the set; 0: none installed
+        std::vector<uint8_t> blob;     // the strings, end to end
+        std::vector<uint32_t> off;     // [n + 1] into blob
+        std::vector<int32_t> ids;      // [n]
+        std::vector<uint2> slots;      // open-addressed set of the strings: {hash of the bytes, index | length << 16}
+        std::vector<uint32_t> filt;    // three 256-bit sets: first bytes, second bytes, lengths
+        uint32_t mask = 0, max_len = 0, n_first = 0, first[4] = {0, 0, 0, 0};
+        int64_t last_matches = 0;
+        DevBuf<uint8_t> d_blob, w_mlen, w_sel;
+        DevBuf<uint32_t> d_off, d_filt;
+        DevBuf<uint2> d_slots;
+        DevBuf<int32_t> d_ids, w_pspecial, w_pstatus, w_pids;
+        DevBuf<int64_t> w_tile, w_mstart, w_poff, w_first, w_poo, w_blk, w_dst;
+        void release() {
+            d_blob.release(); w_mlen.release(); w_sel.release(); d_off.release(); d_filt.release(); d_slots.release();
+            d_ids.release(); w_pspecial.release(); w_pstatus.release(); w_pids.release(); w_tile.release();
+            w_mstart.release(); w_poff.release(); w_first.release(); w_poo.release(); w_blk.release(); w_dst.release();
+        }
+    } sx;
 
     // staging for the host-buffer entry point
     DevBuf<uint8_t> s_bytes;

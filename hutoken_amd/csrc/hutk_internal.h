@@ -240,4 +240,12 @@ LoadError load_tables(const char* vocab_path, const char* special_path, const ch
 // hutk_api.cpp: set the message hutk_last_error() returns; returns `code` (every file with entry points reports through it)
 int api_set_error(int code, const std::string& msg);
 
+// hutk_api.cpp: the encode behind hutk_encode_batch_device, on device buffers and `hip_stream` (its checks, its
+// workspace, every kernel of the direction).  d_word_bits / d_gap_bits, d_first_bits / d_alone_bits: the bitmaps of the
+// regex pre-token path, null for the hand-written splitter.  hutk_special.hip encodes its pieces with it.
+int encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                       int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err,
+                       void* hip_stream, const uint32_t* d_word_bits, const uint32_t* d_gap_bits,
+                       const uint32_t* d_first_bits = nullptr, const uint32_t* d_alone_bits = nullptr);
+
 }  // namespace hutk

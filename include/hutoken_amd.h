@@ -388,6 +388,65 @@ int hutk_token_spans_device(hutk_ctx* ctx, const uint8_t* d_bytes, const int64_t
 int hutk_token_spans(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, const int32_t* ids,
                      const int64_t* id_offsets, int unit, int out_width, void* spans, int32_t* status);
 
+/* ---- special tokens --------------------------------------------------------------------------------------
+ * Byte strings of the text that encode as ONE id each ("<|endoftext|>", chat-template markers), matched on the GPU.  The
+ * reference has no counterpart: it parses a special_token_id argument and drops it, and its word splitter cuts such a
+ * marker into pieces before any table is asked.  hutk_encode_batch, hutk_encode_batch_device and hutk_encode never look
+ * at the set: they stay bit-exact with the reference.
+ *
+ * THE SET.  hutk_ctx_set_special_tokens installs n pairs (string i = bytes[offsets[i] .. offsets[i+1]), ids[i]) in place
+ * of any earlier set; n == 0 removes it (the pointers may then be NULL).  HUTK_E_VALUE, and the set in force stays, for:
+ * more than 1024 pairs, an empty string, a string of more than 255 bytes, a 0x00 byte, two equal strings, an id < 0.  An
+ * id need not be a vocabulary line.  On a host-only context (device = -2) the call validates and builds the tables, no
+ * more.  hutk_ctx_special_token_count: the pairs installed.
+ *
+ * MATCHING.  Inside one document, from left to right: at the cursor a special string matches when its bytes equal the
+ * text there and it ends at or before the document's end (a match never spans two documents); of several that match at
+ * one start the longest is taken, and if the longer ones fail the shorter one that matches; the cursor moves to the
+ * match's end, else one byte on.  Leftmost first, then longest, never overlapping: "aa" on "aaaaa" matches at 0 and 2;
+ * {"ab", "bc"} on "abc" takes "ab" and leaves "c" as text.
+ *
+ * ENCODING.  The matches cut a document into pieces: text, special, text, ..., text (text pieces may be empty).  Its ids
+ * are, in order: for a text piece exactly what hutk_encode_batch_device returns for the piece AS A DOCUMENT OF ITS OWN --
+ * so a context with a prefix gives every non-empty text piece its prefix (Hugging Face's "legacy" behaviour) -- and for a
+ * special piece its one id.  No set installed, or no match in the batch: ids, offsets, status and *d_err are those of
+ * hutk_encode_batch_device.  A DELIBERATE DIFFERENCE from "the document ends there": a text piece that holds a word of
+ * more than 262144 bytes ends in front of that word, ONLY that piece; the pieces behind it are encoded as ever, the
+ * document's status is HUTK_DOC_WORD_TOO_LARGE (the worst of its pieces') and *d_err the note HUTK_E_WORD_TOO_LARGE.
+ *
+ * hutk_special_ids_capacity: an upper bound on the ids of a batch.  Proof.  Let U = the most units an input item can
+ * become and P = the prefix units a document can get, so that hutk_ids_capacity(b, d) = b U + d P + 1 bounds the ids of
+ * any batch of b bytes in d documents.  With k matches the text pieces are n_docs + k documents of at most n_bytes - k
+ * bytes together (a match covers at least one byte) and the special pieces give k ids:
+ *     ids <= (n_bytes - k) U + (n_docs + k) P + k = n_bytes U + n_docs P + k (P + 1 - U),      0 <= k <= n_bytes.
+ * For P + 1 <= U the maximum is at k = 0, otherwise at k = n_bytes; in both cases
+ *     ids <= n_bytes max(U, P + 1) + n_docs P,
+ * and the function returns that + 1.  It is never below hutk_ids_capacity (which alone is NOT a bound for a context with
+ * a prefix: every match can add one more prefix).
+ *
+ * hutk_encode_special_batch_device: the arguments of hutk_encode_batch_device, work enqueued on hip_stream (NULL: the
+ * context's stream).  Unlike that call it SYNCHRONISES THE STREAM ONCE, after the scan for matches: the host needs their
+ * number to size the piece-wise encode.  With zero matches it then runs the plain encode straight into the caller's
+ * buffers; otherwise cut, encode and stitch are enqueued and the call returns without waiting for them.  A context with a
+ * regex pattern: HUTK_E_UNSUPPORTED at the call (as the token spans); ids_cap below hutk_special_ids_capacity() - 1:
+ * HUTK_E_CAPACITY, nothing is enqueued; a NULL buffer: HUTK_E_ARG.  The special pieces are encoded too and their ids
+ * dropped, so a marker that is not valid UTF-8 fails a character-mode context like any such text.  Runs on the context's
+ * first device, serialised with the other calls on the context; the workspace grows by about 2 bytes per input byte
+ * and, with matches, by a second id buffer.  hutk_encode_special_batch: host buffers (copies, calls the device form,
+ * waits; one device, no chunking); returns HUTK_OK, the note HUTK_E_WORD_TOO_LARGE, or the error.
+ * hutk_special_last_matches: the matches the last of these calls found.  hutk_debug_special_tile_bytes: the bytes one
+ * workgroup of the scan owns (a match belongs to the workgroup that owns its first byte). */
+int hutk_ctx_set_special_tokens(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, const int32_t* ids, int64_t n);
+int64_t hutk_ctx_special_token_count(const hutk_ctx* ctx);
+int64_t hutk_special_ids_capacity(const hutk_ctx* ctx, int64_t n_bytes, int64_t n_docs);
+int hutk_encode_special_batch_device(hutk_ctx* ctx, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                                     int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets,
+                                     int32_t* d_status, int32_t* d_err, void* hip_stream);
+int hutk_encode_special_batch(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                              int32_t* ids_out, int64_t ids_cap, int64_t* out_offsets, int32_t* status);
+int64_t hutk_special_last_matches(const hutk_ctx* ctx);
+int hutk_debug_special_tile_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

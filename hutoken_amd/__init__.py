@@ -27,6 +27,8 @@ Offset mapping (not in the reference): `token_spans_device` turns the same devic
 Special tokens (not in the reference, which cuts "<|endoftext|>" into eight ids): `set_special_tokens` installs
 {string: id}; `encode_special`, `batch_encode_special` and `encode_special_packed_device` match them on the GPU and give
 each ONE id, the text between them encoded as ever (csrc/hutk_special.hip).  `encode` / `batch_encode` never look at them.
+`decode_special` / `batch_decode_special` turn such ids back into text (`skip_special_tokens=True` leaves the markers out),
+`decode_packed_device` is the device-tensor form of both decodes; `decode` / `batch_decode` never look at the set either.
 
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
@@ -43,7 +45,8 @@ __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_pack
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
-           "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device"]
+           "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device",
+           "decode_special", "batch_decode_special", "decode_packed_device"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -889,8 +892,9 @@ def encode_special_packed_device(d_bytes, d_offsets, check=True):
     """encode_packed_device with the special tokens of set_special_tokens: every match (leftmost first, then longest,
     inside one document) becomes its one id, the text between the matches is encoded as documents of its own.  Same
     tensors in, the same pair out -- (ids int32[capacity], out_offsets int64[n+1]) -- so collate_padded,
-    SequencePacker.add and the spans' callers take it unchanged (spans over special ids are not defined).  Synchronises
-    the current torch stream once, after the scan for matches."""
+    SequencePacker.add and the spans' callers take it unchanged (spans over special ids are not defined), and
+    decode_packed_device(ids, out_offsets, special=True) gives the text back.  Synchronises the current torch stream once,
+    after the scan for matches."""
     import torch
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
@@ -953,3 +957,129 @@ def encode_special(text):
     if "\0" in text:
         raise ValueError("embedded null character")
     return batch_encode_special([text])[0]
+
+
+def _flat_ids(tokens, batch):
+    """The argument checks of decode / batch_decode -> (ids int32, id_offsets int64)."""
+    import numpy as np
+    if not isinstance(tokens, list):
+        raise TypeError("Failed to parse arguments. Expected a single list of tokens." if batch else
+                        "Argument must be a list of integers")
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT_DECODE)
+    if not batch:
+        ids = np.asarray([int(t) for t in tokens], dtype=np.int64).astype(np.int32)
+        return ids, np.array([0, len(ids)], dtype=np.int64)
+    if len(tokens) <= 0:
+        raise ValueError("No tokens provided.")
+    for item in tokens:
+        if not isinstance(item, list):
+            raise TypeError("Each item must be a list of integers.")
+    offs = np.zeros(len(tokens) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, tokens), dtype=np.int64, count=len(tokens)), out=offs[1:])
+    flat = np.fromiter((int(t) for item in tokens for t in item), dtype=np.int64, count=int(offs[-1])).astype(np.int32)
+    return flat, offs
+
+
+def _skip_flag(skip_special_tokens):
+    if not isinstance(skip_special_tokens, (bool, int)):
+        raise TypeError("skip_special_tokens must be a bool, not %s" % type(skip_special_tokens).__name__)
+    return _capi.DECODE_SKIP_SPECIAL if skip_special_tokens else 0
+
+
+def decode_special(tokens, skip_special_tokens=False):
+    """decode with the special tokens of set_special_tokens: a special id becomes its string (or nothing, with
+    skip_special_tokens=True), and a context with a prefix strips it behind every marker, so that
+    decode_special(encode_special(text)) == text.  Argument checks and exceptions are those of decode."""
+    flags = _skip_flag(skip_special_tokens)
+    try:
+        ids, offs = _flat_ids(tokens, False)
+        out, _oo, _st = _ctx.decode_special_packed(ids, offs, flags)
+        return _ids_to_text(out.tobytes())
+    except ValueError as e:
+        traceback.print_exc(file=sys.stderr)
+        raise ValueError(f"hutoken: Error decoding tokens {tokens}: {e}")
+    except Exception as e:
+        traceback.print_exc(file=sys.stderr)
+        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+
+
+def batch_decode_special(tokens, skip_special_tokens=False):
+    """batch_decode with the special tokens of set_special_tokens -> list[str]; see decode_special."""
+    flags = _skip_flag(skip_special_tokens)
+    try:
+        flat, offs = _flat_ids(tokens, True)
+        out, oo, _st = _ctx.decode_special_packed(flat, offs, flags)
+        raw = out.tobytes()
+        bounds = oo.tolist()
+        return [_ids_to_text(raw[bounds[i]:bounds[i + 1]]) for i in range(len(tokens))]
+    except Exception as e:
+        traceback.print_exc(file=sys.stderr)
+        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+
+
+def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens=False, n_ids=None, check=True):
+    """The counterpart of encode_packed_device: device tensors in (ids int32, id_offsets int64[n+1], as the encode
+    functions return them), device tensors out: (bytes uint8[total], out_offsets int64[n+1]); the text of document i is
+    bytes[out_offsets[i]:out_offsets[i+1]].  special=False is the plain decode, special=True the one with the special
+    tokens of set_special_tokens (encode_special_packed_device's ids), skip_special_tokens=True leaves their strings out.
+    On the current torch stream: a sizes call, ONE synchronising read of the total, then the text call; n_ids= saves the
+    read of id_offsets[-1].  check=True synchronises once more and raises ValueError for an id out of range and
+    RuntimeError for a token that cannot be decoded on its own."""
+    if not isinstance(special, (bool, int)):
+        raise TypeError("special must be a bool, not %s" % type(special).__name__)
+    flags = _skip_flag(skip_special_tokens)
+    if flags and not special:
+        raise ValueError("skip_special_tokens=True needs special=True: the plain decode knows no special tokens")
+    _ragged_args(d_ids, d_id_offsets, n_ids)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT_DECODE)
+    import torch
+    dev = d_ids.device
+    if dev.index != _capi.load().hutk_device_ordinal(_ctx.handle):
+        raise ValueError("the tensors must be on the context's device: the decode runs there")
+    n_docs = d_id_offsets.numel() - 1
+    n_ids = _n_ids(d_ids, d_id_offsets, n_ids)
+    oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    p_ids = d_ids.data_ptr() if n_ids else 0
+
+    def call(out, cap):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if special:
+            _ctx.decode_special_device(p_ids, d_id_offsets.data_ptr(), n_docs, n_ids, flags, out, cap, oo.data_ptr(), 0,
+                                       err.data_ptr(), stream)
+        else:
+            _ctx.decode_device(p_ids or None, d_id_offsets.data_ptr(), n_docs, n_ids, out or None, cap, oo.data_ptr(), None,
+                               err.data_ptr(), stream)
+
+    def both():
+        call(0, 0)
+        total = int(oo[-1].item())  # the one synchronisation the result's size needs
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        if total:
+            call(out.data_ptr(), total)
+        return out[:total]
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            out = both()
+        else:  # (a NULL stream would mean the context's own stream to the C ABI: see _texts_to_device)
+            side = _side_streams.get(dev.index)
+            if side is None:
+                side = _side_streams[dev.index] = torch.cuda.Stream(dev)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                out = both()
+            cur.wait_stream(side)
+            for t in (d_ids, d_id_offsets, oo, err):
+                t.record_stream(side)
+            out.record_stream(cur)
+    if check:
+        code = int(err.item())
+        if code == _capi.E_VALUE:
+            raise ValueError("hutoken_amd: decode_packed_device: Element must be non-negative and less than vocab size.")
+        if code:
+            raise RuntimeError("hutoken_amd: decode_packed_device: device-side error %d%s" % (
+                code, " (a token cannot be decoded on its own)" if code == _capi.E_UNSUPPORTED else ""))
+    return out, oo

@@ -31,12 +31,13 @@ EXPORTS = [
     "hutk_token_spans_device", "hutk_token_spans",
     "hutk_ctx_set_special_tokens", "hutk_ctx_special_token_count", "hutk_special_ids_capacity",
     "hutk_encode_special_batch_device", "hutk_encode_special_batch", "hutk_special_last_matches",
-    "hutk_debug_special_tile_bytes",
+    "hutk_debug_special_tile_bytes", "hutk_decode_special_batch_device", "hutk_decode_special_batch",
 ]
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
 NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
 SPANS_BYTES, SPANS_CHARS = 0, 1
+DECODE_SKIP_SPECIAL = 1  # HUTK_DECODE_SKIP_SPECIAL
 
 _lib = None
 
@@ -203,6 +204,11 @@ def load(build_if_missing=True):
         L.hutk_special_last_matches.argtypes = [vp]
         L.hutk_debug_special_tile_bytes.restype = i32
         L.hutk_debug_special_tile_bytes.argtypes = []
+    if hasattr(L, "hutk_decode_special_batch_device"):
+        L.hutk_decode_special_batch_device.restype = i32
+        L.hutk_decode_special_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
+        L.hutk_decode_special_batch.restype = i32
+        L.hutk_decode_special_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
     _lib = L
     return L
 
@@ -517,6 +523,32 @@ class Context:
         """hutk_encode_special_batch_device on raw device pointers (ints): synchronises `stream` once, after the scan."""
         raise_for(load().hutk_encode_special_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
                                                           d_ids or None, ids_cap, d_out_offsets or None,
+                                                          d_status or None, d_err or None, stream or None))
+
+    def decode_special_packed(self, ids, id_offsets, flags=0):
+        """decode_packed with the context's special tokens (hutk_decode_special_batch; flags: 0 or DECODE_SKIP_SPECIAL):
+        -> (bytes uint8, out_offsets int64[n+1], status int32[n]).  Two calls: sizes, then the text."""
+        import numpy as np
+        L = load()
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
+        n = len(id_offsets) - 1
+        oo = np.zeros(n + 1, dtype=np.int64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        pid = ids.ctypes.data if len(ids) else None
+        raise_for(L.hutk_decode_special_batch(self._h, pid, id_offsets.ctypes.data, n, flags, None, 0, oo.ctypes.data,
+                                              st.ctypes.data))
+        total = int(oo[n])
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        raise_for(L.hutk_decode_special_batch(self._h, pid, id_offsets.ctypes.data, n, flags, out.ctypes.data, total,
+                                              oo.ctypes.data, st.ctypes.data))
+        return out[:total], oo, st[:n]
+
+    def decode_special_device(self, d_ids, d_id_offsets, n_docs, n_ids, flags, d_bytes_out, bytes_cap, d_out_offsets,
+                              d_status=0, d_err=0, stream=0):
+        """hutk_decode_special_batch_device on raw device pointers (ints); asynchronous on `stream`, never synchronises."""
+        raise_for(load().hutk_decode_special_batch_device(self._h, d_ids or None, d_id_offsets or None, n_docs, n_ids,
+                                                          flags, d_bytes_out or None, bytes_cap, d_out_offsets or None,
                                                           d_status or None, d_err or None, stream or None))
 
     def profile(self, enable):

@@ -184,30 +184,12 @@ int upload_tables(hutk_ctx* c) {
     }
     // ---- decode direction ----
     {
-        const size_t N = (size_t)T.dec_n;
-        std::vector<uint2> ent(N ? N : 1), sent;
-        c->dec_max_len = 0;
-        auto pack = [&](uint32_t off, uint32_t len, bool bad) {
-            if (bad) return make_uint2(DEC_TAG_BAD, 0u);
-            if (len > c->dec_max_len) c->dec_max_len = len;
-            if (len > DEC_INLINE_MAX) return make_uint2(DEC_TAG_LONG | (len << 8), off);
-            uint64_t v = len;
-            for (uint32_t j = 0; j < len; j++) v |= (uint64_t)T.dec_blob[off + j] << (8 * (j + 1));
-            return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-        };
-        // DEC_F_PFX_PARTIAL only matters at the front of a document
-        for (size_t i = 0; i < N; i++)
-            ent[i] = pack(T.dec_off[i], T.dec_len[i], T.dec_len[i] == DEC_BAD || (T.dec_flag[i] & ~DEC_F_PFX_PARTIAL));
+        std::vector<uint2> ent, sent;
+        dec_pack_tables(T, ent, sent, c->dec_max_len);
         HUTK_HIP_TRY(c->d_dec_ent.reserve(ent.size()));
         HUTK_HIP_TRY(hipMemcpy(c->d_dec_ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice));
         c->dec.sent = nullptr;
-        if (!T.dec_slen.empty()) {
-            sent.resize(N ? N : 1);
-            for (size_t i = 0; i < N; i++) {
-                const bool strip = T.dec_slen[i] != DEC_NOSTRIP;
-                const uint32_t len = strip ? T.dec_slen[i] : T.dec_len[i];
-                sent[i] = pack(strip ? T.dec_soff[i] : T.dec_off[i], len, len == DEC_BAD || T.dec_flag[i]);
-            }
+        if (!sent.empty()) {
             HUTK_HIP_TRY(c->d_dec_sent.reserve(sent.size()));
             HUTK_HIP_TRY(hipMemcpy(c->d_dec_sent.p, sent.data(), sent.size() * sizeof(uint2), hipMemcpyHostToDevice));
             c->dec.sent = c->d_dec_sent.p;
@@ -300,7 +282,7 @@ void destroy(hutk_ctx* c) {
         c->w_tile_u32.release(); c->w_doc_pos.release(); c->w_counters.release(); c->w_tile_i64.release();
         c->w_exc.release(); c->w_exc_quad.release(); c->w_exc_mid.release(); c->w_exc_wave.release();
         c->d_dec_ent.release(); c->d_dec_sent.release(); c->d_dec_blob.release(); c->dw_first.release();
-        c->dw_state.release(); c->dw_tfd.release(); c->ds_ids.release(); c->ds_status.release();
+        c->dw_state.release(); c->dw_tfd.release(); c->dw_ids.release(); c->ds_ids.release(); c->ds_status.release();
         c->ds_offs.release(); c->ds_oo.release(); c->ds_bytes.release(); c->w_err.release();
         c->sp_bits.release(); c->sp_in_chunk.release(); c->sp_chunk.release(); c->sp_sel.release(); c->ss_spans.release();
         c->sp_ok.release();

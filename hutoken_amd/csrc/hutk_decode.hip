@@ -15,7 +15,8 @@
 //   k_dec_tail    out_offsets of the (empty) documents at the very end
 //
 // The direction's C entry points are at the end of the file: hutk_decode_batch_device (device buffers, asynchronous) and
-// hutk_decode_batch (host buffers, staged through the context's).
+// hutk_decode_batch (host buffers, staged through the context's), in front of them what they share with the decode of
+// special ids (hutk_special.hip): decode_device_impl and decode_host_impl.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -356,14 +357,11 @@ void launch_dec(const DecTables& t, const DecArgs& d, hipStream_t s) {
 
 }  // namespace hutk
 
-using namespace hutk;
+namespace hutk {
 
-extern "C" {
-
-int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
-                             int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
-                             int32_t* d_status, int32_t* d_err, void* hip_stream) {
-    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, const int32_t* d_ids, const int64_t* d_id_offsets,
+                       int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
+                       int32_t* d_status, int32_t* d_err, void* hip_stream) {
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
     if (n_docs < 0 || n_ids < 0 || !d_id_offsets || !d_out_offsets || (n_ids > 0 && !d_ids))
         return api_set_error(HUTK_E_ARG, "bad argument");
@@ -378,6 +376,7 @@ int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d
     HUTK_HIP_TRY(c->dw_state.reserve((size_t)n_tiles + 8));
     HUTK_HIP_TRY(c->dw_tfd.reserve((size_t)n_tiles + 1));
     HUTK_HIP_TRY(c->w_err.reserve(1));
+    if (sp) HUTK_HIP_TRY(c->dw_ids.reserve((size_t)n_ids + 16));
     DecArgs D{};
     D.ids = d_ids;
     D.id_offsets = d_id_offsets;
@@ -394,7 +393,7 @@ int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d
     D.tile_first_doc = c->dw_tfd.p;
     D.help_after = getenv("HUTK_DEC_HELP_AFTER") ? (uint32_t)atol(getenv("HUTK_DEC_HELP_AFTER")) : (1u << 14);  // (0: tests of the fallback)
     HUTK_HIP_TRY(hipMemsetAsync(D.err, 0, 4, s));
-    const bool strip = c->dec.sent != nullptr;  // the first-token bitmap is only needed to strip a prefix
+    const bool strip = t.sent != nullptr;  // the first-token bitmap is only needed to strip a prefix
     if (strip) HUTK_HIP_TRY(hipMemsetAsync(D.first_bits, 0, (size_t)(n_ids / 32 + 4) * 4, s));
     else D.first_bits = nullptr;
     if (d_status && n_docs) HUTK_HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n_docs * 4, s));
@@ -403,15 +402,18 @@ int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d
         return HUTK_OK;
     }
     if (strip) launch_dec_mark(D, s);
+    if (sp) {  // behind k_dec_mark: the pass adds first-token bits of its own
+        launch_dec_remap(*sp, d_ids, c->dw_ids.p, n_ids, D.first_bits, s);
+        D.ids = c->dw_ids.p;
+    }
     HUTK_HIP_TRY(hipMemsetAsync(D.tile_state, 0, (size_t)n_tiles * 8, s));
-    launch_dec(c->dec, D, s);
+    launch_dec(t, D, s);
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }
 
-int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* bytes_out,
-                      int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
-    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
+                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
     if (n_docs < 0 || !id_offsets || !out_offsets) return api_set_error(HUTK_E_ARG, "bad argument");
@@ -428,8 +430,12 @@ int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets
     if (bytes_out && bytes_cap > 0) HUTK_HIP_TRY(c->ds_bytes.reserve((size_t)bytes_cap + 16));
     if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
     HUTK_HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-    int rc = hutk_decode_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, bytes_out ? c->ds_bytes.p : nullptr,
-                                      bytes_cap, c->ds_oo.p, c->ds_status.p, c->w_err.p, s);
+    uint8_t* d_bytes = bytes_out ? c->ds_bytes.p : nullptr;
+    int rc = special_flags < 0
+                 ? hutk_decode_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, d_bytes, bytes_cap, c->ds_oo.p,
+                                            c->ds_status.p, c->w_err.p, s)
+                 : hutk_decode_special_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, special_flags, d_bytes,
+                                                    bytes_cap, c->ds_oo.p, c->ds_status.p, c->w_err.p, s);
     if (rc) return rc;
     int32_t err = 0;
     HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->ds_oo.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -439,6 +445,26 @@ int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets
     if (bytes_out && err == HUTK_OK && out_offsets[n_docs] > 0)
         HUTK_HIP_TRY(hipMemcpy(bytes_out, c->ds_bytes.p, (size_t)out_offsets[n_docs], hipMemcpyDeviceToHost));
     return err == HUTK_OK ? HUTK_OK : api_set_error(err, device_error_message(Direction::Decode, err));
+}
+
+}  // namespace hutk
+
+using namespace hutk;
+
+extern "C" {
+
+int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
+                             int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
+                             int32_t* d_status, int32_t* d_err, void* hip_stream) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    return decode_device_impl(c, c->dec, nullptr, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets,
+                              d_status, d_err, hip_stream);
+}
+
+int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* bytes_out,
+                      int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    return decode_host_impl(c, -1, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
 }
 
 }  // extern "C"

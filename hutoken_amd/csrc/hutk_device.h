@@ -219,6 +219,26 @@ int64_t dec_tile_ids();
 void launch_dec_mark(const DecArgs& d, hipStream_t s);
 void launch_dec(const DecTables& t, const DecArgs& d, hipStream_t s);
 
+// ---- decode of special ids (hutk_special.hip, k_dsp_remap): a pass over the ids IN FRONT of the decode kernels ----
+// The decode tables are extended by one entry per distinct special id (index k: entry n_vocab + k); the pass writes a
+// copy of the ids in which a special id is n_vocab + k, an ordinary id is itself and every other id is -1 (out of range
+// for the extended tables too, so that an id in [n_vocab, n_vocab + specials) does not decode as somebody's marker).
+constexpr int DSP_SLOTS = 4096;  // at most 1024 ids: a quarter full
+constexpr uint32_t DSP_EMPTY = 0xFFFFFFFFu;
+enum : int32_t {
+    DSP_BITS_NONE = 0,   // no prefix to strip: the first-token bitmap is not used
+    DSP_BITS_AFTER = 1,  // specials are emitted: the token behind one starts a run of its own (bit i + 1)
+    DSP_BITS_SKIP = 2    // specials are dropped: a document's first token bit moves to its first ordinary id
+};
+struct DecSpecial {
+    const uint2* slots;  // [DSP_SLOTS] {id, k}, y == DSP_EMPTY: empty; linear probing from dsp_slot(id)
+    int32_t id_min, id_max;  // of the set: almost every ordinary id leaves after two compares
+    int32_t n_vocab;
+    int32_t bits;        // DSP_BITS_*
+};
+void launch_dec_remap(const DecSpecial& sp, const int32_t* ids, int32_t* ids_out, int64_t n_ids, uint32_t* first_bits,
+                      hipStream_t s);
+
 // ---- token spans (hutk_spans.hip): which stretch of its document each id covers ----
 // Rank structure over the batch's character starts (bytes b with (b & 0xC0) != 0x80), built per call: one 64-bit word
 // of start bits per 64 source bytes, the starts before the word inside its chunk of SPAN_CHUNK_BYTES, and the starts

@@ -85,6 +85,7 @@ struct hutk_ctx {
     DevBuf<uint32_t> dw_first;
     DevBuf<unsigned long long> dw_state;
     DevBuf<int64_t> dw_tfd;
+    DevBuf<int32_t> dw_ids;  // hutk_decode_special_batch_device: the ids with the special ones renumbered
     DevBuf<int32_t> ds_ids, ds_status;
     DevBuf<int64_t> ds_offs, ds_oo;
     DevBuf<uint8_t> ds_bytes;
@@ -107,6 +108,16 @@ struct hutk_ctx {
         std::vector<uint32_t> filt;    // three 256-bit sets: first bytes, second bytes, lengths
         uint32_t mask = 0, max_len = 0, n_first = 0, first[4] = {0, 0, 0, 0};
         int64_t last_matches = 0;
+        // decode direction (hutk_decode_special_batch_device): the context's decode tables followed by one entry per
+        // DISTINCT special id, in the order of the ids' first pairs; x_sent: the same behind the first-token entries
+        // (a special's entry there equals its x_ent entry; empty without a prefix); *_skip: the specials' entries have
+        // length 0 (HUTK_DECODE_SKIP_SPECIAL); x_blob: the context's blob, then the strings of more than 7 bytes
+        std::vector<uint2> x_ent, x_sent, x_ent_skip, x_sent_skip, x_slots;
+        std::vector<uint8_t> x_blob;
+        int64_t x_n = 0;  // distinct ids
+        int32_t x_min = 0, x_max = 0;
+        DevBuf<uint2> dx_ent, dx_sent, dx_ent_skip, dx_sent_skip, dx_slots;
+        DevBuf<uint8_t> dx_blob;
         DevBuf<uint8_t> d_blob, w_mlen, w_sel;
         DevBuf<uint32_t> d_off, d_filt;
         DevBuf<uint2> d_slots;
@@ -116,6 +127,8 @@ struct hutk_ctx {
             d_blob.release(); w_mlen.release(); w_sel.release(); d_off.release(); d_filt.release(); d_slots.release();
             d_ids.release(); w_pspecial.release(); w_pstatus.release(); w_pids.release(); w_tile.release();
             w_mstart.release(); w_poff.release(); w_first.release(); w_poo.release(); w_blk.release(); w_dst.release();
+            dx_ent.release(); dx_sent.release(); dx_ent_skip.release(); dx_sent_skip.release(); dx_slots.release();
+            dx_blob.release();
         }
     } sx;
 
@@ -216,6 +229,48 @@ inline int upload_regex_bitmaps(hutk_ctx* c, hipStream_t s, const std::vector<ui
     }
     return HUTK_OK;
 }
+
+// The decode tables of a context as the kernels read them (DecTables): one entry per vocabulary line in `ent`, and in
+// `sent` (a context with a prefix; empty otherwise) the entry of the same token at the front of a document.
+// max_len: the longest decoded token.  hutk_api.cpp uploads them; hutk_special.hip extends them by the special ids.
+inline uint2 dec_pack_entry(const uint8_t* bytes, uint32_t off, uint32_t len, bool bad) {
+    if (bad) return make_uint2(DEC_TAG_BAD, 0u);
+    if (len > DEC_INLINE_MAX) return make_uint2(DEC_TAG_LONG | (len << 8), off);
+    uint64_t v = len;
+    for (uint32_t j = 0; j < len; j++) v |= (uint64_t)bytes[off + j] << (8 * (j + 1));
+    return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+}
+inline void dec_pack_tables(const Tables& T, std::vector<uint2>& ent, std::vector<uint2>& sent, uint32_t& max_len) {
+    const size_t N = (size_t)T.dec_n;
+    ent.assign(N ? N : 1, make_uint2(0, 0));
+    sent.clear();
+    max_len = 0;
+    auto pack = [&](uint32_t off, uint32_t len, bool bad) {
+        if (!bad && len > max_len) max_len = len;
+        return dec_pack_entry(T.dec_blob.data(), off, len, bad);
+    };
+    // DEC_F_PFX_PARTIAL only matters at the front of a document
+    for (size_t i = 0; i < N; i++)
+        ent[i] = pack(T.dec_off[i], T.dec_len[i], T.dec_len[i] == DEC_BAD || (T.dec_flag[i] & ~DEC_F_PFX_PARTIAL));
+    if (T.dec_slen.empty()) return;
+    sent.assign(N ? N : 1, make_uint2(0, 0));
+    for (size_t i = 0; i < N; i++) {
+        const bool strip = T.dec_slen[i] != DEC_NOSTRIP;
+        const uint32_t len = strip ? T.dec_slen[i] : T.dec_len[i];
+        sent[i] = pack(strip ? T.dec_soff[i] : T.dec_off[i], len, len == DEC_BAD || T.dec_flag[i]);
+    }
+}
+
+// hutk_decode.hip: the decode behind hutk_decode_batch_device (the caller has checked c and holds no lock yet): its
+// checks, its workspace, every kernel of the direction, with the tables `t`.  sp != nullptr: the ids are renumbered by
+// launch_dec_remap first (hutk_special.hip), and t are the extended tables.
+int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, const int32_t* d_ids, const int64_t* d_id_offsets,
+                       int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
+                       int32_t* d_status, int32_t* d_err, void* hip_stream);
+// ... and the staging of hutk_decode_batch around it.  special_flags < 0: the plain decode; otherwise
+// hutk_decode_special_batch_device with these flags.
+int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
+                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
 
 // What the host-buffer entry points say about the error word a direction's kernels left (err != HUTK_OK).
 enum class Direction { Encode, Decode, Spans };

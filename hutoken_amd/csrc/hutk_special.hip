@@ -21,6 +21,10 @@
 //                 from there; 16-byte stores
 // No workgroup waits for another one: every order is count, scan, write over three launches.
 //
+// The other direction, ids -> text with special ids among them (hutk_decode_special_batch_device), needs ONE kernel here:
+//   k_dsp_remap   a pass over the ids in front of the decode kernels of hutk_decode.hip, which then run unchanged over
+//                 tables that hutk_ctx_set_special_tokens extended by the special strings (build_decode_specials)
+//
 // The C entry points are at the end of the file.
 #include <hip/hip_runtime.h>
 
@@ -446,6 +450,74 @@ __global__ __launch_bounds__(CP_THREADS) void k_st_copy(SpecArgs A) {
     }
 }
 
+// ---- decode: special ids become entries behind the vocabulary's ----------------------------------------------------
+constexpr int DSP_THREADS = 256, DSP_PER = 4, DSP_TILE = DSP_THREADS * DSP_PER;  // ids per workgroup of the pass
+
+// the same on the host (table build) and on the device (lookup)
+HUTK_HD uint32_t dsp_slot(uint32_t id) { return (id * 0x9E3779B1u) >> 20; }
+static_assert(DSP_SLOTS == 1 << 12, "dsp_slot keeps the top 12 bits");
+
+// index of the special id among the distinct ones, -1: the id is not special
+__device__ __forceinline__ int32_t dsp_index(const DecSpecial& S, int32_t id) {
+    if (id < S.id_min || id > S.id_max) return -1;
+    for (uint32_t s = dsp_slot((uint32_t)id);; s = (s + 1) & (DSP_SLOTS - 1)) {  // (a quarter full at most: it ends)
+        const uint2 e = S.slots[s];
+        if (e.y == DSP_EMPTY) return -1;
+        if ((int32_t)e.x == id) return (int32_t)e.y;
+    }
+}
+
+__device__ __forceinline__ bool dsp_bit(const uint32_t* bits, int64_t i) {
+    return (__hip_atomic_load(&bits[i >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (i & 31)) & 1u;
+}
+
+// out[i] = ids[i] for a vocabulary id, n_vocab + k for the k-th special id, -1 for anything else (an id in
+// [n_vocab, n_vocab + specials) that is not special must NOT reach the extended tables).  first_bits (a context that
+// strips a prefix; k_dec_mark has run) gets the bits the contract adds:
+//   DSP_BITS_AFTER  every run of ordinary ids is a document of its own: bit i + 1 behind a special at i
+//   DSP_BITS_SKIP   the specials are deleted: the lane of a document's first token, when that is special, walks to the
+//                   first id that is not and marks it.  A special never GETS a bit from this pass (a walk ends on an
+//                   ordinary id or on a bit that is set), so a special with a bit is a document's first token; the walk
+//                   stops at the next such token, whose own lane goes on from there: every id is walked over once.
+__global__ __launch_bounds__(DSP_THREADS) void k_dsp_remap(DecSpecial S, const int32_t* ids, int32_t* out, int64_t n_ids,
+                                                           uint32_t* first_bits) {
+    const int64_t i0 = ((int64_t)blockIdx.x * DSP_THREADS + threadIdx.x) * DSP_PER;
+    if (i0 >= n_ids) return;
+    const bool full = i0 + DSP_PER <= n_ids;
+    int32_t id[DSP_PER];
+    if (full && (reinterpret_cast<uintptr_t>(ids) & 15) == 0) {
+        const int4 a = *reinterpret_cast<const int4*>(ids + i0);
+        id[0] = a.x; id[1] = a.y; id[2] = a.z; id[3] = a.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < DSP_PER; k++) id[k] = (i0 + k < n_ids) ? ids[i0 + k] : 0;
+    }
+    int32_t v[DSP_PER];
+#pragma unroll
+    for (int k = 0; k < DSP_PER; k++) {
+        const int64_t i = i0 + k;
+        v[k] = id[k] >= S.n_vocab ? -1 : id[k];
+        if (i >= n_ids) continue;
+        const int32_t x = dsp_index(S, id[k]);
+        if (x < 0) continue;
+        v[k] = S.n_vocab + x;
+        if (S.bits == DSP_BITS_AFTER) {
+            if (i + 1 < n_ids) atomicOr(&first_bits[(i + 1) >> 5], 1u << ((i + 1) & 31));
+        } else if (S.bits == DSP_BITS_SKIP && dsp_bit(first_bits, i)) {
+            int64_t j = i + 1;
+            while (j < n_ids && !dsp_bit(first_bits, j) && dsp_index(S, ids[j]) >= 0) j++;
+            if (j < n_ids) atomicOr(&first_bits[j >> 5], 1u << (j & 31));
+        }
+    }
+    if (full) {  // (out is the context's: 16-byte aligned)
+        *reinterpret_cast<int4*>(out + i0) = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < DSP_PER; k++)
+            if (i0 + k < n_ids) out[i0 + k] = v[k];
+    }
+}
+
 // ---- host: the set -------------------------------------------------------------------------------------------------
 int build_specials(hutk_ctx::Specials& S, const uint8_t* bytes, const int64_t* offsets, const int32_t* ids, int64_t n) {
     if (n > MAX_SPECIALS) return api_set_error(HUTK_E_VALUE, "at most 1024 special tokens");
@@ -517,11 +589,87 @@ int upload_specials(hutk_ctx* c) {
     return HUTK_OK;
 }
 
+// The decode tables of the context extended by the set (hutk_ctx::Specials::x_*): validated and built on the host, whatever
+// the context.  Entry k belongs to the k-th DISTINCT id in the order of the pairs, its bytes are those of the id's first pair.
+int build_decode_specials(const hutk_ctx* c, hutk_ctx::Specials& S) {
+    const Tables& T = c->tab;
+    std::vector<uint2> ent, sent;
+    uint32_t max_len = 0;
+    dec_pack_tables(T, ent, sent, max_len);
+    ent.resize((size_t)T.dec_n);  // (an empty vocabulary has one unused entry)
+    if (!sent.empty()) sent.resize((size_t)T.dec_n);
+    S.x_blob = T.dec_blob;
+    S.x_slots.assign(DSP_SLOTS, make_uint2(0, DSP_EMPTY));
+    S.x_n = 0;
+    S.x_min = INT32_MAX;
+    S.x_max = 0;
+    std::vector<uint2> extra;
+    for (int64_t i = 0; i < S.n; i++) {
+        const int32_t id = S.ids[i];
+        uint32_t s = dsp_slot((uint32_t)id);
+        while (S.x_slots[s].y != DSP_EMPTY && (int32_t)S.x_slots[s].x != id) s = (s + 1) & (DSP_SLOTS - 1);
+        if (S.x_slots[s].y != DSP_EMPTY) continue;  // a later string of the same id: the first one is the id's text
+        S.x_slots[s] = make_uint2((uint32_t)id, (uint32_t)S.x_n++);
+        S.x_min = std::min(S.x_min, id);
+        S.x_max = std::max(S.x_max, id);
+        const uint32_t len = S.off[i + 1] - S.off[i];
+        uint32_t at = S.off[i];
+        const uint8_t* from = S.blob.data();
+        if (len > DEC_INLINE_MAX) {  // (entries start on 4-byte boundaries, as the loader's)
+            S.x_blob.resize((S.x_blob.size() + 3) & ~(size_t)3, 0);
+            at = (uint32_t)S.x_blob.size();
+            S.x_blob.insert(S.x_blob.end(), from + S.off[i], from + S.off[i + 1]);
+            from = S.x_blob.data();
+        }
+        extra.push_back(dec_pack_entry(from, at, len, false));
+    }
+    if (T.dec_n + S.x_n > (int64_t)INT32_MAX) return api_set_error(HUTK_E_UNSUPPORTED, "special tokens: the vocabulary leaves no ids for the decode tables");
+    S.x_blob.resize(((S.x_blob.size() + 3) & ~(size_t)3) + 16, 0);
+    const std::vector<uint2> none(extra.size(), make_uint2(0, 0));  // HUTK_DECODE_SKIP_SPECIAL: no bytes
+    S.x_ent = ent;
+    S.x_ent.insert(S.x_ent.end(), extra.begin(), extra.end());
+    S.x_ent_skip = ent;
+    S.x_ent_skip.insert(S.x_ent_skip.end(), none.begin(), none.end());
+    S.x_sent.clear();
+    S.x_sent_skip.clear();
+    if (!sent.empty()) {
+        S.x_sent = sent;
+        S.x_sent.insert(S.x_sent.end(), extra.begin(), extra.end());
+        S.x_sent_skip = sent;
+        S.x_sent_skip.insert(S.x_sent_skip.end(), none.begin(), none.end());
+    }
+    return HUTK_OK;
+}
+
+template <class V, class D>
+int upload_vec(D& d, const V& v) {
+    HUTK_HIP_TRY(d.reserve(v.size() + 1));
+    if (!v.empty()) HUTK_HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+    return HUTK_OK;
+}
+
+// (behind upload_specials: the device is selected and idle)
+int upload_decode_specials(hutk_ctx* c) {
+    hutk_ctx::Specials& S = c->sx;
+    if (int rc = upload_vec(S.dx_ent, S.x_ent)) return rc;
+    if (int rc = upload_vec(S.dx_ent_skip, S.x_ent_skip)) return rc;
+    if (int rc = upload_vec(S.dx_sent, S.x_sent)) return rc;
+    if (int rc = upload_vec(S.dx_sent_skip, S.x_sent_skip)) return rc;
+    if (int rc = upload_vec(S.dx_slots, S.x_slots)) return rc;
+    return upload_vec(S.dx_blob, S.x_blob);
+}
+
 // prefix units a document can get, units an input item can become: what hutk_ids_capacity multiplies by
 int64_t cap_pad(const hutk_ctx* c) { return hutk_ids_capacity(c, 0, 1) - 1; }
 int64_t cap_units(const hutk_ctx* c) { return hutk_ids_capacity(c, 1, 0) - 1; }
 
 }  // namespace
+
+void launch_dec_remap(const DecSpecial& sp, const int32_t* ids, int32_t* ids_out, int64_t n_ids, uint32_t* first_bits,
+                      hipStream_t s) {
+    hipLaunchKernelGGL(k_dsp_remap, dim3((unsigned)((n_ids + DSP_TILE - 1) / DSP_TILE)), dim3(DSP_THREADS), 0, s, sp, ids,
+                       ids_out, n_ids, first_bits);
+}
 
 }  // namespace hutk
 
@@ -537,10 +685,20 @@ int hutk_ctx_set_special_tokens(hutk_ctx* c, const uint8_t* bytes, const int64_t
         c->sx.n = 0;
         return HUTK_OK;
     }
-    hutk_ctx::Specials fresh;  // (a set that is refused leaves the one in force as it was)
+    hutk_ctx::Specials fresh;  // (a set that is refused leaves the one in force as it was, its decode tables too)
     if (int rc = build_specials(fresh, bytes, offsets, ids, n)) return rc;
+    if (int rc = build_decode_specials(c, fresh)) return rc;
     hutk_ctx::Specials& S = c->sx;
     S.n = 0;
+    S.x_ent.swap(fresh.x_ent);
+    S.x_sent.swap(fresh.x_sent);
+    S.x_ent_skip.swap(fresh.x_ent_skip);
+    S.x_sent_skip.swap(fresh.x_sent_skip);
+    S.x_slots.swap(fresh.x_slots);
+    S.x_blob.swap(fresh.x_blob);
+    S.x_n = fresh.x_n;
+    S.x_min = fresh.x_min;
+    S.x_max = fresh.x_max;
     S.blob.swap(fresh.blob);
     S.off.swap(fresh.off);
     S.ids.swap(fresh.ids);
@@ -550,8 +708,10 @@ int hutk_ctx_set_special_tokens(hutk_ctx* c, const uint8_t* bytes, const int64_t
     S.max_len = fresh.max_len;
     S.n_first = fresh.n_first;
     memcpy(S.first, fresh.first, sizeof S.first);
-    if (!c->host_only)
+    if (!c->host_only) {
         if (int rc = upload_specials(c)) return rc;
+        if (int rc = upload_decode_specials(c)) return rc;
+    }
     S.n = n;
     return HUTK_OK;
 }
@@ -726,6 +886,41 @@ int hutk_encode_special_batch(hutk_ctx* c, const uint8_t* bytes, const int64_t* 
     if (n_ids < 0 || n_ids > ids_cap) return api_set_error(HUTK_E_DEVICE, "hutk_encode_special_batch: bad id count");
     if (n_ids) HUTK_HIP_TRY(hipMemcpy(ids_out, c->s_ids.p, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
     return err;  // HUTK_OK, or the note HUTK_E_WORD_TOO_LARGE (see status)
+}
+
+int hutk_decode_special_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
+                                     int64_t n_ids, int flags, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
+                                     int32_t* d_status, int32_t* d_err, void* hip_stream) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    if (flags & ~HUTK_DECODE_SKIP_SPECIAL) return api_set_error(HUTK_E_ARG, "hutk_decode_special_batch_device: unknown flags");
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    const hutk_ctx::Specials& S = c->sx;
+    if (S.n == 0)  // no set: the plain decode
+        return decode_device_impl(c, c->dec, nullptr, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets,
+                                  d_status, d_err, hip_stream);
+    const bool skip = (flags & HUTK_DECODE_SKIP_SPECIAL) != 0;
+    const bool strip = c->dec.sent != nullptr;
+    DecTables T{};
+    T.ent = skip ? S.dx_ent_skip.p : S.dx_ent.p;
+    T.sent = !strip ? nullptr : skip ? S.dx_sent_skip.p : S.dx_sent.p;
+    T.blob = S.dx_blob.p;
+    T.n = c->dec.n + S.x_n;
+    DecSpecial P{};
+    P.slots = S.dx_slots.p;
+    P.id_min = S.x_min;
+    P.id_max = S.x_max;
+    P.n_vocab = (int32_t)c->dec.n;
+    P.bits = !strip ? DSP_BITS_NONE : skip ? DSP_BITS_SKIP : DSP_BITS_AFTER;
+    return decode_device_impl(c, T, &P, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets, d_status,
+                              d_err, hip_stream);
+}
+
+int hutk_decode_special_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
+                              uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    if (flags & ~HUTK_DECODE_SKIP_SPECIAL) return api_set_error(HUTK_E_ARG, "hutk_decode_special_batch: unknown flags");
+    return decode_host_impl(c, flags, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
 }
 
 }  // extern "C"

@@ -447,6 +447,43 @@ int hutk_encode_special_batch(hutk_ctx* ctx, const uint8_t* bytes, const int64_t
 int64_t hutk_special_last_matches(const hutk_ctx* ctx);
 int hutk_debug_special_tile_bytes(void);
 
+/* DECODING with the set: ids -> text, the other direction of the calls above.  hutk_decode_batch and
+ * hutk_decode_batch_device never look at the set (as the plain encode does not): they stay bit-exact with the reference
+ * and refuse an id that is not a vocabulary line.
+ *
+ * An id is SPECIAL when some installed pair has it -- whether or not it is a vocabulary line as well, and even when that
+ * line cannot be decoded.  Its STRING is the byte string of the first installed pair that carries the id (lowest index);
+ * the bytes are written exactly as installed: a character-mode context maps no special-character values in them.
+ *
+ * flags == 0.  The special ids cut a document's ids into runs of ordinary ids.  The output is, in order, every run
+ * decoded exactly as hutk_decode_batch decodes it AS A DOCUMENT OF ITS OWN, and every special's string.  So a context
+ * with a prefix strips one prefix from the front of the first run and from the front of the run behind every special:
+ * what hutk_encode_special_batch gave every text piece comes off again, and decode(encode(text)) is the text.
+ * flags == HUTK_DECODE_SKIP_SPECIAL.  The output is exactly what hutk_decode_batch gives for the document with its special
+ * ids deleted: they contribute nothing and cause no stripping (for a prefix vocabulary the prefix that stays is the
+ * separator between the pieces).
+ * An id that is neither special nor in [0, number of vocabulary lines): HUTK_DOC_ID_OUT_OF_RANGE and HUTK_E_VALUE -- also
+ * an id just above the vocabulary, which never decodes as somebody's marker.  An ordinary id that cannot be decoded on
+ * its own: HUTK_DOC_ID_UNDECODABLE and HUTK_E_UNSUPPORTED.  As in the plain decode such an id contributes no bytes, its
+ * document is marked, every other token and document is exact.
+ * No set installed: bytes, offsets, status and the error word are those of hutk_decode_batch_device, bit for bit.
+ *
+ * hutk_decode_special_batch_device: the arguments of hutk_decode_batch_device and `flags`, with its promises: bytes_out
+ * == NULL gives out_offsets (the sizes) and status only, HUTK_E_CAPACITY in *d_err when the text does not fit bytes_cap
+ * (nothing is written at or beyond it, offsets and status are complete), d_bytes_out may start at any byte address,
+ * d_ids needs 4-byte alignment (16 take the faster loads).  The call is asynchronous on hip_stream (NULL: the context's)
+ * and NEVER synchronises -- unlike the special encode it needs no count.  It runs on the context's first device,
+ * serialised with the other calls on the context; the workspace grows by 4 bytes per id (a renumbered copy of the ids).
+ * Refused at the call: flag bits other than HUTK_DECODE_SKIP_SPECIAL, a NULL context or buffer (HUTK_E_ARG), a host-only
+ * context (HUTK_E_DEVICE).  Replacing or removing the set takes effect with the next call.
+ * hutk_decode_special_batch: host buffers, staged like hutk_decode_batch and with its return codes. */
+#define HUTK_DECODE_SKIP_SPECIAL 1
+int hutk_decode_special_batch_device(hutk_ctx* ctx, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
+                                     int64_t n_ids, int flags, uint8_t* d_bytes_out, int64_t bytes_cap,
+                                     int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err, void* hip_stream);
+int hutk_decode_special_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
+                              uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

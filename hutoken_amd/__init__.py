@@ -30,6 +30,12 @@ each ONE id, the text between them encoded as ever (csrc/hutk_special.hip).  `en
 `decode_special` / `batch_decode_special` turn such ids back into text (`skip_special_tokens=True` leaves the markers out),
 `decode_packed_device` is the device-tensor form of both decodes; `decode` / `batch_decode` never look at the set either.
 
+Byte fallback (not in the reference, which gives -1 for a character the vocabulary does not hold): `set_byte_fallback`
+installs the ids of the vocabulary's `<0x00>`..`<0xFF>` lines (or 256 ids of the caller's); `encode_fallback`,
+`batch_encode_fallback` and `encode_fallback_packed_device` replace every -1 by the ids of the bytes of the item it
+covers, `decode_fallback` / `batch_decode_fallback` / `decode_packed_device(byte_fallback=True)` turn such ids back into
+the raw bytes (csrc/hutk_fallback.hip).  Every other function ignores the table.
+
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
 the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
@@ -46,7 +52,9 @@ __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_pack
            "collate_padded", "batch_encode_padded", "SequencePacker",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
            "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device",
-           "decode_special", "batch_decode_special", "decode_packed_device"]
+           "decode_special", "batch_decode_special", "decode_packed_device",
+           "set_byte_fallback", "encode_fallback", "batch_encode_fallback", "encode_fallback_packed_device",
+           "decode_fallback", "batch_decode_fallback"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -1018,16 +1026,20 @@ def batch_decode_special(tokens, skip_special_tokens=False):
         raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
 
 
-def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens=False, n_ids=None, check=True):
+def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens=False, n_ids=None, check=True,
+                         byte_fallback=False):
     """The counterpart of encode_packed_device: device tensors in (ids int32, id_offsets int64[n+1], as the encode
     functions return them), device tensors out: (bytes uint8[total], out_offsets int64[n+1]); the text of document i is
     bytes[out_offsets[i]:out_offsets[i+1]].  special=False is the plain decode, special=True the one with the special
     tokens of set_special_tokens (encode_special_packed_device's ids), skip_special_tokens=True leaves their strings out.
     On the current torch stream: a sizes call, ONE synchronising read of the total, then the text call; n_ids= saves the
     read of id_offsets[-1].  check=True synchronises once more and raises ValueError for an id out of range and
-    RuntimeError for a token that cannot be decoded on its own."""
+    RuntimeError for a token that cannot be decoded on its own.  byte_fallback=True: the decode with the table of
+    set_byte_fallback (an id of the table is its one raw byte), alone or together with special=True."""
     if not isinstance(special, (bool, int)):
         raise TypeError("special must be a bool, not %s" % type(special).__name__)
+    if not isinstance(byte_fallback, (bool, int)):
+        raise TypeError("byte_fallback must be a bool, not %s" % type(byte_fallback).__name__)
     flags = _skip_flag(skip_special_tokens)
     if flags and not special:
         raise ValueError("skip_special_tokens=True needs special=True: the plain decode knows no special tokens")
@@ -1046,7 +1058,11 @@ def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens
 
     def call(out, cap):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if special:
+        if byte_fallback:
+            fb = (_capi.FB_SPECIAL if special else 0) | (_capi.FB_SKIP_SPECIAL if flags else 0)
+            _ctx.decode_fallback_device(p_ids, d_id_offsets.data_ptr(), n_docs, n_ids, fb, out, cap, oo.data_ptr(), 0,
+                                        err.data_ptr(), stream)
+        elif special:
             _ctx.decode_special_device(p_ids, d_id_offsets.data_ptr(), n_docs, n_ids, flags, out, cap, oo.data_ptr(), 0,
                                        err.data_ptr(), stream)
         else:
@@ -1083,3 +1099,169 @@ def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens
             raise RuntimeError("hutoken_amd: decode_packed_device: device-side error %d%s" % (
                 code, " (a token cannot be decoded on its own)" if code == _capi.E_UNSUPPORTED else ""))
     return out, oo
+
+
+# ---- byte fallback ---------------------------------------------------------------------------------------------------
+def _fallback_table(table):
+    """The argument of set_byte_fallback -> "auto", None or a list of 256 ints; TypeError / ValueError before anything
+    reaches the library."""
+    if table is None or (isinstance(table, str) and table == "auto"):
+        return table
+    if isinstance(table, (str, bytes)) or not hasattr(table, "__len__") or not hasattr(table, "__iter__"):
+        raise TypeError('a byte-fallback table must be "auto", None or a sequence of 256 ints, not %s' % type(table).__name__)
+    ids = list(table)
+    for b, v in enumerate(ids):
+        if isinstance(v, bool) or not isinstance(v, int):
+            try:
+                import numpy as np
+                if isinstance(v, np.integer):
+                    ids[b] = int(v)
+                    continue
+            except ImportError:
+                pass
+            raise TypeError("the id of byte 0x%02X must be an int, not %s" % (b, type(v).__name__))
+    if len(ids) != 256:
+        raise ValueError("a byte-fallback table holds 256 ids, not %d" % len(ids))
+    for b, v in enumerate(ids):
+        if not 0 <= v < 2**31:
+            raise ValueError("the id of byte 0x%02X must be in [0, 2**31)" % b)
+    if len(set(ids)) != 256:
+        raise ValueError("two bytes of the byte-fallback table have the same id")
+    return ids
+
+
+def set_byte_fallback(table="auto"):
+    """Install the byte-fallback table on the initialised context.  "auto": the ids of the vocabulary's 256 lines
+    "<0x00>".."<0xFF>" (ValueError naming the first missing byte unless all are there); or a sequence of 256 distinct
+    ints in [0, 2**31), the id of every byte value, which need not be vocabulary lines; None removes the table.  A new
+    initialize() starts without one.  Only the *_fallback functions (and decode_packed_device(byte_fallback=True)) look
+    at it: an item the vocabulary does not hold -- a -1 of encode -- becomes the ids of its bytes, and such an id decodes
+    to its one raw byte."""
+    ids = _fallback_table(table)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    if isinstance(ids, str):
+        found, n = _ctx.find_byte_tokens()
+        if n != 256:
+            b = int((found < 0).nonzero()[0][0])
+            raise ValueError("the vocabulary has no line <0x%02X>: %d of the 256 byte-fallback lines were found" % (b, n))
+        ids = found.tolist()
+    _ctx.set_byte_fallback(ids)
+
+
+def _special_arg(special):
+    if not isinstance(special, (bool, int)):
+        raise TypeError("special must be a bool, not %s" % type(special).__name__)
+    return _capi.FB_SPECIAL if special else 0
+
+
+def encode_fallback_packed_device(d_bytes, d_offsets, special=False, check=True):
+    """encode_packed_device with the table of set_byte_fallback: every -1 of the plain encode is replaced, in place, by
+    the ids of the bytes of the one item it covers.  Same tensors in, the same pair out: (ids int32[capacity], out_offsets
+    int64[n+1]).  special=True also cuts at the special tokens of set_special_tokens, as encode_special_packed_device does
+    (and then synchronises the current torch stream once); without it the call is asynchronous unless check=True, which
+    synchronises and raises on a device-side error."""
+    import torch
+    flags = _special_arg(special)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    n_docs = d_offsets.numel() - 1
+    n_bytes = d_bytes.numel()
+    cap = _ctx.special_ids_capacity(n_bytes, n_docs) if flags else _ctx.ids_capacity(n_bytes, n_docs)
+    dev = d_bytes.device
+    ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _ctx.encode_fallback_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, flags, ids.data_ptr(), cap,
+                                oo.data_ptr(), 0, err.data_ptr(), stream)
+    if check:
+        code = int(err.item())
+        if code == _capi.E_UNSUPPORTED:
+            raise ValueError("hutoken_amd: encode_fallback_packed_device: a document's text does not hold the decoded bytes "
+                             "of its tokens where their spans lie; it keeps its plain ids (device-side error %d)" % code)
+        if code not in (0, _capi.E_WORD_TOO_LARGE):
+            raise RuntimeError(f"hutoken_amd: device-side error {code}")
+    return ids, oo
+
+
+def _fallback_texts_to_device(texts, special):
+    """_texts_to_device for the fallback encode (the same handling of torch's NULL stream)."""
+    if not isinstance(texts, list):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    _special_arg(special)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    import torch
+    data, offs = _pack(texts)
+    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
+    d_bytes = torch.from_numpy(data.copy()).to(dev)
+    d_offs = torch.from_numpy(offs).to(dev)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            return encode_fallback_packed_device(d_bytes, d_offs, special)
+        side = _side_streams.get(dev.index)
+        if side is None:
+            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            ids, oo = encode_fallback_packed_device(d_bytes, d_offs, special)
+        cur.wait_stream(side)
+        ids.record_stream(cur)
+        oo.record_stream(cur)
+        return ids, oo
+
+
+def batch_encode_fallback(texts, special=False):
+    """batch_encode with the table of set_byte_fallback -> list[list[int]]; special=True: and the special tokens."""
+    ids, oo = _fallback_texts_to_device(texts, special)
+    bounds = oo.tolist()
+    flat = ids[:bounds[-1]].tolist()
+    return [flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))]
+
+
+def encode_fallback(text, special=False):
+    """encode with the table of set_byte_fallback -> list[int]; special=True: and the special tokens."""
+    if not isinstance(text, str):
+        raise TypeError(f"argument 1 must be str, not {type(text).__name__}")
+    if "\0" in text:
+        raise ValueError("embedded null character")
+    return batch_encode_fallback([text], special)[0]
+
+
+def _fallback_decode_flags(special, skip_special_tokens):
+    flags = _special_arg(special) | (_capi.FB_SKIP_SPECIAL if _skip_flag(skip_special_tokens) else 0)
+    if flags & _capi.FB_SKIP_SPECIAL and not special:
+        raise ValueError("skip_special_tokens=True needs special=True: without it the decode knows no special tokens")
+    return flags
+
+
+def decode_fallback(tokens, special=False, skip_special_tokens=False):
+    """decode (special=True: decode_special) with the table of set_byte_fallback: an id of the table becomes its one raw
+    byte, so that decode_fallback(encode_fallback(text)) == text.  Argument checks and exceptions are those of decode."""
+    flags = _fallback_decode_flags(special, skip_special_tokens)
+    try:
+        ids, offs = _flat_ids(tokens, False)
+        out, _oo, _st = _ctx.decode_fallback_packed(ids, offs, flags)
+        return _ids_to_text(out.tobytes())
+    except ValueError as e:
+        traceback.print_exc(file=sys.stderr)
+        raise ValueError(f"hutoken: Error decoding tokens {tokens}: {e}")
+    except Exception as e:
+        traceback.print_exc(file=sys.stderr)
+        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+
+
+def batch_decode_fallback(tokens, special=False, skip_special_tokens=False):
+    """batch_decode with the table of set_byte_fallback -> list[str]; see decode_fallback."""
+    flags = _fallback_decode_flags(special, skip_special_tokens)
+    try:
+        flat, offs = _flat_ids(tokens, True)
+        out, oo, _st = _ctx.decode_fallback_packed(flat, offs, flags)
+        raw = out.tobytes()
+        bounds = oo.tolist()
+        return [_ids_to_text(raw[bounds[i]:bounds[i + 1]]) for i in range(len(tokens))]
+    except Exception as e:
+        traceback.print_exc(file=sys.stderr)
+        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")

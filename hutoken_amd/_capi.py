@@ -32,12 +32,16 @@ EXPORTS = [
     "hutk_ctx_set_special_tokens", "hutk_ctx_special_token_count", "hutk_special_ids_capacity",
     "hutk_encode_special_batch_device", "hutk_encode_special_batch", "hutk_special_last_matches",
     "hutk_debug_special_tile_bytes", "hutk_decode_special_batch_device", "hutk_decode_special_batch",
+    "hutk_ctx_find_byte_tokens", "hutk_ctx_set_byte_fallback", "hutk_ctx_byte_fallback",
+    "hutk_encode_fallback_batch_device", "hutk_encode_fallback_batch", "hutk_decode_fallback_batch_device",
+    "hutk_decode_fallback_batch",
 ]
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
 NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
 SPANS_BYTES, SPANS_CHARS = 0, 1
 DECODE_SKIP_SPECIAL = 1  # HUTK_DECODE_SKIP_SPECIAL
+FB_SPECIAL, FB_SKIP_SPECIAL = 1, 2  # HUTK_FB_*
 
 _lib = None
 
@@ -209,6 +213,21 @@ def load(build_if_missing=True):
         L.hutk_decode_special_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
         L.hutk_decode_special_batch.restype = i32
         L.hutk_decode_special_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
+    if hasattr(L, "hutk_ctx_set_byte_fallback"):
+        L.hutk_ctx_find_byte_tokens.restype = i32
+        L.hutk_ctx_find_byte_tokens.argtypes = [vp, vp]
+        L.hutk_ctx_set_byte_fallback.restype = i32
+        L.hutk_ctx_set_byte_fallback.argtypes = [vp, vp]
+        L.hutk_ctx_byte_fallback.restype = i32
+        L.hutk_ctx_byte_fallback.argtypes = [vp, vp]
+        L.hutk_encode_fallback_batch_device.restype = i32
+        L.hutk_encode_fallback_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
+        L.hutk_encode_fallback_batch.restype = i32
+        L.hutk_encode_fallback_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
+        L.hutk_decode_fallback_batch_device.restype = i32
+        L.hutk_decode_fallback_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
+        L.hutk_decode_fallback_batch.restype = i32
+        L.hutk_decode_fallback_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
     _lib = L
     return L
 
@@ -550,6 +569,88 @@ class Context:
         raise_for(load().hutk_decode_special_batch_device(self._h, d_ids or None, d_id_offsets or None, n_docs, n_ids,
                                                           flags, d_bytes_out or None, bytes_cap, d_out_offsets or None,
                                                           d_status or None, d_err or None, stream or None))
+
+    def find_byte_tokens(self):
+        """-> (int32[256], found): the ids of the vocabulary keys "<0x00>".."<0xFF>", -1 where there is none."""
+        import numpy as np
+        out = np.zeros(256, dtype=np.int32)
+        found = load().hutk_ctx_find_byte_tokens(self._h, out.ctypes.data)
+        return out, int(found)
+
+    def set_byte_fallback(self, ids256):
+        """Install the byte-fallback table (hutk_ctx_set_byte_fallback): 256 ids, or None to remove it.  ValueError for a
+        table the library refuses."""
+        import numpy as np
+        if ids256 is None:
+            raise_for(load().hutk_ctx_set_byte_fallback(self._h, None))
+            return
+        ids = [int(i) for i in ids256]
+        if len(ids) != 256:
+            raise ValueError("a byte-fallback table holds 256 ids")
+        if any(not -2**31 <= i < 2**31 for i in ids):
+            raise ValueError("the ids of a byte-fallback table must fit an int32")
+        arr = np.array(ids, dtype=np.int32)
+        raise_for(load().hutk_ctx_set_byte_fallback(self._h, arr.ctypes.data))
+
+    @property
+    def byte_fallback(self):
+        """The installed table (int32[256]) or None."""
+        import numpy as np
+        out = np.zeros(256, dtype=np.int32)
+        return out if load().hutk_ctx_byte_fallback(self._h, out.ctypes.data) else None
+
+    def encode_fallback_packed(self, data, offsets, flags=0):
+        """encode_packed with byte fallback (hutk_encode_fallback_batch; flags: 0 or FB_SPECIAL): host numpy buffers in
+        and out.  -> (ids int32, out_offsets int64, status int32, return code); the code E_UNSUPPORTED (documents whose
+        spans did not verify keep their plain ids) is returned, not raised."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        nbytes = int(offsets[n]) if n >= 0 else 0
+        cap = self.special_ids_capacity(nbytes, n) if flags & FB_SPECIAL else self.ids_capacity(nbytes, n)
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        oo = np.zeros(n + 1, dtype=np.int64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        rc = load().hutk_encode_fallback_batch(self._h, data.ctypes.data if nbytes else None, offsets.ctypes.data, n, flags,
+                                               ids.ctypes.data, cap, oo.ctypes.data, st.ctypes.data)
+        if rc not in (OK, E_WORD_TOO_LARGE) and not (rc == E_UNSUPPORTED and int(oo[n]) > 0):
+            raise_for(rc)
+        return ids[: int(oo[n])], oo, st[:n], rc
+
+    def encode_fallback_device(self, d_bytes, d_offsets, n_docs, n_bytes, flags, d_ids, ids_cap, d_out_offsets,
+                               d_status=0, d_err=0, stream=0):
+        """hutk_encode_fallback_batch_device on raw device pointers (ints); asynchronous on `stream` (with FB_SPECIAL it
+        synchronises once, as the special encode does)."""
+        raise_for(load().hutk_encode_fallback_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                           flags, d_ids or None, ids_cap, d_out_offsets or None,
+                                                           d_status or None, d_err or None, stream or None))
+
+    def decode_fallback_packed(self, ids, id_offsets, flags=0):
+        """decode_packed with byte fallback (hutk_decode_fallback_batch; flags: FB_SPECIAL, FB_SKIP_SPECIAL):
+        -> (bytes uint8, out_offsets int64[n+1], status int32[n]).  Two calls: sizes, then the text."""
+        import numpy as np
+        L = load()
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
+        n = len(id_offsets) - 1
+        oo = np.zeros(n + 1, dtype=np.int64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        pid = ids.ctypes.data if len(ids) else None
+        raise_for(L.hutk_decode_fallback_batch(self._h, pid, id_offsets.ctypes.data, n, flags, None, 0, oo.ctypes.data,
+                                               st.ctypes.data))
+        total = int(oo[n])
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        raise_for(L.hutk_decode_fallback_batch(self._h, pid, id_offsets.ctypes.data, n, flags, out.ctypes.data, total,
+                                               oo.ctypes.data, st.ctypes.data))
+        return out[:total], oo, st[:n]
+
+    def decode_fallback_device(self, d_ids, d_id_offsets, n_docs, n_ids, flags, d_bytes_out, bytes_cap, d_out_offsets,
+                               d_status=0, d_err=0, stream=0):
+        """hutk_decode_fallback_batch_device on raw device pointers (ints); asynchronous on `stream`, never synchronises."""
+        raise_for(load().hutk_decode_fallback_batch_device(self._h, d_ids or None, d_id_offsets or None, n_docs, n_ids,
+                                                           flags, d_bytes_out or None, bytes_cap, d_out_offsets or None,
+                                                           d_status or None, d_err or None, stream or None))
 
     def profile(self, enable):
         load().hutk_debug_profile(self._h, 1 if enable else 0)

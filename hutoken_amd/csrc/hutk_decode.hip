@@ -361,7 +361,7 @@ namespace hutk {
 
 int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, const int32_t* d_ids, const int64_t* d_id_offsets,
                        int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
-                       int32_t* d_status, int32_t* d_err, void* hip_stream) {
+                       int32_t* d_status, int32_t* d_err, void* hip_stream, const DecFallback* fb) {
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
     if (n_docs < 0 || n_ids < 0 || !d_id_offsets || !d_out_offsets || (n_ids > 0 && !d_ids))
         return api_set_error(HUTK_E_ARG, "bad argument");
@@ -403,7 +403,8 @@ int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, co
     }
     if (strip) launch_dec_mark(D, s);
     if (sp) {  // behind k_dec_mark: the pass adds first-token bits of its own
-        launch_dec_remap(*sp, d_ids, c->dw_ids.p, n_ids, D.first_bits, s);
+        if (fb) launch_fb_remap(*sp, *fb, d_ids, c->dw_ids.p, n_ids, D.first_bits, s);
+        else launch_dec_remap(*sp, d_ids, c->dw_ids.p, n_ids, D.first_bits, s);
         D.ids = c->dw_ids.p;
     }
     HUTK_HIP_TRY(hipMemsetAsync(D.tile_state, 0, (size_t)n_tiles * 8, s));
@@ -413,7 +414,7 @@ int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, co
 }
 
 int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
-                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
+                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status, int fallback_flags) {
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
     if (n_docs < 0 || !id_offsets || !out_offsets) return api_set_error(HUTK_E_ARG, "bad argument");
@@ -431,7 +432,10 @@ int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const i
     if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
     HUTK_HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
     uint8_t* d_bytes = bytes_out ? c->ds_bytes.p : nullptr;
-    int rc = special_flags < 0
+    int rc = fallback_flags >= 0
+                 ? hutk_decode_fallback_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, fallback_flags, d_bytes,
+                                                     bytes_cap, c->ds_oo.p, c->ds_status.p, c->w_err.p, s)
+             : special_flags < 0
                  ? hutk_decode_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, d_bytes, bytes_cap, c->ds_oo.p,
                                             c->ds_status.p, c->w_err.p, s)
                  : hutk_decode_special_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, special_flags, d_bytes,

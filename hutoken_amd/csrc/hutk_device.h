@@ -238,6 +238,37 @@ struct DecSpecial {
 };
 void launch_dec_remap(const DecSpecial& sp, const int32_t* ids, int32_t* ids_out, int64_t n_ids, uint32_t* first_bits,
                       hipStream_t s);
+// the same on the host (table build) and on the device (lookup)
+HUTK_HD uint32_t dsp_slot(uint32_t id) { return (id * 0x9E3779B1u) >> 20; }
+static_assert(DSP_SLOTS == 1 << 12, "dsp_slot keeps the top 12 bits");
+// index of the special id among the distinct ones, -1: the id is not special
+__device__ __forceinline__ int32_t dsp_index(const DecSpecial& S, int32_t id) {
+    if (id < S.id_min || id > S.id_max) return -1;
+    for (uint32_t s = dsp_slot((uint32_t)id);; s = (s + 1) & (DSP_SLOTS - 1)) {  // (a quarter full at most: it ends)
+        const uint2 e = S.slots[s];
+        if (e.y == DSP_EMPTY) return -1;
+        if ((int32_t)e.x == id) return (int32_t)e.y;
+    }
+}
+__device__ __forceinline__ bool dsp_bit(const uint32_t* bits, int64_t i) {
+    return (__hip_atomic_load(&bits[i >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (i & 31)) & 1u;
+}
+// hutk_special.hip: a[0, n) becomes its exclusive scan, a[n] the sum (one workgroup)
+void launch_scan_i64(int64_t* a, int64_t n, hipStream_t s);
+
+// ---- byte fallback (hutk_fallback.hip) ----
+// Decode: the tables of the special decode with 256 one-byte entries behind them (entry base + b: the byte b); the pass
+// in front of the decode kernels (k_fb_remap: k_dsp_remap and the table's ids) sends a table id there.
+constexpr int FB_SLOTS = 1024;  // 256 ids: a quarter full
+struct DecFallback {
+    const uint2* slots;  // [FB_SLOTS] {id, byte}, y == DSP_EMPTY: empty; linear probing from fb_slot(id)
+    int32_t id_min, id_max;
+    int32_t base;        // index of the entry of byte 0
+};
+HUTK_HD uint32_t fb_slot(uint32_t id) { return (id * 0x9E3779B1u) >> 22; }
+static_assert(FB_SLOTS == 1 << 10, "fb_slot keeps the top 10 bits");
+void launch_fb_remap(const DecSpecial& sp, const DecFallback& fb, const int32_t* ids, int32_t* ids_out, int64_t n_ids,
+                     uint32_t* first_bits, hipStream_t s);
 
 // ---- token spans (hutk_spans.hip): which stretch of its document each id covers ----
 // Rank structure over the batch's character starts (bytes b with (b & 0xC0) != 0x80), built per call: one 64-bit word

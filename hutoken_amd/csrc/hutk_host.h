@@ -132,6 +132,29 @@ struct hutk_ctx {
         }
     } sx;
 
+    // byte fallback (hutk_fallback.hip): the table of hutk_ctx_set_byte_fallback, the decode tables extended by it, and
+    // the workspace of hutk_encode_fallback_batch_device
+    struct Fallback {
+        bool on = false;
+        int32_t ids[256] = {0};
+        bool clash = false;            // an id of the table is a special id too (HUTK_FB_SPECIAL refuses)
+        // decode: [vocabulary lines][the distinct special ids, when a set is installed][256 one-byte entries]
+        int64_t base = 0;              // entries in front of the 256
+        bool strip = false;            // the context strips a prefix: dx_sent* are in use
+        int32_t id_min = 0, id_max = 0;
+        DevBuf<uint2> dx_ent, dx_sent, dx_ent_skip, dx_sent_skip, dx_slots;
+        DevBuf<uint8_t> dx_blob;
+        // encode: the table, the plain encode's outputs (offsets with one more entry: the unused ids behind the batch
+        // as a document), their byte spans and the spans' status, per-tile counts
+        DevBuf<int32_t> d_tab, w_ids, w_spans, w_sstatus, w_serr;
+        DevBuf<int64_t> w_oo, w_doff, w_tile, w_hdr;
+        void release() {
+            dx_ent.release(); dx_sent.release(); dx_ent_skip.release(); dx_sent_skip.release(); dx_slots.release();
+            dx_blob.release(); d_tab.release(); w_ids.release(); w_spans.release(); w_sstatus.release(); w_serr.release();
+            w_oo.release(); w_doff.release(); w_tile.release(); w_hdr.release();
+        }
+    } fb;
+
     // staging for the host-buffer entry point
     DevBuf<uint8_t> s_bytes;
     DevBuf<int64_t> s_offsets, s_out_offsets;
@@ -264,13 +287,28 @@ inline void dec_pack_tables(const Tables& T, std::vector<uint2>& ent, std::vecto
 // hutk_decode.hip: the decode behind hutk_decode_batch_device (the caller has checked c and holds no lock yet): its
 // checks, its workspace, every kernel of the direction, with the tables `t`.  sp != nullptr: the ids are renumbered by
 // launch_dec_remap first (hutk_special.hip), and t are the extended tables.
+// fb != nullptr (with sp): the pass is launch_fb_remap (hutk_fallback.hip), t has the one-byte entries too.
 int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, const int32_t* d_ids, const int64_t* d_id_offsets,
                        int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
-                       int32_t* d_status, int32_t* d_err, void* hip_stream);
+                       int32_t* d_status, int32_t* d_err, void* hip_stream, const DecFallback* fb = nullptr);
 // ... and the staging of hutk_decode_batch around it.  special_flags < 0: the plain decode; otherwise
-// hutk_decode_special_batch_device with these flags.
+// hutk_decode_special_batch_device with these flags.  fallback_flags >= 0: hutk_decode_fallback_batch_device with those.
 int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
-                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
+                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status, int fallback_flags = -1);
+
+// hutk_special.hip: the encode behind hutk_encode_special_batch_device; fallback: the text pieces go through
+// encode_fallback_device_impl instead of encode_device_impl (hutk_encode_fallback_batch_device with HUTK_FB_SPECIAL).
+int encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                        int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status,
+                        int32_t* d_err, void* hip_stream);
+// hutk_fallback.hip: encode_device_impl's arguments (without the regex bitmaps); plain encode, byte spans, expansion.
+// The caller holds c->mu and has checked that a table is installed and that the spans take the context.
+int encode_fallback_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err,
+                                void* hip_stream);
+// ... and the decode tables of the byte-fallback decode, built again from the context's and the special set's whenever
+// either changes (no table installed: nothing to do).  The caller holds c->mu.
+int fallback_rebuild_decode(hutk_ctx* c);
 
 // What the host-buffer entry points say about the error word a direction's kernels left (err != HUTK_OK).
 enum class Direction { Encode, Decode, Spans };

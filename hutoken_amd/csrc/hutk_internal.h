@@ -136,6 +136,7 @@ struct Tables {
     bool rank_is_sym = false;   // ids strictly increase with the symbol index
     bool ident_ids = false;     // id(sym) == sym for every vocabulary symbol
     std::vector<int32_t> sym_id;  // [n_sym]
+    int32_t byte_tok[256] = {0};  // id of the key spelled "<0xHH>" for byte HH, -1: none (hutk_ctx_find_byte_tokens)
 
     // (left, right) -> merged symbol: buckets of two entries (see above); pair_slots.size() == 2 << (32 - pair_shift)
     std::vector<uint64_t> pair_slots;

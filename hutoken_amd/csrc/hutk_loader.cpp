@@ -986,6 +986,12 @@ LoadError load_tables(const char* vocab_path, const char* special_path, const ch
     T = Tables();
     T.is_byte_encoder = is_byte_encoder;
     T.n_keys = (int64_t)vocab.size();
+    for (int b = 0; b < 256; b++) {  // the byte-fallback lines, by their keys (an id of -1 is "absent")
+        char key[8];
+        snprintf(key, sizeof key, "<0x%02X>", b);
+        const auto it = vocab.find(key);
+        T.byte_tok[b] = it != vocab.end() && it->second >= 0 ? it->second : -1;
+    }
     build_decode_tables(vocab, n_lines, special, has_special, special_seq, prefix, is_byte_encoder, T);
     if (merges_path) {
         // a merges file switches the reference to its id-keyed merge loop -- unless the file has no countable

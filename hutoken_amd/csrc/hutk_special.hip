@@ -453,23 +453,7 @@ __global__ __launch_bounds__(CP_THREADS) void k_st_copy(SpecArgs A) {
 // ---- decode: special ids become entries behind the vocabulary's ----------------------------------------------------
 constexpr int DSP_THREADS = 256, DSP_PER = 4, DSP_TILE = DSP_THREADS * DSP_PER;  // ids per workgroup of the pass
 
-// the same on the host (table build) and on the device (lookup)
-HUTK_HD uint32_t dsp_slot(uint32_t id) { return (id * 0x9E3779B1u) >> 20; }
-static_assert(DSP_SLOTS == 1 << 12, "dsp_slot keeps the top 12 bits");
-
-// index of the special id among the distinct ones, -1: the id is not special
-__device__ __forceinline__ int32_t dsp_index(const DecSpecial& S, int32_t id) {
-    if (id < S.id_min || id > S.id_max) return -1;
-    for (uint32_t s = dsp_slot((uint32_t)id);; s = (s + 1) & (DSP_SLOTS - 1)) {  // (a quarter full at most: it ends)
-        const uint2 e = S.slots[s];
-        if (e.y == DSP_EMPTY) return -1;
-        if ((int32_t)e.x == id) return (int32_t)e.y;
-    }
-}
-
-__device__ __forceinline__ bool dsp_bit(const uint32_t* bits, int64_t i) {
-    return (__hip_atomic_load(&bits[i >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (i & 31)) & 1u;
-}
+// (dsp_slot, dsp_index, dsp_bit: hutk_device.h -- the byte-fallback decode's pass uses them too)
 
 // out[i] = ids[i] for a vocabulary id, n_vocab + k for the k-th special id, -1 for anything else (an id in
 // [n_vocab, n_vocab + specials) that is not special must NOT reach the extended tables).  first_bits (a context that
@@ -665,6 +649,8 @@ int64_t cap_units(const hutk_ctx* c) { return hutk_ids_capacity(c, 1, 0) - 1; }
 
 }  // namespace
 
+void launch_scan_i64(int64_t* a, int64_t n, hipStream_t s) { hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, s, a, n); }
+
 void launch_dec_remap(const DecSpecial& sp, const int32_t* ids, int32_t* ids_out, int64_t n_ids, uint32_t* first_bits,
                       hipStream_t s) {
     hipLaunchKernelGGL(k_dsp_remap, dim3((unsigned)((n_ids + DSP_TILE - 1) / DSP_TILE)), dim3(DSP_THREADS), 0, s, sp, ids,
@@ -683,7 +669,7 @@ int hutk_ctx_set_special_tokens(hutk_ctx* c, const uint8_t* bytes, const int64_t
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (n == 0) {
         c->sx.n = 0;
-        return HUTK_OK;
+        return fallback_rebuild_decode(c);  // (the byte-fallback decode's tables hold the set's entries)
     }
     hutk_ctx::Specials fresh;  // (a set that is refused leaves the one in force as it was, its decode tables too)
     if (int rc = build_specials(fresh, bytes, offsets, ids, n)) return rc;
@@ -713,7 +699,7 @@ int hutk_ctx_set_special_tokens(hutk_ctx* c, const uint8_t* bytes, const int64_t
         if (int rc = upload_decode_specials(c)) return rc;
     }
     S.n = n;
-    return HUTK_OK;
+    return fallback_rebuild_decode(c);
 }
 
 int64_t hutk_ctx_special_token_count(const hutk_ctx* c) { return c ? c->sx.n : 0; }
@@ -729,6 +715,20 @@ int64_t hutk_special_ids_capacity(const hutk_ctx* c, int64_t n_bytes, int64_t n_
 int hutk_encode_special_batch_device(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
                                      int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets,
                                      int32_t* d_status, int32_t* d_err, void* hip_stream) {
+    return encode_special_impl(c, false, d_bytes, d_offsets, n_docs, n_bytes, d_ids_out, ids_cap, d_out_offsets, d_status, d_err,
+                               hip_stream);
+}
+
+}  // extern "C"
+
+// fallback: the text pieces are encoded with byte fallback (hutk_fallback.hip, which has checked what that needs)
+int hutk::encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                              int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status,
+                              int32_t* d_err, void* hip_stream) {
+    const auto encode = [&](const int64_t* offs, int64_t n, int32_t* ids, int64_t cap, int64_t* oo, int32_t* status, int32_t* err) {
+        return fallback ? encode_fallback_device_impl(c, d_bytes, offs, n, n_bytes, ids, cap, oo, status, err, hip_stream)
+                        : encode_device_impl(c, d_bytes, offs, n, n_bytes, ids, cap, oo, status, err, hip_stream, nullptr, nullptr);
+    };
     if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to encode on");
     if (n_docs < 0 || n_bytes < 0 || !d_offsets || !d_out_offsets || (n_bytes > 0 && (!d_bytes || !d_ids_out)))
@@ -743,8 +743,7 @@ int hutk_encode_special_batch_device(hutk_ctx* c, const uint8_t* d_bytes, const 
     hutk_ctx::Specials& S = c->sx;
     S.last_matches = 0;
     if (S.n == 0 || n_docs == 0 || n_bytes == 0)  // nothing to find: the plain encode
-        return encode_device_impl(c, d_bytes, d_offsets, n_docs, n_bytes, d_ids_out, ids_cap, d_out_offsets, d_status, d_err,
-                                  hip_stream, nullptr, nullptr);
+        return encode(d_offsets, n_docs, d_ids_out, ids_cap, d_out_offsets, d_status, d_err);
     const int64_t n_tiles = (n_bytes + SC_TILE - 1) / SC_TILE;
     if (n_tiles > 0x7FFFFFFFll) return api_set_error(HUTK_E_ARG, "batch too large");
     HUTK_HIP_TRY(hipSetDevice(c->device));
@@ -796,8 +795,7 @@ int hutk_encode_special_batch_device(hutk_ctx* c, const uint8_t* d_bytes, const 
     if (n_matches < 0 || n_matches > n_bytes) return api_set_error(HUTK_E_DEVICE, "hutk_encode_special_batch_device: bad match count");
     S.last_matches = n_matches;
     if (n_matches == 0)
-        return encode_device_impl(c, d_bytes, d_offsets, n_docs, n_bytes, d_ids_out, ids_cap, d_out_offsets, d_status, d_err,
-                                  hip_stream, nullptr, nullptr);
+        return encode(d_offsets, n_docs, d_ids_out, ids_cap, d_out_offsets, d_status, d_err);
     const int64_t n_pieces = n_docs + 2 * n_matches;
     if (n_pieces > (int64_t)INT32_MAX - 1) return api_set_error(HUTK_E_UNSUPPORTED, "hutk_encode_special_batch_device: too many pieces for one encode");
     const int64_t pieces_cap = hutk_ids_capacity(c, n_bytes, n_pieces);
@@ -831,9 +829,7 @@ int hutk_encode_special_batch_device(hutk_ctx* c, const uint8_t* d_bytes, const 
         HUTK_HIP_TRY(hipGetLastError());
     }
     // the pieces, special ones included (a document's pieces are contiguous, a marker is a few ids), as documents of their own
-    if (int rc = encode_device_impl(c, d_bytes, A.piece_off, n_pieces, n_bytes, S.w_pids.p, pieces_cap, S.w_poo.p, S.w_pstatus.p,
-                                    A.err, hip_stream, nullptr, nullptr))
-        return rc;
+    if (int rc = encode(A.piece_off, n_pieces, S.w_pids.p, pieces_cap, S.w_poo.p, S.w_pstatus.p, A.err)) return rc;
     {
         StreamScope scope(c, hip_stream, false);
         if (scope.rc) return scope.rc;
@@ -850,6 +846,8 @@ int hutk_encode_special_batch_device(hutk_ctx* c, const uint8_t* d_bytes, const 
     }
     return HUTK_OK;
 }
+
+extern "C" {
 
 int hutk_encode_special_batch(hutk_ctx* c, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int32_t* ids_out,
                               int64_t ids_cap, int64_t* out_offsets, int32_t* status) {

@@ -484,6 +484,82 @@ int hutk_decode_special_batch_device(hutk_ctx* ctx, const int32_t* d_ids, const 
 int hutk_decode_special_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
                               uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
 
+/* ---- byte fallback -----------------------------------------------------------------------------------------
+ * SentencePiece-shaped vocabularies carry 256 lines "<0x00>".."<0xFF>": an item the vocabulary does not hold is
+ * encoded as the ids of its bytes, and such an id decodes to its ONE raw byte.  The reference does neither: its encode
+ * gives -1 for the item (core.c:205-207), its decode writes the six characters of the line.  hutk_encode_batch*,
+ * hutk_decode_batch*, the special pair and the spans never look at the table: they stay bit-exact.
+ *
+ * THE TABLE.  int32[256]: the id of every byte value.
+ *   hutk_ctx_find_byte_tokens  out256[b] = the id of the vocabulary key spelled exactly "<0xHH>" (two upper-case hex
+ *       digits of b), -1 when there is none; returns how many were found.  The ids are those of the KEYS the loader read
+ *       (the decode tables map the line "<0x0A>" to what the pretokenizer makes of it).  Works on a host-only context.
+ *   hutk_ctx_set_byte_fallback installs ids256 in place of any earlier table, NULL removes it.  HUTK_E_VALUE, and the
+ *       table in force stays, for an id < 0 or two equal ids.  Ids need not be vocabulary lines.  On a host-only context
+ *       the table is validated and kept, no more.  A new context starts without one.
+ *   hutk_ctx_byte_fallback     returns 1 and the table (out256 may be NULL) when one is installed, else 0.
+ *
+ * ENCODING.  The fallback encode of a document is its plain encode with every -1 replaced, in place and in order, by the
+ * ids table[b] of the bytes b of the ONE item that the -1 covers (an item: see the token spans -- a byte with
+ * is_byte_encoder, otherwise a character of 1..4 bytes, cut short at the document's end).  A -1 is never the product of
+ * a merge and its neighbours never merge across it, so this is what a trainer-consistent SentencePiece encode gives.
+ * Known ids, the order, status, a document cut at an over-long word and the note HUTK_E_WORD_TOO_LARGE are unchanged;
+ * d_out_offsets describe the longer rows.
+ * CAPACITY.  ids_cap >= hutk_ids_capacity() - 1 stays sufficient (with HUTK_FB_SPECIAL: hutk_special_ids_capacity() - 1).
+ * Proof.  hutk_ids_capacity(b, d) = b U + d P + 1 allows U >= 1 ids for every input BYTE (U: the most units an item can
+ * become) and P for a document's prefix.  An unknown item of l bytes was one unit -- one -1 -- of the plain encode and
+ * becomes l ids; the bound already allows l U >= l ids for its l bytes, and no other id is added or changed.  With
+ * HUTK_FB_SPECIAL the same holds for every text piece, and the proof of hutk_special_ids_capacity bounds the pieces.
+ * PIPELINE.  The plain encode into a workspace; the byte spans of its ids (the kernels of hutk_token_spans_device, over
+ * the workspace's CAPACITY, because the host never learns the number of ids: the ids behind the last document are a
+ * document of no bytes whose spans nobody reads); then the expansion: counts per tile of 2048 ids, their scan, the write.
+ * No workgroup of the expansion waits for another one.  The workspace grows by 12 bytes per id the capacity allows.
+ * hutk_encode_fallback_batch_device: the arguments of hutk_encode_batch_device and flags: 0 or HUTK_FB_SPECIAL, which
+ * cuts at the special tokens of hutk_ctx_set_special_tokens exactly as hutk_encode_special_batch_device does and encodes
+ * the text pieces with fallback.  Asynchronous on hip_stream (NULL: the context's stream).  Without HUTK_FB_SPECIAL it
+ * NEVER synchronises (once the workspace has grown); with it, once, where the special encode does.  Runs on the context's
+ * first device, serialised with the other calls on the context.
+ * Refused at the call: no table installed, a context with a regex pattern, a special-character replacement of several
+ * units, a special-character entry for a byte >= 0x80 without is_byte_encoder, a token of 2 MiB or more
+ * (HUTK_E_UNSUPPORTED: what the spans refuse); with HUTK_FB_SPECIAL an id that is both special and in the table
+ * (HUTK_E_VALUE); unknown flag bits, a NULL buffer, more than 2^31 - 3 documents (HUTK_E_ARG); ids_cap below the bound
+ * (HUTK_E_CAPACITY); a host-only context (HUTK_E_DEVICE).  Nothing is written at or beyond d_ids_out + ids_cap.
+ * A document whose spans do not verify (HUTK_DOC_SPAN_MISMATCH there: a special-character value that equals an ordinary
+ * character, say) keeps its plain ids, -1 included, and its status; *d_err = HUTK_E_UNSUPPORTED; every other document is
+ * exact.  Document offsets that do not describe the text, or a document of 2^31 bytes or more: *d_err = HUTK_E_ARG,
+ * the outputs are undefined, nothing is read or written out of bounds.  n_docs == 0 and batches without ids write
+ * offsets only and succeed.
+ * hutk_encode_fallback_batch: host buffers (copies, calls the device form, waits; one device, no chunking); returns
+ * HUTK_OK, the note HUTK_E_WORD_TOO_LARGE, or the error.
+ *
+ * DECODING.  The fallback decode is hutk_decode_batch_device (with HUTK_FB_SPECIAL: hutk_decode_special_batch_device,
+ * HUTK_FB_SKIP_SPECIAL its HUTK_DECODE_SKIP_SPECIAL; the skip flag alone: HUTK_E_ARG) with one change: an id the table
+ * carries decodes to its ONE raw byte, whatever its vocabulary line says -- also where no line has the id.  Such an id
+ * is never stripped of a prefix, and it is no marker: the token behind it is not stripped, and the walk of
+ * HUTK_FB_SKIP_SPECIAL from a document's first token to its first ordinary id ends on it.  So
+ * decode_fallback(encode_fallback(text)) == text for every valid-UTF-8 text that decode(encode(text)) already gives
+ * back apart from its -1s.  All promises of hutk_decode_batch_device carry over: d_bytes_out == NULL gives sizes only,
+ * any output alignment, HUTK_E_CAPACITY with nothing written beyond bytes_cap, a bad id contributes nothing and marks
+ * its document, the call never synchronises.  No table installed: HUTK_E_UNSUPPORTED; with HUTK_FB_SPECIAL an id that
+ * is both special and in the table: HUTK_E_VALUE; a host-only context: HUTK_E_DEVICE.  The tables are those of the
+ * special decode with 256 one-byte entries behind them; a pass over the ids renumbers table ids and special ids.
+ * hutk_decode_fallback_batch: host buffers, staged like hutk_decode_batch and with its return codes. */
+#define HUTK_FB_SPECIAL 1
+#define HUTK_FB_SKIP_SPECIAL 2
+int hutk_ctx_find_byte_tokens(const hutk_ctx* ctx, int32_t out256[256]);
+int hutk_ctx_set_byte_fallback(hutk_ctx* ctx, const int32_t* ids256);
+int hutk_ctx_byte_fallback(const hutk_ctx* ctx, int32_t* out256);
+int hutk_encode_fallback_batch_device(hutk_ctx* ctx, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                                      int64_t n_bytes, int flags, int32_t* d_ids_out, int64_t ids_cap,
+                                      int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err, void* hip_stream);
+int hutk_encode_fallback_batch(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int flags,
+                               int32_t* ids_out, int64_t ids_cap, int64_t* out_offsets, int32_t* status);
+int hutk_decode_fallback_batch_device(hutk_ctx* ctx, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
+                                      int64_t n_ids, int flags, uint8_t* d_bytes_out, int64_t bytes_cap,
+                                      int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err, void* hip_stream);
+int hutk_decode_fallback_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
+                               uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,9 @@ zero-marshalling entry points for packed UTF-8 + offsets.
 
 Collation (not in the reference either): `collate_padded` / `batch_encode_padded` turn the device arrays of
 `encode_packed_device` into padded rows with attention mask and lengths, `SequencePacker` into packed rows of
-`seq_len` tokens with position and segment ids -- one HIP pass each (csrc/hutk_collate.hip).
+`seq_len` tokens with position and segment ids -- one HIP pass each (csrc/hutk_collate.hip).  `collate_windows` /
+`batch_encode_windows` cut documents longer than `max_length` into overlapping windows (`stride`), every window a padded
+row, with `row_map` from rows back to documents.
 
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
@@ -49,7 +51,7 @@ from . import _capi
 
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
-           "collate_padded", "batch_encode_padded", "SequencePacker",
+           "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
            "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device",
            "decode_special", "batch_decode_special", "decode_packed_device",
@@ -641,6 +643,68 @@ def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, p
     return out, mask, lengths
 
 
+def _stride_arg(stride, room):
+    """stride -> int in 0 .. room - 1 (room: the document ids a row holds)."""
+    if isinstance(stride, bool) or not isinstance(stride, int):
+        raise TypeError("stride must be an int, not %s" % type(stride).__name__)
+    if stride < 0 or stride >= room:
+        raise ValueError("stride must be in 0 .. %d (below max_length less the bos/eos tokens), not %d" % (room - 1, stride))
+    return stride
+
+
+def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=None, pad_id=0, padding_side="right",
+                    dtype=None, n_ids=None, n_rows=None, check=False):
+    """Device tensors of encode_packed_device in, every document as overlapping windows out, on the current torch stream:
+    -> (input_ids [n_rows, max_length] of `dtype` (torch.int32, the default, or torch.int64),
+        attention_mask uint8 [n_rows, max_length], lengths int32 [n_rows], row_map int64 [n_rows, 2]).
+    With C = max_length - (bos/eos tokens given) and step = C - stride, a document of n <= C ids is one row (an empty one
+    too); a longer one gives 1 + ceil((n - C) / step) rows, row k holding [bos_id] + its ids [k * step, k * step + C) +
+    [eos_id]; consecutive rows share `stride` ids and the last one is the short one.  Rows are padded with pad_id on
+    `padding_side`; lengths counts bos/eos.  row_map[r] = (document, k * step): element q of unpadded row r that is not
+    bos or eos is ids[offsets[document] + k * step + q - (1 with a bos_id)], so its span is that row of
+    token_spans_device's result.  One small synchronising read gives the number of rows (and one more offsets[-1]);
+    n_rows= and n_ids= avoid them.  check=True synchronises and raises ValueError when the kernels found offsets that do
+    not describe ids or an n_rows that is not the number of rows."""
+    bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
+    s = (bos != _capi.NO_TOKEN) + (eos != _capi.NO_TOKEN)
+    _length_arg("max_length", max_length, s + 1)
+    _stride_arg(stride, max_length - s)
+    if padding_side not in _SIDES:
+        raise ValueError("padding_side must be 'right' or 'left', not %r" % (padding_side,))
+    width, dname = _out_width(dtype)
+    if n_rows is not None:
+        if isinstance(n_rows, bool) or not isinstance(n_rows, int):
+            raise TypeError("n_rows must be an int or None")
+        if n_rows < 0:
+            raise ValueError("n_rows must not be negative")
+    _ragged_args(ids, offsets, n_ids)
+    import torch
+    dev = ids.device
+    n_docs = offsets.numel() - 1
+    n_ids = _n_ids(ids, offsets, n_ids)
+    row_offsets = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.windows_rows_device(offsets.data_ptr(), n_docs, n_ids, max_length, stride, bos, eos,
+                                  row_offsets.data_ptr(), err[0:].data_ptr(), stream)
+        if n_rows is None:
+            n_rows = int(row_offsets[-1].item())  # the one synchronisation; pass n_rows= to avoid it
+            if n_rows < n_docs or n_rows > _capi.windows_rows_bound(n_docs, n_ids, max_length, stride, s):
+                raise ValueError("hutoken_amd: collate_windows: offsets that do not describe ids (%d rows)" % n_rows)
+        out = torch.empty((n_rows, max_length), dtype=getattr(torch, dname), device=dev)
+        mask = torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)
+        lengths = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        row_map = torch.empty((n_rows, 2), dtype=torch.int64, device=dev)
+        _capi.collate_windows_device(ids.data_ptr(), offsets.data_ptr(), row_offsets.data_ptr(), n_docs, n_ids, n_rows,
+                                     max_length, stride, bos, eos, pad,
+                                     _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0, width, out.data_ptr(),
+                                     mask.data_ptr(), lengths.data_ptr(), row_map.data_ptr(), err[1:].data_ptr(), stream)
+    if check:
+        _raise_device_error(err.max(), "collate_windows")
+    return out, mask, lengths, row_map
+
+
 _side_streams = {}
 
 
@@ -680,6 +744,13 @@ def batch_encode_padded(texts, max_length=None, **collate_kwargs):
     collate_padded with `collate_kwargs`, both on the initialised context's GPU."""
     ids, oo = _texts_to_device(texts)
     return collate_padded(ids, oo, max_length, **collate_kwargs)
+
+
+def batch_encode_windows(texts, max_length, stride=0, **collate_kwargs):
+    """A list of str -> collate_windows' (input_ids, attention_mask, lengths, row_map): encode_packed_device, then
+    collate_windows with `collate_kwargs`, both on the initialised context's GPU."""
+    ids, oo = _texts_to_device(texts)
+    return collate_windows(ids, oo, max_length, stride, **collate_kwargs)
 
 
 class SequencePacker:

@@ -35,6 +35,7 @@ EXPORTS = [
     "hutk_ctx_find_byte_tokens", "hutk_ctx_set_byte_fallback", "hutk_ctx_byte_fallback",
     "hutk_encode_fallback_batch_device", "hutk_encode_fallback_batch", "hutk_decode_fallback_batch_device",
     "hutk_decode_fallback_batch",
+    "hutk_windows_rows_bound", "hutk_windows_rows_device", "hutk_collate_windows_device",
 ]
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
@@ -228,6 +229,14 @@ def load(build_if_missing=True):
         L.hutk_decode_fallback_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
         L.hutk_decode_fallback_batch.restype = i32
         L.hutk_decode_fallback_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
+    if hasattr(L, "hutk_collate_windows_device"):
+        L.hutk_windows_rows_bound.restype = i64
+        L.hutk_windows_rows_bound.argtypes = [i64, i64, i64, i64, i32]
+        L.hutk_windows_rows_device.restype = i32
+        L.hutk_windows_rows_device.argtypes = [vp, i64, i64, i64, i64, C.c_int32, C.c_int32, vp, vp, vp]
+        L.hutk_collate_windows_device.restype = i32
+        L.hutk_collate_windows_device.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32,
+                                                  i32, i32, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -759,6 +768,29 @@ def collate_padded_device(d_ids, d_offsets, n_docs, n_ids, max_len, bos_id, eos_
     raise_for(load().hutk_collate_padded_device(d_ids or None, d_offsets or None, n_docs, n_ids, max_len, bos_id,
                                                 eos_id, pad_id, flags, out_width, d_input_ids or None,
                                                 d_mask or None, d_lengths or None, d_err or None, stream or None))
+
+
+def windows_rows_bound(n_docs, n_ids, max_len, stride, s):
+    """hutk_windows_rows_bound (host only): an upper bound of the rows collate_windows_device writes."""
+    n = load().hutk_windows_rows_bound(n_docs, n_ids, max_len, stride, s)
+    if n < 0:
+        raise_for(-n)
+    return n
+
+
+def windows_rows_device(d_offsets, n_docs, n_ids, max_len, stride, bos_id, eos_id, d_row_offsets, d_err=0, stream=0):
+    """hutk_windows_rows_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_windows_rows_device(d_offsets or None, n_docs, n_ids, max_len, stride, bos_id, eos_id,
+                                              d_row_offsets or None, d_err or None, stream or None))
+
+
+def collate_windows_device(d_ids, d_offsets, d_row_offsets, n_docs, n_ids, n_rows, max_len, stride, bos_id, eos_id,
+                           pad_id, flags, out_width, d_input_ids, d_mask=0, d_lengths=0, d_row_map=0, d_err=0, stream=0):
+    """hutk_collate_windows_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_collate_windows_device(d_ids or None, d_offsets or None, d_row_offsets or None, n_docs, n_ids,
+                                                 n_rows, max_len, stride, bos_id, eos_id, pad_id, flags, out_width,
+                                                 d_input_ids or None, d_mask or None, d_lengths or None,
+                                                 d_row_map or None, d_err or None, stream or None))
 
 
 class Packer:

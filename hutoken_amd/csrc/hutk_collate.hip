@@ -5,11 +5,15 @@
 //            attention mask and the lengths                                            (k_collate_padded)
 //   packed   the sequences of all documents laid end to end and cut into rows of seq_len, with position and segment
 //            ids; the unfinished row is carried over to the next call                  (k_collate_packed, k_collate_flush)
+//   windows  a document longer than max_len - s is cut into overlapping windows, every window a padded row, with a map
+//            from rows back to documents; the rows' places come from a count, scan, write over the documents first
+//                                                  (k_windows_count, k_windows_write, k_collate_windows)
 //
-// Both are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
+// All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets: a workgroup owns a contiguous span of output, finds the span's first
 // document with one search by a wavefront, marks the sequence starts of its span in LDS and turns the marks into "document
 // of this position", "where its sequence starts" and "starts since the row began" with one workgroup scan.
+#include <map>
 #include <mutex>
 #include <string>
 
@@ -370,6 +374,222 @@ __global__ __launch_bounds__(TB) void k_collate_flush(const int32_t* c_ids, cons
     }
 }
 
+// ---- windows ------------------------------------------------------------------------------------------------------
+// Document i of n ids gives w(n) rows: one when n <= C (C = L - s ids fit a row), else 1 + ceil((n - C) / step) with
+// step = C - stride; row k of it holds the document's ids [k * step, min(k * step + C, n)).  row_offsets is the
+// exclusive scan of w.  A length that cannot be (negative, above n_ids) is reported and counted as the nearest that can.
+constexpr int WIN_BLOCKS = 4096;  // most workgroups of the count: one k_scan_i64 launch scans their sums
+
+__device__ __forceinline__ int64_t window_count(int64_t dl, int64_t n_ids, int64_t C, int64_t step, int32_t* err) {
+    if (dl < 0 || dl > n_ids) {
+        note_error(err, HUTK_E_ARG);
+        dl = dl < 0 ? 0 : n_ids;
+    }
+    return dl <= C ? 1 : 1 + (dl - C + step - 1) / step;
+}
+
+// exclusive scan over the 256 threads of a workgroup; total: the sum.  s_part: four values of LDS, free again after the call
+__device__ __forceinline__ int64_t block_excl_i64(int64_t v, int64_t* s_part, int64_t& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int64_t p = __shfl_up(incl, off);
+        if (lane >= off) incl += p;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    __syncthreads();
+    int64_t before = incl - v;
+    total = 0;
+#pragma unroll
+    for (int u = 0; u < TB / 64; u++) {
+        if (u < wave) before += s_part[u];
+        total += s_part[u];
+    }
+    __syncthreads();
+    return before;
+}
+
+struct WinRowArgs {
+    const int64_t* offs;
+    int64_t n_docs, n_ids;
+    int64_t C, step;
+    int64_t per_block;  // documents per workgroup, a multiple of TB
+    int64_t* sums;      // [gridDim.x + 1]: the workgroups' row counts, then (launch_scan_i64) their exclusive scan and the sum
+    int64_t* row_offs;
+    int32_t* err;
+};
+
+__global__ __launch_bounds__(TB) void k_windows_count(const WinRowArgs a) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n_docs ? lo + a.per_block : a.n_docs;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids)) note_error(a.err, HUTK_E_ARG);
+    int64_t mine = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += TB) mine += window_count(a.offs[i + 1] - a.offs[i], a.n_ids, a.C, a.step, a.err);
+    int64_t total;
+    (void)block_excl_i64(mine, s_part, total);
+    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(TB) void k_windows_write(const WinRowArgs a) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n_docs ? lo + a.per_block : a.n_docs;
+    int64_t base = a.sums[blockIdx.x];
+    for (int64_t at = lo; at < hi; at += TB) {  // (uniform: every thread meets the barriers of the scan)
+        const int64_t i = at + threadIdx.x;
+        const int64_t w = i < hi ? window_count(a.offs[i + 1] - a.offs[i], a.n_ids, a.C, a.step, nullptr) : 0;
+        int64_t total;
+        const int64_t before = block_excl_i64(w, s_part, total);
+        if (i < hi) a.row_offs[i] = base + before;
+        base += total;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.row_offs[a.n_docs] = a.sums[gridDim.x];
+}
+
+struct WinArgs {
+    const int32_t* ids;
+    const int64_t* offs;
+    const int64_t* rows;  // row_offsets
+    int64_t n_docs, n_ids, n_rows;
+    int32_t L, s, C, step;
+    int32_t bos, eos, pad;
+    int32_t has_bos, has_eos, pad_left;
+    void* out;
+    uint8_t* mask;
+    int32_t* lengths;
+    int64_t* row_map;
+    int32_t* err;
+    int32_t rows_per_block;  // as PadArgs
+    int32_t col_chunks;
+};
+
+// last document whose first row is at or before row x: last_doc_le's search over row_offsets[0, n_docs).  All 64 lanes
+// of a wavefront must call it; all get the answer (at least 0 when row_offsets[0] <= x).
+__device__ __forceinline__ int64_t last_doc_of_row(const WinArgs& a, int64_t x) {
+    int64_t lo = 0, hi = a.n_docs;
+    const int lane = threadIdx.x & 63;
+    while (lo < hi) {
+        const int64_t step = (hi - lo + 63) >> 6;
+        const int64_t at = lo + lane * step;
+        const int hits = __popcll(__ballot(at < hi && a.rows[at] <= x));
+        const int64_t top = lo + hits * step;
+        if (hits) lo += (hits - 1) * step + 1;
+        hi = !hits ? lo : top < hi ? top : hi;
+    }
+    return lo - 1;
+}
+
+// A workgroup writes `rows_per_block` whole rows, or PAD_TILE columns of one long row, as k_collate_padded does.  Its rows
+// come from at most as many consecutive documents (row_offsets grows strictly), beginning with the one a wavefront finds;
+// their row_offsets and offsets are staged in LDS, thread r places row r among them once, and an element is then what it
+// is in k_collate_padded.  Whatever row_offsets and offsets hold, every index stays inside the staged entries and d_ids.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_windows(const WinArgs a) {
+    __shared__ int64_t s_ro[PAD_ROWS + 1], s_off[PAD_ROWS + 1];
+    __shared__ int64_t s_start[PAD_ROWS];  // of the row's window inside its document
+    __shared__ int32_t s_j[PAD_ROWS], s_n[PAD_ROWS];  // the row's document (behind the first staged one), its window's ids
+    __shared__ int64_t s_d0;
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids || a.rows[0] != 0 || a.rows[a.n_docs] != a.n_rows) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
+        return;
+    }
+    const int tid = threadIdx.x;
+    const int64_t blk = blockIdx.x;
+    const int64_t rg = blk / a.col_chunks;
+    const int32_t cc = (int32_t)(blk - rg * a.col_chunks);
+    const int64_t row0 = rg * a.rows_per_block;
+    const int64_t left = a.n_rows - row0;
+    const int32_t nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
+    if (nrows <= 0) return;
+    if (tid < 64) {
+        const int64_t d = last_doc_of_row(a, row0);
+        if (tid == 0) s_d0 = d < 0 ? 0 : d;
+    }
+    __syncthreads();
+    const int64_t d0 = s_d0;
+    const int32_t nd = a.n_docs - d0 < nrows ? (int32_t)(a.n_docs - d0) : nrows;  // staged documents, at least one
+    for (int32_t i = tid; i <= nd; i += TB) {
+        s_ro[i] = a.rows[d0 + i];
+        s_off[i] = a.offs[d0 + i];
+    }
+    __syncthreads();
+    if (tid < nrows) {
+        const int64_t row = row0 + tid;
+        int32_t lo = 0, hi = nd;  // the last staged document whose first row is at or before this one
+        while (hi - lo > 1) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (s_ro[mid] <= row) lo = mid;
+            else hi = mid;
+        }
+        int64_t dl = s_off[lo + 1] - s_off[lo];
+        const int64_t k = row - s_ro[lo];
+        bool bad = dl < 0 || dl > a.n_ids;
+        if (bad) dl = 0;
+        if (k < 0 || k >= window_count(dl, a.n_ids, a.C, a.step, nullptr)) bad = true;  // (a row_offsets that is not the scan of w)
+        int64_t start = 0;
+        int32_t n = 0;
+        if (bad) note_error(a.err, HUTK_E_ARG);
+        else {
+            start = k * a.step;  // < dl: no overflow
+            n = dl - start < a.C ? (int32_t)(dl - start) : a.C;
+        }
+        s_j[tid] = lo;
+        s_start[tid] = start;
+        s_n[tid] = n;
+    }
+    __syncthreads();
+    const bool one_row = a.rows_per_block == 1;
+    const int32_t c0 = cc * PAD_TILE;
+    const int32_t ncols = one_row ? ((a.L - c0) < PAD_TILE ? (a.L - c0) : PAD_TILE) : a.L;
+    const int32_t total = nrows * ncols;
+    constexpr int V = VEC ? 4 : 1;
+    for (int32_t i = tid * V; i < total; i += TB * V) {
+        const int32_t rl = one_row ? 0 : i / a.L;
+        const int32_t c = one_row ? c0 + i : i - rl * a.L;
+        const int32_t j = s_j[rl], n = s_n[rl];
+        const int64_t start = s_start[rl];
+        const int64_t src = s_off[j] + start;
+        const int32_t sl = n + a.s;
+        const int32_t shift = a.pad_left ? a.L - sl : 0;
+        int32_t v[V];
+        uint8_t m[V];
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            const int32_t q = c + e - shift;
+            v[e] = a.pad;
+            m[e] = 0;
+            if (q >= 0 && q < sl) {
+                m[e] = 1;
+                if (a.has_bos && q == 0) v[e] = a.bos;
+                else if (a.has_eos && q == sl - 1) v[e] = a.eos;
+                else {
+                    const int64_t idx = src + q - a.has_bos;
+                    if (idx >= 0 && idx < a.n_ids) v[e] = a.ids[idx];
+                    else note_error(a.err, HUTK_E_ARG);
+                }
+            }
+        }
+        const int64_t at = (row0 + rl) * (int64_t)a.L + c;
+        if constexpr (VEC) {
+            store4<W>(a.out, at, v);
+            if (a.mask) *reinterpret_cast<uchar4*>(a.mask + at) = make_uchar4(m[0], m[1], m[2], m[3]);
+        } else {
+            store1<W>(a.out, at, v[0]);
+            if (a.mask) a.mask[at] = m[0];
+        }
+        if (c == 0) {
+            if (a.lengths) a.lengths[row0 + rl] = sl;
+            if (a.row_map) {
+                int64_t* rm = a.row_map + 2 * (row0 + rl);
+                if constexpr (VEC) *reinterpret_cast<longlong2*>(rm) = make_longlong2(d0 + j, start);
+                else rm[0] = d0 + j, rm[1] = start;
+            }
+        }
+    }
+}
+
 bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 int device_present(const char* who) {
@@ -378,6 +598,27 @@ int device_present(const char* who) {
         return hutk::api_set_error(HUTK_E_DEVICE, std::string(who) + ": no HIP device");
     return HUTK_OK;
 }
+
+// What the window calls share: the sizes they refuse before anything else.  C and step come back for the caller.
+int window_sizes(const char* who, int64_t max_len, int64_t stride, int s, int64_t* C, int64_t* step) {
+    if (max_len < 1 || max_len < s + 1 || max_len > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": max_len must be above the number of bos/eos tokens and below 2^31");
+    if (stride < 0 || stride >= max_len - s)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": stride must be in 0 .. max_len - s - 1");
+    *C = max_len - s;
+    *step = *C - stride;
+    return HUTK_OK;
+}
+
+// The workgroup sums of hutk_windows_rows_device: one small buffer per device, made at the first call there and kept.
+// Calls that share it are serialised like calls on one packer: a mutex on the host, an event on the device.
+struct WinScratch {
+    int64_t* sums = nullptr;  // [WIN_BLOCKS + 1]
+    hipEvent_t ev = nullptr;
+    bool ev_recorded = false;
+};
+std::mutex g_win_mu;
+std::map<int, WinScratch> g_win_scratch;
 
 }  // namespace
 
@@ -447,6 +688,122 @@ int hutk_collate_padded_device(const int32_t* d_ids, const int64_t* d_offsets, i
     } else {
         if (vec) hipLaunchKernelGGL((k_collate_padded<8, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_collate_padded<8, false>), grid, block, 0, st, a);
+    }
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int64_t hutk_windows_rows_bound(int64_t n_docs, int64_t n_ids, int64_t max_len, int64_t stride, int s) {
+    int64_t C, step;
+    if (n_docs < 0 || n_ids < 0 || s < 0 || s > 2) {
+        hutk::api_set_error(HUTK_E_ARG, "hutk_windows_rows_bound: bad arguments");
+        return -HUTK_E_ARG;
+    }
+    if (window_sizes("hutk_windows_rows_bound", max_len, stride, s, &C, &step)) return -HUTK_E_ARG;
+    return n_docs + n_ids / step;  // ceil((n - C) / step) <= n / step, as step <= C
+}
+
+int hutk_windows_rows_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, int64_t max_len, int64_t stride,
+                             int32_t bos_id, int32_t eos_id, int64_t* d_row_offsets, int32_t* d_err, void* hip_stream) {
+    const int s = (bos_id != HUTK_NO_TOKEN) + (eos_id != HUTK_NO_TOKEN);
+    if (n_docs < 0 || n_ids < 0) return hutk::api_set_error(HUTK_E_ARG, "hutk_windows_rows_device: bad arguments");
+    WinRowArgs a;
+    if (int rc = window_sizes("hutk_windows_rows_device", max_len, stride, s, &a.C, &a.step)) return rc;
+    if (int rc = device_present("hutk_windows_rows_device")) return rc;
+    if (!d_row_offsets || (n_docs > 0 && !d_offsets))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_windows_rows_device: a buffer is NULL");
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_docs == 0) {
+        HUTK_HIP_TRY(hipMemsetAsync(d_row_offsets, 0, sizeof(int64_t), st));
+        return HUTK_OK;
+    }
+    // at most WIN_BLOCKS workgroups: beyond WIN_BLOCKS * TB documents each takes several chunks of TB
+    a.per_block = (n_docs + (int64_t)WIN_BLOCKS * TB - 1) / ((int64_t)WIN_BLOCKS * TB) * TB;
+    const int64_t blocks = (n_docs + a.per_block - 1) / a.per_block;
+    int device = 0;
+    HUTK_HIP_TRY(hipGetDevice(&device));
+    std::lock_guard<std::mutex> lock(g_win_mu);
+    WinScratch& w = g_win_scratch[device];
+    if (!w.sums) {
+        HUTK_HIP_TRY(hipMalloc((void**)&w.sums, (WIN_BLOCKS + 1) * sizeof(int64_t)));
+        if (hipError_t e = hipEventCreateWithFlags(&w.ev, hipEventDisableTiming); e != hipSuccess) {
+            (void)hipFree(w.sums);
+            w.sums = nullptr;
+            HUTK_HIP_TRY(e);
+        }
+    }
+    if (w.ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
+    a.offs = d_offsets;
+    a.n_docs = n_docs;
+    a.n_ids = n_ids;
+    a.sums = w.sums;
+    a.row_offs = d_row_offsets;
+    a.err = d_err;
+    const dim3 grid((unsigned)blocks), block(TB);
+    hipLaunchKernelGGL(k_windows_count, grid, block, 0, st, a);
+    hutk::launch_scan_i64(w.sums, blocks, st);
+    hipLaunchKernelGGL(k_windows_write, grid, block, 0, st, a);
+    HUTK_HIP_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipEventRecord(w.ev, st));
+    w.ev_recorded = true;
+    return HUTK_OK;
+}
+
+int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, const int64_t* d_row_offsets,
+                                int64_t n_docs, int64_t n_ids, int64_t n_rows, int64_t max_len, int64_t stride,
+                                int32_t bos_id, int32_t eos_id, int32_t pad_id, int flags, int out_width,
+                                void* d_input_ids, uint8_t* d_mask, int32_t* d_lengths, int64_t* d_row_map,
+                                int32_t* d_err, void* hip_stream) {
+    const int s = (bos_id != HUTK_NO_TOKEN) + (eos_id != HUTK_NO_TOKEN);
+    if (n_docs < 0 || n_ids < 0 || n_rows < 0 || (out_width != 4 && out_width != 8) || (flags & ~HUTK_COLLATE_PAD_LEFT))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_windows_device: bad arguments (of the flags, only "
+                                               "HUTK_COLLATE_PAD_LEFT applies)");
+    int64_t C, step;
+    if (int rc = window_sizes("hutk_collate_windows_device", max_len, stride, s, &C, &step)) return rc;
+    if (int rc = device_present("hutk_collate_windows_device")) return rc;
+    if (n_docs == 0) return HUTK_OK;
+    if (!d_offsets || !d_row_offsets || (n_rows > 0 && !d_input_ids) || (n_ids > 0 && !d_ids))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_windows_device: a buffer is NULL");
+    WinArgs a;
+    a.ids = d_ids;
+    a.offs = d_offsets;
+    a.rows = d_row_offsets;
+    a.n_docs = n_docs;
+    a.n_ids = n_ids;
+    a.n_rows = n_rows;
+    a.L = (int32_t)max_len;
+    a.s = s;
+    a.C = (int32_t)C;
+    a.step = (int32_t)step;
+    a.bos = bos_id;
+    a.eos = eos_id;
+    a.pad = pad_id;
+    a.has_bos = bos_id != HUTK_NO_TOKEN;
+    a.has_eos = eos_id != HUTK_NO_TOKEN;
+    a.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
+    a.out = d_input_ids;
+    a.mask = d_mask;
+    a.lengths = d_lengths;
+    a.row_map = d_row_map;
+    a.err = d_err;
+    int64_t rpb = PAD_TILE / max_len;
+    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
+    a.rows_per_block = (int32_t)rpb;
+    a.col_chunks = rpb == 1 ? (int32_t)((max_len + PAD_TILE - 1) / PAD_TILE) : 1;
+    int64_t blocks = (n_rows + rpb - 1) / rpb * a.col_chunks;
+    if (blocks < 1) blocks = 1;  // (n_rows == 0 with documents: the kernel reports it)
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_windows_device: the batch is too large for one launch");
+    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4) && aligned_to(d_row_map, 16);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    const dim3 grid((unsigned)blocks), block(TB);
+    if (out_width == 4) {
+        if (vec) hipLaunchKernelGGL((k_collate_windows<4, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_collate_windows<4, false>), grid, block, 0, st, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_collate_windows<8, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_collate_windows<8, false>), grid, block, 0, st, a);
     }
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;

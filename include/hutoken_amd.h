@@ -347,6 +347,41 @@ int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_posit
 int64_t hutk_packer_pending(const hutk_packer* p);
 void hutk_packer_destroy(hutk_packer* p);
 
+/* WINDOWS.  A long document becomes several overlapping rows instead of one truncated row (what other tokenizers call
+ * stride with overflowing tokens, truncation on the right).  With C = max_len - s (the document ids a row holds) and
+ * step = C - stride (0 <= stride < C), a document of n ids gives w(n) rows: 1 when n <= C (an empty document too),
+ * 1 + ceil((n - C) / step) otherwise.  Row k of the document holds its ids [k * step, min(k * step + C, n)) as
+ * [bos] ids [eos], padded with pad_id like a padded row; the last window is the short one.  The rows of document 0 come
+ * first, then those of document 1, ..; d_row_offsets int64[n_docs + 1] is the exclusive prefix sum of w, strictly
+ * increasing, d_row_offsets[n_docs] = n_rows.
+ *   the rows bound  host only: n_docs + n_ids / step, at least n_rows for any offsets that describe n_ids ids; -HUTK_E_ARG
+ *                   for sizes the other two calls refuse (s: the number of bos/eos tokens, 0 .. 2).
+ *   the rows call   writes d_row_offsets[0 .. n_docs] in three launches (count, scan, write), so that the caller can read
+ *                   n_rows and allocate.  *d_err receives HUTK_E_ARG for offsets[0] != 0, offsets[n_docs] != n_ids or a
+ *                   document length below 0 or above n_ids (counted as 0 or n_ids; d_row_offsets is always written and
+ *                   always strictly increasing).  The workgroup sums live in a small buffer per device that the first
+ *                   call there allocates; calls that share it are serialised like calls on one packer.
+ *   the fill call   writes d_input_ids[n_rows][max_len] and, where not NULL, d_mask[n_rows][max_len], d_lengths[n_rows]
+ *                   (window ids + s) and d_row_map int64[n_rows][2] = {document, index of the row's first document id
+ *                   inside the document = k * step}.  Element q of an unpadded row that is not bos or eos is
+ *                   d_ids[d_offsets[document] + k * step + q - has_bos].  flags: HUTK_COLLATE_PAD_LEFT only.  *d_err
+ *                   receives HUTK_E_ARG for offsets[0] != 0, offsets[n_docs] != n_ids, d_row_offsets[0] != 0 or
+ *                   d_row_offsets[n_docs] != n_rows (nothing is written then), and for a document length or a
+ *                   d_row_offsets entry that cannot be (such rows hold bos/eos and padding only).  Every index is
+ *                   range-checked: nothing is read outside d_ids or the two offset arrays or written outside the n_rows
+ *                   rows.  n_docs == 0 writes nothing and succeeds.
+ * Refused with HUTK_E_ARG before a device is looked for: max_len < 1, < s + 1 or >= 2^31, stride < 0 or >= max_len - s,
+ * an out_width other than 4 or 8, any flag but HUTK_COLLATE_PAD_LEFT, negative counts.  More than 2^31 - 1 workgroups in
+ * the fill: HUTK_E_UNSUPPORTED. */
+int64_t hutk_windows_rows_bound(int64_t n_docs, int64_t n_ids, int64_t max_len, int64_t stride, int s);
+int hutk_windows_rows_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, int64_t max_len, int64_t stride,
+                             int32_t bos_id, int32_t eos_id, int64_t* d_row_offsets, int32_t* d_err, void* hip_stream);
+int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, const int64_t* d_row_offsets,
+                                int64_t n_docs, int64_t n_ids, int64_t n_rows, int64_t max_len, int64_t stride,
+                                int32_t bos_id, int32_t eos_id, int32_t pad_id, int flags, int out_width,
+                                void* d_input_ids, uint8_t* d_mask, int32_t* d_lengths, int64_t* d_row_map,
+                                int32_t* d_err, void* hip_stream);
+
 /* ---- token spans (offset mapping) ----------------------------------------------------------------------
  * Which stretch of its document each id covers: from the packed text (d_bytes, d_offsets) and the ragged pair that
  * hutk_encode_batch_device wrote for it (d_ids, d_id_offsets; n_ids as in the collation calls: d_id_offsets[n_docs] ==

@@ -9,7 +9,8 @@ def funcs(path):
     for line in open(path):
         m=re.match(r'^(_Z\w+|\w+):\s*; @',line)
         if m: cur=m.group(1);buf=[]
-        if cur is not None: buf.append(re.sub(r'\.L(BB|func_end|func_begin|JTI)\d+','.L\\1',line))  # (labels carry the function's ordinal)
+        if cur is not None:  # (labels carry the function's ordinal: in the code, in loop comments, and in the comments' column)
+            buf.append(re.sub(r'\s+',' ',re.sub(r'\bBB\d+_','BB_',re.sub(r'\.L(BB|func_end|func_begin|JTI)\d+','.L\\1',line)))+'\n')
         if cur and line.startswith('.Lfunc_end'):
             out[cur]=(hashlib.sha256(''.join(buf).encode()).hexdigest()[:12],len(buf));cur=None
     return out

@@ -23,7 +23,7 @@ EXPORTS = [
     "hutk_host_free", "hutk_decode_batch", "hutk_decode_batch_device",
     "hutk_pair_table_entries", "hutk_device_ordinal", "hutk_table_stats", "hutk_last_timing",
     "hutk_set_timing", "hutk_debug_pairs_second", "hutk_debug_long_words", "hutk_debug_profile", "hutk_debug_profile_read", "hutk_debug_profile_raw", "hutk_debug_tile_bytes",
-    "hutk_debug_seam", "hutk_debug_seam2_cut",
+    "hutk_debug_seam", "hutk_debug_seam2_cut", "hutk_debug_tile_kernel",
     "hutk_trainer_create", "hutk_trainer_add", "hutk_trainer_run", "hutk_trainer_stats", "hutk_trainer_destroy",
     "hutk_trainer_debug_counters", "hutk_trainer_create_mode", "hutk_trainer_alphabet",
     "hutk_collate_padded_device", "hutk_packer_create", "hutk_packer_rows", "hutk_packer_add_device",
@@ -145,6 +145,9 @@ def load(build_if_missing=True):
     if hasattr(L, "hutk_debug_seam2_cut"):
         L.hutk_debug_seam2_cut.restype = i32
         L.hutk_debug_seam2_cut.argtypes = [vp, C.c_uint32, C.c_uint32]
+    if hasattr(L, "hutk_debug_tile_kernel"):
+        L.hutk_debug_tile_kernel.restype = i32
+        L.hutk_debug_tile_kernel.argtypes = [vp, i64]
     L.hutk_debug_profile.restype = i32
     L.hutk_debug_profile.argtypes = [vp, i32]
     L.hutk_debug_tile_bytes.restype = i32
@@ -400,6 +403,14 @@ class Context:
     def seam2_cut(self, a3, b3):
         """The seam map's second level: True when no token can span the three-byte characters a3 | b3 (bytes objects)."""
         return bool(load().hutk_debug_seam2_cut(self._h, int.from_bytes(a3, "little"), int.from_bytes(b3, "little")))
+
+    def tile_kernel(self, n_bytes):
+        """Which tile kernel hutk_encode_batch_device gives a plain batch of n_bytes under the environment of this moment:
+        0 = k_tiles, 1 = k_ptiles (the persistent one), 2 = both, chosen on the device.  Launches nothing."""
+        k = load().hutk_debug_tile_kernel(self._h, int(n_bytes))
+        if k < 0:
+            raise_for(E_ARG)
+        return k
 
     def encode_packed(self, data, offsets, want_status=True):
         """Host numpy buffers in, host numpy buffers out.

@@ -46,6 +46,9 @@ int hutk::api_set_error(int code, const std::string& msg) {
 
 namespace {
 
+// the seam map is in use: the vocabulary has one and HUTK_NO_SEAM does not switch it off
+bool seams_wanted(const Tables& T) { return T.seam_on && !(getenv("HUTK_NO_SEAM") && atoi(getenv("HUTK_NO_SEAM"))); }
+
 int upload_tables(hutk_ctx* c) {
     Tables& T = c->tab;
 #define UP(buf, vec)                                                                            \
@@ -103,7 +106,7 @@ int upload_tables(hutk_ctx* c) {
     HUTK_HIP_TRY(c->d_seam.reserve(256));
     HUTK_HIP_TRY(hipMemcpy(c->d_seam.p, T.seam_hi, sizeof T.seam_hi, hipMemcpyHostToDevice));
     D.seam_hi = c->d_seam.p;
-    D.seam_on = T.seam_on && !(getenv("HUTK_NO_SEAM") && atoi(getenv("HUTK_NO_SEAM"))) ? 1 : 0;
+    D.seam_on = seams_wanted(T) ? 1 : 0;
     {   // second level: seam2_part, then the hashed set of character pairs, in one buffer
         const size_t nb = T.seam2_on ? T.seam2_bits.size() : 1;
         std::vector<uint32_t> buf(256 + nb, 0u);
@@ -502,7 +505,7 @@ int64_t hutk_debug_long_words(const hutk_ctx* ctx) { return ctx ? ctx->n_wordl_e
 int hutk_debug_seam(const hutk_ctx* ctx, uint32_t* out256) {
     if (!ctx || !out256) return api_set_error(HUTK_E_ARG, "bad argument");
     memcpy(out256, ctx->tab.seam_hi, sizeof ctx->tab.seam_hi);
-    return ctx->tab.seam_on && !(getenv("HUTK_NO_SEAM") && atoi(getenv("HUTK_NO_SEAM"))) ? 1 : 0;
+    return seams_wanted(ctx->tab) ? 1 : 0;
 }
 // second level: 1 when it is on and says that NO token can span the boundary between the three-byte characters a3 | b3
 // (little-endian 24-bit values) -- asked where hutk_debug_seam's map says "may join"; 0 otherwise
@@ -615,6 +618,36 @@ static int ptiles_mode() {
     return e ? (atoi(e) != 0 ? 1 : 0) : PTILES_DEFAULT;
 }
 
+// What a batch gets: 0 = k_tiles, 1 = k_ptiles, 2 = both, and Workspace::select lets the batch's bytes decide on the device
+// (only where seams cut dense text into short words: without them the choice is k_tiles).  encode_device_impl enqueues by
+// this, and hutk_debug_tile_kernel reports it.
+static int tile_kernels_for(const DevTables& t, const BatchArgs& a) {
+    const int mode = ptiles_takes(t, a) ? ptiles_mode() : 0;
+    return mode == 2 && !t.seam_on ? 0 : mode;
+}
+
+// Host only: what encode_device_impl would enqueue for a plain batch (no regex bitmaps) of n_bytes under the environment
+// of this moment: 0 = k_tiles only, 1 = k_ptiles only, 2 = both, chosen on the device; -1: bad argument.  A host-only
+// context answers from its tables (the seam switch as a context made now would read it).
+int hutk_debug_tile_kernel(const hutk_ctx* c, int64_t n_bytes) {
+    if (!c || n_bytes < 0) {
+        api_set_error(HUTK_E_ARG, "bad argument");
+        return -1;
+    }
+    BatchArgs A{};
+    A.n_bytes = n_bytes;
+    A.n_tiles = (n_bytes + TILE_BYTES - 1) / TILE_BYTES;
+    if (!c->host_only) return tile_kernels_for(c->dt, A);
+    const Tables& T = c->tab;
+    DevTables D{};
+    D.sym16 = T.sym16;
+    D.is_byte_encoder = T.is_byte_encoder;
+    D.rank_is_sym = T.rank_is_sym;
+    D.has_multi = T.has_multi ? 1 : 0;
+    D.seam_on = seams_wanted(T) ? 1 : 0;
+    return tile_kernels_for(D, A);
+}
+
 // (declared in hutk_internal.h: hutk_special.hip encodes the pieces between special tokens with it)
 extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
                                           int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets,
@@ -670,11 +703,13 @@ extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, c
     launch_pre(A, W, s);
     if (c->timing) HUTK_HIP_TRY(hipEventRecord(c->ev[1], s));
     {
-        const int mode = ptiles_takes(c->dt, A) ? ptiles_mode() : 0;
-        W.select = mode == 2 && c->dt.seam_on ? 1 : 0;
-        if (mode == 1 || W.select == 1) launch_ptiles(c->dt, A, W, s);
-        if (mode != 1) {
-            W.select = W.select ? 2 : 0;
+        const int which = tile_kernels_for(c->dt, A);
+        if (which != 0) {
+            W.select = which == 2 ? 1 : 0;
+            launch_ptiles(c->dt, A, W, s);
+        }
+        if (which != 1) {
+            W.select = which == 2 ? 2 : 0;
             launch_tiles(c->dt, A, W, s);
         }
         W.select = 0;

@@ -1067,9 +1067,11 @@ static int pt_grid() {
 }
 
 // Does the persistent kernel take this batch?  (Byte-encoder mode, 16-bit symbols, rank == symbol order, every item one
-// unit, the hand-written splitter, and enough tiles to give every compute unit a few.)
+// unit, the hand-written splitter, and enough tiles to give every compute unit a few: 4 * pt_grid(), or what
+// HUTK_PTILES_MIN_TILES says.  The switch is read on every call, as HUTK_PTILES is: tests/test_gpu_ptiles_edges.py sets 1.)
 bool ptiles_takes(const DevTables& t, const BatchArgs& a) {
-    static const int64_t min_tiles = getenv("HUTK_PTILES_MIN_TILES") ? atoll(getenv("HUTK_PTILES_MIN_TILES")) : 4 * (int64_t)pt_grid();  // (the tests set 1)
+    const char* e = getenv("HUTK_PTILES_MIN_TILES");
+    const int64_t min_tiles = e ? atoll(e) : 4 * (int64_t)pt_grid();
     return t.sym16 && t.is_byte_encoder && t.rank_is_sym && !t.has_multi && !a.word_bits && !a.first_bits &&
            a.n_tiles >= min_tiles;
 }

@@ -235,6 +235,13 @@ int hutk_debug_seam(const hutk_ctx* ctx, uint32_t* out256);
  * it, little-endian.  Returns 1 when no token can span a3 | b3 -- the tile kernel starts a word at b3 although the first
  * level says "may join" -- and 0 otherwise (also when the level is off).  tests/test_seam_cpu.py. */
 int hutk_debug_seam2_cut(const hutk_ctx* ctx, uint32_t a3, uint32_t b3);
+/* Diagnostic, host only (nothing is launched): which tile kernel a plain batch (no regex pattern) of n_bytes would be
+ * given by hutk_encode_batch_device under the environment of this moment (HUTK_PTILES, HUTK_PTILES_MIN_TILES; the seam
+ * switch as the context read it when it was created).  0: the ordinary tile kernel.  1: the persistent one.  2: both are
+ * enqueued and a sample of the batch's bytes decides on the device.  -1: bad argument.  The encode enqueues by the same
+ * function, so a test that means to reach one of the kernels can assert that it does.  A host-only context answers from
+ * its tables.  tests/test_gpu_ptiles_edges.py. */
+int hutk_debug_tile_kernel(const hutk_ctx* ctx, int64_t n_bytes);
 
 /* Diagnostic build aid: clock64 stamps at the phase boundaries of the tile kernel.
  * hutk_debug_profile(ctx, 1), run a batch, then hutk_debug_profile_read returns the

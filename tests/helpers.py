@@ -264,3 +264,96 @@ def long_token_char_vocab(seed):
             entries.append((tok.encode("utf-8"), len(toks)))
             toks.append(tok)
     return entries, special, toks
+
+
+def compare(ctx, orc, docs, tag="", encode=None, want_rc=0):
+    """docs: list[bytes] without 0x00.  Every id, output offset and per-document status of the GPU against the CPU oracle,
+    and the return code: bit-exact.  encode: (data, offsets) -> (ids, out_offsets, status, rc), by default the context's
+    host form (ctx.encode_packed); tests/test_gpu_ptiles_edges.py passes the device form, which no small-batch short cut
+    takes.  want_rc: 0, or the note E_WORD_TOO_LARGE (9) for a batch in which the oracle cuts a document."""
+    import numpy as np
+    from oracle import oracle as O
+    data, offs = O.pack(docs)
+    ids_o, oo_o, st_o = orc.encode_packed(data, offs, num_threads=4)
+    ids_g, oo_g, st_g, rc = (encode or ctx.encode_packed)(data, offs)
+    assert rc == want_rc, f"{tag}: rc={rc}"
+    if not np.array_equal(oo_o, oo_g):
+        bad = int(np.nonzero(oo_o != oo_g)[0][0])
+        d = max(bad - 1, 0)
+        raise AssertionError(
+            f"{tag}: out_offsets differ first at {bad}; doc {d}={docs[d][:200]!r}\n"
+            f" oracle={ids_o[oo_o[d]:oo_o[d + 1]].tolist()[:200]}\n gpu   ={ids_g[oo_g[d]:oo_g[d + 1]].tolist()[:200]}")
+    if not np.array_equal(ids_o, ids_g):
+        k = int(np.nonzero(ids_o != ids_g)[0][0])
+        d = int(np.searchsorted(oo_o, k, side="right") - 1)
+        raise AssertionError(
+            f"{tag}: ids differ first at {k} (doc {d}={docs[d][:200]!r})\n"
+            f" oracle={ids_o[oo_o[d]:oo_o[d + 1]].tolist()[:200]}\n gpu   ={ids_g[oo_g[d]:oo_g[d + 1]].tolist()[:200]}")
+    assert np.array_equal(st_g, st_o), f"{tag}: status"
+    if want_rc == 0:
+        assert (st_g == 0).all()
+
+
+# ---- seeded inputs of tests/test_gpu_parity.py that tests/test_gpu_ptiles_edges.py runs through the persistent tile kernel too
+
+def ragged_docs():
+    """test_document_boundaries_inside_characters: documents end in the middle of multi-byte sequences and tiles end in the
+    middle of words."""
+    rng = random.Random(7)
+    blob = "".join(random_text(rng, max_words=30) for _ in range(400)).encode("utf-8").replace(b"\0", b"")
+    docs, i = [], 0
+    while i < len(blob):
+        n = rng.choice([0, 1, 2, 3, 5, 17, 64, 300, 2047, 2048, 2049, 5000])
+        docs.append(blob[i:i + n])
+        i += n
+    return docs
+
+
+def long_word_docs():
+    """test_long_words_exception_path: words beyond one lane's capacity, beyond the staged window, and beyond the LDS
+    capacity of the exception kernel (1024 units)."""
+    rng = random.Random(11)
+    docs = []
+    for n in [47, 48, 49, 50, 62, 63, 64, 65, 100, 126, 127, 128, 129, 130, 191, 192, 193, 255, 256, 257, 300, 1000, 1023, 1024,
+              1025, 1500, 2045, 2046, 2047, 2048, 2049, 3000, 9000]:
+        docs.append(bytes(rng.choice(b"etaoinshr") for _ in range(n)))
+        docs.append(b"pre " + bytes(rng.choice(b"etaoin") for _ in range(n)) + b" post")
+        docs.append(("漢" * (n // 3 + 1)).encode("utf-8"))
+    docs.append(b"a" * 5000 + b" " + b"b" * 2100)
+    docs.append(b" " * 3000)
+    docs.append(b"1" * 2500 + b"x" * 2500)
+    return docs
+
+
+def later_tile_word_docs():
+    """test_word_ends_in_later_tiles -> (documents, the seeded word maker that made them): words that end exactly on tile
+    limits (multiples of 960 bytes), one to three tiles further on, at a document's end, at the end of the batch, with
+    another long word or nothing behind."""
+    rng = random.Random(960)
+
+    def word(n):
+        return bytes(rng.choice(b"etaoinshrdlu") for _ in range(n))
+    docs = []
+    for lead in (0, 1, 5, 63, 64, 100, 500, 896, 897, 959, 960, 961, 1000):
+        for n in (64, 65, 100, 959 - lead % 960, 960, 961, 1024, 1025, 1919, 1920, 1921, 2880, 3000):
+            if n < 64:
+                continue
+            pre = (word(lead - 1) + b" ") if lead else b""
+            docs.append(pre + word(n))                  # the document ends with the word
+            docs.append(pre + word(n) + b" x")          # a short word behind
+            docs.append(pre + word(n) + b" " + word(n))  # a long one behind
+    docs.append(word(70))      # the batch ends with a long word
+    return docs, word
+
+
+def dense_word_docs():
+    """test_dense_word_tiles: every byte a word (newlines, stray bytes), and two-byte words back to back (the most
+    multi-unit words a tile can start)."""
+    return [b"\n" * 5000, b"\xff\x80" * 3000, b"a " * 4000, b" a" * 4000, b"ab" + b"\tab" * 3000,
+            b"a1" * 3000, b".a" * 3000 + b"!" * 2000, bytes(range(1, 256)) * 20]
+
+
+def merge_loop_words(rng, n_words, lo, hi):
+    """test_merge_pool_overflow: random letter strings over eight rare letters, so nearly none is a vocabulary key and all
+    of them need the merge loop."""
+    return b" ".join(bytes(rng.choice(b"qxzjkvwy") for _ in range(rng.randint(lo, hi))) for _ in range(n_words))

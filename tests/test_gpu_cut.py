@@ -39,15 +39,9 @@ def quiet_char(orc, seam):
     pytest.skip("the vocabulary merges every three-byte character tried")
 
 
-def test_over_long_words_cut_their_documents_on_both_entry_points():
-    from hutoken_amd import _capi, data
-    from oracle import oracle as O
-    vp, sp, kw = data.vocab_files("VG")
-    ctx = _capi.Context(vp, sp, kw["prefix"], kw["is_byte_encoder"])
-    orc = O.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"])
-    seam, on = ctx.seam_map()
-    assert on
-    c = quiet_char(orc, seam)
+def cut_docs(c):
+    """-> (documents around the reference's limit, the oracle's status of each); c: quiet_char().  (tests/
+    test_gpu_ptiles_edges.py runs them again.)"""
     n_ok = (LIMIT - 1) // 3          # a leading space and n_ok characters: at most 262144 bytes
     n_cut = LIMIT // 3 + 1           # more than 262144 bytes without the space
     filler = b"the quick brown fox jumps over the lazy dog. " * 30
@@ -64,9 +58,26 @@ def test_over_long_words_cut_their_documents_on_both_entry_points():
         b"",
         b"last",
     ]
+    return docs, [0, 0, 1, 0, 1, 1, 1, 1, 0, 0, 0]
+
+
+NO_SEAM_DOCS = [b"a b", b"letters over the limit " + b"x" * (LIMIT + 1) + b" dropped", b"kept " + b"x" * (LIMIT - 1) + b" kept", b"z"]
+NO_SEAM_STATUS = [0, 1, 0, 0]
+
+
+def test_over_long_words_cut_their_documents_on_both_entry_points():
+    from hutoken_amd import _capi, data
+    from oracle import oracle as O
+    vp, sp, kw = data.vocab_files("VG")
+    ctx = _capi.Context(vp, sp, kw["prefix"], kw["is_byte_encoder"])
+    orc = O.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"])
+    seam, on = ctx.seam_map()
+    assert on
+    c = quiet_char(orc, seam)
+    docs, want_st = cut_docs(c)
     data_, offs = O.pack(docs)
     ids_o, oo_o, st_o = orc.encode_packed(data_, offs, 8)
-    assert st_o.tolist() == [0, 0, 1, 0, 1, 1, 1, 1, 0, 0, 0]
+    assert st_o.tolist() == want_st
     ids_h, oo_h, st_h, rc = ctx.encode_packed(data_, offs)
     assert rc == 0
     assert st_h.tolist() == st_o.tolist()
@@ -86,10 +97,9 @@ def test_the_same_without_seams(monkeypatch):
     vp, sp, kw = data.vocab_files("VG")
     ctx = _capi.Context(vp, sp, kw["prefix"], kw["is_byte_encoder"])
     orc = O.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"])
-    docs = [b"a b", b"letters over the limit " + b"x" * (LIMIT + 1) + b" dropped", b"kept " + b"x" * (LIMIT - 1) + b" kept", b"z"]
-    data_, offs = O.pack(docs)
+    data_, offs = O.pack(NO_SEAM_DOCS)
     ids_o, oo_o, st_o = orc.encode_packed(data_, offs, 4)
     ids_d, oo_d, st_d, err = device_form(ctx, data_, offs)
-    assert st_d.tolist() == st_o.tolist() == [0, 1, 0, 0]
+    assert st_d.tolist() == st_o.tolist() == NO_SEAM_STATUS
     assert np.array_equal(oo_d, oo_o) and np.array_equal(ids_d, ids_o)
     ctx.close()

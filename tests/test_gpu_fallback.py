@@ -146,12 +146,17 @@ def test_character_vocabulary_with_unknown_characters(tmp_path, oracle_mod, drop
     ctx.close()
 
 
-def test_byte_vocabulary_with_holes(tmp_path, oracle_mod):
+HOLES = (0x62, 0xC3, 0xBC, 0x80)
+
+
+def holes_case(tmp_path, oracle_mod):
+    """-> (context, oracle, fallback table, data, offsets): a byte-level vocabulary that lacks four single bytes, on
+    arbitrary bytes and on text.  (tests/test_gpu_ptiles_edges.py runs it again.)"""
     from hutoken_amd import _capi
     from hutoken_amd import vocab_files as vf
     ents, special = H.random_byte_vocab(3, n_merges=300)
     vis = vf.bytes_to_unicode()
-    lacking = {vf.encode_visible(bytes([b]), vis) for b in (0x62, 0xC3, 0xBC, 0x80)}
+    lacking = {vf.encode_visible(bytes([b]), vis) for b in HOLES}
     ents = [(k, i) for k, i in ents if k not in lacking]
     vp, spath = H.write_vocab(tmp_path, "fbu", ents, special)
     ctx, orc = _capi.Context(vp, spath, None, True, device=0), oracle_mod.Oracle(vp, spath, None, True)
@@ -162,10 +167,15 @@ def test_byte_vocabulary_with_holes(tmp_path, oracle_mod):
     docs = [H.random_bytes_text(rng, rng.randint(0, 120)) for _ in range(1500)]
     docs += [H.random_text(rng, max_words=20).encode("utf-8") for _ in range(1500)]
     d, o = _pack(docs)
+    return ctx, orc, table, d, o
+
+
+def test_byte_vocabulary_with_holes(tmp_path, oracle_mod):
+    ctx, orc, table, d, o = holes_case(tmp_path, oracle_mod)
     want, woo = _check_encode(ctx, S.TokenText(orc), d, o, True, table, "byte vocab with holes")
     ids, oo, _st, _rc = ctx.encode_packed(d, o)
     assert np.array_equal(woo, oo), "every -1 becomes exactly one id"
-    assert set(want[ids == -1].tolist()) <= {100000 + b for b in (0x62, 0xC3, 0xBC, 0x80)}
+    assert set(want[ids == -1].tolist()) <= {100000 + b for b in HOLES}
     ctx.close()
 
 

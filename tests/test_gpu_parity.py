@@ -16,26 +16,7 @@ def _ctx(vp, sp, prefix, is_byte, merges=None):
     return _capi.Context(vp, sp, prefix, is_byte, merges_path=merges)
 
 
-def _compare(ctx, orc, docs, tag=""):
-    """docs: list[bytes] without 0x00."""
-    from oracle import oracle as O
-    data, offs = O.pack(docs)
-    ids_o, oo_o, st_o = orc.encode_packed(data, offs, num_threads=4)
-    ids_g, oo_g, st_g, rc = ctx.encode_packed(data, offs)
-    assert rc == 0, f"{tag}: rc={rc}"
-    if not np.array_equal(oo_o, oo_g):
-        bad = int(np.nonzero(oo_o != oo_g)[0][0])
-        d = max(bad - 1, 0)
-        raise AssertionError(
-            f"{tag}: out_offsets differ first at {bad}; doc {d}={docs[d]!r}\n"
-            f" oracle={ids_o[oo_o[d]:oo_o[d + 1]].tolist()}\n gpu   ={ids_g[oo_g[d]:oo_g[d + 1]].tolist()}")
-    if not np.array_equal(ids_o, ids_g):
-        k = int(np.nonzero(ids_o != ids_g)[0][0])
-        d = int(np.searchsorted(oo_o, k, side="right") - 1)
-        raise AssertionError(
-            f"{tag}: ids differ first at {k} (doc {d}={docs[d]!r})\n"
-            f" oracle={ids_o[oo_o[d]:oo_o[d + 1]].tolist()}\n gpu   ={ids_g[oo_g[d]:oo_g[d + 1]].tolist()}")
-    assert (st_g == 0).all()
+_compare = H.compare
 
 
 @pytest.fixture(scope="module")
@@ -95,29 +76,14 @@ def test_document_boundaries_inside_characters(small_byte):
     """Ragged packing: documents end in the middle of multi-byte sequences and
     tiles end in the middle of words."""
     ctx, orc = small_byte[0]
-    rng = random.Random(7)
-    blob = "".join(H.random_text(rng, max_words=30) for _ in range(400)).encode("utf-8").replace(b"\0", b"")
-    docs, i = [], 0
-    while i < len(blob):
-        n = rng.choice([0, 1, 2, 3, 5, 17, 64, 300, 2047, 2048, 2049, 5000])
-        docs.append(blob[i:i + n])
-        i += n
+    docs = H.ragged_docs()
     _compare(ctx, orc, docs, "ragged")
 
 
 def test_long_words_exception_path(small_byte):
     """Words beyond one lane's capacity (48 units), beyond the staged window,
     and beyond the LDS capacity of the exception kernel (1024 units)."""
-    rng = random.Random(11)
-    docs = []
-    for n in [47, 48, 49, 50, 62, 63, 64, 65, 100, 126, 127, 128, 129, 130, 191, 192, 193, 255, 256, 257, 300, 1000, 1023, 1024,
-              1025, 1500, 2045, 2046, 2047, 2048, 2049, 3000, 9000]:
-        docs.append(bytes(rng.choice(b"etaoinshr") for _ in range(n)))
-        docs.append(b"pre " + bytes(rng.choice(b"etaoin") for _ in range(n)) + b" post")
-        docs.append(("漢" * (n // 3 + 1)).encode("utf-8"))
-    docs.append(b"a" * 5000 + b" " + b"b" * 2100)
-    docs.append(b" " * 3000)
-    docs.append(b"1" * 2500 + b"x" * 2500)
+    docs = H.long_word_docs()
     for ctx, orc in small_byte:
         _compare(ctx, orc, docs, "long")
 
@@ -178,19 +144,7 @@ def test_word_ends_in_later_tiles(vg_files, small_byte, oracle_mod):
     """d_exc_ends: a word whose end its tile cannot see ends at the first word start of the tiles behind it
     (Workspace::tile_first_start): words that end exactly on tile limits (multiples of 960 bytes), one to three tiles
     further on, at a document's end, at the end of the batch, with another long word or nothing behind."""
-    rng = random.Random(960)
-    def word(n):
-        return bytes(rng.choice(b"etaoinshrdlu") for _ in range(n))
-    docs = []
-    for lead in (0, 1, 5, 63, 64, 100, 500, 896, 897, 959, 960, 961, 1000):
-        for n in (64, 65, 100, 959 - lead % 960, 960, 961, 1024, 1025, 1919, 1920, 1921, 2880, 3000):
-            if n < 64:
-                continue
-            pre = (word(lead - 1) + b" ") if lead else b""
-            docs.append(pre + word(n))                  # the document ends with the word
-            docs.append(pre + word(n) + b" x")          # a short word behind
-            docs.append(pre + word(n) + b" " + word(n))  # a long one behind
-    docs.append(word(70))      # the batch ends with a long word
+    docs, word = H.later_tile_word_docs()
     vp, sp, kw = vg_files
     _compare(_ctx(vp, sp, kw["prefix"], kw["is_byte_encoder"]), oracle_mod.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"]), docs, "ends VG")
     for ctx, orc in small_byte[:2]:
@@ -215,8 +169,7 @@ def test_many_exception_words_in_one_tile(vl_files, small_char, oracle_mod):
 def test_dense_word_tiles(small_byte):
     """Tiles packed with the shortest possible words: every byte a word (newlines, stray bytes), and
     two-byte words back to back (the most multi-unit words a tile can start)."""
-    docs = [b"\n" * 5000, b"\xff\x80" * 3000, b"a " * 4000, b" a" * 4000, b"ab" + b"\tab" * 3000,
-            b"a1" * 3000, b".a" * 3000 + b"!" * 2000, bytes(range(1, 256)) * 20]
+    docs = H.dense_word_docs()
     for ctx, orc in small_byte:
         _compare(ctx, orc, docs, "dense")
         _compare(ctx, orc, [bytes([b]) for b in range(1, 256)] * 8, "one-byte-docs")
@@ -228,7 +181,7 @@ def test_merge_pool_overflow(small_byte):
     random letter strings, so nearly none is a vocabulary key and all of them need the merge loop."""
     rng = random.Random(23)
     def words(n_words, lo, hi):
-        return b" ".join(bytes(rng.choice(b"qxzjkvwy") for _ in range(rng.randint(lo, hi))) for _ in range(n_words))
+        return H.merge_loop_words(rng, n_words, lo, hi)
     docs = [words(3000, 2, 3),        # ~270 short merge words per tile
             words(2000, 10, 14),      # ~75 long merge words per tile
             words(1500, 2, 30),       # mixed

@@ -143,10 +143,10 @@ def test_parity(oracle_mod, name, merges, markers):
     assert hutoken_amd.context().special_token_count == 0
 
 
-def test_scan_boundaries(oracle_mod):
-    """A 29-byte marker every T + 1 bytes of a document of 40 T bytes: every alignment across a workgroup's boundary."""
+def scan_boundaries_case():
+    """-> (documents, the marker set, markers inside the first document): a 29-byte marker every T + 1 bytes of a document
+    of 40 T bytes, and markers split over two documents.  (tests/test_gpu_ptiles_edges.py runs it again.)"""
     from hutoken_amd import _capi
-    ctx, orc = _pair(oracle_mod, "VG")
     T = _capi.load().hutk_debug_special_tile_bytes()
     m = b"<|reserved_special_token_12|>"
     assert len(m) == 29
@@ -168,7 +168,13 @@ def test_scan_boundaries(oracle_mod):
             tail]
     d, o = _pack(docs)
     assert bytes(d[-29:]) == m  # a marker ends at the last byte of the batch
-    specials = {m.decode(): 128014}
+    return docs, {m.decode(): 128014}, n_in
+
+
+def test_scan_boundaries(oracle_mod):
+    """A 29-byte marker every T + 1 bytes of a document of 40 T bytes: every alignment across a workgroup's boundary."""
+    ctx, orc = _pair(oracle_mod, "VG")
+    docs, specials, n_in = scan_boundaries_case()
     _check(ctx, orc, docs, specials, "scan boundaries", min_matches=n_in + 1)
     assert ctx.special_last_matches == n_in + 1  # none of the split ones
 
@@ -196,18 +202,24 @@ def test_overlap_rules(oracle_mod):
     _check(ctx, orc, docs, RESERVED, "256 reserved markers", min_matches=60)
 
 
-def test_stitch(oracle_mod):
-    ctx, orc = _pair(oracle_mod, "VG")
+def stitch_cases():
+    """-> [(documents, tag, least number of matches)], all for the marker set {EOT: 50256}; the first one is the long piece
+    between two markers.  (tests/test_gpu_ptiles_edges.py runs them again.)"""
     rng = random.Random(3)
     m = EOT.encode()
     long_text = " ".join(H.random_text(rng, max_words=30, exotic=0.1) for _ in range(120)).encode("utf-8")
-    want_ids, _ = _check(ctx, orc, [b"x", m + long_text + m + b" y", b"z" + m], {EOT: 50256}, "a long piece between two markers",
-                         min_matches=3)
-    assert len(want_ids) > 2048 + 8
-    _check(ctx, orc, [b"before ", m * 5000, b" after"], {EOT: 50256}, "5000 markers back to back", min_matches=5000)
-    docs = [b"in front " + m] + [b""] * 100_000 + [m + b" behind", m]
-    _check(ctx, orc, docs, {EOT: 50256}, "100 000 empty documents", min_matches=3)
-    _check(ctx, orc, [b"", b"a" + m, m + m, b" b", b""], {EOT: 50256}, "first and last document empty", min_matches=3)
+    return [([b"x", m + long_text + m + b" y", b"z" + m], "a long piece between two markers", 3),
+            ([b"before ", m * 5000, b" after"], "5000 markers back to back", 5000),
+            ([b"in front " + m] + [b""] * 100_000 + [m + b" behind", m], "100 000 empty documents", 3),
+            ([b"", b"a" + m, m + m, b" b", b""], "first and last document empty", 3)]
+
+
+def test_stitch(oracle_mod):
+    ctx, orc = _pair(oracle_mod, "VG")
+    for k, (docs, tag, least) in enumerate(stitch_cases()):
+        want_ids, _ = _check(ctx, orc, docs, {EOT: 50256}, tag, min_matches=least)
+        if k == 0:
+            assert len(want_ids) > 2048 + 8
 
 
 def test_no_op(oracle_mod):

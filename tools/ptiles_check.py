@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """k_ptiles (HUTK_PTILES=1) against k_tiles (HUTK_PTILES=0) on the same device buffers: every id and offset equal, a
-sample of the documents against the oracle, and the time of both.  GPU only.
+sample of the documents against the oracle, and the time of both.  GPU only.  This is the TIMING tool: the correctness half
+(both kernels and the automatic choice against the oracle, on the small and odd batches too) is in the suite now,
+tests/test_gpu_ptiles_edges.py.
   ptiles_check.py [CORPUS N_DOCS [VOCAB]] ...   CORPUS: C2 | C3 | C5 | words:LO:HI | cjk"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

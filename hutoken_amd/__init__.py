@@ -178,6 +178,20 @@ def _pack(texts):
     return np.frombuffer(data, dtype=np.uint8), offs
 
 
+def _rows(ids, oo, n):
+    """ids and the n + 1 offsets into them (numpy arrays or tensors) -> the n lists of ids."""
+    bounds = oo.tolist()
+    flat = ids[:bounds[-1]].tolist()
+    return [flat[bounds[i]:bounds[i + 1]] for i in range(n)]
+
+
+def _texts(raw, oo, n):
+    """Decoded bytes (a numpy array) and the n + 1 offsets into them -> the n str."""
+    raw = raw.tobytes()
+    bounds = oo.tolist()
+    return [_ids_to_text(raw[bounds[i]:bounds[i + 1]]) for i in range(n)]
+
+
 def _native_encode(text):
     sh = _capi.shim()
     if sh is not None:
@@ -208,9 +222,7 @@ def _native_batch_encode(texts, num_threads=1):
         return [[] for _ in texts]  # no worker starts (lib.c:784-791)
     # an over-long word ends its document silently, as in the reference (core.c:503)
     ids, oo, _st, _rc = _ctx.encode_packed(data, offs)
-    flat = ids.tolist()
-    bounds = oo.tolist()
-    return [flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))]
+    return _rows(ids, oo, len(texts))
 
 
 def encode(text):
@@ -245,21 +257,33 @@ def encode_packed_device(d_bytes, d_offsets, check=True):
     document i are ids[out_offsets[i]:out_offsets[i+1]].  Asynchronous on the
     current torch stream unless check=True, which synchronises and raises on a
     device-side error."""
+    return _encode_device("plain", d_bytes, d_offsets, 0, check)
+
+
+def _encode_device(kind, d_bytes, d_offsets, flags, check):
+    """What encode_packed_device ("plain"), encode_special_packed_device ("special") and encode_fallback_packed_device
+    ("fallback", with its flags) share: the output tensors, the call on the current torch stream, the check."""
     import torch
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
     n_docs = d_offsets.numel() - 1
     n_bytes = d_bytes.numel()
-    cap = _ctx.ids_capacity(n_bytes, n_docs)
+    cap = (_ctx.special_ids_capacity if kind == "special" or flags else _ctx.ids_capacity)(n_bytes, n_docs)
     dev = d_bytes.device
     ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
     oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _ctx.encode_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap,
-                       oo.data_ptr(), 0, err.data_ptr(), stream)
+    text = (d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes)
+    out = (ids.data_ptr(), cap, oo.data_ptr(), 0, err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if kind == "fallback":
+        _ctx.encode_fallback_device(*text, flags, *out)
+    else:
+        (_ctx.encode_special_device if kind == "special" else _ctx.encode_device)(*text, *out)
     if check:
         code = int(err.item())
+        if kind == "fallback" and code == _capi.E_UNSUPPORTED:
+            raise ValueError("hutoken_amd: encode_fallback_packed_device: a document's text does not hold the decoded bytes "
+                             "of its tokens where their spans lie; it keeps its plain ids (device-side error %d)" % code)
         if code not in (0, _capi.E_WORD_TOO_LARGE):
             raise RuntimeError(f"hutoken_amd: device-side error {code}")
     return ids, oo
@@ -275,31 +299,17 @@ def _ids_to_text(raw):
     return (raw if z < 0 else raw[:z]).decode("utf-8")
 
 
-def _native_decode(tokens):
-    """_hutoken.decode (lib.c:876-951): list[int] -> str."""
-    sh = _capi.shim()
-    if sh is not None:
-        return sh.decode(tokens)
+def _flat_ids(tokens, batch):
+    """The argument checks of decode / batch_decode -> (ids int32, id_offsets int64)."""
     import numpy as np
+    if not isinstance(tokens, list):
+        raise TypeError("Failed to parse arguments. Expected a single list of tokens." if batch else
+                        "Argument must be a list of integers")
     if _ctx is None:
         raise RuntimeError(_NOT_INIT_DECODE)
-    if not isinstance(tokens, list):
-        raise TypeError("Argument must be a list of integers")
-    ids = np.asarray([int(t) for t in tokens], dtype=np.int64).astype(np.int32)  # (int)PyLong_AsLong
-    out, oo, _st = _ctx.decode_packed(ids, np.array([0, len(ids)], dtype=np.int64))
-    return _ids_to_text(out.tobytes())
-
-
-def _native_batch_decode(tokens, num_threads=1):
-    """_hutoken.batch_decode (lib.c:954-1126): list[list[int]] -> list[str]."""
-    sh = _capi.shim()
-    if sh is not None:
-        return sh.batch_decode(tokens, num_threads)
-    import numpy as np
-    if _ctx is None:
-        raise RuntimeError(_NOT_INIT_DECODE)
-    if not isinstance(tokens, list):
-        raise TypeError("Failed to parse arguments. Expected a single list of tokens.")
+    if not batch:
+        ids = np.asarray([int(t) for t in tokens], dtype=np.int64).astype(np.int32)  # (int)PyLong_AsLong
+        return ids, np.array([0, len(ids)], dtype=np.int64)
     if len(tokens) <= 0:
         raise ValueError("No tokens provided.")
     for item in tokens:
@@ -308,32 +318,57 @@ def _native_batch_decode(tokens, num_threads=1):
     offs = np.zeros(len(tokens) + 1, dtype=np.int64)
     np.cumsum(np.fromiter(map(len, tokens), dtype=np.int64, count=len(tokens)), out=offs[1:])
     flat = np.fromiter((int(t) for item in tokens for t in item), dtype=np.int64, count=int(offs[-1])).astype(np.int32)
-    out, oo, _st = _ctx.decode_packed(flat, offs)
-    raw = out.tobytes()
-    bounds = oo.tolist()
-    return [_ids_to_text(raw[bounds[i]:bounds[i + 1]]) for i in range(len(tokens))]
+    return flat, offs
+
+
+def _decode_lists(packed, tokens, batch, *flags):
+    """tokens (a list of ints; batch: a list of such lists) through the context's host decode named `packed`
+    -> str (batch: list of str)."""
+    ids, offs = _flat_ids(tokens, batch)
+    out, oo, _st = getattr(_ctx, packed)(ids, offs, *flags)
+    return _texts(out, oo, len(tokens)) if batch else _ids_to_text(out.tobytes())
+
+
+def _rewrapped(tokens, batch, fn, *args):
+    """fn(*args) with the exceptions of hutoken.decode (reference hutoken.py:140-151: a ValueError stays one and names
+    the tokens) or, batch, of hutoken.batch_decode (hutoken.py:153-160)."""
+    try:
+        return fn(*args)
+    except Exception as e:
+        traceback.print_exc(file=sys.stderr)
+        if isinstance(e, ValueError) and not batch:
+            raise ValueError(f"hutoken: Error decoding tokens {tokens}: {e}")
+        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+
+
+def _native_decode(tokens):
+    """_hutoken.decode (lib.c:876-951): list[int] -> str."""
+    sh = _capi.shim()
+    if sh is not None:
+        return sh.decode(tokens)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT_DECODE)
+    return _decode_lists("decode_packed", tokens, False)
+
+
+def _native_batch_decode(tokens, num_threads=1):
+    """_hutoken.batch_decode (lib.c:954-1126): list[list[int]] -> list[str]."""
+    sh = _capi.shim()
+    if sh is not None:
+        return sh.batch_decode(tokens, num_threads)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT_DECODE)
+    return _decode_lists("decode_packed", tokens, True)
 
 
 def decode(tokens):
     """hutoken.decode (reference hutoken.py:140-151)."""
-    try:
-        return _native_decode(tokens)
-    except ValueError as e:
-        traceback.print_exc(file=sys.stderr)
-        raise ValueError(f"hutoken: Error decoding tokens {tokens}: {e}")
-    except Exception as e:
-        traceback.print_exc(file=sys.stderr)
-        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+    return _rewrapped(tokens, False, _native_decode, tokens)
 
 
 def batch_decode(tokens, num_threads=1):
     """hutoken.batch_decode (reference hutoken.py:153-160)."""
-    try:
-        return _native_batch_decode(tokens, num_threads)
-    except Exception as e:
-        traceback.print_exc(file=sys.stderr)
-        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
-
+    return _rewrapped(tokens, True, _native_batch_decode, tokens, num_threads)
 
 
 # ---- training -------------------------------------------------------------------------------------------------
@@ -708,6 +743,42 @@ def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=N
 _side_streams = {}
 
 
+def _on_torch_stream(dev, fn, used=()):
+    """fn() -- calls of the C ABI on torch's current stream of `dev` -> what fn returns (a tensor, a tuple of them, None).
+    The C ABI reads a NULL stream -- torch's default one -- as "the context's own stream", which no torch stream waits
+    for.  So with that one current, fn runs on a stream of its own which waits for the current one and which the current
+    one then waits for; the tensors in `used` are recorded on that stream, those fn returns on the current one."""
+    import torch
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            return fn()
+        side = _side_streams.get(dev.index)
+        if side is None:
+            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            res = fn()
+        cur.wait_stream(side)
+        for t in used:
+            t.record_stream(side)
+        for t in () if res is None else res if isinstance(res, tuple) else (res,):
+            t.record_stream(cur)
+        return res
+
+
+def _encode_texts(kind, texts, flags=0, with_text=False):
+    """list of str -> (ids, out_offsets) of _encode_device(kind, ..., flags) on the context's device; with_text: and the
+    packed text they were made from, (ids, out_offsets, d_bytes, d_offs).  The caller has checked texts and the context."""
+    import torch
+    data, offs = _pack(texts)
+    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
+    d_bytes = torch.from_numpy(data.copy()).to(dev)  # (a copy: _pack's array is a read-only view of a bytes object)
+    d_offs = torch.from_numpy(offs).to(dev)
+    ids, oo = _on_torch_stream(dev, lambda: _encode_device(kind, d_bytes, d_offs, flags, True))
+    return (ids, oo, d_bytes, d_offs) if with_text else (ids, oo)
+
+
 def _texts_to_device(texts, with_text=False):
     """list of str -> (ids, out_offsets) of encode_packed_device on the context's device; with_text: and the packed
     text they were made from, (ids, out_offsets, d_bytes, d_offs)."""
@@ -715,28 +786,7 @@ def _texts_to_device(texts, with_text=False):
         raise RuntimeError(_NOT_INIT)
     if not isinstance(texts, list):
         raise TypeError("Invalid arguments. Expected a list of strings.")
-    import torch
-    data, offs = _pack(texts)
-    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
-    d_bytes = torch.from_numpy(data.copy()).to(dev)  # (a copy: _pack's array is a read-only view of a bytes object)
-    d_offs = torch.from_numpy(offs).to(dev)
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            ids, oo = encode_packed_device(d_bytes, d_offs)
-            return (ids, oo, d_bytes, d_offs) if with_text else (ids, oo)
-        # The C ABI reads a NULL stream -- torch's default one -- as "the context's own stream", which no torch stream
-        # waits for.  So the encode goes to a stream of its own and the current stream waits for that.
-        side = _side_streams.get(dev.index)
-        if side is None:
-            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            ids, oo = encode_packed_device(d_bytes, d_offs)
-        cur.wait_stream(side)
-        ids.record_stream(cur)
-        oo.record_stream(cur)
-        return (ids, oo, d_bytes, d_offs) if with_text else (ids, oo)
+    return _encode_texts("plain", texts, 0, with_text)
 
 
 def batch_encode_padded(texts, max_length=None, **collate_kwargs):
@@ -880,20 +930,7 @@ def token_spans_device(d_bytes, d_offsets, ids, out_offsets, unit="char", dtype=
         _ctx.token_spans_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, d_bytes.numel(), ids.data_ptr(),
                                 out_offsets.data_ptr(), n_ids, code, width, spans.data_ptr(), status.data_ptr(),
                                 err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            call()
-        else:  # (a NULL stream would mean the context's own stream to the C ABI: see _texts_to_device)
-            side = _side_streams.get(dev.index)
-            if side is None:
-                side = _side_streams[dev.index] = torch.cuda.Stream(dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                call()
-            cur.wait_stream(side)
-            for t in (d_bytes, d_offsets, ids, out_offsets, spans, status, err):
-                t.record_stream(side)
+    _on_torch_stream(dev, call, used=(d_bytes, d_offsets, ids, out_offsets, spans, status, err))
     if check:
         rc = int(err.item())
         if rc == _capi.E_ARG:
@@ -913,12 +950,10 @@ def batch_encode_with_offsets(texts, unit="char"):
     texts[i], so that texts[i][start:end] is the text the token covers (unit="char"; "byte": in the UTF-8 bytes)."""
     _span_unit(unit)
     ids, oo, d_bytes, d_offs = _texts_to_device(texts, with_text=True)
-    bounds = oo.cpu().tolist()
-    spans = token_spans_device(d_bytes, d_offs, ids, oo, unit=unit, n_ids=bounds[-1])
-    flat = ids[:bounds[-1]].cpu().tolist()
-    sp = spans.cpu().tolist()
-    return ([flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))],
-            [[(a, b) for a, b in sp[bounds[i]:bounds[i + 1]]] for i in range(len(texts))])
+    bounds = oo.cpu()  # (one copy down serves the spans' n_ids and both lists)
+    spans = token_spans_device(d_bytes, d_offs, ids, oo, unit=unit, n_ids=int(bounds[-1]))
+    return (_rows(ids, bounds, len(texts)),
+            [[(a, b) for a, b in row] for row in _rows(spans, bounds, len(texts))])
 
 
 def encode_with_offsets(text, unit="char"):
@@ -974,59 +1009,22 @@ def encode_special_packed_device(d_bytes, d_offsets, check=True):
     SequencePacker.add and the spans' callers take it unchanged (spans over special ids are not defined), and
     decode_packed_device(ids, out_offsets, special=True) gives the text back.  Synchronises the current torch stream once,
     after the scan for matches."""
-    import torch
-    if _ctx is None:
-        raise RuntimeError(_NOT_INIT)
-    n_docs = d_offsets.numel() - 1
-    n_bytes = d_bytes.numel()
-    cap = _ctx.special_ids_capacity(n_bytes, n_docs)
-    dev = d_bytes.device
-    ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _ctx.encode_special_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap,
-                               oo.data_ptr(), 0, err.data_ptr(), stream)
-    if check:
-        code = int(err.item())
-        if code not in (0, _capi.E_WORD_TOO_LARGE):
-            raise RuntimeError(f"hutoken_amd: device-side error {code}")
-    return ids, oo
+    return _encode_device("special", d_bytes, d_offsets, 0, check)
 
 
 def _special_texts_to_device(texts):
-    """_texts_to_device for the special-token encode (the same handling of torch's NULL stream)."""
+    """_texts_to_device for the special-token encode."""
     if not isinstance(texts, list):
         raise TypeError("Invalid arguments. Expected a list of strings.")
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
-    import torch
-    data, offs = _pack(texts)
-    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
-    d_bytes = torch.from_numpy(data.copy()).to(dev)
-    d_offs = torch.from_numpy(offs).to(dev)
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            return encode_special_packed_device(d_bytes, d_offs)
-        side = _side_streams.get(dev.index)
-        if side is None:
-            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            ids, oo = encode_special_packed_device(d_bytes, d_offs)
-        cur.wait_stream(side)
-        ids.record_stream(cur)
-        oo.record_stream(cur)
-        return ids, oo
+    return _encode_texts("special", texts)
 
 
 def batch_encode_special(texts):
     """batch_encode with the special tokens of set_special_tokens -> list[list[int]]."""
     ids, oo = _special_texts_to_device(texts)
-    bounds = oo.tolist()
-    flat = ids[:bounds[-1]].tolist()
-    return [flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))]
+    return _rows(ids, oo, len(texts))
 
 
 def encode_special(text):
@@ -1036,28 +1034,6 @@ def encode_special(text):
     if "\0" in text:
         raise ValueError("embedded null character")
     return batch_encode_special([text])[0]
-
-
-def _flat_ids(tokens, batch):
-    """The argument checks of decode / batch_decode -> (ids int32, id_offsets int64)."""
-    import numpy as np
-    if not isinstance(tokens, list):
-        raise TypeError("Failed to parse arguments. Expected a single list of tokens." if batch else
-                        "Argument must be a list of integers")
-    if _ctx is None:
-        raise RuntimeError(_NOT_INIT_DECODE)
-    if not batch:
-        ids = np.asarray([int(t) for t in tokens], dtype=np.int64).astype(np.int32)
-        return ids, np.array([0, len(ids)], dtype=np.int64)
-    if len(tokens) <= 0:
-        raise ValueError("No tokens provided.")
-    for item in tokens:
-        if not isinstance(item, list):
-            raise TypeError("Each item must be a list of integers.")
-    offs = np.zeros(len(tokens) + 1, dtype=np.int64)
-    np.cumsum(np.fromiter(map(len, tokens), dtype=np.int64, count=len(tokens)), out=offs[1:])
-    flat = np.fromiter((int(t) for item in tokens for t in item), dtype=np.int64, count=int(offs[-1])).astype(np.int32)
-    return flat, offs
 
 
 def _skip_flag(skip_special_tokens):
@@ -1071,30 +1047,13 @@ def decode_special(tokens, skip_special_tokens=False):
     skip_special_tokens=True), and a context with a prefix strips it behind every marker, so that
     decode_special(encode_special(text)) == text.  Argument checks and exceptions are those of decode."""
     flags = _skip_flag(skip_special_tokens)
-    try:
-        ids, offs = _flat_ids(tokens, False)
-        out, _oo, _st = _ctx.decode_special_packed(ids, offs, flags)
-        return _ids_to_text(out.tobytes())
-    except ValueError as e:
-        traceback.print_exc(file=sys.stderr)
-        raise ValueError(f"hutoken: Error decoding tokens {tokens}: {e}")
-    except Exception as e:
-        traceback.print_exc(file=sys.stderr)
-        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+    return _rewrapped(tokens, False, _decode_lists, "decode_special_packed", tokens, False, flags)
 
 
 def batch_decode_special(tokens, skip_special_tokens=False):
     """batch_decode with the special tokens of set_special_tokens -> list[str]; see decode_special."""
     flags = _skip_flag(skip_special_tokens)
-    try:
-        flat, offs = _flat_ids(tokens, True)
-        out, oo, _st = _ctx.decode_special_packed(flat, offs, flags)
-        raw = out.tobytes()
-        bounds = oo.tolist()
-        return [_ids_to_text(raw[bounds[i]:bounds[i + 1]]) for i in range(len(tokens))]
-    except Exception as e:
-        traceback.print_exc(file=sys.stderr)
-        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+    return _rewrapped(tokens, True, _decode_lists, "decode_special_packed", tokens, True, flags)
 
 
 def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens=False, n_ids=None, check=True,
@@ -1147,21 +1106,7 @@ def decode_packed_device(d_ids, d_id_offsets, special=False, skip_special_tokens
         if total:
             call(out.data_ptr(), total)
         return out[:total]
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            out = both()
-        else:  # (a NULL stream would mean the context's own stream to the C ABI: see _texts_to_device)
-            side = _side_streams.get(dev.index)
-            if side is None:
-                side = _side_streams[dev.index] = torch.cuda.Stream(dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                out = both()
-            cur.wait_stream(side)
-            for t in (d_ids, d_id_offsets, oo, err):
-                t.record_stream(side)
-            out.record_stream(cur)
+    out = _on_torch_stream(dev, both, used=(d_ids, d_id_offsets, oo, err))
     if check:
         code = int(err.item())
         if code == _capi.E_VALUE:
@@ -1232,64 +1177,23 @@ def encode_fallback_packed_device(d_bytes, d_offsets, special=False, check=True)
     int64[n+1]).  special=True also cuts at the special tokens of set_special_tokens, as encode_special_packed_device does
     (and then synchronises the current torch stream once); without it the call is asynchronous unless check=True, which
     synchronises and raises on a device-side error."""
-    import torch
-    flags = _special_arg(special)
-    if _ctx is None:
-        raise RuntimeError(_NOT_INIT)
-    n_docs = d_offsets.numel() - 1
-    n_bytes = d_bytes.numel()
-    cap = _ctx.special_ids_capacity(n_bytes, n_docs) if flags else _ctx.ids_capacity(n_bytes, n_docs)
-    dev = d_bytes.device
-    ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _ctx.encode_fallback_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, flags, ids.data_ptr(), cap,
-                                oo.data_ptr(), 0, err.data_ptr(), stream)
-    if check:
-        code = int(err.item())
-        if code == _capi.E_UNSUPPORTED:
-            raise ValueError("hutoken_amd: encode_fallback_packed_device: a document's text does not hold the decoded bytes "
-                             "of its tokens where their spans lie; it keeps its plain ids (device-side error %d)" % code)
-        if code not in (0, _capi.E_WORD_TOO_LARGE):
-            raise RuntimeError(f"hutoken_amd: device-side error {code}")
-    return ids, oo
+    return _encode_device("fallback", d_bytes, d_offsets, _special_arg(special), check)
 
 
 def _fallback_texts_to_device(texts, special):
-    """_texts_to_device for the fallback encode (the same handling of torch's NULL stream)."""
+    """_texts_to_device for the fallback encode."""
     if not isinstance(texts, list):
         raise TypeError("Invalid arguments. Expected a list of strings.")
-    _special_arg(special)
+    flags = _special_arg(special)
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
-    import torch
-    data, offs = _pack(texts)
-    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
-    d_bytes = torch.from_numpy(data.copy()).to(dev)
-    d_offs = torch.from_numpy(offs).to(dev)
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        if cur.cuda_stream:
-            return encode_fallback_packed_device(d_bytes, d_offs, special)
-        side = _side_streams.get(dev.index)
-        if side is None:
-            side = _side_streams[dev.index] = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            ids, oo = encode_fallback_packed_device(d_bytes, d_offs, special)
-        cur.wait_stream(side)
-        ids.record_stream(cur)
-        oo.record_stream(cur)
-        return ids, oo
+    return _encode_texts("fallback", texts, flags)
 
 
 def batch_encode_fallback(texts, special=False):
     """batch_encode with the table of set_byte_fallback -> list[list[int]]; special=True: and the special tokens."""
     ids, oo = _fallback_texts_to_device(texts, special)
-    bounds = oo.tolist()
-    flat = ids[:bounds[-1]].tolist()
-    return [flat[bounds[i]:bounds[i + 1]] for i in range(len(texts))]
+    return _rows(ids, oo, len(texts))
 
 
 def encode_fallback(text, special=False):
@@ -1312,27 +1216,10 @@ def decode_fallback(tokens, special=False, skip_special_tokens=False):
     """decode (special=True: decode_special) with the table of set_byte_fallback: an id of the table becomes its one raw
     byte, so that decode_fallback(encode_fallback(text)) == text.  Argument checks and exceptions are those of decode."""
     flags = _fallback_decode_flags(special, skip_special_tokens)
-    try:
-        ids, offs = _flat_ids(tokens, False)
-        out, _oo, _st = _ctx.decode_fallback_packed(ids, offs, flags)
-        return _ids_to_text(out.tobytes())
-    except ValueError as e:
-        traceback.print_exc(file=sys.stderr)
-        raise ValueError(f"hutoken: Error decoding tokens {tokens}: {e}")
-    except Exception as e:
-        traceback.print_exc(file=sys.stderr)
-        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+    return _rewrapped(tokens, False, _decode_lists, "decode_fallback_packed", tokens, False, flags)
 
 
 def batch_decode_fallback(tokens, special=False, skip_special_tokens=False):
     """batch_decode with the table of set_byte_fallback -> list[str]; see decode_fallback."""
     flags = _fallback_decode_flags(special, skip_special_tokens)
-    try:
-        flat, offs = _flat_ids(tokens, True)
-        out, oo, _st = _ctx.decode_fallback_packed(flat, offs, flags)
-        raw = out.tobytes()
-        bounds = oo.tolist()
-        return [_ids_to_text(raw[bounds[i]:bounds[i + 1]]) for i in range(len(tokens))]
-    except Exception as e:
-        traceback.print_exc(file=sys.stderr)
-        raise RuntimeError(f"hutoken: Error decoding tokens: {e}")
+    return _rewrapped(tokens, True, _decode_lists, "decode_fallback_packed", tokens, True, flags)

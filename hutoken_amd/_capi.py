@@ -16,27 +16,85 @@ E_CAPACITY, E_NUL_BYTE, E_WORD_TOO_LARGE, E_INVALID_UTF8 = 7, 8, 9, 10
 DOC_OK, DOC_WORD_TOO_LARGE, DOC_INVALID_UTF8 = 0, 1, 2
 DOC_ID_OUT_OF_RANGE, DOC_ID_UNDECODABLE, DOC_SPAN_MISMATCH = 3, 4, 5
 
-# every symbol include/hutoken_amd.h declares
-EXPORTS = [
-    "hutk_ctx_create", "hutk_ctx_create_merges", "hutk_ctx_set_pattern", "hutk_ctx_add_device", "hutk_ctx_device_count", "hutk_uses_merges", "hutk_ctx_destroy", "hutk_last_error", "hutk_ids_capacity",
-    "hutk_encode_batch", "hutk_encode_batch_device", "hutk_encode", "hutk_vocab_size", "hutk_host_alloc",
-    "hutk_host_free", "hutk_decode_batch", "hutk_decode_batch_device",
-    "hutk_pair_table_entries", "hutk_device_ordinal", "hutk_table_stats", "hutk_last_timing",
-    "hutk_set_timing", "hutk_debug_pairs_second", "hutk_debug_long_words", "hutk_debug_profile", "hutk_debug_profile_read", "hutk_debug_profile_raw", "hutk_debug_tile_bytes",
-    "hutk_debug_seam", "hutk_debug_seam2_cut", "hutk_debug_tile_kernel",
-    "hutk_trainer_create", "hutk_trainer_add", "hutk_trainer_run", "hutk_trainer_stats", "hutk_trainer_destroy",
-    "hutk_trainer_debug_counters", "hutk_trainer_create_mode", "hutk_trainer_alphabet",
-    "hutk_collate_padded_device", "hutk_packer_create", "hutk_packer_rows", "hutk_packer_add_device",
-    "hutk_packer_flush_device", "hutk_packer_pending", "hutk_packer_destroy",
-    "hutk_token_spans_device", "hutk_token_spans",
-    "hutk_ctx_set_special_tokens", "hutk_ctx_special_token_count", "hutk_special_ids_capacity",
-    "hutk_encode_special_batch_device", "hutk_encode_special_batch", "hutk_special_last_matches",
-    "hutk_debug_special_tile_bytes", "hutk_decode_special_batch_device", "hutk_decode_special_batch",
-    "hutk_ctx_find_byte_tokens", "hutk_ctx_set_byte_fallback", "hutk_ctx_byte_fallback",
-    "hutk_encode_fallback_batch_device", "hutk_encode_fallback_batch", "hutk_decode_fallback_batch_device",
-    "hutk_decode_fallback_batch",
-    "hutk_windows_rows_bound", "hutk_windows_rows_device", "hutk_collate_windows_device",
-]
+_vp, _i64, _i32, _s32, _u32, _str = C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_uint32, C.c_char_p
+_pvp, _pi64, _ps32, _pf = C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_s32), C.POINTER(C.c_float)
+_DEV = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]  # the *_batch_device forms of both directions; with flags below
+_DEV_F = [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp]
+_HOST = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]  # the host-buffer forms of both directions; with flags below
+_HOST_F = [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]
+# every symbol include/hutoken_amd.h declares: name -> (restype, argtypes).  load() applies it, so a declared symbol
+# cannot go without a signature (without argtypes ctypes truncates 64-bit arguments silently).
+SIGNATURES = {
+    "hutk_ctx_create": (_i32, [_pvp, _str, _str, _str, _i32, _i32]),
+    "hutk_ctx_create_merges": (_i32, [_pvp, _str, _str, _str, _i32, _str, _i32]),
+    "hutk_ctx_set_pattern": (_i32, [_vp, _str]),
+    "hutk_ctx_add_device": (_i32, [_vp, _i32]),
+    "hutk_ctx_device_count": (_i32, [_vp]),
+    "hutk_uses_merges": (_i32, [_vp]),
+    "hutk_ctx_destroy": (None, [_vp]),
+    "hutk_last_error": (_str, []),
+    "hutk_ids_capacity": (_i64, [_vp, _i64, _i64]),
+    "hutk_encode_batch": (_i32, _HOST),
+    "hutk_encode_batch_device": (_i32, _DEV),
+    "hutk_encode": (_i32, [_vp, _vp, _i64, _vp, _i64, _pi64, _ps32]),
+    "hutk_vocab_size": (_i64, [_vp]),
+    "hutk_host_alloc": (_vp, [C.c_size_t]),
+    "hutk_host_free": (None, [_vp]),
+    "hutk_decode_batch": (_i32, _HOST),
+    "hutk_decode_batch_device": (_i32, _DEV),
+    "hutk_pair_table_entries": (_i64, [_vp]),
+    "hutk_device_ordinal": (_i32, [_vp]),
+    "hutk_table_stats": (_i32, [_vp, _vp]),
+    "hutk_last_timing": (_i32, [_vp, _pf, _pf]),
+    "hutk_set_timing": (None, [_vp, _i32]),
+    "hutk_debug_pairs_second": (_i64, [_vp]),
+    "hutk_debug_long_words": (_i64, [_vp]),
+    "hutk_debug_profile": (_i32, [_vp, _i32]),
+    "hutk_debug_profile_read": (_i32, [_vp, _i64, _vp]),
+    "hutk_debug_profile_raw": (_i32, [_vp, _i64, _vp]),
+    "hutk_debug_tile_bytes": (_i32, []),
+    "hutk_debug_seam": (_i32, [_vp, _vp]),
+    "hutk_debug_seam2_cut": (_i32, [_vp, _u32, _u32]),
+    "hutk_debug_tile_kernel": (_i32, [_vp, _i64]),
+    "hutk_trainer_create": (_i32, [_pvp, _i32]),
+    "hutk_trainer_add": (_i32, [_vp, _vp, _vp, _i64]),
+    "hutk_trainer_run": (_i32, [_vp, _s32, _vp, _vp, _ps32]),
+    "hutk_trainer_stats": (_i32, [_vp, _vp]),
+    "hutk_trainer_destroy": (None, [_vp]),
+    "hutk_trainer_debug_counters": (_i32, [_vp, _vp, _i32]),
+    "hutk_trainer_create_mode": (_i32, [_pvp, _i32, _i32]),
+    "hutk_trainer_alphabet": (_i32, [_vp, _vp, _i64, _vp, _i64, _pi64, _pi64]),
+    "hutk_collate_padded_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _s32, _s32, _s32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_packer_create": (_i32, [_pvp, _i64, _s32, _s32, _s32, _i32, _i32]),
+    "hutk_packer_rows": (_i64, [_vp, _i64, _i64]),
+    "hutk_packer_add_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _pi64, _vp, _vp]),
+    "hutk_packer_flush_device": (_i32, [_vp, _vp, _vp, _vp, _pi64, _vp]),
+    "hutk_packer_pending": (_i64, [_vp]),
+    "hutk_packer_destroy": (None, [_vp]),
+    "hutk_token_spans_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "hutk_token_spans": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "hutk_ctx_set_special_tokens": (_i32, [_vp, _vp, _vp, _vp, _i64]),
+    "hutk_ctx_special_token_count": (_i64, [_vp]),
+    "hutk_special_ids_capacity": (_i64, [_vp, _i64, _i64]),
+    "hutk_encode_special_batch_device": (_i32, _DEV),
+    "hutk_encode_special_batch": (_i32, _HOST),
+    "hutk_special_last_matches": (_i64, [_vp]),
+    "hutk_debug_special_tile_bytes": (_i32, []),
+    "hutk_decode_special_batch_device": (_i32, _DEV_F),
+    "hutk_decode_special_batch": (_i32, _HOST_F),
+    "hutk_ctx_find_byte_tokens": (_i32, [_vp, _vp]),
+    "hutk_ctx_set_byte_fallback": (_i32, [_vp, _vp]),
+    "hutk_ctx_byte_fallback": (_i32, [_vp, _vp]),
+    "hutk_encode_fallback_batch_device": (_i32, _DEV_F),
+    "hutk_encode_fallback_batch": (_i32, _HOST_F),
+    "hutk_decode_fallback_batch_device": (_i32, _DEV_F),
+    "hutk_decode_fallback_batch": (_i32, _HOST_F),
+    "hutk_windows_rows_bound": (_i64, [_i64, _i64, _i64, _i64, _i32]),
+    "hutk_windows_rows_device": (_i32, [_vp, _i64, _i64, _i64, _i64, _s32, _s32, _vp, _vp, _vp]),
+    "hutk_collate_windows_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _s32, _s32, _s32, _i32, _i32,
+                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
 NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
@@ -86,160 +144,10 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError("hutoken_amd: native library %s is missing (run `python -m hutoken_amd.build`)" % path)
     L = C.CDLL(path)
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    L.hutk_ctx_create.restype = i32
-    L.hutk_ctx_create.argtypes = [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p, i32, i32]
-    L.hutk_ctx_create_merges.restype = i32
-    L.hutk_ctx_create_merges.argtypes = [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p, i32, C.c_char_p, i32]
-    if hasattr(L, "hutk_ctx_set_pattern"):  # (older builds under tools/ab.py lack it)
-        L.hutk_ctx_set_pattern.restype = i32
-        L.hutk_ctx_set_pattern.argtypes = [vp, C.c_char_p]
-    L.hutk_uses_merges.restype = i32
-    L.hutk_uses_merges.argtypes = [vp]
-    L.hutk_decode_batch.restype = i32
-    L.hutk_decode_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
-    L.hutk_decode_batch_device.restype = i32
-    L.hutk_decode_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]
-    L.hutk_host_alloc.restype = vp
-    L.hutk_host_alloc.argtypes = [C.c_size_t]
-    L.hutk_host_free.restype = None
-    L.hutk_host_free.argtypes = [vp]
-    L.hutk_ctx_destroy.restype = None
-    L.hutk_ctx_destroy.argtypes = [vp]
-    L.hutk_last_error.restype = C.c_char_p
-    L.hutk_last_error.argtypes = []
-    L.hutk_ids_capacity.restype = i64
-    L.hutk_ids_capacity.argtypes = [vp, i64, i64]
-    L.hutk_encode_batch.restype = i32
-    L.hutk_encode_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
-    L.hutk_encode_batch_device.restype = i32
-    L.hutk_encode_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]
-    L.hutk_encode.restype = i32
-    L.hutk_encode.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(C.c_int32)]
-    L.hutk_vocab_size.restype = i64
-    L.hutk_vocab_size.argtypes = [vp]
-    L.hutk_pair_table_entries.restype = i64
-    L.hutk_pair_table_entries.argtypes = [vp]
-    L.hutk_device_ordinal.restype = i32
-    L.hutk_device_ordinal.argtypes = [vp]
-    L.hutk_last_timing.restype = i32
-    L.hutk_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.hutk_set_timing.restype = None
-    L.hutk_set_timing.argtypes = [vp, i32]
-    L.hutk_table_stats.restype = i32
-    L.hutk_table_stats.argtypes = [vp, vp]
-    if hasattr(L, "hutk_debug_pairs_second"):  # (older builds under tools/ab.py lack it)
-        L.hutk_debug_pairs_second.restype = i64
-        L.hutk_debug_pairs_second.argtypes = [vp]
-    if hasattr(L, "hutk_debug_long_words"):
-        L.hutk_debug_long_words.restype = i64
-        L.hutk_debug_long_words.argtypes = [vp]
-    if hasattr(L, "hutk_ctx_add_device"):
-        L.hutk_ctx_add_device.restype = i32
-        L.hutk_ctx_add_device.argtypes = [vp, i32]
-        L.hutk_ctx_device_count.restype = i32
-        L.hutk_ctx_device_count.argtypes = [vp]
-    if hasattr(L, "hutk_debug_seam"):
-        L.hutk_debug_seam.restype = i32
-        L.hutk_debug_seam.argtypes = [vp, vp]
-    if hasattr(L, "hutk_debug_seam2_cut"):
-        L.hutk_debug_seam2_cut.restype = i32
-        L.hutk_debug_seam2_cut.argtypes = [vp, C.c_uint32, C.c_uint32]
-    if hasattr(L, "hutk_debug_tile_kernel"):
-        L.hutk_debug_tile_kernel.restype = i32
-        L.hutk_debug_tile_kernel.argtypes = [vp, i64]
-    L.hutk_debug_profile.restype = i32
-    L.hutk_debug_profile.argtypes = [vp, i32]
-    L.hutk_debug_tile_bytes.restype = i32
-    L.hutk_debug_tile_bytes.argtypes = []
-    L.hutk_debug_profile_read.restype = i32
-    L.hutk_debug_profile_read.argtypes = [vp, i64, vp]
-    if hasattr(L, "hutk_debug_profile_raw"):
-        L.hutk_debug_profile_raw.restype = i32
-        L.hutk_debug_profile_raw.argtypes = [vp, i64, vp]
-    if hasattr(L, "hutk_trainer_create"):
-        L.hutk_trainer_create.restype = i32
-        L.hutk_trainer_create.argtypes = [C.POINTER(vp), i32]
-        L.hutk_trainer_add.restype = i32
-        L.hutk_trainer_add.argtypes = [vp, vp, vp, i64]
-        L.hutk_trainer_run.restype = i32
-        L.hutk_trainer_run.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
-        L.hutk_trainer_stats.restype = i32
-        L.hutk_trainer_stats.argtypes = [vp, vp]
-        L.hutk_trainer_destroy.restype = None
-        L.hutk_trainer_destroy.argtypes = [vp]
-    if hasattr(L, "hutk_trainer_debug_counters"):
-        L.hutk_trainer_debug_counters.restype = i32
-        L.hutk_trainer_debug_counters.argtypes = [vp, vp, i32]
-    if hasattr(L, "hutk_trainer_create_mode"):
-        L.hutk_trainer_create_mode.restype = i32
-        L.hutk_trainer_create_mode.argtypes = [C.POINTER(vp), i32, i32]
-        L.hutk_trainer_alphabet.restype = i32
-        L.hutk_trainer_alphabet.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    if hasattr(L, "hutk_collate_padded_device"):
-        L.hutk_collate_padded_device.restype = i32
-        L.hutk_collate_padded_device.argtypes = [vp, vp, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, i32, i32,
-                                                 vp, vp, vp, vp, vp]
-        L.hutk_packer_create.restype = i32
-        L.hutk_packer_create.argtypes = [C.POINTER(vp), i64, C.c_int32, C.c_int32, C.c_int32, i32, i32]
-        L.hutk_packer_rows.restype = i64
-        L.hutk_packer_rows.argtypes = [vp, i64, i64]
-        L.hutk_packer_add_device.restype = i32
-        L.hutk_packer_add_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, i64, C.POINTER(i64), vp, vp]
-        L.hutk_packer_flush_device.restype = i32
-        L.hutk_packer_flush_device.argtypes = [vp, vp, vp, vp, C.POINTER(i64), vp]
-        L.hutk_packer_pending.restype = i64
-        L.hutk_packer_pending.argtypes = [vp]
-        L.hutk_packer_destroy.restype = None
-        L.hutk_packer_destroy.argtypes = [vp]
-    if hasattr(L, "hutk_token_spans_device"):
-        L.hutk_token_spans_device.restype = i32
-        L.hutk_token_spans_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp]
-        L.hutk_token_spans.restype = i32
-        L.hutk_token_spans.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
-    if hasattr(L, "hutk_ctx_set_special_tokens"):
-        L.hutk_ctx_set_special_tokens.restype = i32
-        L.hutk_ctx_set_special_tokens.argtypes = [vp, vp, vp, vp, i64]
-        L.hutk_ctx_special_token_count.restype = i64
-        L.hutk_ctx_special_token_count.argtypes = [vp]
-        L.hutk_special_ids_capacity.restype = i64
-        L.hutk_special_ids_capacity.argtypes = [vp, i64, i64]
-        L.hutk_encode_special_batch_device.restype = i32
-        L.hutk_encode_special_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]
-        L.hutk_encode_special_batch.restype = i32
-        L.hutk_encode_special_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
-        L.hutk_special_last_matches.restype = i64
-        L.hutk_special_last_matches.argtypes = [vp]
-        L.hutk_debug_special_tile_bytes.restype = i32
-        L.hutk_debug_special_tile_bytes.argtypes = []
-    if hasattr(L, "hutk_decode_special_batch_device"):
-        L.hutk_decode_special_batch_device.restype = i32
-        L.hutk_decode_special_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
-        L.hutk_decode_special_batch.restype = i32
-        L.hutk_decode_special_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
-    if hasattr(L, "hutk_ctx_set_byte_fallback"):
-        L.hutk_ctx_find_byte_tokens.restype = i32
-        L.hutk_ctx_find_byte_tokens.argtypes = [vp, vp]
-        L.hutk_ctx_set_byte_fallback.restype = i32
-        L.hutk_ctx_set_byte_fallback.argtypes = [vp, vp]
-        L.hutk_ctx_byte_fallback.restype = i32
-        L.hutk_ctx_byte_fallback.argtypes = [vp, vp]
-        L.hutk_encode_fallback_batch_device.restype = i32
-        L.hutk_encode_fallback_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
-        L.hutk_encode_fallback_batch.restype = i32
-        L.hutk_encode_fallback_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
-        L.hutk_decode_fallback_batch_device.restype = i32
-        L.hutk_decode_fallback_batch_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp]
-        L.hutk_decode_fallback_batch.restype = i32
-        L.hutk_decode_fallback_batch.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp]
-    if hasattr(L, "hutk_collate_windows_device"):
-        L.hutk_windows_rows_bound.restype = i64
-        L.hutk_windows_rows_bound.argtypes = [i64, i64, i64, i64, i32]
-        L.hutk_windows_rows_device.restype = i32
-        L.hutk_windows_rows_device.argtypes = [vp, i64, i64, i64, i64, C.c_int32, C.c_int32, vp, vp, vp]
-        L.hutk_collate_windows_device.restype = i32
-        L.hutk_collate_windows_device.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32,
-                                                  i32, i32, vp, vp, vp, vp, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(L, name):  # (an older build under HUTOKEN_AMD_LIB, tools/ab.py, lacks the newer ones)
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -315,8 +223,27 @@ class PinnedArray:
             pass
 
 
-class Context:
+class _Owner:
+    """Owns one handle of the library (self._h) and gives it back through the function named by _destroy, unless somebody
+    else owns it (_owned is False)."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self, "_owned", True):
+                getattr(load(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Owner):
     """Owns one hutk_ctx."""
+    _destroy = "hutk_ctx_destroy"
 
     def __init__(self, vocab_path, special_path, prefix=None, is_byte_encoder=False, device=-1, merges_path=None,
                  devices=None):
@@ -364,18 +291,6 @@ class Context:
         """True when the id-keyed merge path (merges file) is in force."""
         return bool(load().hutk_uses_merges(self._h))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self, "_owned", True):
-                load().hutk_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     @property
     def handle(self):
         return self._h
@@ -412,42 +327,50 @@ class Context:
             raise_for(E_ARG)
         return k
 
-    def encode_packed(self, data, offsets, want_status=True):
-        """Host numpy buffers in, host numpy buffers out.
-        -> (ids int32, out_offsets int64, status int32, return code)"""
+    def _encode_host(self, fn, capacity, data, offsets, flags=()):
+        """Host numpy buffers through the library's host encode `fn` (its flags, if it takes any, as a 1-tuple) with ids
+        for capacity(n_bytes, n_docs).  -> (ids, out_offsets, status, return code); the caller judges the code."""
         import numpy as np
-        L = load()
         data = np.ascontiguousarray(data, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(offsets) - 1
         nbytes = int(offsets[n]) if n >= 0 else 0
-        cap = self.ids_capacity(nbytes, n)
+        cap = capacity(nbytes, n)
         ids = np.empty(max(cap, 1), dtype=np.int32)
         oo = np.zeros(n + 1, dtype=np.int64)
         st = np.zeros(max(n, 1), dtype=np.int32)
-        rc = L.hutk_encode_batch(self._h, data.ctypes.data if nbytes else None, offsets.ctypes.data, n,
-                                 ids.ctypes.data, cap, oo.ctypes.data, st.ctypes.data)
-        if rc not in (OK, E_WORD_TOO_LARGE):
-            raise_for(rc)
+        rc = fn(self._h, data.ctypes.data if nbytes else None, offsets.ctypes.data, n, *flags, ids.ctypes.data, cap,
+                oo.ctypes.data, st.ctypes.data)
         return ids[: int(oo[n])], oo, st[:n], rc
 
-    def decode_packed(self, ids, id_offsets):
-        """Decode direction, host numpy buffers: ids int32 + id_offsets int64[n+1] ->
-        (bytes uint8, out_offsets int64[n+1], status int32[n]).  Two calls: sizes, then the text."""
+    def _decode_host(self, fn, ids, id_offsets, flags=()):
+        """Host numpy buffers through the library's host decode `fn` (flags as in _encode_host), called twice: sizes,
+        then the text.  -> (bytes, out_offsets, status)"""
         import numpy as np
-        L = load()
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
         n = len(id_offsets) - 1
         oo = np.zeros(n + 1, dtype=np.int64)
         st = np.zeros(max(n, 1), dtype=np.int32)
         pid = ids.ctypes.data if len(ids) else None
-        raise_for(L.hutk_decode_batch(self._h, pid, id_offsets.ctypes.data, n, None, 0, oo.ctypes.data, st.ctypes.data))
+        raise_for(fn(self._h, pid, id_offsets.ctypes.data, n, *flags, None, 0, oo.ctypes.data, st.ctypes.data))
         total = int(oo[n])
         out = np.empty(max(total, 1), dtype=np.uint8)
-        raise_for(L.hutk_decode_batch(self._h, pid, id_offsets.ctypes.data, n, out.ctypes.data, total, oo.ctypes.data,
-                                      st.ctypes.data))
+        raise_for(fn(self._h, pid, id_offsets.ctypes.data, n, *flags, out.ctypes.data, total, oo.ctypes.data, st.ctypes.data))
         return out[:total], oo, st[:n]
+
+    def encode_packed(self, data, offsets, want_status=True):
+        """Host numpy buffers in, host numpy buffers out.
+        -> (ids int32, out_offsets int64, status int32, return code)"""
+        r = self._encode_host(load().hutk_encode_batch, self.ids_capacity, data, offsets)
+        if r[3] not in (OK, E_WORD_TOO_LARGE):
+            raise_for(r[3])
+        return r
+
+    def decode_packed(self, ids, id_offsets):
+        """Decode direction, host numpy buffers: ids int32 + id_offsets int64[n+1] ->
+        (bytes uint8, out_offsets int64[n+1], status int32[n]).  Two calls: sizes, then the text."""
+        return self._decode_host(load().hutk_decode_batch, ids, id_offsets)
 
     def decode_device(self, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets, d_status,
                       d_err, stream):
@@ -542,20 +465,10 @@ class Context:
     def encode_special_packed(self, data, offsets):
         """encode_packed with the context's special tokens (hutk_encode_special_batch): host numpy buffers in and out.
         -> (ids int32, out_offsets int64, status int32, return code)"""
-        import numpy as np
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(offsets) - 1
-        nbytes = int(offsets[n]) if n >= 0 else 0
-        cap = self.special_ids_capacity(nbytes, n)
-        ids = np.empty(max(cap, 1), dtype=np.int32)
-        oo = np.zeros(n + 1, dtype=np.int64)
-        st = np.zeros(max(n, 1), dtype=np.int32)
-        rc = load().hutk_encode_special_batch(self._h, data.ctypes.data if nbytes else None, offsets.ctypes.data, n,
-                                              ids.ctypes.data, cap, oo.ctypes.data, st.ctypes.data)
-        if rc not in (OK, E_WORD_TOO_LARGE):
-            raise_for(rc)
-        return ids[: int(oo[n])], oo, st[:n], rc
+        r = self._encode_host(load().hutk_encode_special_batch, self.special_ids_capacity, data, offsets)
+        if r[3] not in (OK, E_WORD_TOO_LARGE):
+            raise_for(r[3])
+        return r
 
     def encode_special_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets,
                               d_status=0, d_err=0, stream=0):
@@ -567,21 +480,7 @@ class Context:
     def decode_special_packed(self, ids, id_offsets, flags=0):
         """decode_packed with the context's special tokens (hutk_decode_special_batch; flags: 0 or DECODE_SKIP_SPECIAL):
         -> (bytes uint8, out_offsets int64[n+1], status int32[n]).  Two calls: sizes, then the text."""
-        import numpy as np
-        L = load()
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
-        n = len(id_offsets) - 1
-        oo = np.zeros(n + 1, dtype=np.int64)
-        st = np.zeros(max(n, 1), dtype=np.int32)
-        pid = ids.ctypes.data if len(ids) else None
-        raise_for(L.hutk_decode_special_batch(self._h, pid, id_offsets.ctypes.data, n, flags, None, 0, oo.ctypes.data,
-                                              st.ctypes.data))
-        total = int(oo[n])
-        out = np.empty(max(total, 1), dtype=np.uint8)
-        raise_for(L.hutk_decode_special_batch(self._h, pid, id_offsets.ctypes.data, n, flags, out.ctypes.data, total,
-                                              oo.ctypes.data, st.ctypes.data))
-        return out[:total], oo, st[:n]
+        return self._decode_host(load().hutk_decode_special_batch, ids, id_offsets, (flags,))
 
     def decode_special_device(self, d_ids, d_id_offsets, n_docs, n_ids, flags, d_bytes_out, bytes_cap, d_out_offsets,
                               d_status=0, d_err=0, stream=0):
@@ -623,20 +522,11 @@ class Context:
         """encode_packed with byte fallback (hutk_encode_fallback_batch; flags: 0 or FB_SPECIAL): host numpy buffers in
         and out.  -> (ids int32, out_offsets int64, status int32, return code); the code E_UNSUPPORTED (documents whose
         spans did not verify keep their plain ids) is returned, not raised."""
-        import numpy as np
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(offsets) - 1
-        nbytes = int(offsets[n]) if n >= 0 else 0
-        cap = self.special_ids_capacity(nbytes, n) if flags & FB_SPECIAL else self.ids_capacity(nbytes, n)
-        ids = np.empty(max(cap, 1), dtype=np.int32)
-        oo = np.zeros(n + 1, dtype=np.int64)
-        st = np.zeros(max(n, 1), dtype=np.int32)
-        rc = load().hutk_encode_fallback_batch(self._h, data.ctypes.data if nbytes else None, offsets.ctypes.data, n, flags,
-                                               ids.ctypes.data, cap, oo.ctypes.data, st.ctypes.data)
-        if rc not in (OK, E_WORD_TOO_LARGE) and not (rc == E_UNSUPPORTED and int(oo[n]) > 0):
-            raise_for(rc)
-        return ids[: int(oo[n])], oo, st[:n], rc
+        capacity = self.special_ids_capacity if flags & FB_SPECIAL else self.ids_capacity
+        r = self._encode_host(load().hutk_encode_fallback_batch, capacity, data, offsets, (flags,))
+        if r[3] not in (OK, E_WORD_TOO_LARGE) and not (r[3] == E_UNSUPPORTED and len(r[0]) > 0):
+            raise_for(r[3])
+        return r
 
     def encode_fallback_device(self, d_bytes, d_offsets, n_docs, n_bytes, flags, d_ids, ids_cap, d_out_offsets,
                                d_status=0, d_err=0, stream=0):
@@ -649,21 +539,7 @@ class Context:
     def decode_fallback_packed(self, ids, id_offsets, flags=0):
         """decode_packed with byte fallback (hutk_decode_fallback_batch; flags: FB_SPECIAL, FB_SKIP_SPECIAL):
         -> (bytes uint8, out_offsets int64[n+1], status int32[n]).  Two calls: sizes, then the text."""
-        import numpy as np
-        L = load()
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
-        n = len(id_offsets) - 1
-        oo = np.zeros(n + 1, dtype=np.int64)
-        st = np.zeros(max(n, 1), dtype=np.int32)
-        pid = ids.ctypes.data if len(ids) else None
-        raise_for(L.hutk_decode_fallback_batch(self._h, pid, id_offsets.ctypes.data, n, flags, None, 0, oo.ctypes.data,
-                                               st.ctypes.data))
-        total = int(oo[n])
-        out = np.empty(max(total, 1), dtype=np.uint8)
-        raise_for(L.hutk_decode_fallback_batch(self._h, pid, id_offsets.ctypes.data, n, flags, out.ctypes.data, total,
-                                               oo.ctypes.data, st.ctypes.data))
-        return out[:total], oo, st[:n]
+        return self._decode_host(load().hutk_decode_fallback_batch, ids, id_offsets, (flags,))
 
     def decode_fallback_device(self, d_ids, d_id_offsets, n_docs, n_ids, flags, d_bytes_out, bytes_cap, d_out_offsets,
                                d_status=0, d_err=0, stream=0):
@@ -701,8 +577,9 @@ TRAINER_COUNTERS = ["pauses", "pair_grows", "pair_shrinks", "pair_rebuilds", "ho
                     "dropped_words", "charset_grows"]
 
 
-class Trainer:
+class Trainer(_Owner):
     """Owns one hutk_trainer (BPE training on the GPU, include/hutoken_amd.h); mode TRAIN_BYTES or TRAIN_CHARS."""
+    _destroy = "hutk_trainer_destroy"
 
     def __init__(self, device=-1, mode=TRAIN_BYTES):
         h = C.c_void_p()
@@ -760,17 +637,6 @@ class Trainer:
         raise_for(load().hutk_trainer_debug_counters(self._h, out.ctypes.data, len(out)))
         return dict(zip(TRAINER_COUNTERS, out.tolist()))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            load().hutk_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def collate_padded_device(d_ids, d_offsets, n_docs, n_ids, max_len, bos_id, eos_id, pad_id, flags, out_width,
                           d_input_ids, d_mask=0, d_lengths=0, d_err=0, stream=0):
@@ -804,8 +670,9 @@ def collate_windows_device(d_ids, d_offsets, d_row_offsets, n_docs, n_ids, n_row
                                                  d_row_map or None, d_err or None, stream or None))
 
 
-class Packer:
+class Packer(_Owner):
     """Owns one hutk_packer (include/hutoken_amd.h): raw device pointers (ints) in, rows written asynchronously."""
+    _destroy = "hutk_packer_destroy"
 
     def __init__(self, seq_len, bos_id=NO_TOKEN, eos_id=NO_TOKEN, pad_id=0, out_width=4, device=-1):
         h = C.c_void_p()
@@ -836,14 +703,3 @@ class Packer:
         raise_for(load().hutk_packer_flush_device(self._h, d_input_ids or None, d_position_ids or None,
                                                   d_segment_ids or None, C.byref(n), stream or None))
         return n.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            load().hutk_packer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

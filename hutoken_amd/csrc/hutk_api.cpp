@@ -289,7 +289,7 @@ void destroy(hutk_ctx* c) {
         c->ds_offs.release(); c->ds_oo.release(); c->ds_bytes.release(); c->w_err.release();
         c->sp_bits.release(); c->sp_in_chunk.release(); c->sp_chunk.release(); c->sp_sel.release(); c->ss_spans.release();
         c->sp_ok.release();
-        c->sx.release();
+        c->sxd.release();
         c->fb.release();
         c->s_bytes.release(); c->s_offsets.release(); c->s_out_offsets.release(); c->s_ids.release();
         c->s_status.release(); c->s_small_in.release(); c->s_small_out.release();

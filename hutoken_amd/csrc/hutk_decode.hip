@@ -16,7 +16,8 @@
 //
 // The direction's C entry points are at the end of the file: hutk_decode_batch_device (device buffers, asynchronous) and
 // hutk_decode_batch (host buffers, staged through the context's), in front of them what they share with the decode of
-// special ids (hutk_special.hip): decode_device_impl and decode_host_impl.
+// special ids (hutk_special.hip) and with byte fallback (hutk_fallback.hip): decode_device_impl (the staging around it,
+// decode_host_impl, is in hutk_host.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -413,44 +414,6 @@ int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, co
     return HUTK_OK;
 }
 
-int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
-                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status, int fallback_flags) {
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
-    if (n_docs < 0 || !id_offsets || !out_offsets) return api_set_error(HUTK_E_ARG, "bad argument");
-    if (int rc = check_offsets(id_offsets, n_docs, true, "id_offsets")) return rc;
-    const int64_t n_ids = id_offsets[n_docs];
-    if (n_ids > 0 && !ids) return api_set_error(HUTK_E_ARG, "bad argument");
-    HUTK_HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    HUTK_HIP_TRY(c->ds_ids.reserve((size_t)n_ids + 16));
-    HUTK_HIP_TRY(c->ds_offs.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->ds_oo.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->ds_status.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->w_err.reserve(1));
-    if (bytes_out && bytes_cap > 0) HUTK_HIP_TRY(c->ds_bytes.reserve((size_t)bytes_cap + 16));
-    if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
-    HUTK_HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-    uint8_t* d_bytes = bytes_out ? c->ds_bytes.p : nullptr;
-    int rc = fallback_flags >= 0
-                 ? hutk_decode_fallback_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, fallback_flags, d_bytes,
-                                                     bytes_cap, c->ds_oo.p, c->ds_status.p, c->w_err.p, s)
-             : special_flags < 0
-                 ? hutk_decode_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, d_bytes, bytes_cap, c->ds_oo.p,
-                                            c->ds_status.p, c->w_err.p, s)
-                 : hutk_decode_special_batch_device(c, c->ds_ids.p, c->ds_offs.p, n_docs, n_ids, special_flags, d_bytes,
-                                                    bytes_cap, c->ds_oo.p, c->ds_status.p, c->w_err.p, s);
-    if (rc) return rc;
-    int32_t err = 0;
-    HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->ds_oo.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
-    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->ds_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
-    HUTK_HIP_TRY(hipStreamSynchronize(s));
-    if (bytes_out && err == HUTK_OK && out_offsets[n_docs] > 0)
-        HUTK_HIP_TRY(hipMemcpy(bytes_out, c->ds_bytes.p, (size_t)out_offsets[n_docs], hipMemcpyDeviceToHost));
-    return err == HUTK_OK ? HUTK_OK : api_set_error(err, device_error_message(Direction::Decode, err));
-}
-
 }  // namespace hutk
 
 using namespace hutk;
@@ -468,7 +431,11 @@ int hutk_decode_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d
 int hutk_decode_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* bytes_out,
                       int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
     if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
-    return decode_host_impl(c, -1, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
+    const auto device = [&](const int32_t* d_ids, const int64_t* d_offs, int64_t n_ids, uint8_t* d_bytes, int64_t* d_oo,
+                            int32_t* d_status, int32_t* d_err, hipStream_t s) {
+        return hutk_decode_batch_device(c, d_ids, d_offs, n_docs, n_ids, d_bytes, bytes_cap, d_oo, d_status, d_err, s);
+    };
+    return decode_host_impl(c, device, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
 }
 
 }  // extern "C"

@@ -288,13 +288,6 @@ __global__ __launch_bounds__(FBR_THREADS) void k_fb_remap(DecSpecial S, DecFallb
     }
 }
 
-template <class V, class D>
-int fb_upload(D& d, const V& v) {
-    HUTK_HIP_TRY(d.reserve(v.size() + 1));
-    if (!v.empty()) HUTK_HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    return HUTK_OK;
-}
-
 // what the spans refuse (hutk_token_spans_device), and a context without a table
 int fb_refusal(const hutk_ctx* c, const char* who) {
     const std::string w(who);
@@ -326,48 +319,28 @@ int fallback_rebuild_decode(hutk_ctx* c) {
     for (int b = 0; b < 256 && S.n; b++)
         F.clash = F.clash || std::find(S.ids.begin(), S.ids.end(), F.ids[b]) != S.ids.end();
     if (c->host_only) return HUTK_OK;
-    const Tables& T = c->tab;
-    std::vector<uint2> ent, sent, ent_skip, sent_skip;
-    std::vector<uint8_t> blob;
-    int64_t x_n = 0;
-    if (S.n) {  // behind the entries of the special ids
-        ent = S.x_ent, sent = S.x_sent, ent_skip = S.x_ent_skip, sent_skip = S.x_sent_skip, blob = S.x_blob, x_n = S.x_n;
-    } else {
-        uint32_t max_len = 0;
-        dec_pack_tables(T, ent, sent, max_len);
-        ent.resize((size_t)T.dec_n);
-        if (!sent.empty()) sent.resize((size_t)T.dec_n);
-        ent_skip = ent, sent_skip = sent, blob = T.dec_blob;
-        blob.resize(((blob.size() + 3) & ~(size_t)3) + 16, 0);
-    }
-    if (T.dec_n + x_n + 256 > (int64_t)INT32_MAX) return api_set_error(HUTK_E_UNSUPPORTED, "byte fallback: the vocabulary leaves no ids for the decode tables");
-    F.strip = !sent.empty();
-    for (int b = 0; b < 256; b++) {
-        const uint8_t byte = (uint8_t)b;
-        const uint2 e = dec_pack_entry(&byte, 0, 1, false);
-        ent.push_back(e);
-        ent_skip.push_back(e);
-        if (F.strip) sent.push_back(e), sent_skip.push_back(e);  // never stripped of a prefix
-    }
-    F.base = T.dec_n + x_n;
-    std::vector<uint2> slots(FB_SLOTS, make_uint2(0, DSP_EMPTY));
+    DecExt::Host X;  // behind the entries of the special ids, when a set is installed
+    std::vector<std::pair<const uint8_t*, uint32_t>> extra;
+    extra.reserve(256);
+    uint8_t byte[256];
+    for (int b = 0; b < 256; b++) byte[b] = (uint8_t)b, extra.emplace_back(&byte[b], 1u);
+    if (int rc = dec_ext_build(c->tab, S.n ? &S.dec : nullptr, extra, false,
+                               "byte fallback: the vocabulary leaves no ids for the decode tables", X))
+        return rc;
+    F.base = c->tab.dec_n + X.n_extra - 256;
+    X.slots.assign(FB_SLOTS, make_uint2(0, DSP_EMPTY));
     F.id_min = INT32_MAX;
     F.id_max = 0;
     for (int b = 0; b < 256; b++) {
         uint32_t s = fb_slot((uint32_t)F.ids[b]);
-        while (slots[s].y != DSP_EMPTY) s = (s + 1) & (FB_SLOTS - 1);
-        slots[s] = make_uint2((uint32_t)F.ids[b], (uint32_t)b);
+        while (X.slots[s].y != DSP_EMPTY) s = (s + 1) & (FB_SLOTS - 1);
+        X.slots[s] = make_uint2((uint32_t)F.ids[b], (uint32_t)b);
         F.id_min = std::min(F.id_min, F.ids[b]);
         F.id_max = std::max(F.id_max, F.ids[b]);
     }
     HUTK_HIP_TRY(hipSetDevice(c->device));
     HUTK_HIP_TRY(hipDeviceSynchronize());  // an earlier asynchronous call may still read the tables
-    if (int rc = fb_upload(F.dx_ent, ent)) return rc;
-    if (int rc = fb_upload(F.dx_ent_skip, ent_skip)) return rc;
-    if (int rc = fb_upload(F.dx_sent, sent)) return rc;
-    if (int rc = fb_upload(F.dx_sent_skip, sent_skip)) return rc;
-    if (int rc = fb_upload(F.dx_slots, slots)) return rc;
-    if (int rc = fb_upload(F.dx_blob, blob)) return rc;
+    if (int rc = F.dec.upload(X)) return rc;
     HUTK_HIP_TRY(F.d_tab.reserve(256));
     HUTK_HIP_TRY(hipMemcpy(F.d_tab.p, F.ids, sizeof F.ids, hipMemcpyHostToDevice));
     return HUTK_OK;
@@ -548,35 +521,21 @@ int hutk_encode_fallback_batch(hutk_ctx* c, const uint8_t* bytes, const int64_t*
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     const int64_t cap = (flags & HUTK_FB_SPECIAL) ? hutk_special_ids_capacity(c, n_bytes, n_docs) : hutk_ids_capacity(c, n_bytes, n_docs);
     if (ids_cap < cap - 1) return api_set_error(HUTK_E_CAPACITY, "ids_cap is below the capacity of the batch");
-    HUTK_HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    HUTK_HIP_TRY(c->s_bytes.reserve((size_t)n_bytes + 16));
-    HUTK_HIP_TRY(c->s_offsets.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->s_ids.reserve((size_t)cap + 16));
-    HUTK_HIP_TRY(c->s_out_offsets.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->s_status.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->w_err.reserve(1));
-    if (c->busy_valid) HUTK_HIP_TRY(hipStreamWaitEvent(s, c->ev_busy, 0));  // (the staging buffers are the context's)
-    if (n_bytes) HUTK_HIP_TRY(hipMemcpyAsync(c->s_bytes.p, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
-    HUTK_HIP_TRY(hipMemcpyAsync(c->s_offsets.p, offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (int rc = hutk_encode_fallback_batch_device(c, c->s_bytes.p, c->s_offsets.p, n_docs, n_bytes, flags, c->s_ids.p, cap,
-                                                   c->s_out_offsets.p, c->s_status.p, c->w_err.p, s))
-        return rc;
-    int32_t err = 0;
-    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
-    HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->s_out_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->s_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
-    HUTK_HIP_TRY(hipStreamSynchronize(s));
-    if (err == HUTK_E_UNSUPPORTED) {  // documents whose spans did not verify kept their plain ids: the rest is exact
-        api_set_error(err, "a document's text does not hold the decoded bytes of its tokens where their spans lie: it keeps its plain ids");
-    } else if (err != HUTK_OK && err != HUTK_E_WORD_TOO_LARGE) {
-        return api_set_error(err, err == HUTK_E_ARG ? "offsets that do not describe the text, or a document of 2^31 bytes or more"
-                                                    : device_error_message(Direction::Encode, err));
-    }
-    const int64_t n_ids = out_offsets[n_docs];
-    if (n_ids < 0 || n_ids > ids_cap) return api_set_error(HUTK_E_DEVICE, "hutk_encode_fallback_batch: bad id count");
-    if (n_ids) HUTK_HIP_TRY(hipMemcpy(ids_out, c->s_ids.p, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
-    return err;  // HUTK_OK, the note HUTK_E_WORD_TOO_LARGE, or HUTK_E_UNSUPPORTED with every other document exact
+    const auto device = [&](const uint8_t* d_bytes, const int64_t* d_offs, int32_t* d_ids, int64_t* d_oo, int32_t* d_status,
+                            int32_t* d_err, hipStream_t s) {
+        return hutk_encode_fallback_batch_device(c, d_bytes, d_offs, n_docs, n_bytes, flags, d_ids, cap, d_oo, d_status, d_err, s);
+    };
+    const auto refuse = [](int err) {
+        if (err == HUTK_E_UNSUPPORTED) {  // documents whose spans did not verify kept their plain ids: the rest is exact
+            api_set_error(err, "a document's text does not hold the decoded bytes of its tokens where their spans lie: it keeps its plain ids");
+            return false;
+        }
+        api_set_error(err, err == HUTK_E_ARG ? "offsets that do not describe the text, or a document of 2^31 bytes or more"
+                                             : device_error_message(Direction::Encode, err));
+        return true;
+    };
+    return encode_host_impl(c, "hutk_encode_fallback_batch", cap, device, refuse, bytes, offsets, n_docs, n_bytes, ids_out, ids_cap,
+                            out_offsets, status);
 }
 
 int hutk_decode_fallback_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
@@ -595,24 +554,19 @@ int hutk_decode_fallback_batch_device(hutk_ctx* c, const int32_t* d_ids, const i
     if (special && F.clash)
         return api_set_error(HUTK_E_VALUE, "hutk_decode_fallback_batch_device: an id is both a special token's and the byte-fallback table's");
     const bool skip = (flags & HUTK_FB_SKIP_SPECIAL) != 0;
-    DecTables T{};
-    T.ent = skip ? F.dx_ent_skip.p : F.dx_ent.p;
-    T.sent = !F.strip ? nullptr : skip ? F.dx_sent_skip.p : F.dx_sent.p;
-    T.blob = F.dx_blob.p;
-    T.n = F.base + 256;
     DecSpecial P{};
-    P.slots = special ? S.dx_slots.p : nullptr;
-    P.id_min = special ? S.x_min : 1;  // (without the set no id is in [1, 0])
-    P.id_max = special ? S.x_max : 0;
+    P.slots = special ? c->sxd.dec.dx_slots.p : nullptr;
+    P.id_min = special ? S.dec.id_min : 1;  // (without the set no id is in [1, 0])
+    P.id_max = special ? S.dec.id_max : 0;
     P.n_vocab = (int32_t)c->dec.n;
-    P.bits = (!F.strip || !special) ? DSP_BITS_NONE : skip ? DSP_BITS_SKIP : DSP_BITS_AFTER;
+    P.bits = (!F.dec.strip || !special) ? DSP_BITS_NONE : skip ? DSP_BITS_SKIP : DSP_BITS_AFTER;
     DecFallback B{};
-    B.slots = F.dx_slots.p;
+    B.slots = F.dec.dx_slots.p;
     B.id_min = F.id_min;
     B.id_max = F.id_max;
     B.base = (int32_t)F.base;
-    return decode_device_impl(c, T, &P, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets, d_status,
-                              d_err, hip_stream, &B);
+    return decode_device_impl(c, F.dec.tables(skip), &P, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets,
+                              d_status, d_err, hip_stream, &B);
 }
 
 int hutk_decode_fallback_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
@@ -621,7 +575,11 @@ int hutk_decode_fallback_batch(hutk_ctx* c, const int32_t* ids, const int64_t* i
     if (flags & ~(HUTK_FB_SPECIAL | HUTK_FB_SKIP_SPECIAL)) return api_set_error(HUTK_E_ARG, "hutk_decode_fallback_batch: unknown flags");
     if ((flags & HUTK_FB_SKIP_SPECIAL) && !(flags & HUTK_FB_SPECIAL))
         return api_set_error(HUTK_E_ARG, "hutk_decode_fallback_batch: HUTK_FB_SKIP_SPECIAL needs HUTK_FB_SPECIAL");
-    return decode_host_impl(c, -1, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status, flags);
+    const auto device = [&](const int32_t* d_ids, const int64_t* d_offs, int64_t n_ids, uint8_t* d_bytes, int64_t* d_oo,
+                            int32_t* d_status, int32_t* d_err, hipStream_t s) {
+        return hutk_decode_fallback_batch_device(c, d_ids, d_offs, n_docs, n_ids, flags, d_bytes, bytes_cap, d_oo, d_status, d_err, s);
+    };
+    return decode_host_impl(c, device, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "hutk_device.h"
@@ -41,6 +42,58 @@ struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
+    }
+};
+
+// A host vector into a device buffer (one element more than it holds, so that an empty one has an address); the device is
+// selected and idle.
+template <class V, class D>
+int upload_vec(D& d, const V& v) {
+    HUTK_HIP_TRY(d.reserve(v.size() + 1));
+    if (!v.empty()) HUTK_HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+    return HUTK_OK;
+}
+
+// Extended decode tables: the context's entries followed by further ones (the special ids, the 256 bytes of the
+// byte-fallback table), as dec_ext_build makes them on the host and upload() puts them on the device.
+struct DecExt {
+    struct Host {
+        // ent: one entry per vocabulary line, then the further ones; sent: the same behind the first-token entries (a
+        // further entry there equals its ent entry; empty without a prefix); *_skip: the forms for "skip the special
+        // tokens"; slots: the open-addressed map of the caller's ids to the further entries; blob: the context's, then
+        // the further strings of more than DEC_INLINE_MAX bytes on 4-byte boundaries, then 16 bytes
+        std::vector<uint2> ent, sent, ent_skip, sent_skip, slots;
+        std::vector<uint8_t> blob;
+        int64_t n_extra = 0;               // further entries behind the vocabulary's
+        int32_t id_min = 0, id_max = 0;    // the range of the ids in slots
+        bool strip = false;                // the context strips a prefix: sent* are in use
+    };
+    DevBuf<uint2> dx_ent, dx_sent, dx_ent_skip, dx_sent_skip, dx_slots;
+    DevBuf<uint8_t> dx_blob;
+    int64_t n = 0;       // entries of the tables on the device
+    bool strip = false;
+    int upload(const Host& h) {
+        if (int rc = upload_vec(dx_ent, h.ent)) return rc;
+        if (int rc = upload_vec(dx_ent_skip, h.ent_skip)) return rc;
+        if (int rc = upload_vec(dx_sent, h.sent)) return rc;
+        if (int rc = upload_vec(dx_sent_skip, h.sent_skip)) return rc;
+        if (int rc = upload_vec(dx_slots, h.slots)) return rc;
+        if (int rc = upload_vec(dx_blob, h.blob)) return rc;
+        n = (int64_t)h.ent.size();
+        strip = h.strip;
+        return HUTK_OK;
+    }
+    DecTables tables(bool skip) const {
+        DecTables t{};
+        t.ent = skip ? dx_ent_skip.p : dx_ent.p;
+        t.sent = !strip ? nullptr : skip ? dx_sent_skip.p : dx_sent.p;
+        t.blob = dx_blob.p;
+        t.n = n;
+        return t;
+    }
+    void release() {
+        dx_ent.release(); dx_sent.release(); dx_ent_skip.release(); dx_sent_skip.release(); dx_slots.release();
+        dx_blob.release();
     }
 };
 
@@ -97,8 +150,9 @@ struct hutk_ctx {
     DevBuf<int32_t> sp_ok;
     uint32_t dec_max_len = 0;  // the longest decoded token, in bytes
 
-    // special tokens (hutk_special.hip): the set as hutk_ctx_set_special_tokens validated it, its tables on the host and
-    // on the device, and the workspace of hutk_encode_special_batch_device
+    // special tokens (hutk_special.hip).  sx: the set as hutk_ctx_set_special_tokens validated it and its tables, on the
+    // host only: default-movable, a fresh one is built aside and moved in.  sxd: the tables on the device and the
+    // workspace of hutk_encode_special_batch_device, which stay where they are when the set changes.
     struct Specials {
         int64_t n = 0;                 // pairs in the set; 0: none installed
         std::vector<uint8_t> blob;     // the strings, end to end
@@ -107,30 +161,26 @@ struct hutk_ctx {
         std::vector<uint2> slots;      // open-addressed set of the strings: {hash of the bytes, index | length << 16}
         std::vector<uint32_t> filt;    // three 256-bit sets: first bytes, second bytes, lengths
         uint32_t mask = 0, max_len = 0, n_first = 0, first[4] = {0, 0, 0, 0};
-        int64_t last_matches = 0;
         // decode direction (hutk_decode_special_batch_device): the context's decode tables followed by one entry per
-        // DISTINCT special id, in the order of the ids' first pairs; x_sent: the same behind the first-token entries
-        // (a special's entry there equals its x_ent entry; empty without a prefix); *_skip: the specials' entries have
-        // length 0 (HUTK_DECODE_SKIP_SPECIAL); x_blob: the context's blob, then the strings of more than 7 bytes
-        std::vector<uint2> x_ent, x_sent, x_ent_skip, x_sent_skip, x_slots;
-        std::vector<uint8_t> x_blob;
-        int64_t x_n = 0;  // distinct ids
-        int32_t x_min = 0, x_max = 0;
-        DevBuf<uint2> dx_ent, dx_sent, dx_ent_skip, dx_sent_skip, dx_slots;
-        DevBuf<uint8_t> dx_blob;
+        // DISTINCT special id, in the order of the ids' first pairs; *_skip: those entries have length 0
+        // (HUTK_DECODE_SKIP_SPECIAL); slots: id -> index among the distinct ids
+        hutk::DecExt::Host dec;
+    } sx;
+    struct SpecialsDev {
+        hutk::DecExt dec;
+        int64_t last_matches = 0;
         DevBuf<uint8_t> d_blob, w_mlen, w_sel;
         DevBuf<uint32_t> d_off, d_filt;
         DevBuf<uint2> d_slots;
         DevBuf<int32_t> d_ids, w_pspecial, w_pstatus, w_pids;
         DevBuf<int64_t> w_tile, w_mstart, w_poff, w_first, w_poo, w_blk, w_dst;
         void release() {
+            dec.release();
             d_blob.release(); w_mlen.release(); w_sel.release(); d_off.release(); d_filt.release(); d_slots.release();
             d_ids.release(); w_pspecial.release(); w_pstatus.release(); w_pids.release(); w_tile.release();
             w_mstart.release(); w_poff.release(); w_first.release(); w_poo.release(); w_blk.release(); w_dst.release();
-            dx_ent.release(); dx_sent.release(); dx_ent_skip.release(); dx_sent_skip.release(); dx_slots.release();
-            dx_blob.release();
         }
-    } sx;
+    } sxd;
 
     // byte fallback (hutk_fallback.hip): the table of hutk_ctx_set_byte_fallback, the decode tables extended by it, and
     // the workspace of hutk_encode_fallback_batch_device
@@ -138,19 +188,17 @@ struct hutk_ctx {
         bool on = false;
         int32_t ids[256] = {0};
         bool clash = false;            // an id of the table is a special id too (HUTK_FB_SPECIAL refuses)
-        // decode: [vocabulary lines][the distinct special ids, when a set is installed][256 one-byte entries]
+        // decode: [vocabulary lines][the distinct special ids, when a set is installed][256 one-byte entries];
+        // dec's slots: table id -> byte
         int64_t base = 0;              // entries in front of the 256
-        bool strip = false;            // the context strips a prefix: dx_sent* are in use
         int32_t id_min = 0, id_max = 0;
-        DevBuf<uint2> dx_ent, dx_sent, dx_ent_skip, dx_sent_skip, dx_slots;
-        DevBuf<uint8_t> dx_blob;
+        hutk::DecExt dec;
         // encode: the table, the plain encode's outputs (offsets with one more entry: the unused ids behind the batch
         // as a document), their byte spans and the spans' status, per-tile counts
         DevBuf<int32_t> d_tab, w_ids, w_spans, w_sstatus, w_serr;
         DevBuf<int64_t> w_oo, w_doff, w_tile, w_hdr;
         void release() {
-            dx_ent.release(); dx_sent.release(); dx_ent_skip.release(); dx_sent_skip.release(); dx_slots.release();
-            dx_blob.release(); d_tab.release(); w_ids.release(); w_spans.release(); w_sstatus.release(); w_serr.release();
+            dec.release(); d_tab.release(); w_ids.release(); w_spans.release(); w_sstatus.release(); w_serr.release();
             w_oo.release(); w_doff.release(); w_tile.release(); w_hdr.release();
         }
     } fb;
@@ -284,32 +332,6 @@ inline void dec_pack_tables(const Tables& T, std::vector<uint2>& ent, std::vecto
     }
 }
 
-// hutk_decode.hip: the decode behind hutk_decode_batch_device (the caller has checked c and holds no lock yet): its
-// checks, its workspace, every kernel of the direction, with the tables `t`.  sp != nullptr: the ids are renumbered by
-// launch_dec_remap first (hutk_special.hip), and t are the extended tables.
-// fb != nullptr (with sp): the pass is launch_fb_remap (hutk_fallback.hip), t has the one-byte entries too.
-int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, const int32_t* d_ids, const int64_t* d_id_offsets,
-                       int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
-                       int32_t* d_status, int32_t* d_err, void* hip_stream, const DecFallback* fb = nullptr);
-// ... and the staging of hutk_decode_batch around it.  special_flags < 0: the plain decode; otherwise
-// hutk_decode_special_batch_device with these flags.  fallback_flags >= 0: hutk_decode_fallback_batch_device with those.
-int decode_host_impl(hutk_ctx* c, int special_flags, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs,
-                     uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status, int fallback_flags = -1);
-
-// hutk_special.hip: the encode behind hutk_encode_special_batch_device; fallback: the text pieces go through
-// encode_fallback_device_impl instead of encode_device_impl (hutk_encode_fallback_batch_device with HUTK_FB_SPECIAL).
-int encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
-                        int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status,
-                        int32_t* d_err, void* hip_stream);
-// hutk_fallback.hip: encode_device_impl's arguments (without the regex bitmaps); plain encode, byte spans, expansion.
-// The caller holds c->mu and has checked that a table is installed and that the spans take the context.
-int encode_fallback_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
-                                int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err,
-                                void* hip_stream);
-// ... and the decode tables of the byte-fallback decode, built again from the context's and the special set's whenever
-// either changes (no table installed: nothing to do).  The caller holds c->mu.
-int fallback_rebuild_decode(hutk_ctx* c);
-
 // What the host-buffer entry points say about the error word a direction's kernels left (err != HUTK_OK).
 enum class Direction { Encode, Decode, Spans };
 inline const char* device_error_message(Direction dir, int err) {
@@ -328,5 +350,135 @@ inline const char* device_error_message(Direction dir, int err) {
         if (t.dir == dir && t.err == err) return t.text;
     return "device-side failure";
 }
+
+// The tables of DecExt on the host: the context's packed tables trimmed to its vocabulary (under == nullptr) or the
+// tables `under` made from them, followed by one entry per string of `extra` ({bytes, length}).  A string of more than
+// DEC_INLINE_MAX bytes goes to the blob, on a 4-byte boundary as the loader's entries; the blob ends on one, plus 16 bytes.
+// skip_empties: the *_skip forms hold entries of length 0 for the strings (they are what "skip" deletes); otherwise the
+// same entries.  More than INT32_MAX entries: HUTK_E_UNSUPPORTED with `refusal`.  out.slots, id_min and id_max are the
+// caller's to fill: only it knows its ids.
+inline int dec_ext_build(const Tables& T, const DecExt::Host* under, const std::vector<std::pair<const uint8_t*, uint32_t>>& extra,
+                         bool skip_empties, const char* refusal, DecExt::Host& out) {
+    int64_t before = 0;
+    if (under) {
+        out.ent = under->ent, out.sent = under->sent, out.ent_skip = under->ent_skip, out.sent_skip = under->sent_skip;
+        out.blob = under->blob;
+        out.blob.resize(out.blob.size() - 16);  // (its tail: put back below)
+        before = under->n_extra;
+    } else {
+        uint32_t max_len = 0;
+        dec_pack_tables(T, out.ent, out.sent, max_len);
+        out.ent.resize((size_t)T.dec_n);  // (an empty vocabulary has one unused entry)
+        if (!out.sent.empty()) out.sent.resize((size_t)T.dec_n);
+        out.ent_skip = out.ent, out.sent_skip = out.sent, out.blob = T.dec_blob;
+    }
+    out.n_extra = before + (int64_t)extra.size();
+    if (T.dec_n + out.n_extra > (int64_t)INT32_MAX) return api_set_error(HUTK_E_UNSUPPORTED, refusal);
+    out.strip = !out.sent.empty();
+    for (const auto& x : extra) {
+        const uint8_t* from = x.first;
+        uint32_t at = 0;
+        if (x.second > DEC_INLINE_MAX) {
+            out.blob.resize((out.blob.size() + 3) & ~(size_t)3, 0);
+            at = (uint32_t)out.blob.size();
+            out.blob.insert(out.blob.end(), from, from + x.second);
+        }
+        const uint2 e = dec_pack_entry(from, at, x.second, false), e_skip = skip_empties ? make_uint2(0, 0) : e;
+        out.ent.push_back(e);
+        out.ent_skip.push_back(e_skip);
+        if (out.strip) out.sent.push_back(e), out.sent_skip.push_back(e_skip);  // never stripped of a prefix
+    }
+    out.blob.resize(((out.blob.size() + 3) & ~(size_t)3) + 16, 0);
+    return HUTK_OK;
+}
+
+// hutk_decode.hip: the decode behind hutk_decode_batch_device (the caller has checked c and holds no lock yet): its
+// checks, its workspace, every kernel of the direction, with the tables `t`.  sp != nullptr: the ids are renumbered by
+// launch_dec_remap first (hutk_special.hip), and t are the extended tables.
+// fb != nullptr (with sp): the pass is launch_fb_remap (hutk_fallback.hip), t has the one-byte entries too.
+int decode_device_impl(hutk_ctx* c, const DecTables& t, const DecSpecial* sp, const int32_t* d_ids, const int64_t* d_id_offsets,
+                       int64_t n_docs, int64_t n_ids, uint8_t* d_bytes_out, int64_t bytes_cap, int64_t* d_out_offsets,
+                       int32_t* d_status, int32_t* d_err, void* hip_stream, const DecFallback* fb = nullptr);
+// ... and the staging of hutk_decode_batch and its special and fallback forms around it (the caller has checked c and its
+// flags).  device(d_ids, d_id_offsets, n_ids, d_bytes_out, d_out_offsets, d_status, d_err, stream): the variant's device
+// entry point on the staged batch.
+template <class Device>
+int decode_host_impl(hutk_ctx* c, Device device, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* bytes_out,
+                     int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
+    if (n_docs < 0 || !id_offsets || !out_offsets) return api_set_error(HUTK_E_ARG, "bad argument");
+    if (int rc = check_offsets(id_offsets, n_docs, true, "id_offsets")) return rc;
+    const int64_t n_ids = id_offsets[n_docs];
+    if (n_ids > 0 && !ids) return api_set_error(HUTK_E_ARG, "bad argument");
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HUTK_HIP_TRY(c->ds_ids.reserve((size_t)n_ids + 16));
+    HUTK_HIP_TRY(c->ds_offs.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ds_oo.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->ds_status.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->w_err.reserve(1));
+    if (bytes_out && bytes_cap > 0) HUTK_HIP_TRY(c->ds_bytes.reserve((size_t)bytes_cap + 16));
+    if (n_ids) HUTK_HIP_TRY(hipMemcpyAsync(c->ds_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(c->ds_offs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    if (int rc = device(c->ds_ids.p, c->ds_offs.p, n_ids, bytes_out ? c->ds_bytes.p : nullptr, c->ds_oo.p, c->ds_status.p,
+                        c->w_err.p, s))
+        return rc;
+    int32_t err = 0;
+    HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->ds_oo.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
+    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->ds_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipStreamSynchronize(s));
+    if (bytes_out && err == HUTK_OK && out_offsets[n_docs] > 0)
+        HUTK_HIP_TRY(hipMemcpy(bytes_out, c->ds_bytes.p, (size_t)out_offsets[n_docs], hipMemcpyDeviceToHost));
+    return err == HUTK_OK ? HUTK_OK : api_set_error(err, device_error_message(Direction::Decode, err));
+}
+
+// The staging of hutk_encode_special_batch and hutk_encode_fallback_batch (`who` in the messages) around their device
+// entry points.  The caller has checked its arguments (n_bytes = offsets[n_docs]), holds c->mu and has computed `cap`, the
+// capacity of the batch (ids_cap >= cap - 1).  device(d_bytes, d_offsets, d_ids, d_out_offsets, d_status, d_err, stream):
+// the entry point on the staged batch.  refuse(err): the error word is neither HUTK_OK nor HUTK_E_WORD_TOO_LARGE; it sets
+// the message and says whether the call ends there (false: a note, the ids are copied down and err is returned).
+template <class Device, class Refuse>
+int encode_host_impl(hutk_ctx* c, const char* who, int64_t cap, Device device, Refuse refuse, const uint8_t* bytes,
+                     const int64_t* offsets, int64_t n_docs, int64_t n_bytes, int32_t* ids_out, int64_t ids_cap,
+                     int64_t* out_offsets, int32_t* status) {
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HUTK_HIP_TRY(c->s_bytes.reserve((size_t)n_bytes + 16));
+    HUTK_HIP_TRY(c->s_offsets.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->s_ids.reserve((size_t)cap + 16));
+    HUTK_HIP_TRY(c->s_out_offsets.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->s_status.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(c->w_err.reserve(1));
+    if (c->busy_valid) HUTK_HIP_TRY(hipStreamWaitEvent(s, c->ev_busy, 0));  // (the staging buffers are the context's)
+    if (n_bytes) HUTK_HIP_TRY(hipMemcpyAsync(c->s_bytes.p, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(c->s_offsets.p, offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    if (int rc = device(c->s_bytes.p, c->s_offsets.p, c->s_ids.p, c->s_out_offsets.p, c->s_status.p, c->w_err.p, s)) return rc;
+    int32_t err = 0;
+    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->s_out_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->s_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+    HUTK_HIP_TRY(hipStreamSynchronize(s));
+    if (err != HUTK_OK && err != HUTK_E_WORD_TOO_LARGE && refuse(err)) return err;
+    const int64_t n_ids = out_offsets[n_docs];
+    if (n_ids < 0 || n_ids > ids_cap) return api_set_error(HUTK_E_DEVICE, std::string(who) + ": bad id count");
+    if (n_ids) HUTK_HIP_TRY(hipMemcpy(ids_out, c->s_ids.p, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
+    return err;  // HUTK_OK, the note HUTK_E_WORD_TOO_LARGE (see status), or what refuse() let pass
+}
+
+// hutk_special.hip: the encode behind hutk_encode_special_batch_device; fallback: the text pieces go through
+// encode_fallback_device_impl instead of encode_device_impl (hutk_encode_fallback_batch_device with HUTK_FB_SPECIAL).
+int encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                        int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status,
+                        int32_t* d_err, void* hip_stream);
+// hutk_fallback.hip: encode_device_impl's arguments (without the regex bitmaps); plain encode, byte spans, expansion.
+// The caller holds c->mu and has checked that a table is installed and that the spans take the context.
+int encode_fallback_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err,
+                                void* hip_stream);
+// ... and the decode tables of the byte-fallback decode, built again from the context's and the special set's whenever
+// either changes (no table installed: nothing to do).  The caller holds c->mu.
+int fallback_rebuild_decode(hutk_ctx* c);
 
 }  // namespace hutk

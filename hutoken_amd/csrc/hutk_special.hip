@@ -556,91 +556,44 @@ int build_specials(hutk_ctx::Specials& S, const uint8_t* bytes, const int64_t* o
     return HUTK_OK;
 }
 
+// (the set's own tables and its decode tables: the device is selected and idle behind the first lines)
 int upload_specials(hutk_ctx* c) {
-    hutk_ctx::Specials& S = c->sx;
+    const hutk_ctx::Specials& S = c->sx;
+    hutk_ctx::SpecialsDev& D = c->sxd;
     HUTK_HIP_TRY(hipSetDevice(c->device));
     HUTK_HIP_TRY(hipDeviceSynchronize());  // an earlier asynchronous call may still read the tables
-    HUTK_HIP_TRY(S.d_blob.reserve(S.blob.size() + 16));
-    HUTK_HIP_TRY(S.d_off.reserve(S.off.size()));
-    HUTK_HIP_TRY(S.d_ids.reserve(S.ids.size() + 1));
-    HUTK_HIP_TRY(S.d_filt.reserve(S.filt.size()));
-    HUTK_HIP_TRY(S.d_slots.reserve(S.slots.size()));
-    HUTK_HIP_TRY(hipMemcpy(S.d_blob.p, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice));
-    HUTK_HIP_TRY(hipMemcpy(S.d_off.p, S.off.data(), S.off.size() * 4, hipMemcpyHostToDevice));
-    HUTK_HIP_TRY(hipMemcpy(S.d_ids.p, S.ids.data(), S.ids.size() * 4, hipMemcpyHostToDevice));
-    HUTK_HIP_TRY(hipMemcpy(S.d_filt.p, S.filt.data(), S.filt.size() * 4, hipMemcpyHostToDevice));
-    HUTK_HIP_TRY(hipMemcpy(S.d_slots.p, S.slots.data(), S.slots.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    return HUTK_OK;
+    HUTK_HIP_TRY(D.d_blob.reserve(S.blob.size() + 16));
+    HUTK_HIP_TRY(D.d_off.reserve(S.off.size()));
+    HUTK_HIP_TRY(D.d_ids.reserve(S.ids.size() + 1));
+    HUTK_HIP_TRY(D.d_filt.reserve(S.filt.size()));
+    HUTK_HIP_TRY(D.d_slots.reserve(S.slots.size()));
+    HUTK_HIP_TRY(hipMemcpy(D.d_blob.p, S.blob.data(), S.blob.size(), hipMemcpyHostToDevice));
+    HUTK_HIP_TRY(hipMemcpy(D.d_off.p, S.off.data(), S.off.size() * 4, hipMemcpyHostToDevice));
+    HUTK_HIP_TRY(hipMemcpy(D.d_ids.p, S.ids.data(), S.ids.size() * 4, hipMemcpyHostToDevice));
+    HUTK_HIP_TRY(hipMemcpy(D.d_filt.p, S.filt.data(), S.filt.size() * 4, hipMemcpyHostToDevice));
+    HUTK_HIP_TRY(hipMemcpy(D.d_slots.p, S.slots.data(), S.slots.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    return D.dec.upload(S.dec);
 }
 
-// The decode tables of the context extended by the set (hutk_ctx::Specials::x_*): validated and built on the host, whatever
+// The decode tables of the context extended by the set (hutk_ctx::Specials::dec): validated and built on the host, whatever
 // the context.  Entry k belongs to the k-th DISTINCT id in the order of the pairs, its bytes are those of the id's first pair.
 int build_decode_specials(const hutk_ctx* c, hutk_ctx::Specials& S) {
-    const Tables& T = c->tab;
-    std::vector<uint2> ent, sent;
-    uint32_t max_len = 0;
-    dec_pack_tables(T, ent, sent, max_len);
-    ent.resize((size_t)T.dec_n);  // (an empty vocabulary has one unused entry)
-    if (!sent.empty()) sent.resize((size_t)T.dec_n);
-    S.x_blob = T.dec_blob;
-    S.x_slots.assign(DSP_SLOTS, make_uint2(0, DSP_EMPTY));
-    S.x_n = 0;
-    S.x_min = INT32_MAX;
-    S.x_max = 0;
-    std::vector<uint2> extra;
+    DecExt::Host& X = S.dec;
+    X.slots.assign(DSP_SLOTS, make_uint2(0, DSP_EMPTY));
+    X.id_min = INT32_MAX;
+    X.id_max = 0;
+    std::vector<std::pair<const uint8_t*, uint32_t>> extra;
     for (int64_t i = 0; i < S.n; i++) {
         const int32_t id = S.ids[i];
         uint32_t s = dsp_slot((uint32_t)id);
-        while (S.x_slots[s].y != DSP_EMPTY && (int32_t)S.x_slots[s].x != id) s = (s + 1) & (DSP_SLOTS - 1);
-        if (S.x_slots[s].y != DSP_EMPTY) continue;  // a later string of the same id: the first one is the id's text
-        S.x_slots[s] = make_uint2((uint32_t)id, (uint32_t)S.x_n++);
-        S.x_min = std::min(S.x_min, id);
-        S.x_max = std::max(S.x_max, id);
-        const uint32_t len = S.off[i + 1] - S.off[i];
-        uint32_t at = S.off[i];
-        const uint8_t* from = S.blob.data();
-        if (len > DEC_INLINE_MAX) {  // (entries start on 4-byte boundaries, as the loader's)
-            S.x_blob.resize((S.x_blob.size() + 3) & ~(size_t)3, 0);
-            at = (uint32_t)S.x_blob.size();
-            S.x_blob.insert(S.x_blob.end(), from + S.off[i], from + S.off[i + 1]);
-            from = S.x_blob.data();
-        }
-        extra.push_back(dec_pack_entry(from, at, len, false));
+        while (X.slots[s].y != DSP_EMPTY && (int32_t)X.slots[s].x != id) s = (s + 1) & (DSP_SLOTS - 1);
+        if (X.slots[s].y != DSP_EMPTY) continue;  // a later string of the same id: the first one is the id's text
+        X.slots[s] = make_uint2((uint32_t)id, (uint32_t)extra.size());
+        X.id_min = std::min(X.id_min, id);
+        X.id_max = std::max(X.id_max, id);
+        extra.emplace_back(S.blob.data() + S.off[i], S.off[i + 1] - S.off[i]);
     }
-    if (T.dec_n + S.x_n > (int64_t)INT32_MAX) return api_set_error(HUTK_E_UNSUPPORTED, "special tokens: the vocabulary leaves no ids for the decode tables");
-    S.x_blob.resize(((S.x_blob.size() + 3) & ~(size_t)3) + 16, 0);
-    const std::vector<uint2> none(extra.size(), make_uint2(0, 0));  // HUTK_DECODE_SKIP_SPECIAL: no bytes
-    S.x_ent = ent;
-    S.x_ent.insert(S.x_ent.end(), extra.begin(), extra.end());
-    S.x_ent_skip = ent;
-    S.x_ent_skip.insert(S.x_ent_skip.end(), none.begin(), none.end());
-    S.x_sent.clear();
-    S.x_sent_skip.clear();
-    if (!sent.empty()) {
-        S.x_sent = sent;
-        S.x_sent.insert(S.x_sent.end(), extra.begin(), extra.end());
-        S.x_sent_skip = sent;
-        S.x_sent_skip.insert(S.x_sent_skip.end(), none.begin(), none.end());
-    }
-    return HUTK_OK;
-}
-
-template <class V, class D>
-int upload_vec(D& d, const V& v) {
-    HUTK_HIP_TRY(d.reserve(v.size() + 1));
-    if (!v.empty()) HUTK_HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    return HUTK_OK;
-}
-
-// (behind upload_specials: the device is selected and idle)
-int upload_decode_specials(hutk_ctx* c) {
-    hutk_ctx::Specials& S = c->sx;
-    if (int rc = upload_vec(S.dx_ent, S.x_ent)) return rc;
-    if (int rc = upload_vec(S.dx_ent_skip, S.x_ent_skip)) return rc;
-    if (int rc = upload_vec(S.dx_sent, S.x_sent)) return rc;
-    if (int rc = upload_vec(S.dx_sent_skip, S.x_sent_skip)) return rc;
-    if (int rc = upload_vec(S.dx_slots, S.x_slots)) return rc;
-    return upload_vec(S.dx_blob, S.x_blob);
+    return dec_ext_build(c->tab, nullptr, extra, true, "special tokens: the vocabulary leaves no ids for the decode tables", X);
 }
 
 // prefix units a document can get, units an input item can become: what hutk_ids_capacity multiplies by
@@ -669,41 +622,24 @@ int hutk_ctx_set_special_tokens(hutk_ctx* c, const uint8_t* bytes, const int64_t
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (n == 0) {
         c->sx.n = 0;
-        return fallback_rebuild_decode(c);  // (the byte-fallback decode's tables hold the set's entries)
+        return fallback_rebuild_decode(c);
     }
-    hutk_ctx::Specials fresh;  // (a set that is refused leaves the one in force as it was, its decode tables too)
+    // A set that is refused leaves the one in force as it was, its decode tables too: the new one is built aside.  While
+    // the uploads run no set is in force (n is 0: a failed upload leaves the device arrays half replaced).  The byte-fallback
+    // decode's tables hold the set's entries: they are rebuilt after every change of the set, its removal above included.
+    hutk_ctx::Specials fresh;
     if (int rc = build_specials(fresh, bytes, offsets, ids, n)) return rc;
     if (int rc = build_decode_specials(c, fresh)) return rc;
-    hutk_ctx::Specials& S = c->sx;
-    S.n = 0;
-    S.x_ent.swap(fresh.x_ent);
-    S.x_sent.swap(fresh.x_sent);
-    S.x_ent_skip.swap(fresh.x_ent_skip);
-    S.x_sent_skip.swap(fresh.x_sent_skip);
-    S.x_slots.swap(fresh.x_slots);
-    S.x_blob.swap(fresh.x_blob);
-    S.x_n = fresh.x_n;
-    S.x_min = fresh.x_min;
-    S.x_max = fresh.x_max;
-    S.blob.swap(fresh.blob);
-    S.off.swap(fresh.off);
-    S.ids.swap(fresh.ids);
-    S.slots.swap(fresh.slots);
-    S.filt.swap(fresh.filt);
-    S.mask = fresh.mask;
-    S.max_len = fresh.max_len;
-    S.n_first = fresh.n_first;
-    memcpy(S.first, fresh.first, sizeof S.first);
-    if (!c->host_only) {
+    c->sx = std::move(fresh);
+    c->sx.n = 0;
+    if (!c->host_only)
         if (int rc = upload_specials(c)) return rc;
-        if (int rc = upload_decode_specials(c)) return rc;
-    }
-    S.n = n;
+    c->sx.n = n;
     return fallback_rebuild_decode(c);
 }
 
 int64_t hutk_ctx_special_token_count(const hutk_ctx* c) { return c ? c->sx.n : 0; }
-int64_t hutk_special_last_matches(const hutk_ctx* c) { return c ? c->sx.last_matches : 0; }
+int64_t hutk_special_last_matches(const hutk_ctx* c) { return c ? c->sxd.last_matches : 0; }
 int hutk_debug_special_tile_bytes(void) { return SC_TILE; }
 
 int64_t hutk_special_ids_capacity(const hutk_ctx* c, int64_t n_bytes, int64_t n_docs) {
@@ -740,23 +676,24 @@ int hutk::encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes
                                                  "matches; the pieces between special tokens are not documents of their own");
     if (ids_cap < hutk_special_ids_capacity(c, n_bytes, n_docs) - 1)
         return api_set_error(HUTK_E_CAPACITY, "ids_cap is below hutk_special_ids_capacity()");
-    hutk_ctx::Specials& S = c->sx;
-    S.last_matches = 0;
+    const hutk_ctx::Specials& S = c->sx;
+    hutk_ctx::SpecialsDev& W = c->sxd;
+    W.last_matches = 0;
     if (S.n == 0 || n_docs == 0 || n_bytes == 0)  // nothing to find: the plain encode
         return encode(d_offsets, n_docs, d_ids_out, ids_cap, d_out_offsets, d_status, d_err);
     const int64_t n_tiles = (n_bytes + SC_TILE - 1) / SC_TILE;
     if (n_tiles > 0x7FFFFFFFll) return api_set_error(HUTK_E_ARG, "batch too large");
     HUTK_HIP_TRY(hipSetDevice(c->device));
-    HUTK_HIP_TRY(S.w_mlen.reserve((size_t)n_bytes + 16));
-    HUTK_HIP_TRY(S.w_sel.reserve((size_t)n_bytes + 16));
-    HUTK_HIP_TRY(S.w_tile.reserve((size_t)n_tiles + 1));
+    HUTK_HIP_TRY(W.w_mlen.reserve((size_t)n_bytes + 16));
+    HUTK_HIP_TRY(W.w_sel.reserve((size_t)n_bytes + 16));
+    HUTK_HIP_TRY(W.w_tile.reserve((size_t)n_tiles + 1));
     HUTK_HIP_TRY(c->w_err.reserve(1));
     SpecTab T{};
-    T.slots = S.d_slots.p;
-    T.blob = S.d_blob.p;
-    T.off = S.d_off.p;
-    T.ids = S.d_ids.p;
-    T.filt = S.d_filt.p;
+    T.slots = W.d_slots.p;
+    T.blob = W.d_blob.p;
+    T.off = W.d_off.p;
+    T.ids = W.d_ids.p;
+    T.filt = W.d_filt.p;
     T.mask = S.mask;
     T.max_len = S.max_len;
     T.n_first = S.n_first;
@@ -767,9 +704,9 @@ int hutk::encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes
     A.n_docs = n_docs;
     A.n_bytes = n_bytes;
     A.n_tiles = n_tiles;
-    A.mlen = S.w_mlen.p;
-    A.sel = S.w_sel.p;
-    A.tile_base = S.w_tile.p;
+    A.mlen = W.w_mlen.p;
+    A.sel = W.w_sel.p;
+    A.tile_base = W.w_tile.p;
     A.err = d_err ? d_err : c->w_err.p;
     A.out_ids = d_ids_out;
     A.ids_cap = ids_cap;
@@ -793,33 +730,33 @@ int hutk::encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes
         HUTK_HIP_TRY(hipStreamSynchronize(s));
     }
     if (n_matches < 0 || n_matches > n_bytes) return api_set_error(HUTK_E_DEVICE, "hutk_encode_special_batch_device: bad match count");
-    S.last_matches = n_matches;
+    W.last_matches = n_matches;
     if (n_matches == 0)
         return encode(d_offsets, n_docs, d_ids_out, ids_cap, d_out_offsets, d_status, d_err);
     const int64_t n_pieces = n_docs + 2 * n_matches;
     if (n_pieces > (int64_t)INT32_MAX - 1) return api_set_error(HUTK_E_UNSUPPORTED, "hutk_encode_special_batch_device: too many pieces for one encode");
     const int64_t pieces_cap = hutk_ids_capacity(c, n_bytes, n_pieces);
     const int64_t n_blocks = (n_pieces + ST_BLOCK - 1) / ST_BLOCK;
-    HUTK_HIP_TRY(S.w_mstart.reserve((size_t)n_matches));
-    HUTK_HIP_TRY(S.w_poff.reserve((size_t)n_pieces + 1));
-    HUTK_HIP_TRY(S.w_pspecial.reserve((size_t)n_pieces));
-    HUTK_HIP_TRY(S.w_first.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(S.w_poo.reserve((size_t)n_pieces + 1));
-    HUTK_HIP_TRY(S.w_pstatus.reserve((size_t)n_pieces));
-    HUTK_HIP_TRY(S.w_pids.reserve((size_t)pieces_cap + 16));
-    HUTK_HIP_TRY(S.w_blk.reserve((size_t)n_blocks + 1));
-    HUTK_HIP_TRY(S.w_dst.reserve((size_t)n_pieces + 1));
-    A.m_start = S.w_mstart.p;
+    HUTK_HIP_TRY(W.w_mstart.reserve((size_t)n_matches));
+    HUTK_HIP_TRY(W.w_poff.reserve((size_t)n_pieces + 1));
+    HUTK_HIP_TRY(W.w_pspecial.reserve((size_t)n_pieces));
+    HUTK_HIP_TRY(W.w_first.reserve((size_t)n_docs + 1));
+    HUTK_HIP_TRY(W.w_poo.reserve((size_t)n_pieces + 1));
+    HUTK_HIP_TRY(W.w_pstatus.reserve((size_t)n_pieces));
+    HUTK_HIP_TRY(W.w_pids.reserve((size_t)pieces_cap + 16));
+    HUTK_HIP_TRY(W.w_blk.reserve((size_t)n_blocks + 1));
+    HUTK_HIP_TRY(W.w_dst.reserve((size_t)n_pieces + 1));
+    A.m_start = W.w_mstart.p;
     A.n_matches = n_matches;
     A.n_pieces = n_pieces;
-    A.piece_off = S.w_poff.p;
-    A.piece_special = S.w_pspecial.p;
-    A.first_piece = S.w_first.p;
-    A.piece_oo = S.w_poo.p;
-    A.piece_status = S.w_pstatus.p;
-    A.piece_ids = S.w_pids.p;
-    A.blk = S.w_blk.p;
-    A.dst = S.w_dst.p;
+    A.piece_off = W.w_poff.p;
+    A.piece_special = W.w_pspecial.p;
+    A.first_piece = W.w_first.p;
+    A.piece_oo = W.w_poo.p;
+    A.piece_status = W.w_pstatus.p;
+    A.piece_ids = W.w_pids.p;
+    A.blk = W.w_blk.p;
+    A.dst = W.w_dst.p;
     {
         StreamScope scope(c, hip_stream, false);
         if (scope.rc) return scope.rc;
@@ -829,7 +766,7 @@ int hutk::encode_special_impl(hutk_ctx* c, bool fallback, const uint8_t* d_bytes
         HUTK_HIP_TRY(hipGetLastError());
     }
     // the pieces, special ones included (a document's pieces are contiguous, a marker is a few ids), as documents of their own
-    if (int rc = encode(A.piece_off, n_pieces, S.w_pids.p, pieces_cap, S.w_poo.p, S.w_pstatus.p, A.err)) return rc;
+    if (int rc = encode(A.piece_off, n_pieces, W.w_pids.p, pieces_cap, W.w_poo.p, W.w_pstatus.p, A.err)) return rc;
     {
         StreamScope scope(c, hip_stream, false);
         if (scope.rc) return scope.rc;
@@ -860,30 +797,13 @@ int hutk_encode_special_batch(hutk_ctx* c, const uint8_t* bytes, const int64_t* 
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     const int64_t cap = hutk_special_ids_capacity(c, n_bytes, n_docs);
     if (ids_cap < cap - 1) return api_set_error(HUTK_E_CAPACITY, "ids_cap is below hutk_special_ids_capacity()");
-    HUTK_HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    HUTK_HIP_TRY(c->s_bytes.reserve((size_t)n_bytes + 16));
-    HUTK_HIP_TRY(c->s_offsets.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->s_ids.reserve((size_t)cap + 16));
-    HUTK_HIP_TRY(c->s_out_offsets.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->s_status.reserve((size_t)n_docs + 1));
-    HUTK_HIP_TRY(c->w_err.reserve(1));
-    if (c->busy_valid) HUTK_HIP_TRY(hipStreamWaitEvent(s, c->ev_busy, 0));  // (the staging buffers are the context's)
-    if (n_bytes) HUTK_HIP_TRY(hipMemcpyAsync(c->s_bytes.p, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
-    HUTK_HIP_TRY(hipMemcpyAsync(c->s_offsets.p, offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (int rc = hutk_encode_special_batch_device(c, c->s_bytes.p, c->s_offsets.p, n_docs, n_bytes, c->s_ids.p, cap,
-                                                  c->s_out_offsets.p, c->s_status.p, c->w_err.p, s))
-        return rc;
-    int32_t err = 0;
-    HUTK_HIP_TRY(hipMemcpyAsync(&err, c->w_err.p, 4, hipMemcpyDeviceToHost, s));
-    HUTK_HIP_TRY(hipMemcpyAsync(out_offsets, c->s_out_offsets.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (status && n_docs) HUTK_HIP_TRY(hipMemcpyAsync(status, c->s_status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
-    HUTK_HIP_TRY(hipStreamSynchronize(s));
-    if (err != HUTK_OK && err != HUTK_E_WORD_TOO_LARGE) return api_set_error(err, device_error_message(Direction::Encode, err));
-    const int64_t n_ids = out_offsets[n_docs];
-    if (n_ids < 0 || n_ids > ids_cap) return api_set_error(HUTK_E_DEVICE, "hutk_encode_special_batch: bad id count");
-    if (n_ids) HUTK_HIP_TRY(hipMemcpy(ids_out, c->s_ids.p, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
-    return err;  // HUTK_OK, or the note HUTK_E_WORD_TOO_LARGE (see status)
+    const auto device = [&](const uint8_t* d_bytes, const int64_t* d_offs, int32_t* d_ids, int64_t* d_oo, int32_t* d_status,
+                            int32_t* d_err, hipStream_t s) {
+        return hutk_encode_special_batch_device(c, d_bytes, d_offs, n_docs, n_bytes, d_ids, cap, d_oo, d_status, d_err, s);
+    };
+    const auto refuse = [](int err) { return api_set_error(err, device_error_message(Direction::Encode, err)), true; };
+    return encode_host_impl(c, "hutk_encode_special_batch", cap, device, refuse, bytes, offsets, n_docs, n_bytes, ids_out, ids_cap,
+                            out_offsets, status);
 }
 
 int hutk_decode_special_batch_device(hutk_ctx* c, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs,
@@ -893,32 +813,30 @@ int hutk_decode_special_batch_device(hutk_ctx* c, const int32_t* d_ids, const in
     if (flags & ~HUTK_DECODE_SKIP_SPECIAL) return api_set_error(HUTK_E_ARG, "hutk_decode_special_batch_device: unknown flags");
     if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to decode on");
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    const hutk_ctx::Specials& S = c->sx;
-    if (S.n == 0)  // no set: the plain decode
+    const DecExt::Host& X = c->sx.dec;
+    if (c->sx.n == 0)  // no set: the plain decode
         return decode_device_impl(c, c->dec, nullptr, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets,
                                   d_status, d_err, hip_stream);
     const bool skip = (flags & HUTK_DECODE_SKIP_SPECIAL) != 0;
-    const bool strip = c->dec.sent != nullptr;
-    DecTables T{};
-    T.ent = skip ? S.dx_ent_skip.p : S.dx_ent.p;
-    T.sent = !strip ? nullptr : skip ? S.dx_sent_skip.p : S.dx_sent.p;
-    T.blob = S.dx_blob.p;
-    T.n = c->dec.n + S.x_n;
     DecSpecial P{};
-    P.slots = S.dx_slots.p;
-    P.id_min = S.x_min;
-    P.id_max = S.x_max;
+    P.slots = c->sxd.dec.dx_slots.p;
+    P.id_min = X.id_min;
+    P.id_max = X.id_max;
     P.n_vocab = (int32_t)c->dec.n;
-    P.bits = !strip ? DSP_BITS_NONE : skip ? DSP_BITS_SKIP : DSP_BITS_AFTER;
-    return decode_device_impl(c, T, &P, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap, d_out_offsets, d_status,
-                              d_err, hip_stream);
+    P.bits = !X.strip ? DSP_BITS_NONE : skip ? DSP_BITS_SKIP : DSP_BITS_AFTER;
+    return decode_device_impl(c, c->sxd.dec.tables(skip), &P, d_ids, d_id_offsets, n_docs, n_ids, d_bytes_out, bytes_cap,
+                              d_out_offsets, d_status, d_err, hip_stream);
 }
 
 int hutk_decode_special_batch(hutk_ctx* c, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
                               uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status) {
     if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
     if (flags & ~HUTK_DECODE_SKIP_SPECIAL) return api_set_error(HUTK_E_ARG, "hutk_decode_special_batch: unknown flags");
-    return decode_host_impl(c, flags, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
+    const auto device = [&](const int32_t* d_ids, const int64_t* d_offs, int64_t n_ids, uint8_t* d_bytes, int64_t* d_oo,
+                            int32_t* d_status, int32_t* d_err, hipStream_t s) {
+        return hutk_decode_special_batch_device(c, d_ids, d_offs, n_docs, n_ids, flags, d_bytes, bytes_cap, d_oo, d_status, d_err, s);
+    };
+    return decode_host_impl(c, device, ids, id_offsets, n_docs, bytes_out, bytes_cap, out_offsets, status);
 }
 
 }  // extern "C"

@@ -286,11 +286,12 @@ def _dev_decode(ctx, ids, offs, flags, shift=0, cap_delta=0, sizes_only=False):
     return raw[shift:shift + max(cap, 0)], raw[shift + max(cap, 0):], oo.cpu().numpy(), st.cpu().numpy()[:n], int(err.item()), rc
 
 
-def _check_decode(ctx, tokens, ids, offs, table, specials, tag):
+def _check_decode(ctx, tokens, ids, offs, table, specials, tag, all_flags=False):
+    """all_flags: the special flags are checked without a set too (they then change nothing)."""
     ids = np.asarray(ids, dtype=np.int32)
     offs = np.asarray(offs, dtype=np.int64)
     for flags, sp, skip in ((0, None, False), (FB_SPECIAL, specials, False), (FB_SPECIAL | FB_SKIP, specials, True)):
-        if flags and not specials:
+        if flags and not specials and not all_flags:
             continue
         want, woo, wst = F.decode_packed(tokens, ids, offs, table, sp, skip)
         if wst.any():
@@ -353,6 +354,134 @@ def test_decode(tmp_path, oracle_mod, lines):
     with pytest.raises(ValueError, match="both"):
         ctx.encode_fallback_packed(d, o, FB_SPECIAL)
     assert _dev_encode(ctx, d, o, FB_SPECIAL)[5] == E_VALUE and _dev_encode(ctx, d, o, 0)[5] == 0
+    ctx.close()
+
+
+FLAG_FORMS = ((0, False), (FB_SPECIAL, False), (FB_SPECIAL | FB_SKIP, True))
+ORDER_LENS = [REMAP_TILE - 1, 1, REMAP_TILE + 1, TILE - 1, 0, TILE + 5]  # both passes' tile edges inside documents
+
+
+def _order_batches(seed, ents, table, eot, bos, pre):
+    """The twelve documents of test_decode and one long batch, for a table and two ids that are special where a set is
+    installed -> [(tag, ids, offsets)]"""
+    fb = lambda s: [int(table[b]) for b in s.encode("utf-8")]
+    docs = [fb("é") + [pre, pre], [pre] + fb("漢"), fb("ő"), [pre, pre], [], fb("😂") + [eot] + fb("a") + [pre], [bos, pre, eot, pre] + fb("ű"),
+            [bos] + fb("é") + [pre], [eot, bos, pre], [bos, eot], [pre] + fb("é") + [eot, bos, pre, pre], []]
+    rng = random.Random(seed)
+    pool = [i for _k, i in ents[256:]] + [int(t) for t in table] * 2 + [eot, bos] * 20
+    out = []
+    for tag, rows in (("by hand", docs), ("long", [[rng.choice(pool) for _ in range(n)] for n in ORDER_LENS])):
+        offs = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in rows], out=offs[1:])
+        out.append((tag, np.asarray([i for x in rows for i in x], dtype=np.int32), offs))
+    return out
+
+
+def _order_expected(tokens, batches, table, specials):
+    """What the reference gives for the batches with this table and this set (None: none) installed, every flag form."""
+    return [(raw.tobytes(), oo.tolist())
+            for _tag, ids, offs in batches for flags, skip in FLAG_FORMS
+            for raw, oo, _st in [F.decode_packed(tokens, ids, offs, table, specials if flags else None, skip)]]
+
+
+def order_plan(ents, special, prefix, is_byte):
+    """The states test_decode_tables_through_every_order_of_installation walks a context through, from the references
+    alone -> (tokens of fallback_ref, DecodeRef, states); a state is a dict of name, table, specials (None: no set), batches
+    (for the fallback decode) and special_batches (ids of vocabulary lines only: for the special decode).  Asserts what
+    catches a stale table: with the tables of the state before it, some document of a state would decode otherwise."""
+    ref = DR.DecodeRef(ents, special, prefix, is_byte)
+    tokens = F.from_decode_ref(ref)
+    by_key = {k: i for k, i in ents}
+    if all(("<0x%02X>" % b).encode() in by_key for b in range(256)):
+        lines = np.array([by_key[("<0x%02X>" % b).encode()] for b in range(256)], dtype=np.int32)
+    else:  # (no such lines: the last 256 lines, whatever their text)
+        lines = np.arange(len(ents) - 256, len(ents), dtype=np.int32)
+    other = np.arange(100000, 100256, dtype=np.int32)
+    free = [i for k, i in ents[256:] if i not in set(lines.tolist())]  # lines that are in no table
+    pre = next((i for k, i in ents if i in free and prefix and k.decode().startswith(prefix) and len(k.decode()) > 1), free[5])
+    line_a, line_b, o1, o2 = free[10], free[11], free[12], free[13]
+    assert len({pre, line_a, line_b, o1, o2}) == 5
+    n = len(ents)
+    set_a = [(b"<|eot|>", n + 5), (b"<|im_start|>", line_a)]  # 7 bytes: inline; 12: in the blob
+    set_b = [(b"<b>", n + 9), (b"<|extends-the-blob|>", line_b), (b"<never-decoded>", n + 9)]  # two strings, one id
+    states = []
+    for k, (name, table, specials, eot, bos) in enumerate((
+            ("1 table only", lines, None, o1, o2), ("2 plus set A", lines, set_a, n + 5, line_a),
+            ("3 set B for set A", lines, set_b, n + 9, line_b), ("4 a refused set", lines, set_b, n + 9, line_b),
+            ("5 set removed", lines, None, line_b, o2), ("6 set A, then the table", lines, set_a, n + 5, line_a),
+            ("7 another table", other, set_a, n + 5, line_a))):
+        seed = 3 if k == 3 else k  # (state 4 asks state 3's questions again)
+        states.append(dict(name=name, table=table, specials=specials, batches=_order_batches(seed, ents, table, eot, bos, pre),
+                           special_batches=_order_batches(seed, ents, lines, eot, bos, pre)))
+    for prev, cur in zip(states, states[1:]):
+        mine = _order_expected(tokens, cur["batches"], cur["table"], cur["specials"])
+        stale = _order_expected(tokens, cur["batches"], prev["table"], prev["specials"])
+        assert (mine == stale) == (cur["name"][0] == "4"), "stale tables would go unnoticed: " + cur["name"]
+    return tokens, ref, states
+
+
+def _check_decode_special(ctx, ref, state):
+    import decode_special_ref as DSR
+    for tag, ids, offs in state["special_batches"]:
+        for flags, skip in ((0, False), (1, True)):  # HUTK_DECODE_SKIP_SPECIAL
+            want, woo = DSR.decode_packed(ref, ids, offs, state["specials"], skip)
+            assert not DSR.status(ref, ids, offs, state["specials"]).any()
+            got, goo, gst = ctx.decode_special_packed(ids, offs, flags)
+            assert np.array_equal(goo, woo) and got.tobytes() == want.tobytes() and not gst.any(), (state["name"], tag, flags)
+
+
+def _check_order_encode(ctx, orc, is_byte, state):
+    texts = ["<|eot|>😂<|im_start|>", "😂<|eot|>漢", "<|im_start|>", "", "a<|eot|>b", "<|im_start|><|eot|>é"]
+    d, o = _pack([t.encode("utf-8") for t in texts])
+    want, woo, wst = F.encode_special(orc, S.TokenText(orc), d, o, dict(state["specials"]), is_byte, state["table"])
+    got, goo, gst, rc = ctx.encode_fallback_packed(d, o, FB_SPECIAL)
+    assert rc == 0 and np.array_equal(goo, woo) and np.array_equal(gst, wst) and np.array_equal(got, want), state["name"]
+    assert (want >= 0).all() and np.isin([i for _s, i in state["specials"]], want).all(), state["name"]
+
+
+def order_vocab(kind):
+    """-> (entries, special, prefix, is_byte_encoder) of the two vocabularies of the test below"""
+    if kind == "char":
+        return (*H.random_char_vocab(5, n_merges=400, drop_chars="őű漢"), "▁", False)
+    return (*H.random_byte_vocab(3, n_merges=300), None, True)
+
+
+@pytest.mark.parametrize("kind", ["char", "byte"])
+def test_decode_tables_through_every_order_of_installation(tmp_path, oracle_mod, kind):
+    """One context through: table; + set A; set B for A; a refused set; no set; no table, set A, the table again; another
+    table.  The decode tables of the set and of the table are rebuilt from one another at every step; in every state both
+    decodes must give what the references give, and order_plan has checked that the tables of the state before would not."""
+    from hutoken_amd import _capi
+    ents, special, prefix, is_byte = order_vocab(kind)
+    vp, spath = H.write_vocab(tmp_path, "order_" + kind, ents, special)
+    ctx, orc = _capi.Context(vp, spath, prefix, is_byte, device=0), oracle_mod.Oracle(vp, spath, prefix, is_byte)
+    tokens, ref, states = order_plan(ents, special, prefix, is_byte)
+
+    def check(state):
+        for tag, ids, offs in state["batches"]:
+            _check_decode(ctx, tokens, ids, offs, state["table"], state["specials"], state["name"] + ", " + tag, all_flags=True)
+        if state["specials"]:
+            _check_decode_special(ctx, ref, state)
+    ctx.set_byte_fallback(states[0]["table"])
+    check(states[0])
+    ctx.set_special_tokens(states[1]["specials"])
+    check(states[1])
+    _check_order_encode(ctx, orc, is_byte, states[1])
+    ctx.set_special_tokens(states[2]["specials"])
+    check(states[2])
+    with pytest.raises(ValueError, match="equal"):
+        ctx.set_special_tokens([(b"<x>", 1), (b"<y>", 2), (b"<x>", 3)])
+    check(states[3])
+    ctx.set_special_tokens([])
+    check(states[4])
+    ctx.set_byte_fallback(None)
+    ctx.set_special_tokens(states[5]["specials"])
+    _check_decode_special(ctx, ref, states[5])
+    ctx.set_byte_fallback(states[5]["table"])
+    check(states[5])
+    _check_order_encode(ctx, orc, is_byte, states[5])
+    ctx.set_byte_fallback(states[6]["table"])
+    check(states[6])
     ctx.close()
 
 

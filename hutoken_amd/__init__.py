@@ -48,6 +48,7 @@ import sys
 import traceback
 
 from . import _capi
+from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
@@ -56,7 +57,7 @@ __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_pack
            "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device",
            "decode_special", "batch_decode_special", "decode_packed_device",
            "set_byte_fallback", "encode_fallback", "batch_encode_fallback", "encode_fallback_packed_device",
-           "decode_fallback", "batch_decode_fallback"]
+           "decode_fallback", "batch_decode_fallback", "normalize_packed_device", "normalize"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -767,39 +768,47 @@ def _on_torch_stream(dev, fn, used=()):
         return res
 
 
-def _encode_texts(kind, texts, flags=0, with_text=False):
+def _encode_texts(kind, texts, flags=0, with_text=False, normalize=None):
     """list of str -> (ids, out_offsets) of _encode_device(kind, ..., flags) on the context's device; with_text: and the
-    packed text they were made from, (ids, out_offsets, d_bytes, d_offs).  The caller has checked texts and the context."""
+    packed text they were made from, (ids, out_offsets, d_bytes, d_offs).  The caller has checked texts and the context.
+    normalize: a normal form ("NFC" ..) the packed text is put into on the GPU between upload and encode
+    (normalize_packed_device: ids, spans and with_text are then those of the normalised text); None: the text as it is."""
     import torch
+    _normalize_arg(normalize)
     data, offs = _pack(texts)
     dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
     d_bytes = torch.from_numpy(data.copy()).to(dev)  # (a copy: _pack's array is a read-only view of a bytes object)
     d_offs = torch.from_numpy(offs).to(dev)
+    if normalize is not None:
+        with torch.cuda.device(dev):
+            d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, normalize)
     ids, oo = _on_torch_stream(dev, lambda: _encode_device(kind, d_bytes, d_offs, flags, True))
     return (ids, oo, d_bytes, d_offs) if with_text else (ids, oo)
 
 
-def _texts_to_device(texts, with_text=False):
+def _texts_to_device(texts, with_text=False, normalize=None):
     """list of str -> (ids, out_offsets) of encode_packed_device on the context's device; with_text: and the packed
-    text they were made from, (ids, out_offsets, d_bytes, d_offs)."""
+    text they were made from, (ids, out_offsets, d_bytes, d_offs).  normalize: see _encode_texts."""
+    _normalize_arg(normalize)
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
     if not isinstance(texts, list):
         raise TypeError("Invalid arguments. Expected a list of strings.")
-    return _encode_texts("plain", texts, 0, with_text)
+    return _encode_texts("plain", texts, 0, with_text, normalize)
 
 
-def batch_encode_padded(texts, max_length=None, **collate_kwargs):
+def batch_encode_padded(texts, max_length=None, *, normalize=None, **collate_kwargs):
     """A list of str -> collate_padded's (input_ids, attention_mask, lengths): encode_packed_device, then
-    collate_padded with `collate_kwargs`, both on the initialised context's GPU."""
-    ids, oo = _texts_to_device(texts)
+    collate_padded with `collate_kwargs`, both on the initialised context's GPU.  normalize="NFC" (.. "NFKD"): the
+    texts are normalised on the GPU first (normalize_packed_device); None: they are encoded as they are."""
+    ids, oo = _texts_to_device(texts, normalize=normalize)
     return collate_padded(ids, oo, max_length, **collate_kwargs)
 
 
-def batch_encode_windows(texts, max_length, stride=0, **collate_kwargs):
+def batch_encode_windows(texts, max_length, stride=0, *, normalize=None, **collate_kwargs):
     """A list of str -> collate_windows' (input_ids, attention_mask, lengths, row_map): encode_packed_device, then
-    collate_windows with `collate_kwargs`, both on the initialised context's GPU."""
-    ids, oo = _texts_to_device(texts)
+    collate_windows with `collate_kwargs`, both on the initialised context's GPU.  normalize: as batch_encode_padded."""
+    ids, oo = _texts_to_device(texts, normalize=normalize)
     return collate_windows(ids, oo, max_length, stride, **collate_kwargs)
 
 
@@ -856,9 +865,10 @@ class SequencePacker:
             _raise_device_error(err, "SequencePacker.add")
         return out
 
-    def add_texts(self, texts):
-        """A list of str: encoded with the initialised context (encode_packed_device), then add()."""
-        ids, oo = _texts_to_device(texts)
+    def add_texts(self, texts, normalize=None):
+        """A list of str: encoded with the initialised context (encode_packed_device), then add().  normalize: as
+        batch_encode_padded."""
+        ids, oo = _texts_to_device(texts, normalize=normalize)
         return self.add(ids, oo)
 
     def flush(self):
@@ -1012,18 +1022,20 @@ def encode_special_packed_device(d_bytes, d_offsets, check=True):
     return _encode_device("special", d_bytes, d_offsets, 0, check)
 
 
-def _special_texts_to_device(texts):
+def _special_texts_to_device(texts, normalize=None):
     """_texts_to_device for the special-token encode."""
+    _normalize_arg(normalize)
     if not isinstance(texts, list):
         raise TypeError("Invalid arguments. Expected a list of strings.")
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
-    return _encode_texts("special", texts)
+    return _encode_texts("special", texts, normalize=normalize)
 
 
-def batch_encode_special(texts):
-    """batch_encode with the special tokens of set_special_tokens -> list[list[int]]."""
-    ids, oo = _special_texts_to_device(texts)
+def batch_encode_special(texts, normalize=None):
+    """batch_encode with the special tokens of set_special_tokens -> list[list[int]].  normalize: as
+    batch_encode_padded (the special strings are matched in the normalised text)."""
+    ids, oo = _special_texts_to_device(texts, normalize)
     return _rows(ids, oo, len(texts))
 
 
@@ -1180,19 +1192,21 @@ def encode_fallback_packed_device(d_bytes, d_offsets, special=False, check=True)
     return _encode_device("fallback", d_bytes, d_offsets, _special_arg(special), check)
 
 
-def _fallback_texts_to_device(texts, special):
+def _fallback_texts_to_device(texts, special, normalize=None):
     """_texts_to_device for the fallback encode."""
+    _normalize_arg(normalize)
     if not isinstance(texts, list):
         raise TypeError("Invalid arguments. Expected a list of strings.")
     flags = _special_arg(special)
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
-    return _encode_texts("fallback", texts, flags)
+    return _encode_texts("fallback", texts, flags, normalize=normalize)
 
 
-def batch_encode_fallback(texts, special=False):
-    """batch_encode with the table of set_byte_fallback -> list[list[int]]; special=True: and the special tokens."""
-    ids, oo = _fallback_texts_to_device(texts, special)
+def batch_encode_fallback(texts, special=False, normalize=None):
+    """batch_encode with the table of set_byte_fallback -> list[list[int]]; special=True: and the special tokens.
+    normalize: as batch_encode_padded."""
+    ids, oo = _fallback_texts_to_device(texts, special, normalize)
     return _rows(ids, oo, len(texts))
 
 
@@ -1223,3 +1237,123 @@ def batch_decode_fallback(tokens, special=False, skip_special_tokens=False):
     """batch_decode with the table of set_byte_fallback -> list[str]; see decode_fallback."""
     flags = _fallback_decode_flags(special, skip_special_tokens)
     return _rewrapped(tokens, True, _decode_lists, "decode_fallback_packed", tokens, True, flags)
+
+
+# ---- Unicode normalisation (hutk_normalize.hip, DESIGN.md section 8e) ----
+_normalizers = {}
+
+
+def _normalize_arg(form):
+    """normalize= of the list-form entry points: None or one of the four forms (TypeError / ValueError otherwise)."""
+    if form is not None:
+        _norm_tables.form_index(form)
+    return form
+
+
+def _normalizer(dev):
+    """The normaliser of a torch device: its tables are built once per process and uploaded once per device."""
+    nz = _normalizers.get(dev.index)
+    if nz is None:
+        nz = _normalizers[dev.index] = _capi.Normalizer(_norm_tables.table_blob(), dev.index)
+    return nz
+
+
+def _packed_text_args(d_bytes, d_offsets):
+    """The (bytes, offsets) pair of encode_packed_device: device tensors, uint8 and int64[n_docs + 1]."""
+    for name, t, want in (("d_bytes", d_bytes, "uint8"), ("d_offsets", d_offsets, "int64")):
+        if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")):
+            raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+        if str(t.dtype).rpartition(".")[2] != want:
+            raise TypeError("%s must have dtype %s, not %s" % (name, want, t.dtype))
+    for name, t in (("d_bytes", d_bytes), ("d_offsets", d_offsets)):
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be one-dimensional and contiguous" % name)
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU: the normalisation runs there and nowhere else" % name)
+    if d_offsets.numel() < 1:
+        raise ValueError("d_offsets must hold at least one entry")
+    if d_bytes.device != d_offsets.device:
+        raise ValueError("d_bytes and d_offsets must be on the same device")
+
+
+def normalize_packed_device(d_bytes, d_offsets, form="NFC", *, n_out=None, copy=False, return_changed=False, check=False):
+    """Unicode normalisation of a packed batch on the GPU, in front of the encoders: device tensors in (uint8 bytes,
+    int64 offsets[n+1], as encode_packed_device takes them), the same pair out -- (bytes uint8[n_out], offsets
+    int64[n+1]), and `changed` uint8[n] (document i differs from its input) with return_changed=True.  Document by
+    document the result is d.decode("utf-8", "surrogateescape") -> unicodedata.normalize(form, .) ->
+    .encode("utf-8", "surrogateescape"): exact at any length, ill-formed bytes are copied and never reached across, a
+    0x00 byte is a character like any other, documents are independent.  form: "NFC", "NFD", "NFKC" or "NFKD".
+
+    Runs on the current torch stream: a sizes call, one synchronising read of the two totals (and the error word), a
+    write call.  When no document changed and copy is False the write call is skipped and the INPUT tensors are
+    returned.  n_out= (the output's size, known from an earlier call) avoids the synchronisation: both calls are
+    enqueued and the text is always written; check=True then synchronises and raises on a device-side error, a wrong
+    n_out included.  Offsets that do not describe d_bytes raise ValueError (with n_out=: only under check=True).
+
+    Needs no initialised context and touches no vocabulary.  Token spans and offsets computed from the result are
+    over the normalised text; nothing maps them back to the original bytes."""
+    fi = _norm_tables.form_index(form)
+    _packed_text_args(d_bytes, d_offsets)
+    if n_out is not None and (isinstance(n_out, bool) or not isinstance(n_out, int)):
+        raise TypeError("n_out must be an int or None")
+    if n_out is not None and n_out < 0:
+        raise ValueError("n_out must not be negative")
+    import torch
+    dev = d_bytes.device
+    nz = _normalizer(dev)
+    n_docs, n_bytes = d_offsets.numel() - 1, d_bytes.numel()
+    with torch.cuda.device(dev):
+        oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        changed = torch.empty(max(n_docs, 1), dtype=torch.uint8, device=dev)
+        small = torch.zeros(4, dtype=torch.int64, device=dev)  # the two totals; the error words of the two calls
+        totals, err = small.data_ptr(), small.data_ptr() + 16
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        text = (fi, d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes)
+        nz.batch_device(*text, 0, 0, oo.data_ptr(), changed.data_ptr(), totals, err, stream)
+        if n_out is None:
+            total, n_changed, code, _ = small.tolist()  # the one synchronisation
+            _raise_normalize_error(code & 0xFFFFFFFF, n_out, total)
+            if n_changed == 0 and not copy:
+                return (d_bytes, d_offsets, changed[:n_docs]) if return_changed else (d_bytes, d_offsets)
+            cap = total
+        else:
+            cap = n_out
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        nz.batch_device(*text, out.data_ptr(), cap, 0, 0, 0, err + 8, stream)
+        if check:
+            total, _n, code, code2 = small.tolist()
+            _raise_normalize_error((code & 0xFFFFFFFF) or (code2 & 0xFFFFFFFF), n_out, total)
+    out = out[:cap]
+    return (out, oo, changed[:n_docs]) if return_changed else (out, oo)
+
+
+def _raise_normalize_error(code, n_out, total):
+    if code == _capi.E_CAPACITY:
+        raise ValueError("hutoken_amd: normalize_packed_device: n_out = %d is below the %d bytes of the result" % (n_out, total))
+    if code:
+        raise ValueError("hutoken_amd: normalize_packed_device: device-side error %d (offsets that do not describe d_bytes)" % code)
+    if n_out is not None and n_out != total:
+        raise ValueError("hutoken_amd: normalize_packed_device: n_out = %d, the result has %d bytes" % (n_out, total))
+
+
+def normalize(texts, form="NFC"):
+    """A list of str -> the list of their normal forms ("NFC", "NFD", "NFKC", "NFKD"), computed on the current GPU
+    (normalize_packed_device; no context is needed).  Equals [unicodedata.normalize(form, t) for t in texts]; lone
+    surrogates U+DC80..U+DCFF pass through as the bytes they escape."""
+    import numpy as np
+    import torch
+    _norm_tables.form_index(form)
+    if not isinstance(texts, list):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    try:
+        chunks = [t.encode("utf-8", "surrogateescape") for t in texts]
+    except AttributeError:
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    offs = np.zeros(len(chunks) + 1, dtype=np.int64)
+    if chunks:
+        np.cumsum(np.fromiter(map(len, chunks), dtype=np.int64, count=len(chunks)), out=offs[1:])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d_bytes = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()).to(dev)
+    out, oo = normalize_packed_device(d_bytes, torch.from_numpy(offs).to(dev), form)
+    raw, bounds = out.cpu().numpy().tobytes(), oo.tolist()
+    return [raw[bounds[i]:bounds[i + 1]].decode("utf-8", "surrogateescape") for i in range(len(chunks))]

@@ -93,6 +93,12 @@ SIGNATURES = {
     "hutk_windows_rows_device": (_i32, [_vp, _i64, _i64, _i64, _i64, _s32, _s32, _vp, _vp, _vp]),
     "hutk_collate_windows_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _s32, _s32, _s32, _i32, _i32,
                                            _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_normalizer_create": (_i32, [_pvp, _i32, _vp, _i64]),
+    "hutk_normalizer_destroy": (None, [_vp]),
+    "hutk_normalizer_info": (_i32, [_vp, _vp]),
+    "hutk_normalize_batch_device": (_i32, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_normalize_batch": (_i32, [_vp, _i32, _vp, _vp, _i64, _pvp, _pvp]),
+    "hutk_debug_norm_chunk_bytes": (_i32, []),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -101,6 +107,7 @@ NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
 SPANS_BYTES, SPANS_CHARS = 0, 1
 DECODE_SKIP_SPECIAL = 1  # HUTK_DECODE_SKIP_SPECIAL
 FB_SPECIAL, FB_SKIP_SPECIAL = 1, 2  # HUTK_FB_*
+NFC, NFD, NFKC, NFKD = 0, 1, 2, 3  # HUTK_NFC ..
 
 _lib = None
 
@@ -703,3 +710,63 @@ class Packer(_Owner):
         raise_for(load().hutk_packer_flush_device(self._h, d_input_ids or None, d_position_ids or None,
                                                   d_segment_ids or None, C.byref(n), stream or None))
         return n.value
+
+
+NORMALIZER_INFO = ["format_version", "unidata", "blob_bytes", "chunk_bytes", "pairs", "decomposition_words", "lead_bytes",
+                   "max_expansion"]
+
+
+class Normalizer(_Owner):
+    """Owns one hutk_normalizer (Unicode normalisation on the GPU, include/hutoken_amd.h): the table blob of
+    hutoken_amd.normalize on one device, and the workspace of its calls."""
+    _destroy = "hutk_normalizer_destroy"
+
+    def __init__(self, blob, device=-1):
+        h = C.c_void_p()
+        buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0")
+        raise_for(load().hutk_normalizer_create(C.byref(h), int(device), C.cast(buf, C.c_void_p), len(blob)))
+        self._h = h
+
+    def info(self):
+        import numpy as np
+        out = np.zeros(8, dtype=np.int64)
+        raise_for(load().hutk_normalizer_info(self._h, out.ctypes.data))
+        d = dict(zip(NORMALIZER_INFO, out.tolist()))
+        for k in ("lead_bytes", "max_expansion"):
+            d[k] = [(d[k] >> (8 * f)) & 0xFF for f in range(4)]
+        return d
+
+    def batch_device(self, form, d_bytes, d_offsets, n_docs, n_bytes, d_out, out_cap, d_out_offsets, d_changed=0,
+                     d_totals=0, d_err=0, stream=0):
+        """hutk_normalize_batch_device on raw device pointers (ints); d_out == 0: the sizes call.  Asynchronous on
+        `stream`, never synchronises."""
+        raise_for(load().hutk_normalize_batch_device(self._h, form, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                     d_out or None, out_cap, d_out_offsets or None, d_changed or None,
+                                                     d_totals or None, d_err or None, stream or None))
+
+    def batch(self, form, data, offsets):
+        """Host numpy buffers in and out (hutk_normalize_batch): -> (bytes uint8, out_offsets int64[n + 1])."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if n < 0:
+            raise TypeError("offsets must hold at least one entry")
+        if int(offsets[n]) > len(data):
+            raise TypeError("offsets point outside data")
+        L = load()
+        out, oo = C.c_void_p(), C.c_void_p()
+        raise_for(L.hutk_normalize_batch(self._h, form, data.ctypes.data if len(data) else None, offsets.ctypes.data, n,
+                                         C.byref(out), C.byref(oo)))
+        try:
+            r_oo = np.frombuffer((C.c_int64 * (n + 1)).from_address(oo.value), dtype=np.int64).copy()
+            total = int(r_oo[n])
+            r_out = np.frombuffer((C.c_uint8 * max(total, 1)).from_address(out.value), dtype=np.uint8)[:total].copy()
+        finally:
+            L.hutk_host_free(out)
+            L.hutk_host_free(oo)
+        return r_out, r_oo
+
+
+def norm_chunk_bytes():
+    return load().hutk_debug_norm_chunk_bytes()

@@ -53,6 +53,25 @@ def is_byte_level(tok):
     return bool(js) and (_has_bytelevel(js.get("pre_tokenizer")) or _has_bytelevel(js.get("decoder")))
 
 
+_NORMAL_FORMS = ("NFC", "NFD", "NFKC", "NFKD")
+
+
+def normalizer_form(tok):
+    """"NFC", "NFD", "NFKC" or "NFKD" when the backend's normalizer is exactly that node, or a Sequence in which it is
+    the only member of these four kinds (its other members -- Replace, Prepend, Strip .. -- are not looked at); None
+    otherwise (no normalizer, another one, several forms).  Reported by export(), not acted on: pass it as normalize=
+    where the text is encoded."""
+    js = _backend_json(tok)
+    node = js.get("normalizer") if js else None
+    if not isinstance(node, dict):
+        return None
+    members = node.get("normalizers") if node.get("type") == "Sequence" else [node]
+    if not isinstance(members, list):
+        return None
+    forms = [m.get("type") for m in members if isinstance(m, dict) and m.get("type") in _NORMAL_FORMS]
+    return forms[0] if len(forms) == 1 else None
+
+
 def _merges_text(tok):
     js = _backend_json(tok)
     if not js:
@@ -139,7 +158,8 @@ def _written(path, what, write):
 def export(reference, **options):
     """Convert a Hugging Face tokenizer into huToken's files (what hutoken.py:44-107 does inline).
 
-    Returns dict(vocab_file, special_chars_file, prefix, is_byte_encoder, merges_file_path, tokenizer)."""
+    Returns dict(vocab_file, special_chars_file, prefix, is_byte_encoder, merges_file_path, tokenizer, normalizer);
+    normalizer: the Unicode normal form the tokenizer applies (normalizer_form), for normalize= of the encode calls."""
     tok = _load(reference)
     folder, stem = _target(reference)
     tok.save_pretrained(folder)
@@ -154,4 +174,5 @@ def export(reference, **options):
     return dict(vocab_file=vocab_path, special_chars_file=special_path,
                 prefix=None if first_piece == "hu" else first_piece[0],
                 is_byte_encoder=1 if byte_level else options.get("is_byte_encoder", 0),
-                merges_file_path=_merges_file(tok, folder, reference), tokenizer=tok)
+                merges_file_path=_merges_file(tok, folder, reference), tokenizer=tok,
+                normalizer=normalizer_form(tok))

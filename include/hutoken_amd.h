@@ -602,6 +602,66 @@ int hutk_decode_fallback_batch_device(hutk_ctx* ctx, const int32_t* d_ids, const
 int hutk_decode_fallback_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, int flags,
                                uint8_t* bytes_out, int64_t bytes_cap, int64_t* out_offsets, int32_t* status);
 
+/* ---- Unicode normalisation --------------------------------------------------------------------------------
+ * NFC, NFD, NFKC, NFKD of a packed batch in front of the encoders (hutk_normalize.hip): the pair
+ * (uint8 bytes, int64 offsets[n_docs + 1]) in, the same pair out, so every *_batch_device call takes the result as it
+ * is.  The reference has no counterpart (it encodes the bytes it is given).  For form F the output document is
+ *     d.decode("utf-8", "surrogateescape") -> unicodedata.normalize(F, .) -> .encode("utf-8", "surrogateescape")
+ * with the Unicode data of the tables' builder: exact at any length; documents are independent (a mark at the start
+ * of a document never combines with the document before); every byte that strict UTF-8 rejects (a lone continuation
+ * byte, an overlong form, an encoded surrogate, a value above U+10FFFF, a sequence the document's end cuts short) is
+ * copied unchanged and normalisation never reaches across it; U+0000 is a character like any other.  Spans and
+ * offsets computed afterwards are over the normalised text: nothing maps them back to the original bytes.
+ *
+ * A normaliser owns the tables on one device and a workspace; it needs no hutk_ctx and no vocabulary.  The tables are
+ * one blob for all four forms, built by hutoken_amd/normalize.py from Python's unicodedata and written to a file by
+ * `python -m hutoken_amd.normalize --write FILE`.  Format (little-endian 32-bit words; offsets in bytes from the
+ * blob's start, multiples of 4):
+ *   header, 32 words: 0 magic 0x4D524E48 ("HNRM")  1 format version (1)  2 Unicode version major << 16 | minor << 8 | patch
+ *     3 size of the blob  4, 5 stage one: offset, entries (uint16[0x110000 >> 7]: block of code point c = stage1[c >> 7])
+ *     6, 7 property blocks: offset, blocks (128 code points a block, two words a code point:
+ *          word 0: bits 0..7 ccc | bit 8 + form: quick check "Yes" | bit 12: can be the second of a composite pair |
+ *                  bits 16..23 / 24..31: ccc of the first character of the full canonical / compatibility decomposition;
+ *          word 1: bits 0..15 / 16..31: word index of the canonical / compatibility decomposition, 0: none)
+ *     8, 9 decompositions: offset, words (an entry: its length 1..18, then that many words code point | second << 21 |
+ *          ccc << 24, fully expanded)   10, 11 composite pairs: offset, slots (a power of two of four-word slots
+ *          {first, second, composite, 0}, first == 0xFFFFFFFF: empty; linear probing from the hash of the pair)
+ *     12 pairs  13 block shift (7)  16..19 per form: the first lead byte that can start an unstable character
+ *     20..23 per form: the largest output / input byte ratio of one character  24..27 per form: first unstable code point
+ *   Hangul is composed and decomposed by arithmetic.  hutk_normalizer_create checks the magic, the version, every
+ *   offset, index and length before anything reads through the blob: HUTK_E_VALUE with a message otherwise.
+ * hutk_normalizer_info: out8 = format version, Unicode version word, blob bytes, chunk bytes, pairs, decomposition
+ * words, the four lead bytes (one byte each, NFC lowest), the four ratios (likewise).
+ *
+ * hutk_normalize_batch_device: two calls, like the decode direction, asynchronous on hip_stream, neither synchronises.
+ *   sizes call (d_out == NULL): d_out_offsets[n_docs + 1], d_changed[i] = the output of document i differs from its
+ *     input (uint8[n_docs], may be NULL), d_totals[0] = output bytes, d_totals[1] = documents changed.
+ *   write call (d_out, out_cap >= d_totals[0]): the text.  It uses the per-chunk state that the sizes call of the same
+ *     batch (same form, pointers and sizes) left in the normaliser's workspace, so that call comes right before it;
+ *     d_out_offsets, d_changed and d_totals may then be NULL and are left alone.  Without such a sizes call it runs
+ *     the sizes stage itself first (d_out_offsets and d_totals are then required).
+ * Work is cut into chunks of hutk_debug_norm_chunk_bytes() bytes of packed text; a chunk without a byte at or above the
+ * form's first unstable lead byte is copied without a table access.  d_err (may be NULL) takes the first device-side
+ * error: HUTK_E_ARG for offsets that do not rise from 0 to n_bytes (nothing else is then computed), HUTK_E_CAPACITY for an
+ * out_cap below the total (nothing is written).  An unknown form, negative sizes, a missing buffer: HUTK_E_ARG at once;
+ * no GPU: HUTK_E_DEVICE.  Calls on one normaliser are serialised (a mutex on the host, an event on the device).
+ * hutk_normalize_batch: host arrays in; the work is done on the GPU; *out (offsets[n_docs] bytes of output at
+ * (*out_offsets)[n_docs]) and *out_offsets (n_docs + 1 entries) are allocated here and given back with hutk_host_free. */
+#define HUTK_NFC 0
+#define HUTK_NFD 1
+#define HUTK_NFKC 2
+#define HUTK_NFKD 3
+typedef struct hutk_normalizer hutk_normalizer;
+int hutk_normalizer_create(hutk_normalizer** out, int device, const uint8_t* blob, int64_t n_blob_bytes);
+void hutk_normalizer_destroy(hutk_normalizer* h);
+int hutk_normalizer_info(const hutk_normalizer* h, int64_t* out8);
+int hutk_normalize_batch_device(hutk_normalizer* h, int form, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                                int64_t n_bytes, uint8_t* d_out, int64_t out_cap, int64_t* d_out_offsets, uint8_t* d_changed,
+                                int64_t* d_totals, int32_t* d_err, void* hip_stream);
+int hutk_normalize_batch(hutk_normalizer* h, int form, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, uint8_t** out,
+                         int64_t** out_offsets);
+int hutk_debug_norm_chunk_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

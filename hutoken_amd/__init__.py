@@ -258,7 +258,17 @@ def encode_packed_device(d_bytes, d_offsets, check=True):
     document i are ids[out_offsets[i]:out_offsets[i+1]].  Asynchronous on the
     current torch stream unless check=True, which synchronises and raises on a
     device-side error."""
-    return _encode_device("plain", d_bytes, d_offsets, 0, check)
+    return _encode_on_current_stream("plain", d_bytes, d_offsets, 0, check)
+
+
+def _encode_on_current_stream(kind, d_bytes, d_offsets, flags, check):
+    """_encode_device where the docstrings say it runs: on torch's current stream, the default one included (which the
+    C ABI would read as "the context's own stream": check=True then read the error word, and the caller the ids, before
+    the kernels had run)."""
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    return _on_torch_stream(d_bytes.device, lambda: _encode_device(kind, d_bytes, d_offsets, flags, check),
+                            used=(d_bytes, d_offsets))
 
 
 def _encode_device(kind, d_bytes, d_offsets, flags, check):
@@ -1019,7 +1029,7 @@ def encode_special_packed_device(d_bytes, d_offsets, check=True):
     SequencePacker.add and the spans' callers take it unchanged (spans over special ids are not defined), and
     decode_packed_device(ids, out_offsets, special=True) gives the text back.  Synchronises the current torch stream once,
     after the scan for matches."""
-    return _encode_device("special", d_bytes, d_offsets, 0, check)
+    return _encode_on_current_stream("special", d_bytes, d_offsets, 0, check)
 
 
 def _special_texts_to_device(texts, normalize=None):
@@ -1189,7 +1199,7 @@ def encode_fallback_packed_device(d_bytes, d_offsets, special=False, check=True)
     int64[n+1]).  special=True also cuts at the special tokens of set_special_tokens, as encode_special_packed_device does
     (and then synchronises the current torch stream once); without it the call is asynchronous unless check=True, which
     synchronises and raises on a device-side error."""
-    return _encode_device("fallback", d_bytes, d_offsets, _special_arg(special), check)
+    return _encode_on_current_stream("fallback", d_bytes, d_offsets, _special_arg(special), check)
 
 
 def _fallback_texts_to_device(texts, special, normalize=None):

@@ -334,7 +334,9 @@ void hutk_trainer_destroy(hutk_trainer* t);
  *   the flush call  writes the kept tokens as one row padded with pad_id, position 0, segment 0 (*n_rows = 1), or
  *                   nothing when none are kept (*n_rows = 0), and empties the stream.
  *   pending         the number of tokens kept.
- * Calls on one packer are serialised like calls on one context: a mutex on the host, an event on the device. */
+ * Calls on one packer are serialised like calls on one context: a mutex on the host, an event on the device.
+ * Alignment, padded and packed alike (d_ids, d_input_ids, d_mask, d_lengths, d_position_ids, d_segment_ids): that of
+ * the element type; 16 bytes gets the wide path. */
 #define HUTK_COLLATE_TRUNC_LEFT 1
 #define HUTK_COLLATE_PAD_LEFT 2
 #define HUTK_NO_TOKEN INT32_MIN
@@ -471,7 +473,8 @@ int hutk_token_spans(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets
  * number to size the piece-wise encode.  With zero matches it then runs the plain encode straight into the caller's
  * buffers; otherwise cut, encode and stitch are enqueued and the call returns without waiting for them.  A context with a
  * regex pattern: HUTK_E_UNSUPPORTED at the call (as the token spans); ids_cap below hutk_special_ids_capacity() - 1:
- * HUTK_E_CAPACITY, nothing is enqueued; a NULL buffer: HUTK_E_ARG.  The special pieces are encoded too and their ids
+ * HUTK_E_CAPACITY, nothing is enqueued; a NULL buffer: HUTK_E_ARG.  Alignment of d_ids_out: that of the element type;
+ * 16 bytes gets the wide path (d_bytes: 16 bytes, else HUTK_E_ARG at the call, as the plain encode).  The special pieces are encoded too and their ids
  * dropped, so a marker that is not valid UTF-8 fails a character-mode context like any such text.  Runs on the context's
  * first device, serialised with the other calls on the context; the workspace grows by about 2 bytes per input byte
  * and, with matches, by a second id buffer.  hutk_encode_special_batch: host buffers (copies, calls the device form,
@@ -566,6 +569,8 @@ int hutk_decode_special_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t* 
  * (HUTK_E_UNSUPPORTED: what the spans refuse); with HUTK_FB_SPECIAL an id that is both special and in the table
  * (HUTK_E_VALUE); unknown flag bits, a NULL buffer, more than 2^31 - 3 documents (HUTK_E_ARG); ids_cap below the bound
  * (HUTK_E_CAPACITY); a host-only context (HUTK_E_DEVICE).  Nothing is written at or beyond d_ids_out + ids_cap.
+ * Alignment of d_ids_out: that of the element type; 16 bytes gets the wide path.  (d_bytes: 16 bytes, as for
+ * hutk_encode_batch_device; anything else is HUTK_E_ARG at the call and nothing is written.)
  * A document whose spans do not verify (HUTK_DOC_SPAN_MISMATCH there: a special-character value that equals an ordinary
  * character, say) keeps its plain ids, -1 included, and its status; *d_err = HUTK_E_UNSUPPORTED; every other document is
  * exact.  Document offsets that do not describe the text, or a document of 2^31 bytes or more: *d_err = HUTK_E_ARG,
@@ -645,6 +650,7 @@ int hutk_decode_fallback_batch(hutk_ctx* ctx, const int32_t* ids, const int64_t*
  * error: HUTK_E_ARG for offsets that do not rise from 0 to n_bytes (nothing else is then computed), HUTK_E_CAPACITY for an
  * out_cap below the total (nothing is written).  An unknown form, negative sizes, a missing buffer: HUTK_E_ARG at once;
  * no GPU: HUTK_E_DEVICE.  Calls on one normaliser are serialised (a mutex on the host, an event on the device).
+ * Alignment of d_bytes and d_out: that of the element type (any byte address); 16 bytes gets the wide path.
  * hutk_normalize_batch: host arrays in; the work is done on the GPU; *out (offsets[n_docs] bytes of output at
  * (*out_offsets)[n_docs]) and *out_offsets (n_docs + 1 entries) are allocated here and given back with hutk_host_free. */
 #define HUTK_NFC 0

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import norm_ref as R
+from view_cases import hungarian as _hungarian
 
 pytestmark = pytest.mark.gpu
 
@@ -77,17 +78,6 @@ def test_ill_formed_fuzz():
 
 def test_random_fuzz():
     _check(R.random_docs())
-
-
-def _hungarian(n_bytes):
-    words = ["\u00e1rv\u00edzt\u0171r\u0151", "t\u00fck\u00f6rf\u00far\u00f3g\u00e9p", "hogy", "a", "\u00e9s", "\u0151szi", "\u00daJS\u00c1G", "Gy\u0151r", "sz\u0151l\u0151", "f\u0171z\u0151", "12", "-", "az", "\u00fcveg"]
-    out, n, i = [], 0, 0
-    while n < n_bytes:
-        w = words[(i * 7 + i // 3) % len(words)]
-        out.append(w)
-        n += len(w.encode("utf-8")) + 1
-        i += 1
-    return " ".join(out)
 
 
 def test_clean_batch_returns_its_input():

@@ -48,6 +48,7 @@ import sys
 import traceback
 
 from . import _capi
+from . import pretokenize as _presplit_tables  # (the module; the package's name `pretokenize` is the function below)
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 
 __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
@@ -57,7 +58,8 @@ __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_pack
            "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device",
            "decode_special", "batch_decode_special", "decode_packed_device",
            "set_byte_fallback", "encode_fallback", "batch_encode_fallback", "encode_fallback_packed_device",
-           "decode_fallback", "batch_decode_fallback", "normalize_packed_device", "normalize"]
+           "decode_fallback", "batch_decode_fallback", "normalize_packed_device", "normalize",
+           "pretokenize_packed_device", "pretokenize", "set_pretokenizer"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -78,7 +80,8 @@ def context():
 
 
 def _native_initialize(vocab_file_path, special_file_path, prefix=None, is_byte_encoder=False,
-                       special_token_id=-1, pattern=None, merges_file_path=None, device=-1, devices=None):
+                       special_token_id=-1, pattern=None, merges_file_path=None, device=-1, devices=None,
+                       pretokenizer=None):
     # mirrors the argument contract of _hutoken.initialize (lib.c:188-215, "ss|zpizz")
     # devices (not in the reference): several GPUs of this process behind batch_encode (hutk_ctx_add_device)
     global _ctx
@@ -92,6 +95,8 @@ def _native_initialize(vocab_file_path, special_file_path, prefix=None, is_byte_
             or not (merges_file_path is None or isinstance(merges_file_path, str)) \
             or not isinstance(special_token_id, int):
         raise TypeError(_BAD_INIT_ARGS)
+    if pretokenizer is not None:
+        _presplit_tables.preset_index(pretokenizer)  # (an unknown name raises before anything is built)
     sh = _capi.shim()
     if sh is not None:
         # the compiled module with the reference's method table owns the context; this wrapper only looks at it
@@ -102,6 +107,8 @@ def _native_initialize(vocab_file_path, special_file_path, prefix=None, is_byte_
             old.close()
         for d in (devices or [])[1:]:
             _ctx.add_device(int(d))
+        if pretokenizer is not None:
+            set_pretokenizer(pretokenizer)
         return None
     # merges_file_path: the id-keyed merge path (lib.c:573-663, core.c:211-337) on the same kernels
     new = _capi.Context(vocab_file_path, special_file_path, prefix, bool(is_byte_encoder), device,
@@ -111,6 +118,12 @@ def _native_initialize(vocab_file_path, special_file_path, prefix=None, is_byte_
         # merge loop run on the GPU
         try:
             new.set_pattern(pattern)
+        except Exception:
+            new.close()
+            raise
+    if pretokenizer is not None:
+        try:
+            new.set_pretokenizer(_presplit_tables.preset_index(pretokenizer), _presplit_tables.table_blob())
         except Exception:
             new.close()
             raise
@@ -128,7 +141,10 @@ def initialize(model_or_path, *args, **kwargs):
     drops it (hutoken.py:30-43 never hands it to _hutoken.initialize); only its Hugging
     Face branch passes `merges_file_path=`.  The positional form is kept as it is; the
     keyword `merges_file_path=` (the native function's own name for it, lib.c:188-205)
-    selects the id-keyed merge path here."""
+    selects the id-keyed merge path here.
+
+    pretokenizer= "gpt2", "cl100k" (alias "llama3") or "qwen2" (both branches): the word split of that tokenizer family,
+    computed on the GPU in front of every encode (set_pretokenizer); absent: the built-in split, as before."""
     if os.path.isfile(model_or_path):
         special_chars_file = args[0] if args else None
         merges_file = args[6] if len(args) > 6 else None
@@ -145,7 +161,8 @@ def initialize(model_or_path, *args, **kwargs):
         if merges_kw and not os.path.isfile(merges_kw):
             raise ValueError(f"The provided merges file '{merges_kw}' does not exist.")
         return _native_initialize(model_or_path, special_chars_file, prefix, is_byte_encoder, token_id,
-                                  regex_pattern, merges_kw, device=device, devices=kwargs.get("devices", None))
+                                  regex_pattern, merges_kw, device=device, devices=kwargs.get("devices", None),
+                                  pretokenizer=kwargs.get("pretokenizer", None))
     # Hugging Face branch (hutoken.py:44-120): convert the tokenizer to huToken's files, then the same native
     # initialisation, on the id-keyed merge path when the tokenizer has merge rules
     from . import hf
@@ -1367,3 +1384,98 @@ def normalize(texts, form="NFC"):
     out, oo = normalize_packed_device(d_bytes, torch.from_numpy(offs).to(dev), form)
     raw, bounds = out.cpu().numpy().tobytes(), oo.tolist()
     return [raw[bounds[i]:bounds[i + 1]].decode("utf-8", "surrogateescape") for i in range(len(chunks))]
+
+
+# ---- split presets (hutk_presplit.hip) ----
+_pretokenizers = {}
+
+
+def _pretokenizer(dev):
+    """The pre-tokeniser of a torch device: its tables are built once per process and uploaded once per device."""
+    pt = _pretokenizers.get(dev.index)
+    if pt is None:
+        pt = _pretokenizers[dev.index] = _capi.Pretokenizer(_presplit_tables.table_blob(), dev.index)
+    return pt
+
+
+def set_pretokenizer(name):
+    """Install a split preset on the initialised context -- "gpt2", "cl100k" (alias "llama3"), "qwen2"; the patterns
+    are hutoken_amd.pretokenize.PATTERNS -- or remove it with None.  Every encoder of the package then splits by it, on the
+    GPU and with no host round trip: encode, batch_encode, the *_packed_device forms, SequencePacker.add_texts,
+    batch_encode_with_offsets, the special-token functions.  The presets are for byte-level vocabularies: a context
+    with a prefix, one with a regex pattern, and the byte-fallback functions refuse (RuntimeError, not supported)."""
+    if _ctx is None:
+        raise RuntimeError("Vocabulary is not initialized for encoding. Call 'initialize' function first.")
+    if name is None:
+        _ctx.set_pretokenizer(None)
+    else:
+        _ctx.set_pretokenizer(_presplit_tables.preset_index(name), _presplit_tables.table_blob())
+
+
+def pretokenize_packed_device(d_bytes, d_offsets, preset, *, return_bits=False):
+    """The word split of a preset -- "gpt2", "cl100k" (alias "llama3") or "qwen2", the patterns of
+    hutoken_amd.pretokenize.PATTERNS -- of a packed batch on the GPU: device tensors in (uint8 bytes, int64 offsets[n+1],
+    as encode_packed_device takes them), (starts, start_offsets) out: the ascending byte positions (int64, into d_bytes)
+    at which a word starts, and int64[n+1] offsets into them, document i's words being starts[start_offsets[i] :
+    start_offsets[i + 1]] (each ends where the next starts, the last at the document's end).  Per document this is
+    [m.start() for m in regex.finditer(pattern, d.decode("utf-8", "surrogateescape"))] in bytes: a byte that strict
+    UTF-8 rejects is one character that is neither letter, number nor whitespace; documents are independent; the
+    classes are those of this interpreter's unicodedata.  d_bytes may be a view at any byte offset.
+
+    Runs on the current torch stream: the split, a count, one synchronising read of the count (and the error word), the
+    listing.  return_bits=True: the bitmap itself instead (int32[n_bytes // 32 + 40], bit p: a word starts at byte p,
+    the bit at n_bytes set), enqueued without any synchronisation; offsets that do not describe d_bytes then leave it
+    unwritten.  Otherwise they raise ValueError.  Needs no initialised context and touches no vocabulary."""
+    pi = _presplit_tables.preset_index(preset)
+    _packed_text_args(d_bytes, d_offsets)
+    import torch
+    dev = d_bytes.device
+    pt = _pretokenizer(dev)
+    n_docs, n_bytes = d_offsets.numel() - 1, d_bytes.numel()
+    n_words = n_bytes // 32 + 1
+    with torch.cuda.device(dev):
+        bits = torch.empty(n_bytes // 32 + 40, dtype=torch.int32, device=dev)
+        small = torch.zeros(2, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        pt.batch_device(pi, d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, bits.data_ptr(), small.data_ptr(), stream)
+        if return_bits:
+            return bits
+        before = torch.zeros(n_words + 1, dtype=torch.int64, device=dev)
+        pt.starts_device(bits.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, before.data_ptr(), 0, 0, stream)
+        code = int(small[0])  # the one synchronisation
+        if code:
+            raise ValueError("hutoken_amd: pretokenize_packed_device: device-side error %d (offsets that do not describe d_bytes)" % code)
+        total = int(before[n_words]) - 1
+        starts = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+        start_offs = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        pt.starts_device(bits.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, before.data_ptr(), starts.data_ptr(),
+                         start_offs.data_ptr(), stream)
+    return starts[:total], start_offs
+
+
+def pretokenize(texts, preset):
+    """A list of str -> for each the list of its words under the preset ("gpt2", "cl100k" / "llama3", "qwen2"), what
+    pre_tokenize_str gives elsewhere, split on the current GPU (pretokenize_packed_device; no context is needed).  The
+    words of a text concatenate to it."""
+    import numpy as np
+    import torch
+    _presplit_tables.preset_index(preset)
+    if not isinstance(texts, list):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    try:
+        chunks = [t.encode("utf-8", "surrogateescape") for t in texts]
+    except AttributeError:
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    offs = np.zeros(len(chunks) + 1, dtype=np.int64)
+    if chunks:
+        np.cumsum(np.fromiter(map(len, chunks), dtype=np.int64, count=len(chunks)), out=offs[1:])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    raw = b"".join(chunks)
+    d_bytes = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev)
+    starts, so = pretokenize_packed_device(d_bytes, torch.from_numpy(offs).to(dev), preset)
+    starts, so = starts.tolist(), so.tolist()
+    out = []
+    for i in range(len(chunks)):
+        edges = starts[so[i]:so[i + 1]] + [int(offs[i + 1])]
+        out.append([raw[a:b].decode("utf-8", "surrogateescape") for a, b in zip(edges, edges[1:])])
+    return out

@@ -28,6 +28,8 @@ SIGNATURES = {
     "hutk_ctx_create": (_i32, [_pvp, _str, _str, _str, _i32, _i32]),
     "hutk_ctx_create_merges": (_i32, [_pvp, _str, _str, _str, _i32, _str, _i32]),
     "hutk_ctx_set_pattern": (_i32, [_vp, _str]),
+    "hutk_ctx_set_pretokenizer": (_i32, [_vp, _i32, _vp, _i64]),
+    "hutk_ctx_pretokenizer": (_i32, [_vp]),
     "hutk_ctx_add_device": (_i32, [_vp, _i32]),
     "hutk_ctx_device_count": (_i32, [_vp]),
     "hutk_uses_merges": (_i32, [_vp]),
@@ -98,7 +100,12 @@ SIGNATURES = {
     "hutk_normalizer_info": (_i32, [_vp, _vp]),
     "hutk_normalize_batch_device": (_i32, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "hutk_normalize_batch": (_i32, [_vp, _i32, _vp, _vp, _i64, _pvp, _pvp]),
+    "hutk_pretokenizer_create": (_i32, [_pvp, _i32, _vp, _i64]),
+    "hutk_pretokenizer_destroy": (None, [_vp]),
+    "hutk_pretokenize_batch_device": (_i32, [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "hutk_pretokenize_starts_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hutk_debug_norm_chunk_bytes": (_i32, []),
+    "hutk_debug_presplit_chunk_bytes": (_i32, []),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -292,6 +299,20 @@ class Context(_Owner):
     def set_pattern(self, pattern):
         """The regex pre-token path (initialize's `pattern`, a POSIX ERE); None: the hand-written splitter."""
         raise_for(load().hutk_ctx_set_pattern(self._h, None if pattern is None else pattern.encode("utf-8")))
+
+    def set_pretokenizer(self, preset, blob=None):
+        """A split preset (index into hutoken_amd.pretokenize.PRESETS) with its table blob; None: the built-in split."""
+        if preset is None:
+            raise_for(load().hutk_ctx_set_pretokenizer(self._h, -1, None, 0))
+            return
+        buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0")
+        raise_for(load().hutk_ctx_set_pretokenizer(self._h, int(preset), C.cast(buf, C.c_void_p), len(blob)))
+
+    @property
+    def pretokenizer(self):
+        """The installed preset's index, None: none."""
+        p = load().hutk_ctx_pretokenizer(self._h)
+        return None if p < 0 else p
 
     @property
     def uses_merges(self):
@@ -770,3 +791,29 @@ class Normalizer(_Owner):
 
 def norm_chunk_bytes():
     return load().hutk_debug_norm_chunk_bytes()
+
+
+class Pretokenizer(_Owner):
+    """Owns one hutk_pretokenizer (the split presets on the GPU, include/hutoken_amd.h): the class tables of
+    hutoken_amd.pretokenize on one device, and the workspace of its calls."""
+    _destroy = "hutk_pretokenizer_destroy"
+
+    def __init__(self, blob, device=-1):
+        h = C.c_void_p()
+        buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0")
+        raise_for(load().hutk_pretokenizer_create(C.byref(h), int(device), C.cast(buf, C.c_void_p), len(blob)))
+        self._h = h
+
+    def batch_device(self, preset, d_bytes, d_offsets, n_docs, n_bytes, d_word_bits, d_err=0, stream=0):
+        """hutk_pretokenize_batch_device on raw device pointers (ints).  Asynchronous on `stream`, never synchronises."""
+        raise_for(load().hutk_pretokenize_batch_device(self._h, preset, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                       d_word_bits or None, d_err or None, stream or None))
+
+    def starts_device(self, d_word_bits, d_offsets, n_docs, n_bytes, d_before, d_starts=0, d_start_offsets=0, stream=0):
+        """hutk_pretokenize_starts_device; d_starts == 0: the counting call."""
+        raise_for(load().hutk_pretokenize_starts_device(self._h, d_word_bits or None, d_offsets or None, n_docs, n_bytes,
+                                                        d_before or None, d_starts or None, d_start_offsets or None, stream or None))
+
+
+def presplit_chunk_bytes():
+    return load().hutk_debug_presplit_chunk_bytes()

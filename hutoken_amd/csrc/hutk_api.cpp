@@ -308,6 +308,7 @@ void destroy(hutk_ctx* c) {
         for (auto& e : c->ev)
             if (e) (void)hipEventDestroy(e);
         if (c->ev_busy) (void)hipEventDestroy(c->ev_busy);
+        if (c->pretok) hutk_pretokenizer_destroy(c->pretok);
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -481,6 +482,16 @@ int hutk_ctx_add_device(hutk_ctx* c, int device) {
         return rc;
     }
     p->pattern = c->pattern;
+    if (c->presplit >= 0) {  // the preset goes with it: its tables are uploaded once per device
+        const int prc = hutk_pretokenizer_create(&p->pretok, device, c->presplit_blob.data(), (int64_t)c->presplit_blob.size());
+        if (prc) {
+            std::string keep = g_err;
+            destroy(p);
+            g_err = keep;
+            return prc;
+        }
+        p->presplit = c->presplit;
+    }
     c->peers.push_back(p);
     c->peer_ids.emplace_back();
     return HUTK_OK;
@@ -602,6 +613,8 @@ int hutk_ctx_set_pattern(hutk_ctx* c, const char* pattern) {
         assign("");
         return HUTK_OK;
     }
+    if (c->presplit >= 0)
+        return api_set_error(HUTK_E_UNSUPPORTED, "a split preset is installed (hutk_ctx_set_pretokenizer): a context splits by one of the two");
     regex_t re;
     if (!*pattern || regcomp(&re, pattern, REG_EXTENDED) != 0)
         return api_set_error(HUTK_E_VALUE, "Regex could not be compiled.");  // core.c:352-358
@@ -609,6 +622,39 @@ int hutk_ctx_set_pattern(hutk_ctx* c, const char* pattern) {
     assign(pattern);
     return HUTK_OK;
 }
+
+int hutk_ctx_set_pretokenizer(hutk_ctx* c, int preset, const uint8_t* tables, int64_t n_bytes) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    if (preset < HUTK_PRESPLIT_NONE || preset > HUTK_PRESPLIT_QWEN2) return api_set_error(HUTK_E_ARG, "preset must be HUTK_PRESPLIT_NONE, _GPT2, _CL100K or _QWEN2");
+    if (preset == HUTK_PRESPLIT_NONE) {
+        std::lock_guard<std::recursive_mutex> lock(c->mu);
+        c->presplit = -1;
+        for (hutk_ctx* p : c->peers) {
+            std::lock_guard<std::recursive_mutex> plock(p->mu);
+            p->presplit = -1;
+        }
+        return HUTK_OK;
+    }
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: the split presets run on the device");
+    if (c->tab.has_prefix) return api_set_error(HUTK_E_UNSUPPORTED, "a split preset on a context with a prefix: the presets are for byte-level vocabularies");
+    if (!c->pattern.empty()) return api_set_error(HUTK_E_UNSUPPORTED, "a regex pattern is set (hutk_ctx_set_pattern): a context splits by one of the two");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    std::vector<hutk_ctx*> all{c};
+    all.insert(all.end(), c->peers.begin(), c->peers.end());
+    for (hutk_ctx* p : all) {  // (the tables are validated by the first create, before anything changes)
+        std::lock_guard<std::recursive_mutex> plock(p->mu);
+        if (!p->pretok)
+            if (int rc = hutk_pretokenizer_create(&p->pretok, p->device, tables, n_bytes)) return rc;
+    }
+    if (c->presplit_blob.empty()) c->presplit_blob.assign(tables, tables + n_bytes);
+    for (hutk_ctx* p : all) {
+        std::lock_guard<std::recursive_mutex> plock(p->mu);
+        p->presplit = preset;
+    }
+    return HUTK_OK;
+}
+
+int hutk_ctx_pretokenizer(const hutk_ctx* c) { return c ? c->presplit : HUTK_PRESPLIT_NONE; }
 
 // Which tile kernel for the batches both can take: HUTK_PTILES=1 / 0 the persistent one (hutk_ptiles.hip) / k_tiles;
 // unset ("auto"): both are enqueued and the batch's own bytes decide on the device (Workspace::select): the persistent
@@ -701,6 +747,15 @@ extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, c
         return HUTK_OK;
     }
     launch_pre(A, W, s);
+    if (!A.word_bits && c->presplit >= 0) {
+        // A split preset: the word starts are written on the device, into the context's bitmap (StreamScope has waited
+        // for the call that read it last), and the kernels go on as on the regex path -- no stretch is dropped, so there
+        // are no gap bits; nothing comes down to the host
+        HUTK_HIP_TRY(c->w_wbits.reserve((size_t)(n_bytes / 32 + 40)));
+        rc = hutk_pretokenize_batch_device(c->pretok, c->presplit, d_bytes, d_offsets, n_docs, n_bytes, c->w_wbits.p, nullptr, s);
+        if (rc) return rc;
+        A.word_bits = c->w_wbits.p;
+    }
     if (c->timing) HUTK_HIP_TRY(hipEventRecord(c->ev[1], s));
     {
         const int which = tile_kernels_for(c->dt, A);
@@ -956,7 +1011,7 @@ static int encode_batch_host(hutk_ctx* c, const uint8_t* bytes, const int64_t* o
             BatchArgs probe{};
             probe.n_tiles = (n_bytes + TILE_BYTES - 1) / TILE_BYTES;
             constexpr size_t ONE_OUT = 64 * 1024, ONE_FLAG = SMALL_HOST_BYTES - 64;
-            if (one_shot_on && c->small_host && one_shot_takes(c->dt, probe) && in_size <= ONE_OUT && ONE_OUT + out_size <= ONE_FLAG) {
+            if (one_shot_on && c->presplit < 0 && c->small_host && one_shot_takes(c->dt, probe) && in_size <= ONE_OUT && ONE_OUT + out_size <= ONE_FLAG) {
                 uint8_t* h = static_cast<uint8_t*>(c->small_host);
                 memcpy(h + in_offs, offsets, ((size_t)n_docs + 1) * 8);
                 memcpy(h + in_bytes, bytes, (size_t)n_bytes);

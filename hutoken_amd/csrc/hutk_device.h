@@ -180,6 +180,7 @@ struct BatchArgs {
     // regex pre-token path (a pattern was given to initialize): bit p of word_bits = a word or a dropped stretch starts
     // at byte p (bits up to and including n_bytes, padded with zero words); bit p of gap_bits = what starts at p is a
     // stretch no match covers (no ids).  Both null: the hand-written splitter (the automaton in k_tiles).
+    // A split preset (hutk_presplit.hip) writes word_bits on the device and leaves gap_bits null: nothing is dropped.
     const uint32_t* word_bits;
     const uint32_t* gap_bits;
     // ... together with a prefix (core.c:364-366, 421-451: the prefix goes with the FIRST MATCH of a document): bit p of

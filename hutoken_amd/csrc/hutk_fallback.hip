@@ -293,6 +293,7 @@ int fb_refusal(const hutk_ctx* c, const char* who) {
     const std::string w(who);
     if (!c->fb.on) return api_set_error(HUTK_E_UNSUPPORTED, w + ": no byte-fallback table is installed (hutk_ctx_set_byte_fallback)");
     if (!c->pattern.empty()) return api_set_error(HUTK_E_UNSUPPORTED, w + ": a regex pattern drops the text between its matches; the tokens do not tile the document");
+    if (c->presplit >= 0) return api_set_error(HUTK_E_UNSUPPORTED, w + ": a split preset is installed: a byte-level vocabulary holds all 256 bytes, there is nothing to fall back to");
     if (c->tab.has_multi) return api_set_error(HUTK_E_UNSUPPORTED, w + ": a special-character replacement of several units");
     if (!c->tab.is_byte_encoder)
         for (int b = 0x80; b < 256; b++)

@@ -121,6 +121,11 @@ struct hutk_ctx {
     // regex pre-token path: the pattern of initialize() (empty: the hand-written splitter) and the bitmaps of a batch
     std::string pattern;
     DevBuf<uint32_t> w_wbits, w_gbits, w_fbits, w_abits;
+    // a split preset (hutk_ctx_set_pretokenizer, HUTK_PRESPLIT_*; -1: none): encode_device_impl has pretok write w_wbits on
+    // the device in front of its kernels.  presplit_blob: the tables, for the devices hutk_ctx_add_device adds later
+    int presplit = -1;
+    struct hutk_pretokenizer* pretok = nullptr;
+    std::vector<uint8_t> presplit_blob;
     hutk::DevTables dt{};
 
     // workspace

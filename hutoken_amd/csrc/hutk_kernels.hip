@@ -523,7 +523,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
             if (lo >= limit) own = 0;
             else if (lo + 16 > limit) own &= (1u << (limit - lo)) - 1u;
         }
-        if (!A.word_bits) {
+        if (!A.word_bits || !A.gap_bits) {  // (the regex path's host has cut such words already, and its dropped stretches are no words;
+                                            // a split preset -- start bits without gap bits -- leaves them to k_cut like the automaton)
             // The reference ends a document at a word of more than 262144 bytes (core.c:402-407).  With seams such a word can
             // be a run of short ones here, so k_cut looks for what every such word leaves behind: at least 272 tiles in
             // a row without a start of the reference's own (with_start: taken before the seams came in).  The lanes

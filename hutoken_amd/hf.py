@@ -72,6 +72,38 @@ def normalizer_form(tok):
     return forms[0] if len(forms) == 1 else None
 
 
+def pretokenizer_preset(tok):
+    """The split preset (hutoken_amd.pretokenize) the backend's pre-tokenizer is: "gpt2" for a ByteLevel node that uses
+    its own regex, "cl100k" or "qwen2" for a Split whose pattern string is exactly that preset's -- the node itself or a
+    member of a Sequence (a ByteLevel without its regex behind a Split only maps bytes) -- when there is exactly one
+    such node; None otherwise.  Reported by export(), not acted on: pass it as pretokenizer= to initialize()."""
+    from .pretokenize import PATTERNS
+    js = _backend_json(tok)
+    node = js.get("pre_tokenizer") if js else None
+    if not isinstance(node, dict):
+        return None
+    members = node.get("pretokenizers") if node.get("type") == "Sequence" else [node]
+    if not isinstance(members, list):
+        return None
+    found = []
+    for m in members:
+        if not isinstance(m, dict):
+            return None
+        if m.get("type") == "ByteLevel":
+            if m.get("use_regex", True):
+                found.append("gpt2")
+        elif m.get("type") == "Split":
+            pat = m.get("pattern")
+            text = pat.get("Regex") if isinstance(pat, dict) else None
+            names = [k for k in ("cl100k", "qwen2") if PATTERNS[k] == text]
+            if not names or m.get("behavior", "Isolated").lower() != "isolated" or m.get("invert"):
+                return None  # another split: not one of the presets
+            found.append(names[0])
+        else:
+            return None
+    return found[0] if len(found) == 1 else None
+
+
 def _merges_text(tok):
     js = _backend_json(tok)
     if not js:
@@ -158,8 +190,10 @@ def _written(path, what, write):
 def export(reference, **options):
     """Convert a Hugging Face tokenizer into huToken's files (what hutoken.py:44-107 does inline).
 
-    Returns dict(vocab_file, special_chars_file, prefix, is_byte_encoder, merges_file_path, tokenizer, normalizer);
-    normalizer: the Unicode normal form the tokenizer applies (normalizer_form), for normalize= of the encode calls."""
+    Returns dict(vocab_file, special_chars_file, prefix, is_byte_encoder, merges_file_path, tokenizer, normalizer,
+    pretokenizer); normalizer: the Unicode normal form the tokenizer applies (normalizer_form), for normalize= of the
+    encode calls; pretokenizer: the split preset its pre-tokenizer is (pretokenizer_preset), for pretokenizer= of
+    initialize().  Both are reported, not applied."""
     tok = _load(reference)
     folder, stem = _target(reference)
     tok.save_pretrained(folder)
@@ -175,4 +209,4 @@ def export(reference, **options):
                 prefix=None if first_piece == "hu" else first_piece[0],
                 is_byte_encoder=1 if byte_level else options.get("is_byte_encoder", 0),
                 merges_file_path=_merges_file(tok, folder, reference), tokenizer=tok,
-                normalizer=normalizer_form(tok))
+                normalizer=normalizer_form(tok), pretokenizer=pretokenizer_preset(tok))

@@ -668,6 +668,59 @@ int hutk_normalize_batch(hutk_normalizer* h, int form, const uint8_t* bytes, con
                          int64_t** out_offsets);
 int hutk_debug_norm_chunk_bytes(void);
 
+/* ---- Split presets: the GPT-2, cl100k (Llama 3) and Qwen2 pre-tokenisation ------------------------------------
+ * The word split of byte-level BPE vocabularies on the device (hutk_presplit.hip).  A word starts
+ * where regex.findall(pattern, d.decode("utf-8", "surrogateescape")) starts a match:
+ *   HUTK_PRESPLIT_GPT2    's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
+ *   HUTK_PRESPLIT_CL100K  (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ *   HUTK_PRESPLIT_QWEN2   the same with \p{N} in place of \p{N}{1,3}
+ * \p{L}, \p{N}: general categories L*, N* of the tables' Unicode version; \s: the 25 White_Space code points; under (?i:)
+ * s also matches U+017F and no other letter has a partner outside ASCII.  A byte that strict UTF-8 rejects is one
+ * character that is neither letter, number nor whitespace.  Documents are independent; every byte lies in some word.
+ *
+ * A pre-tokeniser owns the class tables on one device and a small workspace; it needs no hutk_ctx.  The tables are one
+ * blob, built by hutoken_amd/pretokenize.py from Python's unicodedata and written to a file by
+ * `python -m hutoken_amd.pretokenize --write FILE`.  Format (little-endian 32-bit words; offsets in bytes, multiples of 4):
+ *   header, 16 words: 0 magic "HPTK" (0x4B545048), 1 version (1), 2 Unicode version (major << 16 | minor << 8 | patch),
+ *     3 blob bytes, 4/5 stage one: offset, entries (uint16[0x110000 >> 7], the block of code point c), 6/7 class blocks:
+ *     offset, blocks (8 words a block: two bits a code point, c at bits 2 * (c & 15) of word (c & 127) >> 4; 0 other,
+ *     1 letter, 2 number, 3 whitespace), 8 the block shift (7).
+ *   hutk_pretokenizer_create checks the magic, the version and every offset, size and block index before anything reads
+ *   through them (HUTK_E_VALUE).
+ *
+ * hutk_pretokenize_batch_device: asynchronous on hip_stream, never synchronises (growing the workspace for a larger
+ * batch than any before waits for the device once).  d_bytes at any alignment.  d_word_bits: n_bytes / 32 + 40 words;
+ * bit p is set where a word starts, the bit at n_bytes is set, the rest is zero -- the bitmap the encoders take.  The
+ * offsets are checked on the device: they rise from 0 to n_bytes, else HUTK_E_ARG in *d_err (may be NULL) and nothing
+ * else is written.  Calls on one pre-tokeniser are serialised (a mutex on the host, an event on the device).
+ *
+ * hutk_pretokenize_starts_device turns the bitmap into positions, in two calls on the same stream: d_starts == NULL
+ * counts (d_before: n_bytes / 32 + 2 values; afterwards d_before[n_bytes / 32 + 1] - 1 is the number of words); with
+ * d_starts (room for that many) it writes the ascending byte positions of the word starts and d_start_offsets[n_docs + 1],
+ * the index of every document's first word. */
+#define HUTK_PRESPLIT_NONE (-1)
+#define HUTK_PRESPLIT_GPT2 0
+#define HUTK_PRESPLIT_CL100K 1
+#define HUTK_PRESPLIT_QWEN2 2
+typedef struct hutk_pretokenizer hutk_pretokenizer;
+int hutk_pretokenizer_create(hutk_pretokenizer** out, int device, const uint8_t* blob, int64_t n_blob_bytes);
+void hutk_pretokenizer_destroy(hutk_pretokenizer* h);
+int hutk_pretokenize_batch_device(hutk_pretokenizer* h, int preset, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                                  int64_t n_bytes, uint32_t* d_word_bits, int32_t* d_err, void* hip_stream);
+int hutk_pretokenize_starts_device(hutk_pretokenizer* h, const uint32_t* d_word_bits, const int64_t* d_offsets, int64_t n_docs,
+                                   int64_t n_bytes, int64_t* d_before, int64_t* d_starts, int64_t* d_start_offsets, void* hip_stream);
+/* On a context: hutk_ctx_set_pretokenizer installs a preset (HUTK_PRESPLIT_NONE removes it; tables / n_bytes: the blob,
+ * uploaded once per device of the context, hutk_ctx_add_device's later ones included); hutk_ctx_pretokenizer reads it.
+ * Every encode of the context -- hutk_encode_batch_device, hutk_encode_batch and its chunked path, hutk_encode, the
+ * special-token and span calls -- then splits by the preset, on the device, with no copy down and no synchronisation; a
+ * word of more than 262144 bytes ends its document in front of it (HUTK_DOC_WORD_TOO_LARGE), as with the built-in split.
+ * HUTK_E_UNSUPPORTED: a context with a prefix (the presets are for byte-level vocabularies); a preset while a regex
+ * pattern is set, and hutk_ctx_set_pattern while a preset is; the byte-fallback calls on a context with a preset. */
+int hutk_ctx_set_pretokenizer(hutk_ctx* ctx, int preset, const uint8_t* tables, int64_t n_bytes);
+int hutk_ctx_pretokenizer(const hutk_ctx* ctx);
+/* the chunk of text one workgroup splits (tests lay their cases out around it) */
+int hutk_debug_presplit_chunk_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,9 @@ Collation (not in the reference either): `collate_padded` / `batch_encode_padded
 `encode_packed_device` into padded rows with attention mask and lengths, `SequencePacker` into packed rows of
 `seq_len` tokens with position and segment ids -- one HIP pass each (csrc/hutk_collate.hip).  `collate_windows` /
 `batch_encode_windows` cut documents longer than `max_length` into overlapping windows (`stride`), every window a padded
-row, with `row_map` from rows back to documents.
+row, with `row_map` from rows back to documents.  `collate_pairs` / `batch_encode_pairs` put two texts into one row,
+[bos] A sep B [eos] with token type ids and the longest_first / only_first / only_second truncation;
+`collate_pair_windows` / `batch_encode_pair_windows` cut the named side into overlapping windows instead.
 
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
@@ -59,7 +61,8 @@ __all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_pack
            "decode_special", "batch_decode_special", "decode_packed_device",
            "set_byte_fallback", "encode_fallback", "batch_encode_fallback", "encode_fallback_packed_device",
            "decode_fallback", "batch_decode_fallback", "normalize_packed_device", "normalize",
-           "pretokenize_packed_device", "pretokenize", "set_pretokenizer"]
+           "pretokenize_packed_device", "pretokenize", "set_pretokenizer",
+           "collate_pairs", "collate_pair_windows", "batch_encode_pairs", "batch_encode_pair_windows"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -837,6 +840,191 @@ def batch_encode_windows(texts, max_length, stride=0, *, normalize=None, **colla
     collate_windows with `collate_kwargs`, both on the initialised context's GPU.  normalize: as batch_encode_padded."""
     ids, oo = _texts_to_device(texts, normalize=normalize)
     return collate_windows(ids, oo, max_length, stride, **collate_kwargs)
+
+
+_PAIR_STRATEGIES = {"longest_first": _capi.PAIR_LONGEST_FIRST, "only_first": _capi.PAIR_ONLY_FIRST,
+                    "only_second": _capi.PAIR_ONLY_SECOND}
+
+
+def _sep_arg(sep_ids):
+    """sep_ids -> tuple of at most 4 int32 values, none of them the C ABI's "absent"."""
+    if not isinstance(sep_ids, (tuple, list)):
+        raise TypeError("sep_ids must be a tuple or list of ints, not %s" % type(sep_ids).__name__)
+    if len(sep_ids) > _capi.PAIR_MAX_SEP:
+        raise ValueError("sep_ids must hold at most %d ids, not %d" % (_capi.PAIR_MAX_SEP, len(sep_ids)))
+    return tuple(_token_arg("sep_ids[%d]" % i, v, False) for i, v in enumerate(sep_ids))
+
+
+def _pair_args(ids_a, offsets_a, ids_b, offsets_b):
+    """The two ragged pairs of collate_pairs: device tensors on one device, as many documents on both sides."""
+    four = (("ids_a", ids_a, "int32"), ("offsets_a", offsets_a, "int64"), ("ids_b", ids_b, "int32"),
+            ("offsets_b", offsets_b, "int64"))
+    for name, t, want in four:
+        if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")):
+            raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+        if str(t.dtype).rpartition(".")[2] != want:
+            raise TypeError("%s must have dtype %s, not %s" % (name, want, t.dtype))
+    for name, t, _want in four:
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be one-dimensional and contiguous" % name)
+    if offsets_a.numel() < 1:
+        raise ValueError("offsets_a must hold at least one entry")
+    if offsets_a.numel() != offsets_b.numel():
+        raise ValueError("offsets_a and offsets_b must describe as many documents (%d and %d)"
+                         % (offsets_a.numel() - 1, offsets_b.numel() - 1))
+    for name, t, _want in four:
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU: the collation runs there and nowhere else" % name)
+        if t.device != ids_a.device:
+            raise ValueError("%s must be on the same device as ids_a" % name)
+
+
+def _pair_template(bos_id, sep_ids, eos_id, pad_id, truncation, padding_side, dtype):
+    bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
+    sep = _sep_arg(sep_ids)
+    s = (bos != _capi.NO_TOKEN) + len(sep) + (eos != _capi.NO_TOKEN)
+    if not isinstance(truncation, str) or truncation not in _PAIR_STRATEGIES:
+        raise ValueError("truncation must be 'longest_first', 'only_first' or 'only_second', not %r" % (truncation,))
+    if padding_side not in _SIDES:
+        raise ValueError("padding_side must be 'right' or 'left', not %r" % (padding_side,))
+    width, dname = _out_width(dtype)
+    return bos, sep, eos, pad, s, _PAIR_STRATEGIES[truncation], width, dname
+
+
+def collate_pairs(ids_a, offsets_a, ids_b, offsets_b, max_length=None, *, truncation="longest_first", bos_id=None,
+                  sep_ids=(), eos_id=None, pad_id=0, padding_side="right", dtype=None, check=False):
+    """Two ragged pairs of one device in, one row per pair of documents out, on the current torch stream:
+    -> (input_ids [n, max_length] of `dtype` (torch.int32, the default, or torch.int64), attention_mask uint8
+        [n, max_length], token_type_ids uint8 [n, max_length], lengths int32 [n]).
+    Row i is [bos_id] + A' + sep_ids + B' + [eos_id] with A = ids_a[offsets_a[i]:offsets_a[i+1]], B likewise; offsets_x[0]
+    may be any base, so one encode_packed_device call over texts_a + texts_b serves both sides: ids_a = ids_b = ids,
+    offsets_a = oo[:n+1], offsets_b = oo[n:].  With R = max_length - s ids of room (s: bos, separators, eos) both sides
+    are cut on the right to (ka, kb): nothing when they fit; "longest_first" takes from the longer side until both are
+    equal and then from both (the longer one keeps the odd id, B on a tie); "only_first" / "only_second" cut the named
+    side, and the other one only when it alone exceeds R.  token_type_ids is 0 on bos, A' and the separators, 1 on B' and
+    eos, 0 on padding; lengths is ka + kb + s.  max_length=None pads to the longest pair with nothing cut (one small
+    synchronising read); a given one never synchronises.  check=True synchronises and raises ValueError when the kernel
+    found offsets outside 0 <= offsets[0] <= .. <= offsets[n] <= ids.numel()."""
+    bos, sep, eos, pad, s, strategy, width, dname = _pair_template(bos_id, sep_ids, eos_id, pad_id, truncation,
+                                                                   padding_side, dtype)
+    if max_length is not None:
+        _length_arg("max_length", max_length, s + 1)
+    _pair_args(ids_a, offsets_a, ids_b, offsets_b)
+    import torch
+    dev = ids_a.device
+    n = offsets_a.numel() - 1
+    if max_length is None:
+        both = (offsets_a[1:] - offsets_a[:-1]).clamp_(min=0) + (offsets_b[1:] - offsets_b[:-1]).clamp_(min=0)
+        max_length = _length_arg("max_length", s + max(1, int(both.max().item()) if n else 1), s + 1)
+    out = torch.empty((n, max_length), dtype=getattr(torch, dname), device=dev)
+    mask = torch.empty((n, max_length), dtype=torch.uint8, device=dev)
+    types = torch.empty((n, max_length), dtype=torch.uint8, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0
+
+    def call():
+        _capi.collate_pairs_device(ids_a.data_ptr(), offsets_a.data_ptr(), ids_b.data_ptr(), offsets_b.data_ptr(), 0, n,
+                                   ids_a.numel(), ids_b.numel(), n, max_length, 0, strategy, bos, sep, eos, pad, flags,
+                                   width, out.data_ptr(), mask.data_ptr(), types.data_ptr(), lengths.data_ptr(), 0,
+                                   err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out, mask, types, lengths
+    res = _on_torch_stream(dev, call, used=(ids_a, offsets_a, ids_b, offsets_b, err))
+    if check:
+        _raise_device_error(err, "collate_pairs")
+    return res
+
+
+def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=0, *, truncation="only_second",
+                         bos_id=None, sep_ids=(), eos_id=None, pad_id=0, padding_side="right", dtype=None, n_rows=None,
+                         check=False):
+    """collate_pairs with the side `truncation` names ("only_second", the default, or "only_first") cut into overlapping
+    windows instead of truncated -- question + long context for extractive QA:
+    -> (input_ids, attention_mask, token_type_ids [n_rows, max_length], lengths int32 [n_rows], row_map int64 [n_rows, 2]).
+    The other side keeps its first ko = min(its ids, R); the cut side of n ids has C = R - ko ids of room per row: one row
+    when n <= C or C == 0 (the cut side is then empty), otherwise step = max(1, C - stride) and 1 + ceil((n - C) / step)
+    rows, row k holding its ids [k * step, k * step + C) with the whole kept side; the last window is the short one.
+    The rows of pair 0 come first, then those of pair 1, ..; row_map[r] = (pair, k * step), so the spans of the cut side
+    are rows of token_spans_device's result.  "longest_first" is refused: its overflow is a cross product of both sides'
+    windows.  One small synchronising read gives the number of rows; n_rows= avoids it.  check=True synchronises and
+    raises ValueError for offsets outside their condition or an n_rows that is not the number of rows."""
+    bos, sep, eos, pad, s, strategy, width, dname = _pair_template(bos_id, sep_ids, eos_id, pad_id, truncation,
+                                                                   padding_side, dtype)
+    if strategy == _capi.PAIR_LONGEST_FIRST:
+        raise ValueError("truncation must be 'only_first' or 'only_second' here: the windows of 'longest_first' are a cross "
+                         "product of both sides' windows, which this does not produce")
+    _length_arg("max_length", max_length, s + 1)
+    _stride_arg(stride, max_length - s)
+    if n_rows is not None:
+        if isinstance(n_rows, bool) or not isinstance(n_rows, int):
+            raise TypeError("n_rows must be an int or None")
+        if n_rows < 0:
+            raise ValueError("n_rows must not be negative")
+    _pair_args(ids_a, offsets_a, ids_b, offsets_b)
+    import torch
+    dev = ids_a.device
+    n = offsets_a.numel() - 1
+    cap_a, cap_b = ids_a.numel(), ids_b.numel()
+    bound = _capi.pair_rows_bound(n, cap_b if strategy == _capi.PAIR_ONLY_SECOND else cap_a, max_length, stride, s)
+    if n_rows is not None and not n <= n_rows <= bound:
+        raise ValueError("n_rows must be in %d .. %d (the pairs .. the pairs and the ids of the cut side), not %d"
+                         % (n, bound, n_rows))
+    row_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+    flags = _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0
+
+    def call():
+        nonlocal n_rows
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.pair_rows_device(offsets_a.data_ptr(), offsets_b.data_ptr(), n, cap_a, cap_b, max_length, stride, strategy,
+                               bos, sep, eos, row_offsets.data_ptr(), err[0:].data_ptr(), stream)
+        if n_rows is None:
+            n_rows = int(row_offsets[-1].item())  # the one synchronisation; pass n_rows= to avoid it
+            if not n <= n_rows <= bound:
+                raise ValueError("hutoken_amd: collate_pair_windows: offsets that do not describe ids (%d rows)" % n_rows)
+        out = torch.empty((n_rows, max_length), dtype=getattr(torch, dname), device=dev)
+        mask = torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)
+        types = torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)
+        lengths = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        row_map = torch.empty((n_rows, 2), dtype=torch.int64, device=dev)
+        _capi.collate_pairs_device(ids_a.data_ptr(), offsets_a.data_ptr(), ids_b.data_ptr(), offsets_b.data_ptr(),
+                                   row_offsets.data_ptr(), n, cap_a, cap_b, n_rows, max_length, stride, strategy, bos, sep,
+                                   eos, pad, flags, width, out.data_ptr(), mask.data_ptr(), types.data_ptr(),
+                                   lengths.data_ptr(), row_map.data_ptr(), err[1:].data_ptr(), stream)
+        return out, mask, types, lengths, row_map
+    res = _on_torch_stream(dev, call, used=(ids_a, offsets_a, ids_b, offsets_b, row_offsets, err))
+    if check:
+        _raise_device_error(err.max(), "collate_pair_windows")
+    return res
+
+
+def _pair_texts_to_device(texts_a, texts_b, normalize):
+    """Two lists of str -> (ids, offsets_a, offsets_b): one encode of texts_a + texts_b, both sides views of its offsets."""
+    _normalize_arg(normalize)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    if not isinstance(texts_a, list) or not isinstance(texts_b, list):
+        raise TypeError("Invalid arguments. Expected two lists of strings.")
+    if len(texts_a) != len(texts_b):
+        raise ValueError("texts_a and texts_b must hold as many texts (%d and %d)" % (len(texts_a), len(texts_b)))
+    n = len(texts_a)
+    ids, oo = _encode_texts("plain", texts_a + texts_b, 0, False, normalize)
+    return ids, oo[:n + 1], oo[n:]
+
+
+def batch_encode_pairs(texts_a, texts_b, max_length=None, *, normalize=None, **collate_kwargs):
+    """Two lists of str -> collate_pairs' (input_ids, attention_mask, token_type_ids, lengths): one
+    encode_packed_device call over texts_a + texts_b, then collate_pairs with `collate_kwargs` on views of its result,
+    on the initialised context's GPU.  normalize: as batch_encode_padded."""
+    ids, oa, ob = _pair_texts_to_device(texts_a, texts_b, normalize)
+    return collate_pairs(ids, oa, ids, ob, max_length, **collate_kwargs)
+
+
+def batch_encode_pair_windows(texts_a, texts_b, max_length, stride=0, *, normalize=None, **collate_kwargs):
+    """Two lists of str -> collate_pair_windows' (input_ids, attention_mask, token_type_ids, lengths, row_map); see
+    batch_encode_pairs."""
+    ids, oa, ob = _pair_texts_to_device(texts_a, texts_b, normalize)
+    return collate_pair_windows(ids, oa, ids, ob, max_length, stride, **collate_kwargs)
 
 
 class SequencePacker:

@@ -95,6 +95,10 @@ SIGNATURES = {
     "hutk_windows_rows_device": (_i32, [_vp, _i64, _i64, _i64, _i64, _s32, _s32, _vp, _vp, _vp]),
     "hutk_collate_windows_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _s32, _s32, _s32, _i32, _i32,
                                            _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_pair_rows_bound": (_i64, [_i64, _i64, _i64, _i64, _i32]),
+    "hutk_pair_rows_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _s32, _vp, _i32, _s32, _vp, _vp, _vp]),
+    "hutk_collate_pairs_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _s32, _vp,
+                                         _i32, _s32, _s32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hutk_normalizer_create": (_i32, [_pvp, _i32, _vp, _i64]),
     "hutk_normalizer_destroy": (None, [_vp]),
     "hutk_normalizer_info": (_i32, [_vp, _vp]),
@@ -111,6 +115,7 @@ EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
 COLLATE_TRUNC_LEFT, COLLATE_PAD_LEFT = 1, 2
 NO_TOKEN = -2**31  # HUTK_NO_TOKEN: "no bos / no eos"
+PAIR_LONGEST_FIRST, PAIR_ONLY_FIRST, PAIR_ONLY_SECOND, PAIR_MAX_SEP = 0, 1, 2, 4  # HUTK_PAIR_*
 SPANS_BYTES, SPANS_CHARS = 0, 1
 DECODE_SKIP_SPECIAL = 1  # HUTK_DECODE_SKIP_SPECIAL
 FB_SPECIAL, FB_SKIP_SPECIAL = 1, 2  # HUTK_FB_*
@@ -696,6 +701,42 @@ def collate_windows_device(d_ids, d_offsets, d_row_offsets, n_docs, n_ids, n_row
                                                  n_rows, max_len, stride, bos_id, eos_id, pad_id, flags, out_width,
                                                  d_input_ids or None, d_mask or None, d_lengths or None,
                                                  d_row_map or None, d_err or None, stream or None))
+
+
+def _sep_array(sep_ids):
+    """tuple of ints -> (a ctypes int32 array the call may read, its length); the C ABI checks the values."""
+    sep_ids = tuple(sep_ids)
+    return (_s32 * max(1, len(sep_ids)))(*sep_ids), len(sep_ids)
+
+
+def pair_rows_bound(n_pairs, n_cut_ids, max_len, stride, s):
+    """hutk_pair_rows_bound (host only): an upper bound of the rows the windows form of collate_pairs_device writes."""
+    n = load().hutk_pair_rows_bound(n_pairs, n_cut_ids, max_len, stride, s)
+    if n < 0:
+        raise_for(-n)
+    return n
+
+
+def pair_rows_device(d_offsets_a, d_offsets_b, n_pairs, cap_a, cap_b, max_len, stride, strategy, bos_id, sep_ids, eos_id,
+                     d_row_offsets, d_err=0, stream=0):
+    """hutk_pair_rows_device on raw device pointers (ints); sep_ids: a tuple of ints; asynchronous on `stream`."""
+    sep, n_sep = _sep_array(sep_ids)
+    raise_for(load().hutk_pair_rows_device(d_offsets_a or None, d_offsets_b or None, n_pairs, cap_a, cap_b, max_len, stride,
+                                           strategy, bos_id, sep, n_sep, eos_id, d_row_offsets or None, d_err or None,
+                                           stream or None))
+
+
+def collate_pairs_device(d_ids_a, d_offsets_a, d_ids_b, d_offsets_b, d_row_offsets, n_pairs, cap_a, cap_b, n_rows, max_len,
+                         stride, strategy, bos_id, sep_ids, eos_id, pad_id, flags, out_width, d_input_ids, d_mask=0,
+                         d_token_types=0, d_lengths=0, d_row_map=0, d_err=0, stream=0):
+    """hutk_collate_pairs_device on raw device pointers (ints); d_row_offsets 0: one row per pair; sep_ids: a tuple of
+    ints; asynchronous on `stream`."""
+    sep, n_sep = _sep_array(sep_ids)
+    raise_for(load().hutk_collate_pairs_device(d_ids_a or None, d_offsets_a or None, d_ids_b or None, d_offsets_b or None,
+                                               d_row_offsets or None, n_pairs, cap_a, cap_b, n_rows, max_len, stride,
+                                               strategy, bos_id, sep, n_sep, eos_id, pad_id, flags, out_width,
+                                               d_input_ids or None, d_mask or None, d_token_types or None,
+                                               d_lengths or None, d_row_map or None, d_err or None, stream or None))
 
 
 class Packer(_Owner):

@@ -8,6 +8,9 @@
 //   windows  a document longer than max_len - s is cut into overlapping windows, every window a padded row, with a map
 //            from rows back to documents; the rows' places come from a count, scan, write over the documents first
 //                                                  (k_windows_count, k_windows_write, k_collate_windows)
+//   pairs    document i of two ragged pairs in one row, [bos] A sep.. B [eos], cut by one of three strategies, with
+//            token type ids; or the named side in windows, the other side whole in every row
+//                                                  (k_pair_count, k_pair_write, k_collate_pairs)
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets: a workgroup owns a contiguous span of output, finds the span's first
@@ -590,6 +593,274 @@ __global__ __launch_bounds__(TB) void k_collate_windows(const WinArgs a) {
     }
 }
 
+// ---- pairs --------------------------------------------------------------------------------------------------------
+// Row i is [bos] A' sep.. B' [eos] of document i of two ragged pairs.  With R = L - s ids of room
+// (s: bos, the separators, eos) the kept lengths (ka, kb) follow the truncation strategy; in the windows form the named
+// side is cut into windows of C = R - (ids kept of the other side) and row_offsets is the exclusive scan of the pairs'
+// window counts.  Either side's offsets may begin anywhere in its ids: document i of side X is valid when
+// 0 <= offsets_x[i] <= offsets_x[i + 1] <= cap_x; any other is reported and counts as empty.
+__device__ __forceinline__ int64_t side_len(int64_t o0, int64_t o1, int64_t cap, int32_t* err) {
+    if (o0 < 0 || o1 < o0 || o1 > cap) {
+        note_error(err, HUTK_E_ARG);
+        return 0;
+    }
+    return o1 - o0;
+}
+
+// the ids of A and B that stay in one row of R; longest_first is the closed form, not a loop
+__device__ __forceinline__ void pair_lengths(int64_t na, int64_t nb, int64_t R, int strategy, int32_t& ka, int32_t& kb) {
+    if (na + nb > R) {
+        if (strategy == HUTK_PAIR_ONLY_FIRST) {
+            nb = nb < R ? nb : R;
+            na = na < R - nb ? na : R - nb;
+        } else if (strategy == HUTK_PAIR_ONLY_SECOND) {
+            na = na < R ? na : R;
+            nb = nb < R - na ? nb : R - na;
+        } else {
+            const bool swap = na > nb;
+            int64_t n1 = swap ? nb : na, n2;  // the shorter and the longer side
+            n2 = n1 > R ? n1 : n1 > R - n1 ? n1 : R - n1;
+            if (n1 + n2 > R) {
+                n1 = R / 2;
+                n2 = n1 + R % 2;  // the longer side gets the odd id; on a tie that is B
+            }
+            na = swap ? n2 : n1;
+            nb = swap ? n1 : n2;
+        }
+    }
+    ka = (int32_t)na;
+    kb = (int32_t)nb;
+}
+
+// rows of one pair in the windows form: the cut side has n ids, the other one no.  C: the cut side's room per row
+__device__ __forceinline__ int64_t pair_window_count(int64_t n, int64_t no, int64_t R, int64_t stride, int64_t& C, int64_t& step) {
+    C = R - (no < R ? no : R);
+    step = C - stride > 1 ? C - stride : 1;
+    return n <= C || C == 0 ? 1 : 1 + (n - C + step - 1) / step;
+}
+
+struct PairRowArgs {
+    const int64_t *offs_a, *offs_b;
+    int64_t n_pairs, cap_a, cap_b;
+    int64_t R, stride;
+    int32_t cut_b;      // only_second: B is the side in windows
+    int64_t per_block;  // as WinRowArgs
+    int64_t* sums;
+    int64_t* row_offs;
+    int32_t* err;
+};
+
+__device__ __forceinline__ int64_t pair_rows_of(const PairRowArgs& a, int64_t i, int32_t* err) {
+    const int64_t na = side_len(a.offs_a[i], a.offs_a[i + 1], a.cap_a, err);
+    const int64_t nb = side_len(a.offs_b[i], a.offs_b[i + 1], a.cap_b, err);
+    int64_t C, step;
+    return a.cut_b ? pair_window_count(nb, na, a.R, a.stride, C, step) : pair_window_count(na, nb, a.R, a.stride, C, step);
+}
+
+__global__ __launch_bounds__(TB) void k_pair_count(const PairRowArgs a) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n_pairs ? lo + a.per_block : a.n_pairs;
+    int64_t mine = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += TB) mine += pair_rows_of(a, i, a.err);
+    int64_t total;
+    (void)block_excl_i64(mine, s_part, total);
+    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(TB) void k_pair_write(const PairRowArgs a) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n_pairs ? lo + a.per_block : a.n_pairs;
+    int64_t base = a.sums[blockIdx.x];
+    for (int64_t at = lo; at < hi; at += TB) {  // (uniform: every thread meets the barriers of the scan)
+        const int64_t i = at + threadIdx.x;
+        const int64_t w = i < hi ? pair_rows_of(a, i, nullptr) : 0;
+        int64_t total;
+        const int64_t before = block_excl_i64(w, s_part, total);
+        if (i < hi) a.row_offs[i] = base + before;
+        base += total;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.row_offs[a.n_pairs] = a.sums[gridDim.x];
+}
+
+struct PairArgs {
+    const int32_t *ids_a, *ids_b;
+    const int64_t *offs_a, *offs_b;
+    const int64_t* rows;  // row_offsets: the windows form; NULL: row i is pair i
+    int64_t n_pairs, cap_a, cap_b, n_rows;
+    int32_t L, s, R, stride, strategy;
+    int32_t bos, eos, pad;
+    int32_t sep0, sep1, sep2, sep3;  // (no array: a kernel argument indexed at run time lives in scratch)
+    int32_t has_bos, n_sep, pad_left;
+    void* out;
+    uint8_t* mask;
+    uint8_t* types;
+    int32_t* lengths;
+    int64_t* row_map;
+    int32_t* err;
+    int32_t rows_per_block;  // as PadArgs
+    int32_t col_chunks;
+};
+
+// last_doc_of_row over the pairs
+__device__ __forceinline__ int64_t last_pair_of_row(const PairArgs& a, int64_t x) {
+    int64_t lo = 0, hi = a.n_pairs;
+    const int lane = threadIdx.x & 63;
+    while (lo < hi) {
+        const int64_t step = (hi - lo + 63) >> 6;
+        const int64_t at = lo + lane * step;
+        const int hits = __popcll(__ballot(at < hi && a.rows[at] <= x));
+        const int64_t top = lo + hits * step;
+        if (hits) lo += (hits - 1) * step + 1;
+        hi = !hits ? lo : top < hi ? top : hi;
+    }
+    return lo - 1;
+}
+
+// The block shape of k_collate_padded and k_collate_windows.  Thread r places row r once: its pair (itself, or in the
+// windows form found among the staged row_offsets as k_collate_windows finds a document), both sides' offsets, ka, kb
+// and the window's start go to LDS; an element is then a few comparisons against the row's four boundaries and at most
+// one dword read.  Whatever the offsets hold, every index stays inside the offsets arrays and the two id buffers.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_pairs(const PairArgs a) {
+    __shared__ int64_t s_ro[PAD_ROWS + 1];
+    __shared__ int64_t s_srca[PAD_ROWS], s_srcb[PAD_ROWS];  // index of element q in ids_a / ids_b, less q
+    __shared__ int64_t s_start[PAD_ROWS];                   // of the row's window inside the cut side
+    __shared__ int32_t s_ka[PAD_ROWS], s_kb[PAD_ROWS], s_j[PAD_ROWS];
+    __shared__ int64_t s_d0;
+    const bool win = a.rows != nullptr;
+    if (win && (a.rows[0] != 0 || a.rows[a.n_pairs] != a.n_rows)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
+        return;
+    }
+    const int tid = threadIdx.x;
+    const int64_t blk = blockIdx.x;
+    const int64_t rg = blk / a.col_chunks;
+    const int32_t cc = (int32_t)(blk - rg * a.col_chunks);
+    const int64_t row0 = rg * a.rows_per_block;
+    const int64_t left = a.n_rows - row0;
+    const int32_t nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
+    if (nrows <= 0) return;
+    int64_t d0 = row0;  // the first pair of this workgroup's rows
+    int32_t nd = nrows;
+    if (win) {
+        if (tid < 64) {
+            const int64_t d = last_pair_of_row(a, row0);
+            if (tid == 0) s_d0 = d < 0 ? 0 : d;
+        }
+        __syncthreads();
+        d0 = s_d0;
+        nd = a.n_pairs - d0 < nrows ? (int32_t)(a.n_pairs - d0) : nrows;  // staged pairs, at least one
+        for (int32_t i = tid; i <= nd; i += TB) s_ro[i] = a.rows[d0 + i];
+        __syncthreads();
+    }
+    if (tid < nrows) {
+        int32_t lo = tid;
+        int64_t k = 0;
+        if (win) {
+            const int64_t row = row0 + tid;
+            int32_t hi = nd;  // the last staged pair whose first row is at or before this one
+            lo = 0;
+            while (hi - lo > 1) {
+                const int32_t mid = (lo + hi) >> 1;
+                if (s_ro[mid] <= row) lo = mid;
+                else hi = mid;
+            }
+            k = row - s_ro[lo];
+        }
+        const int64_t p = d0 + lo;
+        const int64_t a0 = a.offs_a[p], b0 = a.offs_b[p];
+        const int64_t na = side_len(a0, a.offs_a[p + 1], a.cap_a, a.err);
+        const int64_t nb = side_len(b0, a.offs_b[p + 1], a.cap_b, a.err);
+        int32_t ka = 0, kb = 0;
+        int64_t start = 0;
+        const bool cut_b = a.strategy == HUTK_PAIR_ONLY_SECOND;
+        if (!win) pair_lengths(na, nb, a.R, a.strategy, ka, kb);
+        else {
+            int64_t C, step;
+            const int64_t n = cut_b ? nb : na;
+            const int64_t w = pair_window_count(n, cut_b ? na : nb, a.R, a.stride, C, step);
+            if (k < 0 || k >= w) note_error(a.err, HUTK_E_ARG);  // (a row_offsets that is not the scan of the counts)
+            else {
+                start = k * step;  // < n, or 0
+                const int32_t kn = n - start < C ? (int32_t)(n - start) : (int32_t)C;
+                const int32_t ko = a.R - (int32_t)C;
+                ka = cut_b ? ko : kn;
+                kb = cut_b ? kn : ko;
+            }
+        }
+        s_j[tid] = lo;
+        s_start[tid] = start;
+        s_ka[tid] = ka;
+        s_kb[tid] = kb;
+        s_srca[tid] = a0 + (cut_b ? 0 : start) - a.has_bos;
+        s_srcb[tid] = b0 + (cut_b ? start : 0) - (a.has_bos + ka + a.n_sep);
+    }
+    __syncthreads();
+    const bool one_row = a.rows_per_block == 1;
+    const int32_t c0 = cc * PAD_TILE;
+    const int32_t ncols = one_row ? ((a.L - c0) < PAD_TILE ? (a.L - c0) : PAD_TILE) : a.L;
+    const int32_t total = nrows * ncols;
+    constexpr int V = VEC ? 4 : 1;
+    for (int32_t i = tid * V; i < total; i += TB * V) {
+        const int32_t rl = one_row ? 0 : i / a.L;
+        const int32_t c = one_row ? c0 + i : i - rl * a.L;
+        const int32_t ka = s_ka[rl], kb = s_kb[rl];
+        const int64_t srca = s_srca[rl], srcb = s_srcb[rl];
+        const int32_t end_a = a.has_bos + ka, end_sep = end_a + a.n_sep, end_b = end_sep + kb;
+        const int32_t sl = ka + kb + a.s;
+        const int32_t shift = a.pad_left ? a.L - sl : 0;
+        int32_t v[V];
+        uint8_t m[V], t[V];
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            const int32_t q = c + e - shift;
+            v[e] = a.pad;
+            m[e] = 0;
+            t[e] = 0;
+            if (q >= 0 && q < sl) {
+                m[e] = 1;
+                if (q < a.has_bos) v[e] = a.bos;
+                else if (q < end_a) {
+                    const int64_t idx = srca + q;
+                    if (idx >= 0 && idx < a.cap_a) v[e] = a.ids_a[idx];
+                    else note_error(a.err, HUTK_E_ARG);
+                } else if (q < end_sep) {
+                    const int32_t u = q - end_a;
+                    v[e] = u == 0 ? a.sep0 : u == 1 ? a.sep1 : u == 2 ? a.sep2 : a.sep3;
+                } else if (q < end_b) {
+                    t[e] = 1;
+                    const int64_t idx = srcb + q;
+                    if (idx >= 0 && idx < a.cap_b) v[e] = a.ids_b[idx];
+                    else note_error(a.err, HUTK_E_ARG);
+                } else {
+                    t[e] = 1;
+                    v[e] = a.eos;
+                }
+            }
+        }
+        const int64_t at = (row0 + rl) * (int64_t)a.L + c;
+        if constexpr (VEC) {
+            store4<W>(a.out, at, v);
+            if (a.mask) *reinterpret_cast<uchar4*>(a.mask + at) = make_uchar4(m[0], m[1], m[2], m[3]);
+            if (a.types) *reinterpret_cast<uchar4*>(a.types + at) = make_uchar4(t[0], t[1], t[2], t[3]);
+        } else {
+            store1<W>(a.out, at, v[0]);
+            if (a.mask) a.mask[at] = m[0];
+            if (a.types) a.types[at] = t[0];
+        }
+        if (c == 0) {
+            if (a.lengths) a.lengths[row0 + rl] = sl;
+            if (a.row_map) {
+                int64_t* rm = a.row_map + 2 * (row0 + rl);
+                if constexpr (VEC) *reinterpret_cast<longlong2*>(rm) = make_longlong2(d0 + s_j[rl], s_start[rl]);
+                else rm[0] = d0 + s_j[rl], rm[1] = s_start[rl];
+            }
+        }
+    }
+}
+
 bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 int device_present(const char* who) {
@@ -619,6 +890,52 @@ struct WinScratch {
 };
 std::mutex g_win_mu;
 std::map<int, WinScratch> g_win_scratch;
+
+// The current device's scratch, made at its first use there, with `st` waiting for the last call that used it.  The
+// caller holds g_win_mu until it has recorded the event behind its own kernels (scratch_used).
+int scratch_for(hipStream_t st, WinScratch** out) {
+    int device = 0;
+    HUTK_HIP_TRY(hipGetDevice(&device));
+    WinScratch& w = g_win_scratch[device];
+    if (!w.sums) {
+        HUTK_HIP_TRY(hipMalloc((void**)&w.sums, (WIN_BLOCKS + 1) * sizeof(int64_t)));
+        if (hipError_t e = hipEventCreateWithFlags(&w.ev, hipEventDisableTiming); e != hipSuccess) {
+            (void)hipFree(w.sums);
+            w.sums = nullptr;
+            HUTK_HIP_TRY(e);
+        }
+    }
+    if (w.ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
+    *out = &w;
+    return HUTK_OK;
+}
+
+int scratch_used(WinScratch* w, hipStream_t st) {
+    HUTK_HIP_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipEventRecord(w->ev, st));
+    w->ev_recorded = true;
+    return HUTK_OK;
+}
+
+// What the pair calls share: the sizes they refuse before anything else.  s (bos, separators, eos) and R = max_len - s
+// come back for the caller.
+int pair_sizes(const char* who, int64_t max_len, int64_t stride, int strategy, int32_t bos_id, const int32_t* sep_ids,
+               int n_sep, int32_t eos_id, int* s, int64_t* R) {
+    if (strategy != HUTK_PAIR_LONGEST_FIRST && strategy != HUTK_PAIR_ONLY_FIRST && strategy != HUTK_PAIR_ONLY_SECOND)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": strategy must be one of HUTK_PAIR_*");
+    if (n_sep < 0 || n_sep > HUTK_PAIR_MAX_SEP || (n_sep > 0 && !sep_ids))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": sep_ids must hold 0 .. 4 ids");
+    for (int i = 0; i < n_sep; i++)
+        if (sep_ids[i] == HUTK_NO_TOKEN)
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": sep_ids must not hold HUTK_NO_TOKEN");
+    *s = (bos_id != HUTK_NO_TOKEN) + n_sep + (eos_id != HUTK_NO_TOKEN);
+    if (max_len < 1 || max_len < *s + 1 || max_len > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": max_len must be above the number of bos/sep/eos tokens and below 2^31");
+    if (stride < 0 || stride >= max_len - *s)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": stride must be in 0 .. max_len - s - 1");
+    *R = max_len - *s;
+    return HUTK_OK;
+}
 
 }  // namespace
 
@@ -721,33 +1038,20 @@ int hutk_windows_rows_device(const int64_t* d_offsets, int64_t n_docs, int64_t n
     // at most WIN_BLOCKS workgroups: beyond WIN_BLOCKS * TB documents each takes several chunks of TB
     a.per_block = (n_docs + (int64_t)WIN_BLOCKS * TB - 1) / ((int64_t)WIN_BLOCKS * TB) * TB;
     const int64_t blocks = (n_docs + a.per_block - 1) / a.per_block;
-    int device = 0;
-    HUTK_HIP_TRY(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_win_mu);
-    WinScratch& w = g_win_scratch[device];
-    if (!w.sums) {
-        HUTK_HIP_TRY(hipMalloc((void**)&w.sums, (WIN_BLOCKS + 1) * sizeof(int64_t)));
-        if (hipError_t e = hipEventCreateWithFlags(&w.ev, hipEventDisableTiming); e != hipSuccess) {
-            (void)hipFree(w.sums);
-            w.sums = nullptr;
-            HUTK_HIP_TRY(e);
-        }
-    }
-    if (w.ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, w.ev, 0));
+    WinScratch* w;
+    if (int rc = scratch_for(st, &w)) return rc;
     a.offs = d_offsets;
     a.n_docs = n_docs;
     a.n_ids = n_ids;
-    a.sums = w.sums;
+    a.sums = w->sums;
     a.row_offs = d_row_offsets;
     a.err = d_err;
     const dim3 grid((unsigned)blocks), block(TB);
     hipLaunchKernelGGL(k_windows_count, grid, block, 0, st, a);
-    hutk::launch_scan_i64(w.sums, blocks, st);
+    hutk::launch_scan_i64(w->sums, blocks, st);
     hipLaunchKernelGGL(k_windows_write, grid, block, 0, st, a);
-    HUTK_HIP_TRY(hipGetLastError());
-    HUTK_HIP_TRY(hipEventRecord(w.ev, st));
-    w.ev_recorded = true;
-    return HUTK_OK;
+    return scratch_used(w, st);
 }
 
 int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, const int64_t* d_row_offsets,
@@ -804,6 +1108,136 @@ int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, 
     } else {
         if (vec) hipLaunchKernelGGL((k_collate_windows<8, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_collate_windows<8, false>), grid, block, 0, st, a);
+    }
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int64_t hutk_pair_rows_bound(int64_t n_pairs, int64_t n_cut_ids, int64_t max_len, int64_t stride, int s) {
+    int64_t C, step;
+    if (n_pairs < 0 || n_cut_ids < 0 || s < 0 || s > 2 + HUTK_PAIR_MAX_SEP) {
+        hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_bound: bad arguments");
+        return -HUTK_E_ARG;
+    }
+    if (window_sizes("hutk_pair_rows_bound", max_len, stride, s, &C, &step)) return -HUTK_E_ARG;
+    return n_pairs + n_cut_ids;  // a pair of n > C >= 1 cut ids has 1 + ceil((n - C) / step) <= n rows, as step >= 1
+}
+
+int hutk_pair_rows_device(const int64_t* d_offsets_a, const int64_t* d_offsets_b, int64_t n_pairs, int64_t cap_a,
+                          int64_t cap_b, int64_t max_len, int64_t stride, int strategy, int32_t bos_id,
+                          const int32_t* sep_ids, int n_sep, int32_t eos_id, int64_t* d_row_offsets, int32_t* d_err,
+                          void* hip_stream) {
+    if (n_pairs < 0 || cap_a < 0 || cap_b < 0) return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_device: bad arguments");
+    int s;
+    PairRowArgs a;
+    if (int rc = pair_sizes("hutk_pair_rows_device", max_len, stride, strategy, bos_id, sep_ids, n_sep, eos_id, &s, &a.R))
+        return rc;
+    if (strategy == HUTK_PAIR_LONGEST_FIRST)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_device: strategy must name the side that is cut into windows "
+                                               "(HUTK_PAIR_ONLY_FIRST or HUTK_PAIR_ONLY_SECOND)");
+    if (int rc = device_present("hutk_pair_rows_device")) return rc;
+    if (!d_row_offsets || (n_pairs > 0 && (!d_offsets_a || !d_offsets_b)))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_device: a buffer is NULL");
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_pairs == 0) {
+        HUTK_HIP_TRY(hipMemsetAsync(d_row_offsets, 0, sizeof(int64_t), st));
+        return HUTK_OK;
+    }
+    a.per_block = (n_pairs + (int64_t)WIN_BLOCKS * TB - 1) / ((int64_t)WIN_BLOCKS * TB) * TB;
+    const int64_t blocks = (n_pairs + a.per_block - 1) / a.per_block;
+    std::lock_guard<std::mutex> lock(g_win_mu);
+    WinScratch* w;
+    if (int rc = scratch_for(st, &w)) return rc;
+    a.offs_a = d_offsets_a;
+    a.offs_b = d_offsets_b;
+    a.n_pairs = n_pairs;
+    a.cap_a = cap_a;
+    a.cap_b = cap_b;
+    a.stride = stride;
+    a.cut_b = strategy == HUTK_PAIR_ONLY_SECOND;
+    a.sums = w->sums;
+    a.row_offs = d_row_offsets;
+    a.err = d_err;
+    const dim3 grid((unsigned)blocks), block(TB);
+    hipLaunchKernelGGL(k_pair_count, grid, block, 0, st, a);
+    hutk::launch_scan_i64(w->sums, blocks, st);
+    hipLaunchKernelGGL(k_pair_write, grid, block, 0, st, a);
+    return scratch_used(w, st);
+}
+
+int hutk_collate_pairs_device(const int32_t* d_ids_a, const int64_t* d_offsets_a, const int32_t* d_ids_b,
+                              const int64_t* d_offsets_b, const int64_t* d_row_offsets, int64_t n_pairs, int64_t cap_a,
+                              int64_t cap_b, int64_t n_rows, int64_t max_len, int64_t stride, int strategy,
+                              int32_t bos_id, const int32_t* sep_ids, int n_sep, int32_t eos_id, int32_t pad_id,
+                              int flags, int out_width, void* d_input_ids, uint8_t* d_mask, uint8_t* d_token_types,
+                              int32_t* d_lengths, int64_t* d_row_map, int32_t* d_err, void* hip_stream) {
+    if (n_pairs < 0 || cap_a < 0 || cap_b < 0 || n_rows < 0 || (out_width != 4 && out_width != 8) ||
+        (flags & ~HUTK_COLLATE_PAD_LEFT))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_pairs_device: bad arguments (of the flags, only "
+                                               "HUTK_COLLATE_PAD_LEFT applies)");
+    int s;
+    int64_t R;
+    if (int rc = pair_sizes("hutk_collate_pairs_device", max_len, stride, strategy, bos_id, sep_ids, n_sep, eos_id, &s, &R))
+        return rc;
+    if (d_row_offsets && strategy == HUTK_PAIR_LONGEST_FIRST)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_pairs_device: with d_row_offsets the strategy must name the side "
+                                               "that is cut into windows (HUTK_PAIR_ONLY_FIRST or HUTK_PAIR_ONLY_SECOND)");
+    if (!d_row_offsets && n_rows != n_pairs)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_pairs_device: without d_row_offsets n_rows must be n_pairs");
+    if (int rc = device_present("hutk_collate_pairs_device")) return rc;
+    if (n_pairs == 0) return HUTK_OK;
+    if (!d_offsets_a || !d_offsets_b || (n_rows > 0 && !d_input_ids) || (cap_a > 0 && !d_ids_a) || (cap_b > 0 && !d_ids_b))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_pairs_device: a buffer is NULL");
+    PairArgs a;
+    a.ids_a = d_ids_a;
+    a.ids_b = d_ids_b;
+    a.offs_a = d_offsets_a;
+    a.offs_b = d_offsets_b;
+    a.rows = d_row_offsets;
+    a.n_pairs = n_pairs;
+    a.cap_a = cap_a;
+    a.cap_b = cap_b;
+    a.n_rows = n_rows;
+    a.L = (int32_t)max_len;
+    a.s = s;
+    a.R = (int32_t)R;
+    a.stride = (int32_t)stride;
+    a.strategy = strategy;
+    a.bos = bos_id;
+    a.eos = eos_id;
+    a.pad = pad_id;
+    a.sep0 = n_sep > 0 ? sep_ids[0] : 0;
+    a.sep1 = n_sep > 1 ? sep_ids[1] : 0;
+    a.sep2 = n_sep > 2 ? sep_ids[2] : 0;
+    a.sep3 = n_sep > 3 ? sep_ids[3] : 0;
+    a.has_bos = bos_id != HUTK_NO_TOKEN;
+    a.n_sep = n_sep;
+    a.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
+    a.out = d_input_ids;
+    a.mask = d_mask;
+    a.types = d_token_types;
+    a.lengths = d_lengths;
+    a.row_map = d_row_map;
+    a.err = d_err;
+    int64_t rpb = PAD_TILE / max_len;
+    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
+    a.rows_per_block = (int32_t)rpb;
+    a.col_chunks = rpb == 1 ? (int32_t)((max_len + PAD_TILE - 1) / PAD_TILE) : 1;
+    int64_t blocks = (n_rows + rpb - 1) / rpb * a.col_chunks;
+    if (blocks < 1) blocks = 1;  // (n_rows == 0 with pairs: the kernel reports it)
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_pairs_device: the batch is too large for one launch");
+    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4) && aligned_to(d_token_types, 4) &&
+                     aligned_to(d_row_map, 16);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    const dim3 grid((unsigned)blocks), block(TB);
+    if (out_width == 4) {
+        if (vec) hipLaunchKernelGGL((k_collate_pairs<4, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_collate_pairs<4, false>), grid, block, 0, st, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_collate_pairs<8, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_collate_pairs<8, false>), grid, block, 0, st, a);
     }
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;

@@ -391,6 +391,54 @@ int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, 
                                 void* d_input_ids, uint8_t* d_mask, int32_t* d_lengths, int64_t* d_row_map,
                                 int32_t* d_err, void* hip_stream);
 
+/* PAIRS.  Two texts in one row: row i is [bos] A' sep_ids B' [eos] of document i of two ragged pairs on one device,
+ * (d_ids_a, d_offsets_a int64[n_pairs + 1]) and (d_ids_b, d_offsets_b).  Unlike the calls above, offsets_x[0] may be any
+ * base: document i of side X is d_ids_x[offsets_x[i] .. offsets_x[i + 1]) and 0 <= offsets_x[0] <= .. <=
+ * offsets_x[n_pairs] <= cap_x (the elements of d_ids_x) is what holds; both sides may share one ids buffer, and the
+ * offsets need only their own 8-byte alignment.  sep_ids: a HOST array of n_sep = 0 .. HUTK_PAIR_MAX_SEP ids, none of
+ * them HUTK_NO_TOKEN; s = [bos] + n_sep + [eos]; R = max_len - s >= 1 ids of room.  Both sides are cut on the right,
+ * A' = A[0 .. ka), B' = B[0 .. kb); with na + nb <= R nothing is cut, otherwise by strategy
+ *   HUTK_PAIR_LONGEST_FIRST  n1 <= n2 the shorter and longer length: n2 = n1 > R ? n1 : max(n1, R - n1); if still
+ *                            n1 + n2 > R: n1 = R / 2, n2 = n1 + R % 2 (the longer side gets the odd id, on a tie B)
+ *   HUTK_PAIR_ONLY_FIRST     kb = min(nb, R), ka = min(na, R - kb)
+ *   HUTK_PAIR_ONLY_SECOND    ka = min(na, R), kb = min(nb, R - ka)    (the side not named is cut only when it alone
+ *                            exceeds R)
+ * d_token_types uint8[n_rows][max_len] (may be NULL) is 0 on bos, A' and every separator, 1 on B' and eos, 0 on padding;
+ * d_lengths is ka + kb + s; d_mask and padding as in the padded rows.
+ *   the fill, one row per pair   d_row_offsets == NULL and n_rows == n_pairs; any strategy; stride is checked and unused.
+ *   the fill, windows            d_row_offsets from the rows call; HUTK_PAIR_ONLY_FIRST or _SECOND names the side that is
+ *                   cut into windows (HUTK_PAIR_LONGEST_FIRST: HUTK_E_ARG).  The other side keeps ko = min(no, R) ids and
+ *                   the cut side of n ids has C = R - ko ids of room per row: one row when n <= C or C == 0 (the cut
+ *                   side is then empty), else step = max(1, C - stride) and 1 + ceil((n - C) / step) rows, row k holding
+ *                   the cut side's ids [k * step, min(k * step + C, n)) with the whole kept side.  d_row_map
+ *                   int64[n_rows][2] = {pair, k * step} (may be NULL; the one-row form writes {pair, 0}).
+ *   the rows call   writes d_row_offsets int64[n_pairs + 1], the exclusive prefix sum of the pairs' row counts, always
+ *                   strictly increasing, in three launches that share the windows' per-device buffer.
+ *   the rows bound  host only: n_pairs + n_cut_ids (the ids of the cut side), at least n_rows for offsets that fit their
+ *                   condition; -HUTK_E_ARG for sizes the other calls refuse (s: 0 .. 6).
+ * *d_err receives HUTK_E_ARG for a document outside its condition (it counts as empty: its rows hold the other side,
+ * the template's tokens and padding), and in the windows form for d_row_offsets[0] != 0 or d_row_offsets[n_pairs] !=
+ * n_rows (nothing is written then) or an entry that is not the scan of the counts.  Every index is range-checked:
+ * nothing is read outside the offsets or the ids or written outside the n_rows rows.  n_pairs == 0 writes nothing.
+ * Refused with HUTK_E_ARG before a device is looked for: max_len < s + 1 or >= 2^31, stride < 0 or >= R, an unknown
+ * strategy, n_sep outside 0 .. 4 or an absent id in sep_ids, an out_width other than 4 or 8, any flag but
+ * HUTK_COLLATE_PAD_LEFT, negative counts. */
+#define HUTK_PAIR_LONGEST_FIRST 0
+#define HUTK_PAIR_ONLY_FIRST 1
+#define HUTK_PAIR_ONLY_SECOND 2
+#define HUTK_PAIR_MAX_SEP 4
+int64_t hutk_pair_rows_bound(int64_t n_pairs, int64_t n_cut_ids, int64_t max_len, int64_t stride, int s);
+int hutk_pair_rows_device(const int64_t* d_offsets_a, const int64_t* d_offsets_b, int64_t n_pairs, int64_t cap_a,
+                          int64_t cap_b, int64_t max_len, int64_t stride, int strategy, int32_t bos_id,
+                          const int32_t* sep_ids, int n_sep, int32_t eos_id, int64_t* d_row_offsets, int32_t* d_err,
+                          void* hip_stream);
+int hutk_collate_pairs_device(const int32_t* d_ids_a, const int64_t* d_offsets_a, const int32_t* d_ids_b,
+                              const int64_t* d_offsets_b, const int64_t* d_row_offsets, int64_t n_pairs, int64_t cap_a,
+                              int64_t cap_b, int64_t n_rows, int64_t max_len, int64_t stride, int strategy,
+                              int32_t bos_id, const int32_t* sep_ids, int n_sep, int32_t eos_id, int32_t pad_id,
+                              int flags, int out_width, void* d_input_ids, uint8_t* d_mask, uint8_t* d_token_types,
+                              int32_t* d_lengths, int64_t* d_row_map, int32_t* d_err, void* hip_stream);
+
 /* ---- token spans (offset mapping) ----------------------------------------------------------------------
  * Which stretch of its document each id covers: from the packed text (d_bytes, d_offsets) and the ragged pair that
  * hutk_encode_batch_device wrote for it (d_ids, d_id_offsets; n_ids as in the collation calls: d_id_offsets[n_docs] ==

@@ -627,20 +627,30 @@ def _out_width(dtype):
     return (4 if name == "int32" else 8), name
 
 
-def _ragged_args(ids, offsets, n_ids):
-    """The (ids, offsets) pair of encode_packed_device: device tensors, int32 and int64[n_docs + 1]."""
-    for name, t, want in (("ids", ids, "int32"), ("offsets", offsets, "int64")):
+def _device_tensors(named, sizes):
+    """named: (name, tensor, dtype name) of every argument that must be a one-dimensional contiguous torch tensor of that
+    dtype on the GPU.  What can be said without a GPU is said first: sizes() raises what the caller asks of the tensors'
+    lengths once they are known to be tensors of one dimension."""
+    for name, t, want in named:
         if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")):
             raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
         if str(t.dtype).rpartition(".")[2] != want:
             raise TypeError("%s must have dtype %s, not %s" % (name, want, t.dtype))
-    for name, t in (("ids", ids), ("offsets", offsets)):
+    for name, t, _want in named:
         if t.dim() != 1 or not t.is_contiguous():
             raise ValueError("%s must be one-dimensional and contiguous" % name)
+    sizes()
+    for name, t, _want in named:
         if not t.is_cuda:
             raise ValueError("%s must be on the GPU: the collation runs there and nowhere else" % name)
-    if offsets.numel() < 1:
-        raise ValueError("offsets must hold at least one entry")
+
+
+def _ragged_args(ids, offsets, n_ids):
+    """The (ids, offsets) pair of encode_packed_device: device tensors, int32 and int64[n_docs + 1]."""
+    def sizes():
+        if offsets.numel() < 1:
+            raise ValueError("offsets must hold at least one entry")
+    _device_tensors((("ids", ids, "int32"), ("offsets", offsets, "int64")), sizes)
     if ids.device != offsets.device:
         raise ValueError("ids and offsets must be on the same device")
     if n_ids is not None:
@@ -662,6 +672,28 @@ def _raise_device_error(err, what):
     code = int(err.item())
     if code:
         raise ValueError("hutoken_amd: %s: device-side error %d (offsets that do not describe ids)" % (what, code))
+
+
+def _n_rows_arg(n_rows):
+    if n_rows is not None:
+        if isinstance(n_rows, bool) or not isinstance(n_rows, int):
+            raise TypeError("n_rows must be an int or None")
+        if n_rows < 0:
+            raise ValueError("n_rows must not be negative")
+
+
+def _row_tensors(dev, n_rows, max_length, dname, types=False, row_map=False):
+    """The outputs of a row layout, in the order the collate_* functions return them:
+    (input_ids, attention_mask[, token_type_ids], lengths[, row_map])."""
+    import torch
+    res = [torch.empty((n_rows, max_length), dtype=getattr(torch, dname), device=dev),
+           torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)]
+    if types:
+        res.append(torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev))
+    res.append(torch.empty(n_rows, dtype=torch.int32, device=dev))
+    if row_map:
+        res.append(torch.empty((n_rows, 2), dtype=torch.int64, device=dev))
+    return tuple(res)
 
 
 _SIDES = ("right", "left")
@@ -694,9 +726,7 @@ def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, p
     if max_length is None:
         longest = int((offsets[1:] - offsets[:-1]).max().item()) if n_docs else 0
         max_length = _length_arg("max_length", max(1, s, longest + s), 1)
-    out = torch.empty((n_docs, max_length), dtype=getattr(torch, dname), device=dev)
-    mask = torch.empty((n_docs, max_length), dtype=torch.uint8, device=dev)
-    lengths = torch.empty(n_docs, dtype=torch.int32, device=dev)
+    out, mask, lengths = _row_tensors(dev, n_docs, max_length, dname)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     flags = (_capi.COLLATE_TRUNC_LEFT if truncation == "left" else 0) | \
             (_capi.COLLATE_PAD_LEFT if padding_side == "left" else 0)
@@ -738,11 +768,7 @@ def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=N
     if padding_side not in _SIDES:
         raise ValueError("padding_side must be 'right' or 'left', not %r" % (padding_side,))
     width, dname = _out_width(dtype)
-    if n_rows is not None:
-        if isinstance(n_rows, bool) or not isinstance(n_rows, int):
-            raise TypeError("n_rows must be an int or None")
-        if n_rows < 0:
-            raise ValueError("n_rows must not be negative")
+    _n_rows_arg(n_rows)
     _ragged_args(ids, offsets, n_ids)
     import torch
     dev = ids.device
@@ -758,10 +784,7 @@ def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=N
             n_rows = int(row_offsets[-1].item())  # the one synchronisation; pass n_rows= to avoid it
             if n_rows < n_docs or n_rows > _capi.windows_rows_bound(n_docs, n_ids, max_length, stride, s):
                 raise ValueError("hutoken_amd: collate_windows: offsets that do not describe ids (%d rows)" % n_rows)
-        out = torch.empty((n_rows, max_length), dtype=getattr(torch, dname), device=dev)
-        mask = torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)
-        lengths = torch.empty(n_rows, dtype=torch.int32, device=dev)
-        row_map = torch.empty((n_rows, 2), dtype=torch.int64, device=dev)
+        out, mask, lengths, row_map = _row_tensors(dev, n_rows, max_length, dname, row_map=True)
         _capi.collate_windows_device(ids.data_ptr(), offsets.data_ptr(), row_offsets.data_ptr(), n_docs, n_ids, n_rows,
                                      max_length, stride, bos, eos, pad,
                                      _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0, width, out.data_ptr(),
@@ -859,22 +882,15 @@ def _pair_args(ids_a, offsets_a, ids_b, offsets_b):
     """The two ragged pairs of collate_pairs: device tensors on one device, as many documents on both sides."""
     four = (("ids_a", ids_a, "int32"), ("offsets_a", offsets_a, "int64"), ("ids_b", ids_b, "int32"),
             ("offsets_b", offsets_b, "int64"))
-    for name, t, want in four:
-        if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")):
-            raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
-        if str(t.dtype).rpartition(".")[2] != want:
-            raise TypeError("%s must have dtype %s, not %s" % (name, want, t.dtype))
+
+    def sizes():
+        if offsets_a.numel() < 1:
+            raise ValueError("offsets_a must hold at least one entry")
+        if offsets_a.numel() != offsets_b.numel():
+            raise ValueError("offsets_a and offsets_b must describe as many documents (%d and %d)"
+                             % (offsets_a.numel() - 1, offsets_b.numel() - 1))
+    _device_tensors(four, sizes)
     for name, t, _want in four:
-        if t.dim() != 1 or not t.is_contiguous():
-            raise ValueError("%s must be one-dimensional and contiguous" % name)
-    if offsets_a.numel() < 1:
-        raise ValueError("offsets_a must hold at least one entry")
-    if offsets_a.numel() != offsets_b.numel():
-        raise ValueError("offsets_a and offsets_b must describe as many documents (%d and %d)"
-                         % (offsets_a.numel() - 1, offsets_b.numel() - 1))
-    for name, t, _want in four:
-        if not t.is_cuda:
-            raise ValueError("%s must be on the GPU: the collation runs there and nowhere else" % name)
         if t.device != ids_a.device:
             raise ValueError("%s must be on the same device as ids_a" % name)
 
@@ -916,10 +932,7 @@ def collate_pairs(ids_a, offsets_a, ids_b, offsets_b, max_length=None, *, trunca
     if max_length is None:
         both = (offsets_a[1:] - offsets_a[:-1]).clamp_(min=0) + (offsets_b[1:] - offsets_b[:-1]).clamp_(min=0)
         max_length = _length_arg("max_length", s + max(1, int(both.max().item()) if n else 1), s + 1)
-    out = torch.empty((n, max_length), dtype=getattr(torch, dname), device=dev)
-    mask = torch.empty((n, max_length), dtype=torch.uint8, device=dev)
-    types = torch.empty((n, max_length), dtype=torch.uint8, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    out, mask, types, lengths = _row_tensors(dev, n, max_length, dname, types=True)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     flags = _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0
 
@@ -955,11 +968,7 @@ def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=
                          "product of both sides' windows, which this does not produce")
     _length_arg("max_length", max_length, s + 1)
     _stride_arg(stride, max_length - s)
-    if n_rows is not None:
-        if isinstance(n_rows, bool) or not isinstance(n_rows, int):
-            raise TypeError("n_rows must be an int or None")
-        if n_rows < 0:
-            raise ValueError("n_rows must not be negative")
+    _n_rows_arg(n_rows)
     _pair_args(ids_a, offsets_a, ids_b, offsets_b)
     import torch
     dev = ids_a.device
@@ -982,11 +991,7 @@ def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=
             n_rows = int(row_offsets[-1].item())  # the one synchronisation; pass n_rows= to avoid it
             if not n <= n_rows <= bound:
                 raise ValueError("hutoken_amd: collate_pair_windows: offsets that do not describe ids (%d rows)" % n_rows)
-        out = torch.empty((n_rows, max_length), dtype=getattr(torch, dname), device=dev)
-        mask = torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)
-        types = torch.empty((n_rows, max_length), dtype=torch.uint8, device=dev)
-        lengths = torch.empty(n_rows, dtype=torch.int32, device=dev)
-        row_map = torch.empty((n_rows, 2), dtype=torch.int64, device=dev)
+        out, mask, types, lengths, row_map = _row_tensors(dev, n_rows, max_length, dname, types=True, row_map=True)
         _capi.collate_pairs_device(ids_a.data_ptr(), offsets_a.data_ptr(), ids_b.data_ptr(), offsets_b.data_ptr(),
                                    row_offsets.data_ptr(), n, cap_a, cap_b, n_rows, max_length, stride, strategy, bos, sep,
                                    eos, pad, flags, width, out.data_ptr(), mask.data_ptr(), types.data_ptr(),

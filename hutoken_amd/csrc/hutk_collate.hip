@@ -1,34 +1,39 @@
 // hutk_collate.hip -- collation of encoded batches on the GPU: the ragged (ids, offsets) pair that hutk_encode_batch_device
-// writes becomes what a model reads.  Two layouts (include/hutoken_amd.h):
+// writes becomes what a model reads.  Two families of layouts (include/hutoken_amd.h):
 //
-//   padded   one document per row of max_len elements: [bos] ids [eos], truncated, padded left or right, with the
-//            attention mask and the lengths                                            (k_collate_padded)
+//   rows     a row of max_len elements is [bos] A' sep.. B' [eos], padded left or right, with the attention mask and the
+//            lengths.  ONE writer (write_rows) turns a planned row into elements; a kernel is a planner that says which
+//            item a row belongs to, where its ids start and how many stay, and then calls the writer:
+//              padded   row i is document i, truncated on either side                   (k_collate_padded)
+//              windows  a document longer than max_len - s is cut into overlapping windows, with a map from rows back to
+//                       documents                                                       (k_collate_windows)
+//              pairs    document i of two ragged pairs in one row, cut by one of three strategies, with token type ids;
+//                       or the named side in windows, the other side whole in every row (k_collate_pairs)
+//            The rows' places in the two windows forms come from ONE count, scan, write over the items first
+//            (k_rows_count, k_rows_write over "rows of item i": DocRows, PairRows).
 //   packed   the sequences of all documents laid end to end and cut into rows of seq_len, with position and segment
 //            ids; the unfinished row is carried over to the next call                  (k_collate_packed, k_collate_flush)
-//   windows  a document longer than max_len - s is cut into overlapping windows, every window a padded row, with a map
-//            from rows back to documents; the rows' places come from a count, scan, write over the documents first
-//                                                  (k_windows_count, k_windows_write, k_collate_windows)
-//   pairs    document i of two ragged pairs in one row, [bos] A sep.. B [eos], cut by one of three strategies, with
-//            token type ids; or the named side in windows, the other side whole in every row
-//                                                  (k_pair_count, k_pair_write, k_collate_pairs)
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
-// length allows.  No element searches the offsets: a workgroup owns a contiguous span of output, finds the span's first
-// document with one search by a wavefront, marks the sequence starts of its span in LDS and turns the marks into "document
-// of this position", "where its sequence starts" and "starts since the row began" with one workgroup scan.
+// length allows.  No element searches the offsets.  A workgroup of the row layouts stages the plan of its rows in LDS
+// once; one of the packed layout owns a contiguous span of output, finds the span's first document with one search by a
+// wavefront, marks the sequence starts of its span in LDS and turns the marks into "document of this position", "where
+// its sequence starts" and "starts since the row began" with one workgroup scan.
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "hutk_host.h"
+#include "hutk_wave.h"
 
 namespace {
 
 constexpr int TB = 256;          // threads per workgroup
 constexpr int SPAN = 2048;       // packed: stream positions per workgroup (8 per thread)
 constexpr int PER = SPAN / TB;   // packed: positions a thread scans
-constexpr int PAD_TILE = 4096;   // padded: output elements per workgroup
-constexpr int PAD_ROWS = 256;    // padded: most rows per workgroup
+constexpr int PAD_TILE = 4096;   // rows: output elements per workgroup
+constexpr int PAD_ROWS = 256;    // rows: most rows per workgroup
 
 __device__ __forceinline__ void note_error(int32_t* err, int code) {
     if (err) atomicCAS(err, 0, code);
@@ -51,86 +56,155 @@ __device__ __forceinline__ void store1(void* base, int64_t i, int32_t v) {
     else static_cast<int64_t*>(base)[i] = v;
 }
 
-// ---- padded -------------------------------------------------------------------------------------------------------
-struct PadArgs {
-    const int32_t* ids;
-    const int64_t* offs;
-    int64_t n_docs, n_ids;
-    int32_t L, s;
+// ---- rows: the tile and the writer ----------------------------------------------------------------------------------
+// What the writer reads, the same for every row layout.  Padded and windows have one side, A; what only pairs have
+// stays unset there and is never read (write_rows<.., PAIR = false>).
+struct RowArgs {
+    const int32_t *ids_a, *ids_b;
+    int64_t cap_a, cap_b;  // elements of ids_a / ids_b: no id is read from outside them
+    int32_t L, s;          // row length; bos, separators and eos together
     int32_t bos, eos, pad;
-    int32_t has_bos, has_eos, trunc_left, pad_left;
+    int32_t sep0, sep1, sep2, sep3;  // (no array: a kernel argument indexed at run time lives in scratch)
+    int32_t has_bos, n_sep, pad_left;
     void* out;
     uint8_t* mask;
+    uint8_t* types;
     int32_t* lengths;
+    int64_t* row_map;  // NULL: none (padded, pairs without windows)
     int32_t* err;
     int32_t rows_per_block;  // > 1 only when rows_per_block * L <= PAD_TILE
     int32_t col_chunks;      // pieces of PAD_TILE columns a row is cut into (1 unless rows_per_block == 1)
 };
 
-// A workgroup writes `rows_per_block` whole rows, or PAD_TILE columns of one long row.  The offsets of its rows are staged
-// in LDS once; an element is then a few integer operations and (inside the document) one dword read.
-template <int W, bool VEC>
-__global__ __launch_bounds__(TB) void k_collate_padded(const PadArgs a) {
-    __shared__ int64_t s_off[PAD_ROWS + 1];
-    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids) {  // nothing is read through offsets that do not fit the ids
-        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
-        return;
-    }
+// A workgroup writes `rows_per_block` whole rows, or PAD_TILE columns of one long row: rows row0 .. row0 + nrows - 1,
+// of each the columns c0 .. c0 + ncols - 1.  nrows <= 0: the workgroup has nothing to write.
+struct RowTile {
+    int64_t row0;
+    int32_t nrows, c0, ncols, total;
+    bool one_row;
+};
+
+__device__ __forceinline__ RowTile row_tile(const RowArgs& a, int64_t n_rows) {
+    RowTile t;
     const int64_t blk = blockIdx.x;
     const int64_t rg = blk / a.col_chunks;
     const int32_t cc = (int32_t)(blk - rg * a.col_chunks);
-    const int64_t row0 = rg * a.rows_per_block;
-    const int64_t left = a.n_docs - row0;
-    const int32_t nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
-    for (int32_t i = threadIdx.x; i <= nrows; i += TB) s_off[i] = a.offs[row0 + i];
-    __syncthreads();
-    const bool one_row = a.rows_per_block == 1;
-    const int32_t c0 = cc * PAD_TILE;
-    const int32_t ncols = one_row ? ((a.L - c0) < PAD_TILE ? (a.L - c0) : PAD_TILE) : a.L;
-    const int32_t total = nrows * ncols;
+    t.row0 = rg * a.rows_per_block;
+    const int64_t left = n_rows - t.row0;
+    t.nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
+    t.one_row = a.rows_per_block == 1;
+    t.c0 = cc * PAD_TILE;
+    t.ncols = t.one_row ? ((a.L - t.c0) < PAD_TILE ? (a.L - t.c0) : PAD_TILE) : a.L;
+    t.total = t.nrows * t.ncols;
+    return t;
+}
+
+// One planned row: ka ids of A and kb ids of B stay (kb: pairs only).  Element q of the unpadded row that is an id of A
+// is ids_a[srca + q], one of B ids_b[srcb + q].  (item, start) is the row's entry of row_map.
+struct RowPlan {
+    int32_t ka, kb;
+    int64_t srca, srcb;
+    int64_t item, start;
+};
+
+// The elements of a tile, V neighbours per thread (VEC: the row length is a multiple of 4 and the outputs are aligned).
+// plan(r) gives the plan of the tile's row r from wherever the calling kernel keeps it; an element is then a few
+// comparisons against the row's boundaries and at most one dword read.  PAIR = false compiles the separators, the B side
+// and the token types away.  Whatever a plan holds, no id is read from outside ids_a[0, cap_a) and ids_b[0, cap_b).
+template <int W, bool VEC, bool PAIR, class Plan>
+__device__ __forceinline__ void write_rows(const RowArgs& a, const RowTile& t, Plan plan) {
     constexpr int V = VEC ? 4 : 1;
-    const int32_t room = a.L - a.s;
-    for (int32_t i = threadIdx.x * V; i < total; i += TB * V) {
-        const int32_t rl = one_row ? 0 : i / a.L;
-        const int32_t c = one_row ? c0 + i : i - rl * a.L;
-        const int64_t o0 = s_off[rl], o1 = s_off[rl + 1];
-        int64_t dl = o1 - o0;
-        if (dl < 0) {
-            dl = 0;
-            note_error(a.err, HUTK_E_ARG);
-        }
-        const int32_t n = dl > room ? room : (int32_t)dl;  // the document's own ids that stay
-        const int64_t src = a.trunc_left ? o1 - n : o0;
-        const int32_t sl = n + a.s;
+    for (int32_t i = threadIdx.x * V; i < t.total; i += TB * V) {
+        const int32_t rl = t.one_row ? 0 : i / a.L;
+        const int32_t c = t.one_row ? t.c0 + i : i - rl * a.L;
+        const RowPlan p = plan(rl);
+        const int32_t end_a = a.has_bos + p.ka;
+        const int32_t end_sep = PAIR ? end_a + a.n_sep : end_a, end_b = PAIR ? end_sep + p.kb : end_a;
+        const int32_t sl = p.ka + (PAIR ? p.kb : 0) + a.s;
         const int32_t shift = a.pad_left ? a.L - sl : 0;
         int32_t v[V];
-        uint8_t m[V];
+        uint8_t m[V], ty[V];
 #pragma unroll
         for (int e = 0; e < V; e++) {
             const int32_t q = c + e - shift;
             v[e] = a.pad;
             m[e] = 0;
+            ty[e] = 0;
             if (q >= 0 && q < sl) {
                 m[e] = 1;
-                if (a.has_bos && q == 0) v[e] = a.bos;
-                else if (a.has_eos && q == sl - 1) v[e] = a.eos;
-                else {
-                    const int64_t idx = src + q - a.has_bos;
-                    if (idx >= 0 && idx < a.n_ids) v[e] = a.ids[idx];
+                if (q < a.has_bos) v[e] = a.bos;
+                else if (q < end_a) {
+                    const int64_t idx = p.srca + q;
+                    if (idx >= 0 && idx < a.cap_a) v[e] = a.ids_a[idx];
                     else note_error(a.err, HUTK_E_ARG);
+                } else if (PAIR && q < end_sep) {
+                    const int32_t u = q - end_a;
+                    v[e] = u == 0 ? a.sep0 : u == 1 ? a.sep1 : u == 2 ? a.sep2 : a.sep3;
+                } else if (PAIR && q < end_b) {
+                    ty[e] = 1;
+                    const int64_t idx = p.srcb + q;
+                    if (idx >= 0 && idx < a.cap_b) v[e] = a.ids_b[idx];
+                    else note_error(a.err, HUTK_E_ARG);
+                } else {
+                    ty[e] = 1;
+                    v[e] = a.eos;
                 }
             }
         }
-        const int64_t at = (row0 + rl) * (int64_t)a.L + c;
+        const int64_t at = (t.row0 + rl) * (int64_t)a.L + c;
         if constexpr (VEC) {
             store4<W>(a.out, at, v);
             if (a.mask) *reinterpret_cast<uchar4*>(a.mask + at) = make_uchar4(m[0], m[1], m[2], m[3]);
+            if (PAIR && a.types) *reinterpret_cast<uchar4*>(a.types + at) = make_uchar4(ty[0], ty[1], ty[2], ty[3]);
         } else {
             store1<W>(a.out, at, v[0]);
             if (a.mask) a.mask[at] = m[0];
+            if (PAIR && a.types) a.types[at] = ty[0];
         }
-        if (c == 0 && a.lengths) a.lengths[row0 + rl] = sl;
+        if (c == 0) {
+            if (a.lengths) a.lengths[t.row0 + rl] = sl;
+            if (a.row_map) {
+                int64_t* rm = a.row_map + 2 * (t.row0 + rl);
+                if constexpr (VEC) *reinterpret_cast<longlong2*>(rm) = make_longlong2(p.item, p.start);
+                else rm[0] = p.item, rm[1] = p.start;
+            }
+        }
     }
+}
+
+// ---- padded -------------------------------------------------------------------------------------------------------
+struct PadArgs {
+    RowArgs r;  // (ids_a, cap_a: the ids and their number)
+    const int64_t* offs;
+    int64_t n_docs;
+    int32_t trunc_left;
+};
+
+// Row i is document i.  The offsets of the tile's rows are staged in LDS once and ARE the plan: what stays of a
+// document follows from its two offsets in a few integer operations.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_padded(const PadArgs a) {
+    __shared__ int64_t s_off[PAD_ROWS + 1];
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.r.cap_a) {  // nothing is read through offsets that do not fit the ids
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.r.err, HUTK_E_ARG);
+        return;
+    }
+    const RowTile t = row_tile(a.r, a.n_docs);
+    for (int32_t i = threadIdx.x; i <= t.nrows; i += TB) s_off[i] = a.offs[t.row0 + i];
+    __syncthreads();
+    const int32_t room = a.r.L - a.r.s;
+    write_rows<W, VEC, false>(a.r, t, [&](int32_t rl) {
+        const int64_t o0 = s_off[rl], o1 = s_off[rl + 1];
+        int64_t dl = o1 - o0;
+        if (dl < 0) {
+            dl = 0;
+            note_error(a.r.err, HUTK_E_ARG);
+        }
+        RowPlan p{};
+        p.ka = dl > room ? room : (int32_t)dl;  // the document's own ids that stay
+        p.srca = (a.trunc_left ? o1 - p.ka : o0) - a.r.has_bos;
+        return p;
+    });
 }
 
 // ---- packed -------------------------------------------------------------------------------------------------------
@@ -155,21 +229,10 @@ struct PackArgs {
     int32_t spans_per_row;   // L >= SPAN: workgroups per row
 };
 
-// last document whose sequence begins at or before stream position x; -1 when none does.  One wavefront searches: each
-// round its 64 lanes probe evenly spaced documents of the range and count the hits, so 2^20 documents take four dependent
-// loads where a binary search takes twenty.  All 64 lanes must call it; all get the answer.
+// last document whose sequence begins at or before stream position x; -1 when none does.  All 64 lanes of a wavefront
+// must call it; all get the answer.
 __device__ __forceinline__ int64_t last_doc_le(const PackArgs& a, int64_t x) {
-    int64_t lo = 0, hi = a.n_docs;  // documents below lo begin at or before x, those from hi on behind it
-    const int lane = threadIdx.x & 63;
-    while (lo < hi) {
-        const int64_t step = (hi - lo + 63) >> 6;
-        const int64_t at = lo + lane * step;
-        const int hits = __popcll(__ballot(at < hi && a.P + a.offs[at] + at * a.s <= x));
-        const int64_t top = lo + hits * step;  // the first probe that missed
-        if (hits) lo += (hits - 1) * step + 1;
-        hi = !hits ? lo : top < hi ? top : hi;
-    }
-    return lo - 1;
+    return hutk::wave_count_leading(a.n_docs, [&](int64_t j) { return a.P + a.offs[j] + j * a.s <= x; }) - 1;
 }
 
 template <int W, bool VEC>
@@ -377,12 +440,81 @@ __global__ __launch_bounds__(TB) void k_collate_flush(const int32_t* c_ids, cons
     }
 }
 
-// ---- windows ------------------------------------------------------------------------------------------------------
-// Document i of n ids gives w(n) rows: one when n <= C (C = L - s ids fit a row), else 1 + ceil((n - C) / step) with
-// step = C - stride; row k of it holds the document's ids [k * step, min(k * step + C, n)).  row_offsets is the
-// exclusive scan of w.  A length that cannot be (negative, above n_ids) is reported and counted as the nearest that can.
+// ---- the rows scan --------------------------------------------------------------------------------------------------
+// In the two windows forms item i (a document, a pair) gives rows(i) >= 1 rows, and row_offsets is the exclusive scan
+// of rows: a count per workgroup, one k_scan_i64 launch over the workgroups' sums, and the write.  `Rows` is "rows of
+// item i": rows(i, err) reports what is wrong with the item to err (NULL in the write: it was reported in the count).
 constexpr int WIN_BLOCKS = 4096;  // most workgroups of the count: one k_scan_i64 launch scans their sums
 
+struct ScanArgs {
+    int64_t n;          // items
+    int64_t per_block;  // items per workgroup, a multiple of TB
+    int64_t* sums;      // [gridDim.x + 1]: the workgroups' row counts, then (launch_scan_i64) their exclusive scan and the sum
+    int64_t* row_offs;
+    int32_t* err;
+};
+
+template <class Rows>
+__global__ __launch_bounds__(TB) void k_rows_count(const ScanArgs a, const Rows rows) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n ? lo + a.per_block : a.n;
+    int64_t mine = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += TB) mine += rows(i, a.err);
+    int64_t total;
+    (void)hutk::block_excl(mine, s_part, total);
+    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+}
+
+template <class Rows>
+__global__ __launch_bounds__(TB) void k_rows_write(const ScanArgs a, const Rows rows) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n ? lo + a.per_block : a.n;
+    int64_t base = a.sums[blockIdx.x];
+    for (int64_t at = lo; at < hi; at += TB) {  // (uniform: every thread meets the barriers of the scan)
+        const int64_t i = at + threadIdx.x;
+        const int64_t w = i < hi ? rows(i, nullptr) : 0;
+        int64_t total;
+        const int64_t before = hutk::block_excl(w, s_part, total);
+        if (i < hi) a.row_offs[i] = base + before;
+        base += total;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.row_offs[a.n] = a.sums[gridDim.x];
+}
+
+// The items of a tile's rows in the windows forms.  They are at most as many consecutive items as the tile has rows
+// (row_offsets grows strictly), beginning with the last one whose first row is at or before the tile's first, which a
+// wavefront finds.  Returns that item (at least 0) and stages row_offsets of it and the nd - 1 behind it, and of the one
+// behind those, in s_ro; the caller's barrier makes them visible.  Every thread of the workgroup must call it.
+__device__ __forceinline__ int64_t stage_items(const int64_t* row_offs, int64_t n, const RowTile& t, int64_t* s_ro,
+                                               int64_t* s_d0, int32_t& nd) {
+    if (threadIdx.x < 64) {
+        const int64_t d = hutk::wave_count_leading(n, [&](int64_t i) { return row_offs[i] <= t.row0; }) - 1;
+        if (threadIdx.x == 0) *s_d0 = d < 0 ? 0 : d;
+    }
+    __syncthreads();
+    const int64_t d0 = *s_d0;
+    nd = n - d0 < t.nrows ? (int32_t)(n - d0) : t.nrows;  // staged items, at least one
+    for (int32_t i = threadIdx.x; i <= nd; i += TB) s_ro[i] = row_offs[d0 + i];
+    return d0;
+}
+
+// the last of the nd staged items whose first row is at or before `row`
+__device__ __forceinline__ int32_t staged_item_of_row(const int64_t* s_ro, int32_t nd, int64_t row) {
+    int32_t lo = 0, hi = nd;
+    while (hi - lo > 1) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (s_ro[mid] <= row) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ---- windows ------------------------------------------------------------------------------------------------------
+// Document i of n ids gives w(n) rows: one when n <= C (C = L - s ids fit a row), else 1 + ceil((n - C) / step) with
+// step = C - stride; row k of it holds the document's ids [k * step, min(k * step + C, n)).  A length that cannot be
+// (negative, above n_ids) is reported and counted as the nearest that can.
 __device__ __forceinline__ int64_t window_count(int64_t dl, int64_t n_ids, int64_t C, int64_t step, int32_t* err) {
     if (dl < 0 || dl > n_ids) {
         note_error(err, HUTK_E_ARG);
@@ -391,149 +523,54 @@ __device__ __forceinline__ int64_t window_count(int64_t dl, int64_t n_ids, int64
     return dl <= C ? 1 : 1 + (dl - C + step - 1) / step;
 }
 
-// exclusive scan over the 256 threads of a workgroup; total: the sum.  s_part: four values of LDS, free again after the call
-__device__ __forceinline__ int64_t block_excl_i64(int64_t v, int64_t* s_part, int64_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t p = __shfl_up(incl, off);
-        if (lane >= off) incl += p;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int64_t before = incl - v;
-    total = 0;
-#pragma unroll
-    for (int u = 0; u < TB / 64; u++) {
-        if (u < wave) before += s_part[u];
-        total += s_part[u];
-    }
-    __syncthreads();
-    return before;
-}
-
-struct WinRowArgs {
+struct DocRows {
     const int64_t* offs;
     int64_t n_docs, n_ids;
     int64_t C, step;
-    int64_t per_block;  // documents per workgroup, a multiple of TB
-    int64_t* sums;      // [gridDim.x + 1]: the workgroups' row counts, then (launch_scan_i64) their exclusive scan and the sum
-    int64_t* row_offs;
-    int32_t* err;
-};
-
-__global__ __launch_bounds__(TB) void k_windows_count(const WinRowArgs a) {
-    __shared__ int64_t s_part[TB / 64];
-    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
-    const int64_t hi = lo + a.per_block < a.n_docs ? lo + a.per_block : a.n_docs;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids)) note_error(a.err, HUTK_E_ARG);
-    int64_t mine = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += TB) mine += window_count(a.offs[i + 1] - a.offs[i], a.n_ids, a.C, a.step, a.err);
-    int64_t total;
-    (void)block_excl_i64(mine, s_part, total);
-    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(TB) void k_windows_write(const WinRowArgs a) {
-    __shared__ int64_t s_part[TB / 64];
-    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
-    const int64_t hi = lo + a.per_block < a.n_docs ? lo + a.per_block : a.n_docs;
-    int64_t base = a.sums[blockIdx.x];
-    for (int64_t at = lo; at < hi; at += TB) {  // (uniform: every thread meets the barriers of the scan)
-        const int64_t i = at + threadIdx.x;
-        const int64_t w = i < hi ? window_count(a.offs[i + 1] - a.offs[i], a.n_ids, a.C, a.step, nullptr) : 0;
-        int64_t total;
-        const int64_t before = block_excl_i64(w, s_part, total);
-        if (i < hi) a.row_offs[i] = base + before;
-        base += total;
+    __device__ int64_t operator()(int64_t i, int32_t* err) const {
+        if (i == 0 && (offs[0] != 0 || offs[n_docs] != n_ids)) note_error(err, HUTK_E_ARG);
+        return window_count(offs[i + 1] - offs[i], n_ids, C, step, err);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.row_offs[a.n_docs] = a.sums[gridDim.x];
-}
+};
 
 struct WinArgs {
-    const int32_t* ids;
+    RowArgs r;  // (ids_a, cap_a: the ids and their number)
     const int64_t* offs;
     const int64_t* rows;  // row_offsets
-    int64_t n_docs, n_ids, n_rows;
-    int32_t L, s, C, step;
-    int32_t bos, eos, pad;
-    int32_t has_bos, has_eos, pad_left;
-    void* out;
-    uint8_t* mask;
-    int32_t* lengths;
-    int64_t* row_map;
-    int32_t* err;
-    int32_t rows_per_block;  // as PadArgs
-    int32_t col_chunks;
+    int64_t n_docs, n_rows;
+    int32_t C, step;
 };
 
-// last document whose first row is at or before row x: last_doc_le's search over row_offsets[0, n_docs).  All 64 lanes
-// of a wavefront must call it; all get the answer (at least 0 when row_offsets[0] <= x).
-__device__ __forceinline__ int64_t last_doc_of_row(const WinArgs& a, int64_t x) {
-    int64_t lo = 0, hi = a.n_docs;
-    const int lane = threadIdx.x & 63;
-    while (lo < hi) {
-        const int64_t step = (hi - lo + 63) >> 6;
-        const int64_t at = lo + lane * step;
-        const int hits = __popcll(__ballot(at < hi && a.rows[at] <= x));
-        const int64_t top = lo + hits * step;
-        if (hits) lo += (hits - 1) * step + 1;
-        hi = !hits ? lo : top < hi ? top : hi;
-    }
-    return lo - 1;
-}
-
-// A workgroup writes `rows_per_block` whole rows, or PAD_TILE columns of one long row, as k_collate_padded does.  Its rows
-// come from at most as many consecutive documents (row_offsets grows strictly), beginning with the one a wavefront finds;
-// their row_offsets and offsets are staged in LDS, thread r places row r among them once, and an element is then what it
-// is in k_collate_padded.  Whatever row_offsets and offsets hold, every index stays inside the staged entries and d_ids.
+// The planner: the tile's documents are found and staged (stage_items) with their offsets, and thread r places row r
+// among them once.  Whatever row_offsets and offsets hold, every index stays inside the staged entries and d_ids.
 template <int W, bool VEC>
 __global__ __launch_bounds__(TB) void k_collate_windows(const WinArgs a) {
     __shared__ int64_t s_ro[PAD_ROWS + 1], s_off[PAD_ROWS + 1];
     __shared__ int64_t s_start[PAD_ROWS];  // of the row's window inside its document
     __shared__ int32_t s_j[PAD_ROWS], s_n[PAD_ROWS];  // the row's document (behind the first staged one), its window's ids
     __shared__ int64_t s_d0;
-    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_ids || a.rows[0] != 0 || a.rows[a.n_docs] != a.n_rows) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.r.cap_a || a.rows[0] != 0 || a.rows[a.n_docs] != a.n_rows) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.r.err, HUTK_E_ARG);
         return;
     }
     const int tid = threadIdx.x;
-    const int64_t blk = blockIdx.x;
-    const int64_t rg = blk / a.col_chunks;
-    const int32_t cc = (int32_t)(blk - rg * a.col_chunks);
-    const int64_t row0 = rg * a.rows_per_block;
-    const int64_t left = a.n_rows - row0;
-    const int32_t nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
-    if (nrows <= 0) return;
-    if (tid < 64) {
-        const int64_t d = last_doc_of_row(a, row0);
-        if (tid == 0) s_d0 = d < 0 ? 0 : d;
-    }
+    const RowTile t = row_tile(a.r, a.n_rows);
+    if (t.nrows <= 0) return;
+    int32_t nd;
+    const int64_t d0 = stage_items(a.rows, a.n_docs, t, s_ro, &s_d0, nd);
+    for (int32_t i = tid; i <= nd; i += TB) s_off[i] = a.offs[d0 + i];
     __syncthreads();
-    const int64_t d0 = s_d0;
-    const int32_t nd = a.n_docs - d0 < nrows ? (int32_t)(a.n_docs - d0) : nrows;  // staged documents, at least one
-    for (int32_t i = tid; i <= nd; i += TB) {
-        s_ro[i] = a.rows[d0 + i];
-        s_off[i] = a.offs[d0 + i];
-    }
-    __syncthreads();
-    if (tid < nrows) {
-        const int64_t row = row0 + tid;
-        int32_t lo = 0, hi = nd;  // the last staged document whose first row is at or before this one
-        while (hi - lo > 1) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (s_ro[mid] <= row) lo = mid;
-            else hi = mid;
-        }
+    if (tid < t.nrows) {
+        const int64_t row = t.row0 + tid;
+        const int32_t lo = staged_item_of_row(s_ro, nd, row);
         int64_t dl = s_off[lo + 1] - s_off[lo];
         const int64_t k = row - s_ro[lo];
-        bool bad = dl < 0 || dl > a.n_ids;
+        bool bad = dl < 0 || dl > a.r.cap_a;
         if (bad) dl = 0;
-        if (k < 0 || k >= window_count(dl, a.n_ids, a.C, a.step, nullptr)) bad = true;  // (a row_offsets that is not the scan of w)
+        if (k < 0 || k >= window_count(dl, a.r.cap_a, a.C, a.step, nullptr)) bad = true;  // (a row_offsets that is not the scan of w)
         int64_t start = 0;
         int32_t n = 0;
-        if (bad) note_error(a.err, HUTK_E_ARG);
+        if (bad) note_error(a.r.err, HUTK_E_ARG);
         else {
             start = k * a.step;  // < dl: no overflow
             n = dl - start < a.C ? (int32_t)(dl - start) : a.C;
@@ -543,54 +580,15 @@ __global__ __launch_bounds__(TB) void k_collate_windows(const WinArgs a) {
         s_n[tid] = n;
     }
     __syncthreads();
-    const bool one_row = a.rows_per_block == 1;
-    const int32_t c0 = cc * PAD_TILE;
-    const int32_t ncols = one_row ? ((a.L - c0) < PAD_TILE ? (a.L - c0) : PAD_TILE) : a.L;
-    const int32_t total = nrows * ncols;
-    constexpr int V = VEC ? 4 : 1;
-    for (int32_t i = tid * V; i < total; i += TB * V) {
-        const int32_t rl = one_row ? 0 : i / a.L;
-        const int32_t c = one_row ? c0 + i : i - rl * a.L;
-        const int32_t j = s_j[rl], n = s_n[rl];
-        const int64_t start = s_start[rl];
-        const int64_t src = s_off[j] + start;
-        const int32_t sl = n + a.s;
-        const int32_t shift = a.pad_left ? a.L - sl : 0;
-        int32_t v[V];
-        uint8_t m[V];
-#pragma unroll
-        for (int e = 0; e < V; e++) {
-            const int32_t q = c + e - shift;
-            v[e] = a.pad;
-            m[e] = 0;
-            if (q >= 0 && q < sl) {
-                m[e] = 1;
-                if (a.has_bos && q == 0) v[e] = a.bos;
-                else if (a.has_eos && q == sl - 1) v[e] = a.eos;
-                else {
-                    const int64_t idx = src + q - a.has_bos;
-                    if (idx >= 0 && idx < a.n_ids) v[e] = a.ids[idx];
-                    else note_error(a.err, HUTK_E_ARG);
-                }
-            }
-        }
-        const int64_t at = (row0 + rl) * (int64_t)a.L + c;
-        if constexpr (VEC) {
-            store4<W>(a.out, at, v);
-            if (a.mask) *reinterpret_cast<uchar4*>(a.mask + at) = make_uchar4(m[0], m[1], m[2], m[3]);
-        } else {
-            store1<W>(a.out, at, v[0]);
-            if (a.mask) a.mask[at] = m[0];
-        }
-        if (c == 0) {
-            if (a.lengths) a.lengths[row0 + rl] = sl;
-            if (a.row_map) {
-                int64_t* rm = a.row_map + 2 * (row0 + rl);
-                if constexpr (VEC) *reinterpret_cast<longlong2*>(rm) = make_longlong2(d0 + j, start);
-                else rm[0] = d0 + j, rm[1] = start;
-            }
-        }
-    }
+    write_rows<W, VEC, false>(a.r, t, [&](int32_t rl) {
+        const int32_t j = s_j[rl];
+        RowPlan p{};
+        p.ka = s_n[rl];
+        p.start = s_start[rl];
+        p.srca = s_off[j] + p.start - a.r.has_bos;
+        p.item = d0 + j;
+        return p;
+    });
 }
 
 // ---- pairs --------------------------------------------------------------------------------------------------------
@@ -639,89 +637,30 @@ __device__ __forceinline__ int64_t pair_window_count(int64_t n, int64_t no, int6
     return n <= C || C == 0 ? 1 : 1 + (n - C + step - 1) / step;
 }
 
-struct PairRowArgs {
+struct PairRows {
     const int64_t *offs_a, *offs_b;
-    int64_t n_pairs, cap_a, cap_b;
+    int64_t cap_a, cap_b;
     int64_t R, stride;
-    int32_t cut_b;      // only_second: B is the side in windows
-    int64_t per_block;  // as WinRowArgs
-    int64_t* sums;
-    int64_t* row_offs;
-    int32_t* err;
-};
-
-__device__ __forceinline__ int64_t pair_rows_of(const PairRowArgs& a, int64_t i, int32_t* err) {
-    const int64_t na = side_len(a.offs_a[i], a.offs_a[i + 1], a.cap_a, err);
-    const int64_t nb = side_len(a.offs_b[i], a.offs_b[i + 1], a.cap_b, err);
-    int64_t C, step;
-    return a.cut_b ? pair_window_count(nb, na, a.R, a.stride, C, step) : pair_window_count(na, nb, a.R, a.stride, C, step);
-}
-
-__global__ __launch_bounds__(TB) void k_pair_count(const PairRowArgs a) {
-    __shared__ int64_t s_part[TB / 64];
-    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
-    const int64_t hi = lo + a.per_block < a.n_pairs ? lo + a.per_block : a.n_pairs;
-    int64_t mine = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += TB) mine += pair_rows_of(a, i, a.err);
-    int64_t total;
-    (void)block_excl_i64(mine, s_part, total);
-    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(TB) void k_pair_write(const PairRowArgs a) {
-    __shared__ int64_t s_part[TB / 64];
-    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
-    const int64_t hi = lo + a.per_block < a.n_pairs ? lo + a.per_block : a.n_pairs;
-    int64_t base = a.sums[blockIdx.x];
-    for (int64_t at = lo; at < hi; at += TB) {  // (uniform: every thread meets the barriers of the scan)
-        const int64_t i = at + threadIdx.x;
-        const int64_t w = i < hi ? pair_rows_of(a, i, nullptr) : 0;
-        int64_t total;
-        const int64_t before = block_excl_i64(w, s_part, total);
-        if (i < hi) a.row_offs[i] = base + before;
-        base += total;
+    int32_t cut_b;  // only_second: B is the side in windows
+    __device__ int64_t operator()(int64_t i, int32_t* err) const {
+        const int64_t na = side_len(offs_a[i], offs_a[i + 1], cap_a, err);
+        const int64_t nb = side_len(offs_b[i], offs_b[i + 1], cap_b, err);
+        int64_t C, step;
+        return cut_b ? pair_window_count(nb, na, R, stride, C, step) : pair_window_count(na, nb, R, stride, C, step);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.row_offs[a.n_pairs] = a.sums[gridDim.x];
-}
+};
 
 struct PairArgs {
-    const int32_t *ids_a, *ids_b;
+    RowArgs r;
     const int64_t *offs_a, *offs_b;
     const int64_t* rows;  // row_offsets: the windows form; NULL: row i is pair i
-    int64_t n_pairs, cap_a, cap_b, n_rows;
-    int32_t L, s, R, stride, strategy;
-    int32_t bos, eos, pad;
-    int32_t sep0, sep1, sep2, sep3;  // (no array: a kernel argument indexed at run time lives in scratch)
-    int32_t has_bos, n_sep, pad_left;
-    void* out;
-    uint8_t* mask;
-    uint8_t* types;
-    int32_t* lengths;
-    int64_t* row_map;
-    int32_t* err;
-    int32_t rows_per_block;  // as PadArgs
-    int32_t col_chunks;
+    int64_t n_pairs, n_rows;
+    int32_t R, stride, strategy;
 };
 
-// last_doc_of_row over the pairs
-__device__ __forceinline__ int64_t last_pair_of_row(const PairArgs& a, int64_t x) {
-    int64_t lo = 0, hi = a.n_pairs;
-    const int lane = threadIdx.x & 63;
-    while (lo < hi) {
-        const int64_t step = (hi - lo + 63) >> 6;
-        const int64_t at = lo + lane * step;
-        const int hits = __popcll(__ballot(at < hi && a.rows[at] <= x));
-        const int64_t top = lo + hits * step;
-        if (hits) lo += (hits - 1) * step + 1;
-        hi = !hits ? lo : top < hi ? top : hi;
-    }
-    return lo - 1;
-}
-
-// The block shape of k_collate_padded and k_collate_windows.  Thread r places row r once: its pair (itself, or in the
-// windows form found among the staged row_offsets as k_collate_windows finds a document), both sides' offsets, ka, kb
-// and the window's start go to LDS; an element is then a few comparisons against the row's four boundaries and at most
-// one dword read.  Whatever the offsets hold, every index stays inside the offsets arrays and the two id buffers.
+// The planner, both forms.  Thread r places row r once: its pair (itself, or in the windows form found among the staged
+// row_offsets as k_collate_windows finds a document), both sides' offsets, ka, kb and the window's start go to LDS.
+// Whatever the offsets hold, every index stays inside the offsets arrays and the two id buffers.
 template <int W, bool VEC>
 __global__ __launch_bounds__(TB) void k_collate_pairs(const PairArgs a) {
     __shared__ int64_t s_ro[PAD_ROWS + 1];
@@ -731,48 +670,29 @@ __global__ __launch_bounds__(TB) void k_collate_pairs(const PairArgs a) {
     __shared__ int64_t s_d0;
     const bool win = a.rows != nullptr;
     if (win && (a.rows[0] != 0 || a.rows[a.n_pairs] != a.n_rows)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.err, HUTK_E_ARG);
+        if (blockIdx.x == 0 && threadIdx.x == 0) note_error(a.r.err, HUTK_E_ARG);
         return;
     }
     const int tid = threadIdx.x;
-    const int64_t blk = blockIdx.x;
-    const int64_t rg = blk / a.col_chunks;
-    const int32_t cc = (int32_t)(blk - rg * a.col_chunks);
-    const int64_t row0 = rg * a.rows_per_block;
-    const int64_t left = a.n_rows - row0;
-    const int32_t nrows = left < a.rows_per_block ? (int32_t)left : a.rows_per_block;
-    if (nrows <= 0) return;
-    int64_t d0 = row0;  // the first pair of this workgroup's rows
-    int32_t nd = nrows;
+    const RowTile t = row_tile(a.r, a.n_rows);
+    if (t.nrows <= 0) return;
+    int64_t d0 = t.row0;  // the first pair of this workgroup's rows
+    int32_t nd = t.nrows;
     if (win) {
-        if (tid < 64) {
-            const int64_t d = last_pair_of_row(a, row0);
-            if (tid == 0) s_d0 = d < 0 ? 0 : d;
-        }
-        __syncthreads();
-        d0 = s_d0;
-        nd = a.n_pairs - d0 < nrows ? (int32_t)(a.n_pairs - d0) : nrows;  // staged pairs, at least one
-        for (int32_t i = tid; i <= nd; i += TB) s_ro[i] = a.rows[d0 + i];
+        d0 = stage_items(a.rows, a.n_pairs, t, s_ro, &s_d0, nd);
         __syncthreads();
     }
-    if (tid < nrows) {
+    if (tid < t.nrows) {
         int32_t lo = tid;
         int64_t k = 0;
         if (win) {
-            const int64_t row = row0 + tid;
-            int32_t hi = nd;  // the last staged pair whose first row is at or before this one
-            lo = 0;
-            while (hi - lo > 1) {
-                const int32_t mid = (lo + hi) >> 1;
-                if (s_ro[mid] <= row) lo = mid;
-                else hi = mid;
-            }
-            k = row - s_ro[lo];
+            lo = staged_item_of_row(s_ro, nd, t.row0 + tid);
+            k = t.row0 + tid - s_ro[lo];
         }
         const int64_t p = d0 + lo;
         const int64_t a0 = a.offs_a[p], b0 = a.offs_b[p];
-        const int64_t na = side_len(a0, a.offs_a[p + 1], a.cap_a, a.err);
-        const int64_t nb = side_len(b0, a.offs_b[p + 1], a.cap_b, a.err);
+        const int64_t na = side_len(a0, a.offs_a[p + 1], a.r.cap_a, a.r.err);
+        const int64_t nb = side_len(b0, a.offs_b[p + 1], a.r.cap_b, a.r.err);
         int32_t ka = 0, kb = 0;
         int64_t start = 0;
         const bool cut_b = a.strategy == HUTK_PAIR_ONLY_SECOND;
@@ -781,7 +701,7 @@ __global__ __launch_bounds__(TB) void k_collate_pairs(const PairArgs a) {
             int64_t C, step;
             const int64_t n = cut_b ? nb : na;
             const int64_t w = pair_window_count(n, cut_b ? na : nb, a.R, a.stride, C, step);
-            if (k < 0 || k >= w) note_error(a.err, HUTK_E_ARG);  // (a row_offsets that is not the scan of the counts)
+            if (k < 0 || k >= w) note_error(a.r.err, HUTK_E_ARG);  // (a row_offsets that is not the scan of the counts)
             else {
                 start = k * step;  // < n, or 0
                 const int32_t kn = n - start < C ? (int32_t)(n - start) : (int32_t)C;
@@ -794,79 +714,70 @@ __global__ __launch_bounds__(TB) void k_collate_pairs(const PairArgs a) {
         s_start[tid] = start;
         s_ka[tid] = ka;
         s_kb[tid] = kb;
-        s_srca[tid] = a0 + (cut_b ? 0 : start) - a.has_bos;
-        s_srcb[tid] = b0 + (cut_b ? start : 0) - (a.has_bos + ka + a.n_sep);
+        s_srca[tid] = a0 + (cut_b ? 0 : start) - a.r.has_bos;
+        s_srcb[tid] = b0 + (cut_b ? start : 0) - (a.r.has_bos + ka + a.r.n_sep);
     }
     __syncthreads();
-    const bool one_row = a.rows_per_block == 1;
-    const int32_t c0 = cc * PAD_TILE;
-    const int32_t ncols = one_row ? ((a.L - c0) < PAD_TILE ? (a.L - c0) : PAD_TILE) : a.L;
-    const int32_t total = nrows * ncols;
-    constexpr int V = VEC ? 4 : 1;
-    for (int32_t i = tid * V; i < total; i += TB * V) {
-        const int32_t rl = one_row ? 0 : i / a.L;
-        const int32_t c = one_row ? c0 + i : i - rl * a.L;
-        const int32_t ka = s_ka[rl], kb = s_kb[rl];
-        const int64_t srca = s_srca[rl], srcb = s_srcb[rl];
-        const int32_t end_a = a.has_bos + ka, end_sep = end_a + a.n_sep, end_b = end_sep + kb;
-        const int32_t sl = ka + kb + a.s;
-        const int32_t shift = a.pad_left ? a.L - sl : 0;
-        int32_t v[V];
-        uint8_t m[V], t[V];
-#pragma unroll
-        for (int e = 0; e < V; e++) {
-            const int32_t q = c + e - shift;
-            v[e] = a.pad;
-            m[e] = 0;
-            t[e] = 0;
-            if (q >= 0 && q < sl) {
-                m[e] = 1;
-                if (q < a.has_bos) v[e] = a.bos;
-                else if (q < end_a) {
-                    const int64_t idx = srca + q;
-                    if (idx >= 0 && idx < a.cap_a) v[e] = a.ids_a[idx];
-                    else note_error(a.err, HUTK_E_ARG);
-                } else if (q < end_sep) {
-                    const int32_t u = q - end_a;
-                    v[e] = u == 0 ? a.sep0 : u == 1 ? a.sep1 : u == 2 ? a.sep2 : a.sep3;
-                } else if (q < end_b) {
-                    t[e] = 1;
-                    const int64_t idx = srcb + q;
-                    if (idx >= 0 && idx < a.cap_b) v[e] = a.ids_b[idx];
-                    else note_error(a.err, HUTK_E_ARG);
-                } else {
-                    t[e] = 1;
-                    v[e] = a.eos;
-                }
-            }
-        }
-        const int64_t at = (row0 + rl) * (int64_t)a.L + c;
-        if constexpr (VEC) {
-            store4<W>(a.out, at, v);
-            if (a.mask) *reinterpret_cast<uchar4*>(a.mask + at) = make_uchar4(m[0], m[1], m[2], m[3]);
-            if (a.types) *reinterpret_cast<uchar4*>(a.types + at) = make_uchar4(t[0], t[1], t[2], t[3]);
-        } else {
-            store1<W>(a.out, at, v[0]);
-            if (a.mask) a.mask[at] = m[0];
-            if (a.types) a.types[at] = t[0];
-        }
-        if (c == 0) {
-            if (a.lengths) a.lengths[row0 + rl] = sl;
-            if (a.row_map) {
-                int64_t* rm = a.row_map + 2 * (row0 + rl);
-                if constexpr (VEC) *reinterpret_cast<longlong2*>(rm) = make_longlong2(d0 + s_j[rl], s_start[rl]);
-                else rm[0] = d0 + s_j[rl], rm[1] = s_start[rl];
-            }
-        }
-    }
+    write_rows<W, VEC, true>(a.r, t, [&](int32_t rl) {
+        return RowPlan{s_ka[rl], s_kb[rl], s_srca[rl], s_srcb[rl], d0 + s_j[rl], s_start[rl]};
+    });
 }
 
 bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
-int device_present(const char* who) {
+int device_present(const char* who, int* count = nullptr) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return hutk::api_set_error(HUTK_E_DEVICE, std::string(who) + ": no HIP device");
+    if (count) *count = n;
+    return HUTK_OK;
+}
+
+// f(W, VEC) with out_width and vec as compile-time constants: the four instantiations every collation kernel has
+template <class F>
+void with_width_vec(int out_width, bool vec, F f) {
+    using W4 = std::integral_constant<int, 4>;
+    using W8 = std::integral_constant<int, 8>;
+    if (out_width == 4) {
+        if (vec) f(W4{}, std::true_type{});
+        else f(W4{}, std::false_type{});
+    } else {
+        if (vec) f(W8{}, std::true_type{});
+        else f(W8{}, std::false_type{});
+    }
+}
+
+// The host half of the row tile.  What the three row calls fill in of RowArgs alike; the sides' ids and the separators
+// are the caller's.
+RowArgs row_args(int64_t max_len, int s, int32_t bos_id, int32_t eos_id, int32_t pad_id, int flags, void* d_input_ids,
+                 uint8_t* d_mask, uint8_t* d_token_types, int32_t* d_lengths, int64_t* d_row_map, int32_t* d_err) {
+    RowArgs r = {};
+    r.L = (int32_t)max_len;
+    r.s = s;
+    r.bos = bos_id;
+    r.eos = eos_id;
+    r.pad = pad_id;
+    r.has_bos = bos_id != HUTK_NO_TOKEN;
+    r.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
+    r.out = d_input_ids;
+    r.mask = d_mask;
+    r.types = d_token_types;
+    r.lengths = d_lengths;
+    r.row_map = d_row_map;
+    r.err = d_err;
+    return r;
+}
+
+// The tile of rows of r.L elements, the workgroups that write n_rows of them, and whether they may store 16 bytes at once
+int row_grid(const char* who, RowArgs& r, int64_t n_rows, int64_t* blocks, bool* vec) {
+    int64_t rpb = PAD_TILE / r.L;
+    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
+    r.rows_per_block = (int32_t)rpb;
+    r.col_chunks = rpb == 1 ? (int32_t)(((int64_t)r.L + PAD_TILE - 1) / PAD_TILE) : 1;
+    *blocks = (n_rows + rpb - 1) / rpb * r.col_chunks;
+    if (*blocks < 1) *blocks = 1;  // (n_rows == 0 with items: the kernel reports it)
+    if (*blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, std::string(who) + ": the batch is too large for one launch");
+    *vec = r.L % 4 == 0 && aligned_to(r.out, 16) && aligned_to(r.mask, 4) && aligned_to(r.types, 4) && aligned_to(r.row_map, 16);
     return HUTK_OK;
 }
 
@@ -881,8 +792,8 @@ int window_sizes(const char* who, int64_t max_len, int64_t stride, int s, int64_
     return HUTK_OK;
 }
 
-// The workgroup sums of hutk_windows_rows_device: one small buffer per device, made at the first call there and kept.
-// Calls that share it are serialised like calls on one packer: a mutex on the host, an event on the device.
+// The workgroup sums of the rows scan: one small buffer per device, made at the first call there and kept.  Calls that
+// share it are serialised like calls on one packer: a mutex on the host, an event on the device.
 struct WinScratch {
     int64_t* sums = nullptr;  // [WIN_BLOCKS + 1]
     hipEvent_t ev = nullptr;
@@ -915,6 +826,32 @@ int scratch_used(WinScratch* w, hipStream_t st) {
     HUTK_HIP_TRY(hipEventRecord(w->ev, st));
     w->ev_recorded = true;
     return HUTK_OK;
+}
+
+// d_row_offsets[0 .. n] = the exclusive scan of rows(i) over the n items and its sum; d_err is cleared first
+template <class Rows>
+int rows_scan(const Rows& rows, int64_t n, int64_t* d_row_offsets, int32_t* d_err, hipStream_t st) {
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n == 0) {
+        HUTK_HIP_TRY(hipMemsetAsync(d_row_offsets, 0, sizeof(int64_t), st));
+        return HUTK_OK;
+    }
+    ScanArgs a;
+    a.n = n;
+    // at most WIN_BLOCKS workgroups: beyond WIN_BLOCKS * TB items each takes several chunks of TB
+    a.per_block = (n + (int64_t)WIN_BLOCKS * TB - 1) / ((int64_t)WIN_BLOCKS * TB) * TB;
+    const int64_t blocks = (n + a.per_block - 1) / a.per_block;
+    std::lock_guard<std::mutex> lock(g_win_mu);
+    WinScratch* w;
+    if (int rc = scratch_for(st, &w)) return rc;
+    a.sums = w->sums;
+    a.row_offs = d_row_offsets;
+    a.err = d_err;
+    const dim3 grid((unsigned)blocks), block(TB);
+    hipLaunchKernelGGL(k_rows_count<Rows>, grid, block, 0, st, a, rows);
+    hutk::launch_scan_i64(w->sums, blocks, st);
+    hipLaunchKernelGGL(k_rows_write<Rows>, grid, block, 0, st, a, rows);
+    return scratch_used(w, st);
 }
 
 // What the pair calls share: the sizes they refuse before anything else.  s (bos, separators, eos) and R = max_len - s
@@ -972,40 +909,20 @@ int hutk_collate_padded_device(const int32_t* d_ids, const int64_t* d_offsets, i
     if (!d_offsets || !d_input_ids || (n_ids > 0 && !d_ids))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_padded_device: a buffer is NULL");
     PadArgs a;
-    a.ids = d_ids;
+    a.r = row_args(max_len, s, bos_id, eos_id, pad_id, flags, d_input_ids, d_mask, nullptr, d_lengths, nullptr, d_err);
+    a.r.ids_a = d_ids;
+    a.r.cap_a = n_ids;
     a.offs = d_offsets;
     a.n_docs = n_docs;
-    a.n_ids = n_ids;
-    a.L = (int32_t)max_len;
-    a.s = s;
-    a.bos = bos_id;
-    a.eos = eos_id;
-    a.pad = pad_id;
-    a.has_bos = bos_id != HUTK_NO_TOKEN;
-    a.has_eos = eos_id != HUTK_NO_TOKEN;
     a.trunc_left = (flags & HUTK_COLLATE_TRUNC_LEFT) != 0;
-    a.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
-    a.out = d_input_ids;
-    a.mask = d_mask;
-    a.lengths = d_lengths;
-    a.err = d_err;
-    int64_t rpb = PAD_TILE / max_len;
-    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
-    a.rows_per_block = (int32_t)rpb;
-    a.col_chunks = rpb == 1 ? (int32_t)((max_len + PAD_TILE - 1) / PAD_TILE) : 1;
-    const int64_t blocks = (n_docs + rpb - 1) / rpb * a.col_chunks;
-    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_padded_device: the batch is too large for one launch");
-    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4);
+    int64_t blocks;
+    bool vec;
+    if (int rc = row_grid("hutk_collate_padded_device", a.r, n_docs, &blocks, &vec)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
-    const dim3 grid((unsigned)blocks), block(TB);
-    if (out_width == 4) {
-        if (vec) hipLaunchKernelGGL((k_collate_padded<4, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_collate_padded<4, false>), grid, block, 0, st, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((k_collate_padded<8, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_collate_padded<8, false>), grid, block, 0, st, a);
-    }
+    with_width_vec(out_width, vec, [&](auto w, auto v) {
+        hipLaunchKernelGGL((k_collate_padded<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    });
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }
@@ -1024,34 +941,15 @@ int hutk_windows_rows_device(const int64_t* d_offsets, int64_t n_docs, int64_t n
                              int32_t bos_id, int32_t eos_id, int64_t* d_row_offsets, int32_t* d_err, void* hip_stream) {
     const int s = (bos_id != HUTK_NO_TOKEN) + (eos_id != HUTK_NO_TOKEN);
     if (n_docs < 0 || n_ids < 0) return hutk::api_set_error(HUTK_E_ARG, "hutk_windows_rows_device: bad arguments");
-    WinRowArgs a;
-    if (int rc = window_sizes("hutk_windows_rows_device", max_len, stride, s, &a.C, &a.step)) return rc;
+    DocRows rows;
+    if (int rc = window_sizes("hutk_windows_rows_device", max_len, stride, s, &rows.C, &rows.step)) return rc;
     if (int rc = device_present("hutk_windows_rows_device")) return rc;
     if (!d_row_offsets || (n_docs > 0 && !d_offsets))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_windows_rows_device: a buffer is NULL");
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
-    if (n_docs == 0) {
-        HUTK_HIP_TRY(hipMemsetAsync(d_row_offsets, 0, sizeof(int64_t), st));
-        return HUTK_OK;
-    }
-    // at most WIN_BLOCKS workgroups: beyond WIN_BLOCKS * TB documents each takes several chunks of TB
-    a.per_block = (n_docs + (int64_t)WIN_BLOCKS * TB - 1) / ((int64_t)WIN_BLOCKS * TB) * TB;
-    const int64_t blocks = (n_docs + a.per_block - 1) / a.per_block;
-    std::lock_guard<std::mutex> lock(g_win_mu);
-    WinScratch* w;
-    if (int rc = scratch_for(st, &w)) return rc;
-    a.offs = d_offsets;
-    a.n_docs = n_docs;
-    a.n_ids = n_ids;
-    a.sums = w->sums;
-    a.row_offs = d_row_offsets;
-    a.err = d_err;
-    const dim3 grid((unsigned)blocks), block(TB);
-    hipLaunchKernelGGL(k_windows_count, grid, block, 0, st, a);
-    hutk::launch_scan_i64(w->sums, blocks, st);
-    hipLaunchKernelGGL(k_windows_write, grid, block, 0, st, a);
-    return scratch_used(w, st);
+    rows.offs = d_offsets;
+    rows.n_docs = n_docs;
+    rows.n_ids = n_ids;
+    return rows_scan(rows, n_docs, d_row_offsets, d_err, (hipStream_t)hip_stream);
 }
 
 int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, const int64_t* d_row_offsets,
@@ -1070,45 +968,23 @@ int hutk_collate_windows_device(const int32_t* d_ids, const int64_t* d_offsets, 
     if (!d_offsets || !d_row_offsets || (n_rows > 0 && !d_input_ids) || (n_ids > 0 && !d_ids))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_windows_device: a buffer is NULL");
     WinArgs a;
-    a.ids = d_ids;
+    a.r = row_args(max_len, s, bos_id, eos_id, pad_id, flags, d_input_ids, d_mask, nullptr, d_lengths, d_row_map, d_err);
+    a.r.ids_a = d_ids;
+    a.r.cap_a = n_ids;
     a.offs = d_offsets;
     a.rows = d_row_offsets;
     a.n_docs = n_docs;
-    a.n_ids = n_ids;
     a.n_rows = n_rows;
-    a.L = (int32_t)max_len;
-    a.s = s;
     a.C = (int32_t)C;
     a.step = (int32_t)step;
-    a.bos = bos_id;
-    a.eos = eos_id;
-    a.pad = pad_id;
-    a.has_bos = bos_id != HUTK_NO_TOKEN;
-    a.has_eos = eos_id != HUTK_NO_TOKEN;
-    a.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
-    a.out = d_input_ids;
-    a.mask = d_mask;
-    a.lengths = d_lengths;
-    a.row_map = d_row_map;
-    a.err = d_err;
-    int64_t rpb = PAD_TILE / max_len;
-    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
-    a.rows_per_block = (int32_t)rpb;
-    a.col_chunks = rpb == 1 ? (int32_t)((max_len + PAD_TILE - 1) / PAD_TILE) : 1;
-    int64_t blocks = (n_rows + rpb - 1) / rpb * a.col_chunks;
-    if (blocks < 1) blocks = 1;  // (n_rows == 0 with documents: the kernel reports it)
-    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_windows_device: the batch is too large for one launch");
-    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4) && aligned_to(d_row_map, 16);
+    int64_t blocks;
+    bool vec;
+    if (int rc = row_grid("hutk_collate_windows_device", a.r, n_rows, &blocks, &vec)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
-    const dim3 grid((unsigned)blocks), block(TB);
-    if (out_width == 4) {
-        if (vec) hipLaunchKernelGGL((k_collate_windows<4, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_collate_windows<4, false>), grid, block, 0, st, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((k_collate_windows<8, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_collate_windows<8, false>), grid, block, 0, st, a);
-    }
+    with_width_vec(out_width, vec, [&](auto w, auto v) {
+        hipLaunchKernelGGL((k_collate_windows<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    });
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }
@@ -1129,8 +1005,8 @@ int hutk_pair_rows_device(const int64_t* d_offsets_a, const int64_t* d_offsets_b
                           void* hip_stream) {
     if (n_pairs < 0 || cap_a < 0 || cap_b < 0) return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_device: bad arguments");
     int s;
-    PairRowArgs a;
-    if (int rc = pair_sizes("hutk_pair_rows_device", max_len, stride, strategy, bos_id, sep_ids, n_sep, eos_id, &s, &a.R))
+    PairRows rows;
+    if (int rc = pair_sizes("hutk_pair_rows_device", max_len, stride, strategy, bos_id, sep_ids, n_sep, eos_id, &s, &rows.R))
         return rc;
     if (strategy == HUTK_PAIR_LONGEST_FIRST)
         return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_device: strategy must name the side that is cut into windows "
@@ -1138,32 +1014,13 @@ int hutk_pair_rows_device(const int64_t* d_offsets_a, const int64_t* d_offsets_b
     if (int rc = device_present("hutk_pair_rows_device")) return rc;
     if (!d_row_offsets || (n_pairs > 0 && (!d_offsets_a || !d_offsets_b)))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_rows_device: a buffer is NULL");
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
-    if (n_pairs == 0) {
-        HUTK_HIP_TRY(hipMemsetAsync(d_row_offsets, 0, sizeof(int64_t), st));
-        return HUTK_OK;
-    }
-    a.per_block = (n_pairs + (int64_t)WIN_BLOCKS * TB - 1) / ((int64_t)WIN_BLOCKS * TB) * TB;
-    const int64_t blocks = (n_pairs + a.per_block - 1) / a.per_block;
-    std::lock_guard<std::mutex> lock(g_win_mu);
-    WinScratch* w;
-    if (int rc = scratch_for(st, &w)) return rc;
-    a.offs_a = d_offsets_a;
-    a.offs_b = d_offsets_b;
-    a.n_pairs = n_pairs;
-    a.cap_a = cap_a;
-    a.cap_b = cap_b;
-    a.stride = stride;
-    a.cut_b = strategy == HUTK_PAIR_ONLY_SECOND;
-    a.sums = w->sums;
-    a.row_offs = d_row_offsets;
-    a.err = d_err;
-    const dim3 grid((unsigned)blocks), block(TB);
-    hipLaunchKernelGGL(k_pair_count, grid, block, 0, st, a);
-    hutk::launch_scan_i64(w->sums, blocks, st);
-    hipLaunchKernelGGL(k_pair_write, grid, block, 0, st, a);
-    return scratch_used(w, st);
+    rows.offs_a = d_offsets_a;
+    rows.offs_b = d_offsets_b;
+    rows.cap_a = cap_a;
+    rows.cap_b = cap_b;
+    rows.stride = stride;
+    rows.cut_b = strategy == HUTK_PAIR_ONLY_SECOND;
+    return rows_scan(rows, n_pairs, d_row_offsets, d_err, (hipStream_t)hip_stream);
 }
 
 int hutk_collate_pairs_device(const int32_t* d_ids_a, const int64_t* d_offsets_a, const int32_t* d_ids_b,
@@ -1190,55 +1047,32 @@ int hutk_collate_pairs_device(const int32_t* d_ids_a, const int64_t* d_offsets_a
     if (!d_offsets_a || !d_offsets_b || (n_rows > 0 && !d_input_ids) || (cap_a > 0 && !d_ids_a) || (cap_b > 0 && !d_ids_b))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_collate_pairs_device: a buffer is NULL");
     PairArgs a;
-    a.ids_a = d_ids_a;
-    a.ids_b = d_ids_b;
+    a.r = row_args(max_len, s, bos_id, eos_id, pad_id, flags, d_input_ids, d_mask, d_token_types, d_lengths, d_row_map, d_err);
+    a.r.ids_a = d_ids_a;
+    a.r.ids_b = d_ids_b;
+    a.r.cap_a = cap_a;
+    a.r.cap_b = cap_b;
+    a.r.sep0 = n_sep > 0 ? sep_ids[0] : 0;
+    a.r.sep1 = n_sep > 1 ? sep_ids[1] : 0;
+    a.r.sep2 = n_sep > 2 ? sep_ids[2] : 0;
+    a.r.sep3 = n_sep > 3 ? sep_ids[3] : 0;
+    a.r.n_sep = n_sep;
     a.offs_a = d_offsets_a;
     a.offs_b = d_offsets_b;
     a.rows = d_row_offsets;
     a.n_pairs = n_pairs;
-    a.cap_a = cap_a;
-    a.cap_b = cap_b;
     a.n_rows = n_rows;
-    a.L = (int32_t)max_len;
-    a.s = s;
     a.R = (int32_t)R;
     a.stride = (int32_t)stride;
     a.strategy = strategy;
-    a.bos = bos_id;
-    a.eos = eos_id;
-    a.pad = pad_id;
-    a.sep0 = n_sep > 0 ? sep_ids[0] : 0;
-    a.sep1 = n_sep > 1 ? sep_ids[1] : 0;
-    a.sep2 = n_sep > 2 ? sep_ids[2] : 0;
-    a.sep3 = n_sep > 3 ? sep_ids[3] : 0;
-    a.has_bos = bos_id != HUTK_NO_TOKEN;
-    a.n_sep = n_sep;
-    a.pad_left = (flags & HUTK_COLLATE_PAD_LEFT) != 0;
-    a.out = d_input_ids;
-    a.mask = d_mask;
-    a.types = d_token_types;
-    a.lengths = d_lengths;
-    a.row_map = d_row_map;
-    a.err = d_err;
-    int64_t rpb = PAD_TILE / max_len;
-    rpb = rpb < 1 ? 1 : rpb > PAD_ROWS ? PAD_ROWS : rpb;
-    a.rows_per_block = (int32_t)rpb;
-    a.col_chunks = rpb == 1 ? (int32_t)((max_len + PAD_TILE - 1) / PAD_TILE) : 1;
-    int64_t blocks = (n_rows + rpb - 1) / rpb * a.col_chunks;
-    if (blocks < 1) blocks = 1;  // (n_rows == 0 with pairs: the kernel reports it)
-    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_collate_pairs_device: the batch is too large for one launch");
-    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4) && aligned_to(d_token_types, 4) &&
-                     aligned_to(d_row_map, 16);
+    int64_t blocks;
+    bool vec;
+    if (int rc = row_grid("hutk_collate_pairs_device", a.r, n_rows, &blocks, &vec)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
-    const dim3 grid((unsigned)blocks), block(TB);
-    if (out_width == 4) {
-        if (vec) hipLaunchKernelGGL((k_collate_pairs<4, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_collate_pairs<4, false>), grid, block, 0, st, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((k_collate_pairs<8, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_collate_pairs<8, false>), grid, block, 0, st, a);
-    }
+    with_width_vec(out_width, vec, [&](auto w, auto v) {
+        hipLaunchKernelGGL((k_collate_pairs<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    });
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }
@@ -1250,8 +1084,7 @@ int hutk_packer_create(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32
     if (seq_len < 1 || seq_len > INT32_MAX || (out_width != 4 && out_width != 8))
         return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_create: seq_len must be in 1 .. 2^31 - 1 and out_width 4 or 8");
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no HIP device");
+    if (int rc = device_present("hutk_packer_create", &n)) return rc;
     if (device < 0) HUTK_HIP_TRY(hipGetDevice(&device));
     if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no such device");
     HUTK_HIP_TRY(hipSetDevice(device));
@@ -1338,14 +1171,9 @@ int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* 
         if (p->ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, p->ev, 0));
         const bool vec = p->L % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_position_ids, 16) &&
                          aligned_to(d_segment_ids, 16);
-        const dim3 grid((unsigned)blocks), block(TB);
-        if (p->width == 4) {
-            if (vec) hipLaunchKernelGGL((k_collate_packed<4, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_collate_packed<4, false>), grid, block, 0, st, a);
-        } else {
-            if (vec) hipLaunchKernelGGL((k_collate_packed<8, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_collate_packed<8, false>), grid, block, 0, st, a);
-        }
+        with_width_vec(p->width, vec, [&](auto w, auto v) {
+            hipLaunchKernelGGL((k_collate_packed<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+        });
         HUTK_HIP_TRY(hipGetLastError());
         HUTK_HIP_TRY(hipEventRecord(p->ev, st));
         p->ev_recorded = true;

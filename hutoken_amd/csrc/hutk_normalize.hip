@@ -21,6 +21,7 @@
 
 #include "hutk_host.h"
 #include "hutk_norm.h"
+#include "hutk_wave.h"
 
 namespace {
 
@@ -78,56 +79,18 @@ __device__ __forceinline__ bool slice_dirty(const NormArgs& a, int64_t at, int64
     return d;
 }
 
-// exclusive scan over the 256 lanes; total: the sum.  s_part: four values of LDS, free again after the call
-__device__ __forceinline__ int64_t block_excl_i64(int64_t v, int64_t* s_part, int64_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t p = __shfl_up(incl, off);
-        if (lane >= off) incl += p;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int64_t before = incl - v;
-    total = 0;
-#pragma unroll
-    for (int u = 0; u < TB / 64; u++) {
-        if (u < wave) before += s_part[u];
-        total += s_part[u];
-    }
-    __syncthreads();
-    return before;
-}
-
 // what every kernel of a chunk starts with: its byte range, the documents that start in it, the spills at both edges
 struct ChunkInfo {
     int64_t c0, c1, dlo, dhi;
     int sp0, sp1;
 };
-// first i in [0, n] with offs[i] >= v (offs[n] >= v), by one wavefront: each round its 64 lanes probe evenly spaced entries
-// and count the hits, so 2^20 documents take four dependent loads where a binary search takes twenty.  All 64 lanes must
-// call it; all get the answer (N::first_doc_at_or_after is the same function for one caller).
-__device__ __forceinline__ int64_t wave_first_doc_at_or_after(const int64_t* offs, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;  // entries below lo are below v, those from hi on are not
-    const int lane = threadIdx.x & 63;
-    while (lo < hi) {
-        const int64_t step = (hi - lo + 63) >> 6;
-        const int64_t at = lo + lane * step;
-        const int hits = __popcll(__ballot(at < hi && offs[at] < v));
-        const int64_t top = lo + hits * step;  // the first probe that missed
-        if (hits) lo += (hits - 1) * step + 1;
-        hi = !hits ? lo : top < hi ? top : hi;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ void chunk_info(const NormArgs& a, int64_t k, int64_t* s_doc, int* s_sp, ChunkInfo& ci) {
     ci.c0 = k * N::CHUNK_BYTES;
     ci.c1 = ci.c0 + N::CHUNK_BYTES < a.x.n_bytes ? ci.c0 + N::CHUNK_BYTES : a.x.n_bytes;
     if (threadIdx.x < 128) {  // two wavefronts side by side: the front edge and the back edge
         const int64_t edge = threadIdx.x < 64 ? ci.c0 : ci.c1;
-        const int64_t d = wave_first_doc_at_or_after(a.x.offs, a.x.n_docs, edge);
+        // the first document at or after the edge (N::first_doc_at_or_after is the same function for one caller)
+        const int64_t d = hutk::wave_count_leading(a.x.n_docs, [&](int64_t i) { return a.x.offs[i] < edge; });
         if ((threadIdx.x & 63) == 0) {
             s_doc[threadIdx.x >> 6] = d;
             s_sp[threadIdx.x >> 6] = N::edge_spill(a.x, edge, d);
@@ -165,7 +128,7 @@ __global__ __launch_bounds__(TB) void k_norm_sizes(const NormArgs a) {
                      [&](int64_t p, int64_t before) { s_emit[p - ci.c0] = (uint16_t)before; }, a.changed);
     }
     int64_t total;
-    s_excl[tid] = block_excl_i64(sink.pos, s_part, total);
+    s_excl[tid] = hutk::block_excl(sink.pos, s_part, total);
     __syncthreads();
     if (tid == 0) {
         a.chunk_base[k] = total;
@@ -227,7 +190,7 @@ __global__ __launch_bounds__(TB) void k_norm_docs(const NormArgs a) {
         mine = a.changed[d] != 0;
     }
     int64_t sum;
-    (void)block_excl_i64(mine, s_part, sum);
+    (void)hutk::block_excl(mine, s_part, sum);
     if (threadIdx.x == 0) {
         if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals + 1), (unsigned long long)sum);
         if (blockIdx.x == 0) {
@@ -272,7 +235,7 @@ __global__ __launch_bounds__(TB) void k_norm_write(const NormArgs a) {
     N::CountSink count;
     if (at < ci.c1) N::slice_run(a.T, a.x, d, at, e, high, count, [](int64_t, int64_t) {}, nullptr);
     int64_t total;
-    const int64_t before = block_excl_i64(count.pos, s_part, total);
+    const int64_t before = hutk::block_excl(count.pos, s_part, total);
     if (at < ci.c1 && count.pos) {
         N::WriteSink sink{a.out, a.out_cap, base + before};
         N::slice_run(a.T, a.x, d, at, e, high, sink, [](int64_t, int64_t) {}, nullptr);

@@ -17,6 +17,7 @@
 
 #include "hutk_host.h"
 #include "hutk_presplit.h"
+#include "hutk_wave.h"
 
 namespace {
 
@@ -53,22 +54,6 @@ __global__ __launch_bounds__(TB) void k_ps_check(const SplitArgs a) {
     }
 }
 
-// first i in [0, n] with offs[i] >= v (offs[n] >= v), by one wavefront: each round its 64 lanes probe evenly spaced
-// entries.  All 64 lanes must call it; all get the answer.
-__device__ __forceinline__ int64_t wave_first_at_or_after(const int64_t* offs, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;
-    const int lane = threadIdx.x & 63;
-    while (lo < hi) {
-        const int64_t step = (hi - lo + 63) >> 6;
-        const int64_t at = lo + lane * step;
-        const int hits = __popcll(__ballot(at < hi && offs[at] < v));
-        const int64_t top = lo + hits * step;
-        if (hits) lo += (hits - 1) * step + 1;
-        hi = !hits ? lo : top < hi ? top : hi;
-    }
-    return lo;
-}
-
 struct Staged {
     P::Win W;
     int64_t c0, c1;
@@ -91,7 +76,7 @@ __device__ __forceinline__ void stage(const SplitArgs& a, int64_t k, uint4* s_ra
     for (int j = tid; j < WIN / 4; j += TB) s_code[j] = 0;
     for (int j = tid; j < WIN / 32 + 1; j += TB) s_doc[j] = 0;
     __syncthreads();
-    const int64_t dlo = wave_first_at_or_after(a.offs, a.n_docs, w0);
+    const int64_t dlo = hutk::wave_count_leading(a.n_docs, [&](int64_t i) { return a.offs[i] < w0; });  // the first document at or after w0
     for (int64_t d = dlo + tid; d <= a.n_docs; d += TB) {
         const int64_t o = a.offs[d] - w0;
         if (o >= WIN) break;

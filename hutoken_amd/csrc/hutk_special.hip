@@ -34,6 +34,7 @@
 #include <string>
 
 #include "hutk_host.h"
+#include "hutk_wave.h"
 
 namespace hutk {
 
@@ -91,34 +92,6 @@ struct SpecArgs {
 
 __device__ __forceinline__ void sc_raise(int32_t* err, int32_t code) { atomicCAS(err, 0, code); }
 __device__ __forceinline__ bool in_set(const uint32_t* set, uint32_t b) { return (set[b >> 5] >> (b & 31)) & 1u; }
-
-template <class V>
-__device__ __forceinline__ V wave_incl(V v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const V p = __shfl_up(v, off);
-        if (lane >= off) v += p;
-    }
-    return v;
-}
-
-// exclusive scan over the 256 threads of a workgroup; total: the sum.  s_part: four values of LDS, free again after the call
-template <class V>
-__device__ __forceinline__ V block_excl(V v, V* s_part, V& total) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const V incl = wave_incl(v, lane);
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    V before = incl - v;
-    total = 0;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        if (u < wave) before += s_part[u];
-        total += s_part[u];
-    }
-    __syncthreads();
-    return before;
-}
 
 // 16 bytes of a byte array at pos (a multiple of 16; the array is 16-byte aligned) as four words, zeros beyond n
 __device__ __forceinline__ uint4 load16(const uint8_t* a, int64_t pos, int64_t n) {

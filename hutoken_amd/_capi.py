@@ -58,6 +58,7 @@ SIGNATURES = {
     "hutk_debug_seam": (_i32, [_vp, _vp]),
     "hutk_debug_seam2_cut": (_i32, [_vp, _u32, _u32]),
     "hutk_debug_tile_kernel": (_i32, [_vp, _i64]),
+    "hutk_debug_exc_counts": (_i32, [_vp, _vp]),
     "hutk_trainer_create": (_i32, [_pvp, _i32]),
     "hutk_trainer_add": (_i32, [_vp, _vp, _vp, _i64]),
     "hutk_trainer_run": (_i32, [_vp, _s32, _vp, _vp, _ps32]),
@@ -359,6 +360,17 @@ class Context(_Owner):
         if k < 0:
             raise_for(E_ARG)
         return k
+
+    def exc_counts(self):
+        """Where the exception words of the most recent encode went (encode_device(), its stream synchronised by the
+        caller, or a host form): {"exc": records, "lists": [up to 128 units, up to 256, up to 512, up to 1024, a wavefront
+        each], "tail": 0 the full tail / 1 k_tail_small / 2 the one-launch k_tiles alone / 3 k_tail_small behind it,
+        "has_multi": bool}.  One device-to-host copy, no launch."""
+        import numpy as np
+        out = np.zeros(8, dtype=np.int64)
+        raise_for(load().hutk_debug_exc_counts(self._h, out.ctypes.data))
+        v = out.tolist()
+        return {"exc": v[0], "lists": v[1:6], "tail": v[6], "has_multi": bool(v[7])}
 
     def _encode_host(self, fn, capacity, data, offsets, flags=()):
         """Host numpy buffers through the library's host encode `fn` (its flags, if it takes any, as a 1-tuple) with ids

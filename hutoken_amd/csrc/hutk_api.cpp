@@ -694,6 +694,23 @@ int hutk_debug_tile_kernel(const hutk_ctx* c, int64_t n_bytes) {
     return tile_kernels_for(D, A);
 }
 
+// Where the exception words of the context's most recent encode went: the device's counts as the batch left them (k_pre,
+// or the one-launch kernel, zeroes them at the next call only) and the tail the host enqueued -- encode_device_impl's, or
+// encode_one_shot's for a host-form batch of up to four tiles.  The caller has synchronised the stream.
+int hutk_debug_exc_counts(const hutk_ctx* c, int64_t* out8) {
+    if (!c || !out8) return api_set_error(HUTK_E_ARG, "bad argument");
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to encode on");
+    if (c->last_tail < 0 || !c->w_counters.p) return api_set_error(HUTK_E_ARG, "no encode yet");
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    uint32_t ctr[N_COUNTERS];
+    HUTK_HIP_TRY(hipMemcpy(ctr, c->w_counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
+    const int slot[6] = {CTR_EXC, CTR_G2_COUNT, CTR_G4_COUNT, CTR_G8_COUNT, CTR_G16_COUNT, CTR_WAVE_COUNT};
+    for (int i = 0; i < 6; i++) out8[i] = ctr[slot[i]];
+    out8[6] = c->last_tail;
+    out8[7] = c->dt.has_multi ? 1 : 0;
+    return HUTK_OK;
+}
+
 // (declared in hutk_internal.h: hutk_special.hip encodes the pieces between special tokens with it)
 extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
                                           int64_t n_bytes, int32_t* d_ids_out, int64_t ids_cap, int64_t* d_out_offsets,
@@ -770,6 +787,7 @@ extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, c
         W.select = 0;
     }
     if (c->timing) HUTK_HIP_TRY(hipEventRecord(c->ev[2], s));
+    c->last_tail = small_tail(A) ? 1 : 0;
     if (small_tail(A)) {
         launch_tail_small(c->dt, A, W, s);
     } else {
@@ -955,6 +973,7 @@ static int encode_one_shot(hutk_ctx* c, const uint8_t* m_bytes, const int64_t* m
             break;
         }
     }
+    c->last_tail = f == 2 ? 3 : 2;
     if (f == 2) {  // exception words: their stages, the scan and the copy-out behind the tile kernel
         W.one_flag = nullptr;
         launch_tail_small(c->dt, A, W, s);

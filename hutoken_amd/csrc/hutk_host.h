@@ -135,6 +135,7 @@ struct hutk_ctx {
     DevBuf<int64_t> w_tile_i64;
     DevBuf<hutk::ExcRec> w_exc;
     DevBuf<uint32_t> w_exc_quad, w_exc_mid, w_exc_wave;
+    int last_tail = -1;  // the tail enqueued last: 0 k_exc_a .. k_finish, 1 k_tail_small (encode_device_impl); 2 none, 3 k_tail_small behind the one-launch k_tiles (encode_one_shot); -1 none yet (hutk_debug_exc_counts)
 
     // decode direction: tables and workspace
     DevBuf<uint2> d_dec_ent, d_dec_sent;

@@ -242,6 +242,19 @@ int hutk_debug_seam2_cut(const hutk_ctx* ctx, uint32_t a3, uint32_t b3);
  * function, so a test that means to reach one of the kernels can assert that it does.  A host-only context answers from
  * its tables.  tests/test_gpu_ptiles_edges.py. */
 int hutk_debug_tile_kernel(const hutk_ctx* ctx, int64_t n_bytes);
+/* Diagnostic: where the exception words (more than 32 units or 63 bytes, an end outside their tile's window, items of
+ * several units) of the context's most recent encode went: hutk_encode_batch_device, or a host-form call, which reports
+ * the last batch it enqueued.  The caller has synchronised that call's stream (the host forms have); nothing is launched,
+ * the device's counters are copied once (the next encode zeroes them).  out8: exception records; the entries of the five
+ * lists by length -- up to 128 units, up to 256, up to 512, up to 1024 (two, four, eight and sixteen lanes per word;
+ * vocabularies without those routines leave them 0) and the words that get a wavefront each; the tail the host enqueued:
+ * 0 = the exception, scan and finish kernels, 1 = the one-wavefront tail of a batch of at most 32 tiles and 4096
+ * documents, 2 = none, the one-launch tile kernel of a host-form batch of at most four tiles did everything (no exception
+ * word), 3 = the one-wavefront tail behind that one-launch kernel; 1 when the vocabulary has items of several units.  A
+ * host-form batch that fell back from the one-launch kernel to the three launches reports 0 or 1.  A test that means to
+ * reach one of the routines can assert that its batch did.  HUTK_E_ARG before the first encode.
+ * tests/test_gpu_exc_kinds.py. */
+int hutk_debug_exc_counts(const hutk_ctx* ctx, int64_t* out8);
 
 /* Diagnostic build aid: clock64 stamps at the phase boundaries of the tile kernel.
  * hutk_debug_profile(ctx, 1), run a batch, then hutk_debug_profile_read returns the

@@ -15,7 +15,6 @@ two must be equal.
 Constants cited below: TILE_BYTES = 960, LOOKBACK = 16, HALO = 64, LANE_MAX_UNITS = 32, LANE_MAX_BYTES = 63 (hutk_device.h);
 PT_SLOTS = 30, PT_QCAP = 2048, PT_STAGE = 256, PT_ROOM_AHEAD = 64, PT_WAVES = 16 (hutk_ptiles.hip).  G is the kernel's
 grid: the compute units rounded down to a multiple of 8 (pt_grid()), read from the device.  Needs a real MI355X."""
-import contextlib
 import os
 import random
 
@@ -23,6 +22,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from helpers import DeviceBatch as _Batch, device_encoder as _encoder, env_switches as _env, side_stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -46,26 +46,6 @@ def auto(monkeypatch):
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     monkeypatch.setenv("HUTK_PTILES_MIN_TILES", "1")
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    """Switches for the time of one call, None = unset (HUTK_PTILES is read by every encode, the others when a context is
-    made)."""
-    old = {k: os.environ.get(k) for k in kv}
-    for k, v in kv.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.fixture(scope="module")
@@ -113,76 +93,6 @@ def _seams_on(ctx):
 def _grid():
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8
-
-
-_side = None
-
-
-def _stream():
-    """One stream for the module.  (Not torch's current one: that is the null stream, for which the context takes its own.)"""
-    global _side
-    if _side is None:
-        import torch
-        _side = torch.cuda.Stream(torch.device("cuda", 0))
-    return _side
-
-
-class _Batch:
-    """A batch on the device; run() encodes it through hutk_encode_batch_device into fresh output buffers.  A device error --
-    a HIP failure, or HUTK_E_DEVICE from the kernel's own watchdog -- ends the whole session: nothing more is started on a
-    GPU that has faulted or hung."""
-
-    def __init__(self, ctx, data, offs):
-        import torch
-        self.ctx, self.dev = ctx, torch.device("cuda", 0)
-        self.n, self.nb = len(offs) - 1, int(offs[-1])
-        self.db = torch.from_numpy(np.array(data[:self.nb], dtype=np.uint8, copy=True)).to(self.dev)
-        self.do = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.int64)).to(self.dev)
-        self.cap = ctx.ids_capacity(self.nb, self.n)
-
-    def run(self, stream=None):
-        import torch
-        ids = torch.full((max(self.cap, 1),), -7, dtype=torch.int32, device=self.dev)
-        oo = torch.full((self.n + 1,), -7, dtype=torch.int64, device=self.dev)
-        st = torch.full((max(self.n, 1),), -7, dtype=torch.int32, device=self.dev)
-        err = torch.full((1,), -7, dtype=torch.int32, device=self.dev)
-        s = stream if stream is not None else _stream()
-        s.wait_stream(torch.cuda.current_stream(self.dev))  # (the copies and fills above)
-        try:
-            self.ctx.encode_device(self.db.data_ptr(), self.do.data_ptr(), self.n, self.nb, ids.data_ptr(), self.cap,
-                                   oo.data_ptr(), st.data_ptr(), err.data_ptr(), s.cuda_stream)
-            s.synchronize()
-            e = int(err.item())
-        except RuntimeError as ex:
-            pytest.exit("device failure, nothing more is run: %s" % ex, returncode=3)
-        if e == E_DEVICE:
-            pytest.exit("HUTK_E_DEVICE (the kernel's watchdog), nothing more is run", returncode=3)
-        oo = oo.cpu().numpy()
-        if e not in (0, E_WORD_TOO_LARGE):  # (an error: ids and offsets are not defined)
-            return np.zeros(0, dtype=np.int32), oo, st.cpu().numpy()[:self.n], e
-        total = int(oo[-1])
-        assert 0 <= total <= self.cap, total
-        return ids[:total].cpu().numpy(), oo, st.cpu().numpy()[:self.n], e
-
-
-def _encoder(ctx, want, twin):
-    """-> encode(data, offsets) for H.compare: asserts that hutk_debug_tile_kernel reports `want` for the batch, encodes it
-    on the device and, with `twin`, once more through k_tiles on the same buffers: everything the two write must be equal."""
-    def encode(data, offs):
-        nb = int(offs[-1])
-        assert ctx.tile_kernel(nb) == (want if nb else 0), "the batch would not be given the kernel this test is about"
-        b = _Batch(ctx, data, offs)
-        got = b.run()
-        if twin:
-            with _env(HUTK_PTILES="0"):
-                assert ctx.tile_kernel(nb) == 0
-                ref = b.run()
-            assert got[3] == ref[3], ("error word", got[3], ref[3])
-            assert np.array_equal(got[2], ref[2]), "status differs from k_tiles"
-            assert np.array_equal(got[1], ref[1]), "out_offsets differ from k_tiles"
-            assert np.array_equal(got[0], ref[0]), "ids differ from k_tiles"
-        return got
-    return encode
 
 
 def _check(ctx, orc, docs, tag, want=1, twin=True, want_rc=0):

@@ -53,7 +53,7 @@ from . import _capi
 from . import pretokenize as _presplit_tables  # (the module; the package's name `pretokenize` is the function below)
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 
-__all__ = ["initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -700,7 +700,7 @@ _SIDES = ("right", "left")
 
 
 def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, pad_id=0, truncation="right",
-                   padding_side="right", dtype=None, n_ids=None, check=False):
+                   padding_side="right", dtype=None, n_ids=None, check=False, return_plan=False):
     """Device tensors of encode_packed_device in, a padded batch out, on the current torch stream:
     -> (input_ids [n_docs, max_length] of `dtype` (torch.int32, the default, or torch.int64),
         attention_mask uint8 [n_docs, max_length], lengths int32 [n_docs]).
@@ -708,7 +708,8 @@ def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, p
     first (truncation="right") or last ("left") max_length - s of the document's ids; pad_id fills the rest on
     `padding_side`.  max_length=None pads to the longest sequence (one small synchronising read); a given one
     synchronises only to read offsets[-1], and not at all with n_ids=.  check=True synchronises and raises ValueError
-    when the kernel found offsets that do not describe ids."""
+    when the kernel found offsets that do not describe ids.  return_plan=True appends row_plan int64 [n_docs, 8], the
+    rows' geometry for gather_rows and answer_positions (one more launch on the same stream, no synchronisation)."""
     bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
     s = (bos != _capi.NO_TOKEN) + (eos != _capi.NO_TOKEN)
     if max_length is not None:
@@ -727,16 +728,20 @@ def collate_padded(ids, offsets, max_length=None, *, bos_id=None, eos_id=None, p
         longest = int((offsets[1:] - offsets[:-1]).max().item()) if n_docs else 0
         max_length = _length_arg("max_length", max(1, s, longest + s), 1)
     out, mask, lengths = _row_tensors(dev, n_docs, max_length, dname)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    err = torch.zeros(2 if return_plan else 1, dtype=torch.int32, device=dev)  # one word per call
     flags = (_capi.COLLATE_TRUNC_LEFT if truncation == "left" else 0) | \
             (_capi.COLLATE_PAD_LEFT if padding_side == "left" else 0)
+    plan = torch.empty((n_docs, 8), dtype=torch.int64, device=dev) if return_plan else None
     with torch.cuda.device(dev):
         _capi.collate_padded_device(ids.data_ptr(), offsets.data_ptr(), n_docs, n_ids, max_length, bos, eos, pad, flags,
                                     width, out.data_ptr(), mask.data_ptr(), lengths.data_ptr(), err.data_ptr(),
                                     torch.cuda.current_stream(dev).cuda_stream)
+        if return_plan:
+            _capi.padded_plan_device(offsets.data_ptr(), n_docs, n_ids, max_length, bos, eos, flags, plan.data_ptr(),
+                                     err[1:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if check:
-        _raise_device_error(err, "collate_padded")
-    return out, mask, lengths
+        _raise_device_error(err.max(), "collate_padded")
+    return (out, mask, lengths, plan) if return_plan else (out, mask, lengths)
 
 
 def _stride_arg(stride, room):
@@ -749,7 +754,7 @@ def _stride_arg(stride, room):
 
 
 def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=None, pad_id=0, padding_side="right",
-                    dtype=None, n_ids=None, n_rows=None, check=False):
+                    dtype=None, n_ids=None, n_rows=None, check=False, return_plan=False):
     """Device tensors of encode_packed_device in, every document as overlapping windows out, on the current torch stream:
     -> (input_ids [n_rows, max_length] of `dtype` (torch.int32, the default, or torch.int64),
         attention_mask uint8 [n_rows, max_length], lengths int32 [n_rows], row_map int64 [n_rows, 2]).
@@ -760,7 +765,8 @@ def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=N
     bos or eos is ids[offsets[document] + k * step + q - (1 with a bos_id)], so its span is that row of
     token_spans_device's result.  One small synchronising read gives the number of rows (and one more offsets[-1]);
     n_rows= and n_ids= avoid them.  check=True synchronises and raises ValueError when the kernels found offsets that do
-    not describe ids or an n_rows that is not the number of rows."""
+    not describe ids or an n_rows that is not the number of rows.  return_plan=True appends row_plan int64 [n_rows, 8]
+    (see collate_padded)."""
     bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
     s = (bos != _capi.NO_TOKEN) + (eos != _capi.NO_TOKEN)
     _length_arg("max_length", max_length, s + 1)
@@ -775,7 +781,9 @@ def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=N
     n_docs = offsets.numel() - 1
     n_ids = _n_ids(ids, offsets, n_ids)
     row_offsets = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
-    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+    err = torch.zeros(3 if return_plan else 2, dtype=torch.int32, device=dev)  # one word per call
+    plan = None
+    flags = _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _capi.windows_rows_device(offsets.data_ptr(), n_docs, n_ids, max_length, stride, bos, eos,
@@ -786,12 +794,15 @@ def collate_windows(ids, offsets, max_length, stride=0, *, bos_id=None, eos_id=N
                 raise ValueError("hutoken_amd: collate_windows: offsets that do not describe ids (%d rows)" % n_rows)
         out, mask, lengths, row_map = _row_tensors(dev, n_rows, max_length, dname, row_map=True)
         _capi.collate_windows_device(ids.data_ptr(), offsets.data_ptr(), row_offsets.data_ptr(), n_docs, n_ids, n_rows,
-                                     max_length, stride, bos, eos, pad,
-                                     _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0, width, out.data_ptr(),
+                                     max_length, stride, bos, eos, pad, flags, width, out.data_ptr(),
                                      mask.data_ptr(), lengths.data_ptr(), row_map.data_ptr(), err[1:].data_ptr(), stream)
+        if return_plan:
+            plan = torch.empty((n_rows, 8), dtype=torch.int64, device=dev)
+            _capi.windows_plan_device(offsets.data_ptr(), row_offsets.data_ptr(), n_docs, n_ids, n_rows, max_length, stride,
+                                      bos, eos, flags, plan.data_ptr(), err[2:].data_ptr(), stream)
     if check:
         _raise_device_error(err.max(), "collate_windows")
-    return out, mask, lengths, row_map
+    return (out, mask, lengths, row_map, plan) if return_plan else (out, mask, lengths, row_map)
 
 
 _side_streams = {}
@@ -850,19 +861,61 @@ def _texts_to_device(texts, with_text=False, normalize=None):
     return _encode_texts("plain", texts, 0, with_text, normalize)
 
 
-def batch_encode_padded(texts, max_length=None, *, normalize=None, **collate_kwargs):
+def _feature_args(return_offsets_mapping, offsets_unit, return_word_ids):
+    """What the batch_encode_* row functions check of their feature arguments before anything is encoded."""
+    for name, v in (("return_offsets_mapping", return_offsets_mapping), ("return_word_ids", return_word_ids)):
+        if not isinstance(v, bool):
+            raise TypeError("%s must be a bool, not %s" % (name, type(v).__name__))
+    _span_unit(offsets_unit)
+    if return_word_ids and _ctx is not None and _ctx.pretokenizer is None:
+        raise ValueError(_NO_PRESET)
+
+
+def _rows_with_features(collate, kwargs, text, return_offsets_mapping, offsets_unit, return_word_ids):
+    """collate(return_plan=..) -> its result with the rows' offset mapping and word ids appended, in that order: the
+    per-token arrays of the one encode call (text: its ids, offsets and packed text) laid out by the rows' plan."""
+    if not (return_offsets_mapping or return_word_ids):
+        return collate(**kwargs)
+    ids, oo, d_bytes, d_offs = text
+    want_plan = kwargs.pop("return_plan", False)
+    res = collate(return_plan=True, **kwargs)
+    plan = res[-1]
+    res = res if want_plan else res[:-1]
+    max_length = res[0].shape[1]
+    n_ids = int(oo[-1].item())
+    if return_offsets_mapping:
+        spans = token_spans_device(d_bytes, d_offs, ids, oo, unit=offsets_unit, n_ids=n_ids)
+        res += (gather_rows(plan, max_length, spans, fill=0),)
+    if return_word_ids:
+        words = token_word_ids_device(d_bytes, d_offs, ids, oo, n_ids=n_ids)
+        res += (gather_rows(plan, max_length, words, fill=-1),)
+    return res
+
+
+def batch_encode_padded(texts, max_length=None, *, normalize=None, return_offsets_mapping=False, offsets_unit="char",
+                        return_word_ids=False, **collate_kwargs):
     """A list of str -> collate_padded's (input_ids, attention_mask, lengths): encode_packed_device, then
     collate_padded with `collate_kwargs`, both on the initialised context's GPU.  normalize="NFC" (.. "NFKD"): the
-    texts are normalised on the GPU first (normalize_packed_device); None: they are encoded as they are."""
-    ids, oo = _texts_to_device(texts, normalize=normalize)
-    return collate_padded(ids, oo, max_length, **collate_kwargs)
+    texts are normalised on the GPU first (normalize_packed_device); None: they are encoded as they are.
+    return_offsets_mapping=True appends offset_mapping int32 [n_rows, L, 2], the span of every token in its text in
+    `offsets_unit` ("char" or "byte") and (0, 0) on the other columns; return_word_ids=True then appends word_ids int32
+    [n_rows, L], the word of its text each token starts in and -1 on the other columns (token_word_ids_device: the
+    context needs a split preset).  Both are token_spans_device / token_word_ids_device through gather_rows."""
+    _feature_args(return_offsets_mapping, offsets_unit, return_word_ids)
+    text = _texts_to_device(texts, with_text=True, normalize=normalize)
+    return _rows_with_features(lambda **kw: collate_padded(text[0], text[1], max_length, **kw), collate_kwargs,
+                               text, return_offsets_mapping, offsets_unit, return_word_ids)
 
 
-def batch_encode_windows(texts, max_length, stride=0, *, normalize=None, **collate_kwargs):
+def batch_encode_windows(texts, max_length, stride=0, *, normalize=None, return_offsets_mapping=False,
+                         offsets_unit="char", return_word_ids=False, **collate_kwargs):
     """A list of str -> collate_windows' (input_ids, attention_mask, lengths, row_map): encode_packed_device, then
-    collate_windows with `collate_kwargs`, both on the initialised context's GPU.  normalize: as batch_encode_padded."""
-    ids, oo = _texts_to_device(texts, normalize=normalize)
-    return collate_windows(ids, oo, max_length, stride, **collate_kwargs)
+    collate_windows with `collate_kwargs`, both on the initialised context's GPU.  normalize, return_offsets_mapping,
+    offsets_unit, return_word_ids: as batch_encode_padded."""
+    _feature_args(return_offsets_mapping, offsets_unit, return_word_ids)
+    text = _texts_to_device(texts, with_text=True, normalize=normalize)
+    return _rows_with_features(lambda **kw: collate_windows(text[0], text[1], max_length, stride, **kw), collate_kwargs,
+                               text, return_offsets_mapping, offsets_unit, return_word_ids)
 
 
 _PAIR_STRATEGIES = {"longest_first": _capi.PAIR_LONGEST_FIRST, "only_first": _capi.PAIR_ONLY_FIRST,
@@ -908,7 +961,7 @@ def _pair_template(bos_id, sep_ids, eos_id, pad_id, truncation, padding_side, dt
 
 
 def collate_pairs(ids_a, offsets_a, ids_b, offsets_b, max_length=None, *, truncation="longest_first", bos_id=None,
-                  sep_ids=(), eos_id=None, pad_id=0, padding_side="right", dtype=None, check=False):
+                  sep_ids=(), eos_id=None, pad_id=0, padding_side="right", dtype=None, check=False, return_plan=False):
     """Two ragged pairs of one device in, one row per pair of documents out, on the current torch stream:
     -> (input_ids [n, max_length] of `dtype` (torch.int32, the default, or torch.int64), attention_mask uint8
         [n, max_length], token_type_ids uint8 [n, max_length], lengths int32 [n]).
@@ -920,7 +973,8 @@ def collate_pairs(ids_a, offsets_a, ids_b, offsets_b, max_length=None, *, trunca
     side, and the other one only when it alone exceeds R.  token_type_ids is 0 on bos, A' and the separators, 1 on B' and
     eos, 0 on padding; lengths is ka + kb + s.  max_length=None pads to the longest pair with nothing cut (one small
     synchronising read); a given one never synchronises.  check=True synchronises and raises ValueError when the kernel
-    found offsets outside 0 <= offsets[0] <= .. <= offsets[n] <= ids.numel()."""
+    found offsets outside 0 <= offsets[0] <= .. <= offsets[n] <= ids.numel().  return_plan=True appends row_plan int64
+    [n, 8] (see collate_padded)."""
     bos, sep, eos, pad, s, strategy, width, dname = _pair_template(bos_id, sep_ids, eos_id, pad_id, truncation,
                                                                    padding_side, dtype)
     if max_length is not None:
@@ -933,24 +987,30 @@ def collate_pairs(ids_a, offsets_a, ids_b, offsets_b, max_length=None, *, trunca
         both = (offsets_a[1:] - offsets_a[:-1]).clamp_(min=0) + (offsets_b[1:] - offsets_b[:-1]).clamp_(min=0)
         max_length = _length_arg("max_length", s + max(1, int(both.max().item()) if n else 1), s + 1)
     out, mask, types, lengths = _row_tensors(dev, n, max_length, dname, types=True)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    err = torch.zeros(2 if return_plan else 1, dtype=torch.int32, device=dev)  # one word per call
     flags = _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0
 
     def call():
+        stream = torch.cuda.current_stream(dev).cuda_stream
         _capi.collate_pairs_device(ids_a.data_ptr(), offsets_a.data_ptr(), ids_b.data_ptr(), offsets_b.data_ptr(), 0, n,
                                    ids_a.numel(), ids_b.numel(), n, max_length, 0, strategy, bos, sep, eos, pad, flags,
                                    width, out.data_ptr(), mask.data_ptr(), types.data_ptr(), lengths.data_ptr(), 0,
-                                   err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        return out, mask, types, lengths
+                                   err.data_ptr(), stream)
+        if not return_plan:
+            return out, mask, types, lengths
+        plan = torch.empty((n, 8), dtype=torch.int64, device=dev)
+        _capi.pair_plan_device(offsets_a.data_ptr(), offsets_b.data_ptr(), 0, n, ids_a.numel(), ids_b.numel(), n, max_length,
+                               0, strategy, bos, sep, eos, flags, plan.data_ptr(), err[1:].data_ptr(), stream)
+        return out, mask, types, lengths, plan
     res = _on_torch_stream(dev, call, used=(ids_a, offsets_a, ids_b, offsets_b, err))
     if check:
-        _raise_device_error(err, "collate_pairs")
+        _raise_device_error(err.max(), "collate_pairs")
     return res
 
 
 def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=0, *, truncation="only_second",
                          bos_id=None, sep_ids=(), eos_id=None, pad_id=0, padding_side="right", dtype=None, n_rows=None,
-                         check=False):
+                         check=False, return_plan=False):
     """collate_pairs with the side `truncation` names ("only_second", the default, or "only_first") cut into overlapping
     windows instead of truncated -- question + long context for extractive QA:
     -> (input_ids, attention_mask, token_type_ids [n_rows, max_length], lengths int32 [n_rows], row_map int64 [n_rows, 2]).
@@ -960,7 +1020,8 @@ def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=
     The rows of pair 0 come first, then those of pair 1, ..; row_map[r] = (pair, k * step), so the spans of the cut side
     are rows of token_spans_device's result.  "longest_first" is refused: its overflow is a cross product of both sides'
     windows.  One small synchronising read gives the number of rows; n_rows= avoids it.  check=True synchronises and
-    raises ValueError for offsets outside their condition or an n_rows that is not the number of rows."""
+    raises ValueError for offsets outside their condition or an n_rows that is not the number of rows.  return_plan=True
+    appends row_plan int64 [n_rows, 8] (see collate_padded)."""
     bos, sep, eos, pad, s, strategy, width, dname = _pair_template(bos_id, sep_ids, eos_id, pad_id, truncation,
                                                                    padding_side, dtype)
     if strategy == _capi.PAIR_LONGEST_FIRST:
@@ -979,7 +1040,7 @@ def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=
         raise ValueError("n_rows must be in %d .. %d (the pairs .. the pairs and the ids of the cut side), not %d"
                          % (n, bound, n_rows))
     row_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+    err = torch.zeros(3 if return_plan else 2, dtype=torch.int32, device=dev)  # one word per call
     flags = _capi.COLLATE_PAD_LEFT if padding_side == "left" else 0
 
     def call():
@@ -996,7 +1057,12 @@ def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=
                                    row_offsets.data_ptr(), n, cap_a, cap_b, n_rows, max_length, stride, strategy, bos, sep,
                                    eos, pad, flags, width, out.data_ptr(), mask.data_ptr(), types.data_ptr(),
                                    lengths.data_ptr(), row_map.data_ptr(), err[1:].data_ptr(), stream)
-        return out, mask, types, lengths, row_map
+        if not return_plan:
+            return out, mask, types, lengths, row_map
+        plan = torch.empty((n_rows, 8), dtype=torch.int64, device=dev)
+        _capi.pair_plan_device(offsets_a.data_ptr(), offsets_b.data_ptr(), row_offsets.data_ptr(), n, cap_a, cap_b, n_rows,
+                               max_length, stride, strategy, bos, sep, eos, flags, plan.data_ptr(), err[2:].data_ptr(), stream)
+        return out, mask, types, lengths, row_map, plan
     res = _on_torch_stream(dev, call, used=(ids_a, offsets_a, ids_b, offsets_b, row_offsets, err))
     if check:
         _raise_device_error(err.max(), "collate_pair_windows")
@@ -1004,7 +1070,8 @@ def collate_pair_windows(ids_a, offsets_a, ids_b, offsets_b, max_length, stride=
 
 
 def _pair_texts_to_device(texts_a, texts_b, normalize):
-    """Two lists of str -> (ids, offsets_a, offsets_b): one encode of texts_a + texts_b, both sides views of its offsets."""
+    """Two lists of str -> (ids, offsets_a, offsets_b, text): one encode of texts_a + texts_b, both sides views of its
+    offsets; text: (ids, out_offsets, d_bytes, d_offsets) of that one call."""
     _normalize_arg(normalize)
     if _ctx is None:
         raise RuntimeError(_NOT_INIT)
@@ -1013,23 +1080,30 @@ def _pair_texts_to_device(texts_a, texts_b, normalize):
     if len(texts_a) != len(texts_b):
         raise ValueError("texts_a and texts_b must hold as many texts (%d and %d)" % (len(texts_a), len(texts_b)))
     n = len(texts_a)
-    ids, oo = _encode_texts("plain", texts_a + texts_b, 0, False, normalize)
-    return ids, oo[:n + 1], oo[n:]
+    text = _encode_texts("plain", texts_a + texts_b, 0, True, normalize)
+    return text[0], text[1][:n + 1], text[1][n:], text
 
 
-def batch_encode_pairs(texts_a, texts_b, max_length=None, *, normalize=None, **collate_kwargs):
+def batch_encode_pairs(texts_a, texts_b, max_length=None, *, normalize=None, return_offsets_mapping=False,
+                       offsets_unit="char", return_word_ids=False, **collate_kwargs):
     """Two lists of str -> collate_pairs' (input_ids, attention_mask, token_type_ids, lengths): one
     encode_packed_device call over texts_a + texts_b, then collate_pairs with `collate_kwargs` on views of its result,
-    on the initialised context's GPU.  normalize: as batch_encode_padded."""
-    ids, oa, ob = _pair_texts_to_device(texts_a, texts_b, normalize)
-    return collate_pairs(ids, oa, ids, ob, max_length, **collate_kwargs)
+    on the initialised context's GPU.  normalize, return_offsets_mapping, offsets_unit, return_word_ids: as
+    batch_encode_padded; the spans and word ids of either side count from the start of that side's own text."""
+    _feature_args(return_offsets_mapping, offsets_unit, return_word_ids)
+    ids, oa, ob, text = _pair_texts_to_device(texts_a, texts_b, normalize)
+    return _rows_with_features(lambda **kw: collate_pairs(ids, oa, ids, ob, max_length, **kw), collate_kwargs,
+                               text, return_offsets_mapping, offsets_unit, return_word_ids)
 
 
-def batch_encode_pair_windows(texts_a, texts_b, max_length, stride=0, *, normalize=None, **collate_kwargs):
+def batch_encode_pair_windows(texts_a, texts_b, max_length, stride=0, *, normalize=None, return_offsets_mapping=False,
+                              offsets_unit="char", return_word_ids=False, **collate_kwargs):
     """Two lists of str -> collate_pair_windows' (input_ids, attention_mask, token_type_ids, lengths, row_map); see
     batch_encode_pairs."""
-    ids, oa, ob = _pair_texts_to_device(texts_a, texts_b, normalize)
-    return collate_pair_windows(ids, oa, ids, ob, max_length, stride, **collate_kwargs)
+    _feature_args(return_offsets_mapping, offsets_unit, return_word_ids)
+    ids, oa, ob, text = _pair_texts_to_device(texts_a, texts_b, normalize)
+    return _rows_with_features(lambda **kw: collate_pair_windows(ids, oa, ids, ob, max_length, stride, **kw), collate_kwargs,
+                               text, return_offsets_mapping, offsets_unit, return_word_ids)
 
 
 class SequencePacker:
@@ -1672,3 +1746,179 @@ def pretokenize(texts, preset):
         edges = starts[so[i]:so[i + 1]] + [int(offs[i + 1])]
         out.append([raw[a:b].decode("utf-8", "surrogateescape") for a, b in zip(edges, edges[1:])])
     return out
+
+
+# ---- row-aligned features: the gather, word ids, answer positions -----------------------------------------
+_NO_PRESET = ("word ids need a split preset (set_pretokenizer, or preset=): the built-in splitter's word starts are not on "
+              "the device as a bitmap")
+
+
+def _is_tensor(t):
+    return hasattr(t, "data_ptr") and hasattr(t, "is_cuda") and hasattr(t, "dtype")
+
+
+def _dtype_name(t):
+    return str(t.dtype).rpartition(".")[2]
+
+
+def _plan_arg(row_plan):
+    if not _is_tensor(row_plan):
+        raise TypeError("row_plan must be a torch tensor, not %s" % type(row_plan).__name__)
+    if _dtype_name(row_plan) != "int64":
+        raise TypeError("row_plan must have dtype int64, not %s" % row_plan.dtype)
+    if row_plan.dim() != 2 or row_plan.shape[1] != 8 or not row_plan.is_contiguous():
+        raise ValueError("row_plan must be contiguous and of shape [n_rows, 8]")
+
+
+def _records_arg(name, t, pairs_only=False):
+    """A per-token array: [n] or [n, 2], int32 or int64, contiguous -> (dtype name, record bytes)."""
+    if not _is_tensor(t):
+        raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+    dname = _dtype_name(t)
+    if dname not in ("int32", "int64"):
+        raise TypeError("%s must have dtype int32 or int64, not %s" % (name, t.dtype))
+    shape_ok = (t.dim() == 2 and t.shape[1] == 2) or (t.dim() == 1 and not pairs_only)
+    if not shape_ok or not t.is_contiguous():
+        raise ValueError("%s must be contiguous and of shape %s[n, 2]" % (name, "" if pairs_only else "[n] or "))
+    return dname, (4 if dname == "int32" else 8) * (2 if t.dim() == 2 else 1)
+
+
+def _fill_arg(fill, per, dname):
+    """fill -> the record as bytes: an int, or with records of two values a pair of ints (an int then fills both)."""
+    import struct
+    vals = tuple(fill) if isinstance(fill, (tuple, list)) else (fill,)
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in vals):
+        raise TypeError("fill must be an int or a pair of ints")
+    if len(vals) not in (1, per):
+        raise ValueError("fill must be an int%s, not %d values" % (" or a pair of ints" if per == 2 else "", len(vals)))
+    bits = 31 if dname == "int32" else 63
+    if any(not -2**bits <= v < 2**bits for v in vals):
+        raise ValueError("fill must fit %s" % dname)
+    return struct.pack("<%d%s" % (per, "i" if dname == "int32" else "q"), *(vals * per if len(vals) == 1 else vals))
+
+
+def gather_rows(row_plan, max_length, values_a, values_b=None, *, fill=0, check=False):
+    """Any per-token array in the rows' shape: row_plan int64 [n_rows, 8] (return_plan=True of a collate_* call made with
+    this max_length) and values_a, a device tensor [n] or [n, 2] of int32 or int64 indexed like that call's ids_a (spans,
+    word ids, labels) -> [n_rows, max_length] or [n_rows, max_length, 2] of the same dtype: the value of the token a
+    column holds, `fill` (an int, or a pair of ints for [n, 2]) where it holds bos, a separator, eos or padding.
+    values_b: the B side's array, like ids_b; None reads both sides from values_a -- the one-encode-call case of
+    batch_encode_pairs.  On the current torch stream, never synchronises; check=True does and raises ValueError for a
+    plan that points outside the row or the values (nothing is read or written out of bounds either way)."""
+    _plan_arg(row_plan)
+    _length_arg("max_length", max_length, 1)
+    dname, rec = _records_arg("values_a", values_a)
+    if values_b is not None and (_records_arg("values_b", values_b) != (dname, rec)):
+        raise TypeError("values_b must have the dtype and the record shape of values_a")
+    per = 2 if values_a.dim() == 2 else 1
+    fill_bytes = _fill_arg(fill, per, dname)
+    vb = values_a if values_b is None else values_b
+    for name, t in (("row_plan", row_plan), ("values_a", values_a), ("values_b", vb)):
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU: the gather runs there and nowhere else" % name)
+        if t.device != row_plan.device:
+            raise ValueError("%s must be on the device of row_plan" % name)
+    import torch
+    dev = row_plan.device
+    n_rows = row_plan.shape[0]
+    out = torch.empty((n_rows, max_length) + ((2,) if per == 2 else ()), dtype=values_a.dtype, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.rows_gather_device(row_plan.data_ptr(), n_rows, max_length, values_a.data_ptr(), values_a.shape[0],
+                                 vb.data_ptr(), vb.shape[0], rec, fill_bytes, out.data_ptr(), err.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        return out
+    _on_torch_stream(dev, call, used=(row_plan, values_a, vb, err))
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: gather_rows: a row_plan that points outside its row or the values (device-side "
+                         "error %d)" % int(err.item()))
+    return out
+
+
+def answer_positions(row_plan, spans, answers, *, side="b", check=False):
+    """The columns at which an answer starts and ends in every row, for extractive QA: row_plan int64 [n_rows, 8], spans
+    [n, 2] (int32 or int64) of the tokens of `side` ("a" or "b"; indexed like that side's ids, e.g. token_spans_device
+    of the one encode call), answers [n_items, 2] with (start, end) of item i's answer in the spans' unit, from the start
+    of that side's text, (-1, -1) or start >= end for none -> int32 [n_rows, 2].  An answer lies in a row when the row's
+    tokens of that side cover it: the start column is that of the last token starting at or before `start`, the end
+    column that of the first token ending at or after `end` (run_qa's rule, on the window's own tokens); a row that
+    does not hold the whole answer gets (-1, -1), which the caller maps to its CLS column.  On the current torch stream,
+    never synchronises; check=True does and raises ValueError for a plan that points outside spans or answers."""
+    _plan_arg(row_plan)
+    dname, rec = _records_arg("spans", spans, pairs_only=True)
+    _records_arg("answers", answers, pairs_only=True)
+    if side not in ("a", "b"):
+        raise ValueError("side must be 'a' or 'b', not %r" % (side,))
+    for name, t in (("row_plan", row_plan), ("spans", spans), ("answers", answers)):
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU: the search runs there and nowhere else" % name)
+        if t.device != row_plan.device:
+            raise ValueError("%s must be on the device of row_plan" % name)
+    import torch
+    dev = row_plan.device
+    n_rows = row_plan.shape[0]
+    ans = answers if answers.dtype == spans.dtype else answers.to(spans.dtype)
+    out = torch.empty((n_rows, 2), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.rows_answers_device(row_plan.data_ptr(), n_rows, 1 if side == "b" else 0, spans.data_ptr(), rec // 2,
+                                  spans.shape[0], ans.data_ptr(), ans.shape[0], out.data_ptr(), err.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream)
+        return out
+    _on_torch_stream(dev, call, used=(row_plan, spans, ans, err))
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: answer_positions: a row_plan that points outside spans or answers (device-side "
+                         "error %d)" % int(err.item()))
+    return out
+
+
+def token_word_ids_device(d_bytes, d_offsets, ids, out_offsets, *, preset=None, n_ids=None, check=True):
+    """The packed text and what encode_packed_device made of it (as token_spans_device takes them) -> a device tensor
+    int32 [n_ids]: the word of its document each token starts in, counted from 0 -- what word_ids() gives elsewhere,
+    for aligning word-level labels (NER, POS) to tokens.  The words are those of a split preset ("gpt2", "cl100k" /
+    "llama3", "qwen2"); preset=None uses the one installed on the context (set_pretokenizer).  A context without one and
+    no preset= raises ValueError: the built-in splitter's word starts are not on the device as a bitmap, so there is
+    nothing to rank the tokens in.  Runs the split's bitmap, its prefix counts, the byte spans (token_spans_device) and
+    the rank kernel on the current torch stream.  check=True synchronises and raises as token_spans_device does, and
+    ValueError naming the first document that has a token with a word start strictly inside it: its ids were made
+    under another split (the other documents' word ids are exact)."""
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    if preset is None:
+        pi = _ctx.pretokenizer
+        if pi is None:
+            raise ValueError(_NO_PRESET)
+    else:
+        pi = _presplit_tables.preset_index(preset)
+    spans = token_spans_device(d_bytes, d_offsets, ids, out_offsets, unit="byte", n_ids=n_ids, check=check)
+    import torch
+    dev = ids.device
+    n_docs, n_bytes, n_ids = d_offsets.numel() - 1, d_bytes.numel(), spans.shape[0]
+    pt = _pretokenizer(dev)
+    words = torch.empty(n_ids, dtype=torch.int32, device=dev)
+    bits = torch.empty(n_bytes // 32 + 40, dtype=torch.int32, device=dev)
+    before = torch.zeros(n_bytes // 32 + 2, dtype=torch.int64, device=dev)
+    status = torch.zeros(max(n_docs, 1), dtype=torch.int32, device=dev)
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+
+    def call():
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        pt.batch_device(pi, d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, bits.data_ptr(), err[0:].data_ptr(), stream)
+        pt.starts_device(bits.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, before.data_ptr(), 0, 0, stream)
+        _capi.token_word_ids_device(bits.data_ptr(), before.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes,
+                                    spans.data_ptr(), 4, out_offsets.data_ptr(), n_ids, words.data_ptr(), status.data_ptr(),
+                                    err[1:].data_ptr(), stream)
+        return words
+    _on_torch_stream(dev, call, used=(d_bytes, d_offsets, out_offsets, spans, bits, before, status, err))
+    if check:
+        codes = err.tolist()
+        if codes[0] or codes[1] == _capi.E_ARG:
+            raise TypeError("hutoken_amd: token_word_ids_device: offsets that do not describe the tensors")
+        if codes[1]:
+            which = int(torch.nonzero(status[:n_docs]).flatten()[0].item())
+            raise ValueError("hutoken_amd: token_word_ids_device: document %d: a token holds a word start of the %s split "
+                             "strictly inside it: the ids were made under another split (device-side error %d)"
+                             % (which, _presplit_tables.PRESETS[pi], codes[1]))
+    return words

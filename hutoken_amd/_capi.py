@@ -111,6 +111,14 @@ SIGNATURES = {
     "hutk_pretokenize_starts_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hutk_debug_norm_chunk_bytes": (_i32, []),
     "hutk_debug_presplit_chunk_bytes": (_i32, []),
+    "hutk_padded_plan_device": (_i32, [_vp, _i64, _i64, _i64, _s32, _s32, _i32, _vp, _vp, _vp]),
+    "hutk_windows_plan_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _s32, _s32, _i32, _vp, _vp, _vp]),
+    "hutk_pair_plan_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _s32, _vp, _i32, _s32, _i32,
+                                     _vp, _vp, _vp]),
+    "hutk_rows_gather_device": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hutk_token_word_ids_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_debug_word_ids_tile": (_i32, []),
+    "hutk_rows_answers_device": (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -749,6 +757,56 @@ def collate_pairs_device(d_ids_a, d_offsets_a, d_ids_b, d_offsets_b, d_row_offse
                                                strategy, bos_id, sep, n_sep, eos_id, pad_id, flags, out_width,
                                                d_input_ids or None, d_mask or None, d_token_types or None,
                                                d_lengths or None, d_row_map or None, d_err or None, stream or None))
+
+
+def padded_plan_device(d_offsets, n_docs, n_ids, max_len, bos_id, eos_id, flags, d_plan, d_err=0, stream=0):
+    """hutk_padded_plan_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_padded_plan_device(d_offsets or None, n_docs, n_ids, max_len, bos_id, eos_id, flags,
+                                             d_plan or None, d_err or None, stream or None))
+
+
+def windows_plan_device(d_offsets, d_row_offsets, n_docs, n_ids, n_rows, max_len, stride, bos_id, eos_id, flags, d_plan,
+                        d_err=0, stream=0):
+    """hutk_windows_plan_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_windows_plan_device(d_offsets or None, d_row_offsets or None, n_docs, n_ids, n_rows, max_len,
+                                              stride, bos_id, eos_id, flags, d_plan or None, d_err or None, stream or None))
+
+
+def pair_plan_device(d_offsets_a, d_offsets_b, d_row_offsets, n_pairs, cap_a, cap_b, n_rows, max_len, stride, strategy,
+                     bos_id, sep_ids, eos_id, flags, d_plan, d_err=0, stream=0):
+    """hutk_pair_plan_device on raw device pointers (ints); d_row_offsets 0: one row per pair; sep_ids: a tuple of ints;
+    asynchronous on `stream`."""
+    sep, n_sep = _sep_array(sep_ids)
+    raise_for(load().hutk_pair_plan_device(d_offsets_a or None, d_offsets_b or None, d_row_offsets or None, n_pairs, cap_a,
+                                           cap_b, n_rows, max_len, stride, strategy, bos_id, sep, n_sep, eos_id, flags,
+                                           d_plan or None, d_err or None, stream or None))
+
+
+def rows_gather_device(d_plan, n_rows, max_len, d_values_a, n_a, d_values_b, n_b, rec_bytes, fill, d_out, d_err=0, stream=0):
+    """hutk_rows_gather_device on raw device pointers (ints); fill: the record as bytes of length rec_bytes;
+    asynchronous on `stream`."""
+    buf = (C.c_uint8 * 16).from_buffer_copy(bytes(fill).ljust(16, b"\0"))
+    raise_for(load().hutk_rows_gather_device(d_plan or None, n_rows, max_len, d_values_a or None, n_a, d_values_b or None,
+                                             n_b, rec_bytes, C.cast(buf, C.c_void_p), d_out or None, d_err or None,
+                                             stream or None))
+
+
+def token_word_ids_device(d_word_bits, d_before, d_offsets, n_docs, n_bytes, d_spans, span_width, d_id_offsets, n_ids,
+                          d_word_ids, d_status=0, d_err=0, stream=0):
+    """hutk_token_word_ids_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_token_word_ids_device(d_word_bits or None, d_before or None, d_offsets or None, n_docs, n_bytes,
+                                                d_spans or None, span_width, d_id_offsets or None, n_ids,
+                                                d_word_ids or None, d_status or None, d_err or None, stream or None))
+
+
+def word_ids_tile():
+    return load().hutk_debug_word_ids_tile()
+
+
+def rows_answers_device(d_plan, n_rows, side, d_spans, span_width, n_spans, d_answers, n_items, d_out, d_err=0, stream=0):
+    """hutk_rows_answers_device on raw device pointers (ints); side: 0 for A, 1 for B; asynchronous on `stream`."""
+    raise_for(load().hutk_rows_answers_device(d_plan or None, n_rows, side, d_spans or None, span_width, n_spans,
+                                              d_answers or None, n_items, d_out or None, d_err or None, stream or None))
 
 
 class Packer(_Owner):

@@ -13,12 +13,18 @@
 //            (k_rows_count, k_rows_write over "rows of item i": DocRows, PairRows).
 //   packed   the sequences of all documents laid end to end and cut into rows of seq_len, with position and segment
 //            ids; the unfinished row is carried over to the next call                  (k_collate_packed, k_collate_flush)
+// and what makes the per-token information of a row arrive in the row's shape: the geometry of
+// the rows as a device array, the row plan, written by a planner per row layout that places a row with the device
+// functions its collate kernel places it with (k_plan_padded, k_plan_windows, k_plan_pairs); the gather of any
+// per-token array into the rows' shape by a plan (k_rows_gather); the columns of an answer in every row
+// (k_rows_answers).
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets.  A workgroup of the row layouts stages the plan of its rows in LDS
 // once; one of the packed layout owns a contiguous span of output, finds the span's first document with one search by a
 // wavefront, marks the sequence starts of its span in LDS and turns the marks into "document of this position", "where
 // its sequence starts" and "starts since the row began" with one workgroup scan.
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -533,6 +539,27 @@ struct DocRows {
     }
 };
 
+// Row `row` among the nd staged documents (stage_items; s_off: their offsets): which one (behind the first staged),
+// where its window starts inside the document and how many ids it holds.  A length or a row_offsets that cannot be is
+// reported and gives an empty row.  What k_collate_windows and k_plan_windows both place a row with.
+__device__ __forceinline__ int32_t window_row(const int64_t* s_ro, const int64_t* s_off, int32_t nd, int64_t row, int64_t cap,
+                                              int32_t C, int32_t step, int32_t* err, int64_t& start, int32_t& n) {
+    const int32_t lo = staged_item_of_row(s_ro, nd, row);
+    int64_t dl = s_off[lo + 1] - s_off[lo];
+    const int64_t k = row - s_ro[lo];
+    bool bad = dl < 0 || dl > cap;
+    if (bad) dl = 0;
+    if (k < 0 || k >= window_count(dl, cap, C, step, nullptr)) bad = true;  // (a row_offsets that is not the scan of w)
+    start = 0;
+    n = 0;
+    if (bad) note_error(err, HUTK_E_ARG);
+    else {
+        start = k * step;  // < dl: no overflow
+        n = dl - start < C ? (int32_t)(dl - start) : C;
+    }
+    return lo;
+}
+
 struct WinArgs {
     RowArgs r;  // (ids_a, cap_a: the ids and their number)
     const int64_t* offs;
@@ -561,21 +588,9 @@ __global__ __launch_bounds__(TB) void k_collate_windows(const WinArgs a) {
     for (int32_t i = tid; i <= nd; i += TB) s_off[i] = a.offs[d0 + i];
     __syncthreads();
     if (tid < t.nrows) {
-        const int64_t row = t.row0 + tid;
-        const int32_t lo = staged_item_of_row(s_ro, nd, row);
-        int64_t dl = s_off[lo + 1] - s_off[lo];
-        const int64_t k = row - s_ro[lo];
-        bool bad = dl < 0 || dl > a.r.cap_a;
-        if (bad) dl = 0;
-        if (k < 0 || k >= window_count(dl, a.r.cap_a, a.C, a.step, nullptr)) bad = true;  // (a row_offsets that is not the scan of w)
-        int64_t start = 0;
-        int32_t n = 0;
-        if (bad) note_error(a.r.err, HUTK_E_ARG);
-        else {
-            start = k * a.step;  // < dl: no overflow
-            n = dl - start < a.C ? (int32_t)(dl - start) : a.C;
-        }
-        s_j[tid] = lo;
+        int64_t start;
+        int32_t n;
+        s_j[tid] = window_row(s_ro, s_off, nd, t.row0 + tid, a.r.cap_a, a.C, a.step, a.r.err, start, n);
         s_start[tid] = start;
         s_n[tid] = n;
     }
@@ -658,6 +673,50 @@ struct PairArgs {
     int32_t R, stride, strategy;
 };
 
+// One placed row of pairs: its pair (behind the first of the workgroup), the ids kept of both sides, the window's start
+// inside the cut side, and the index of the first id of either side that the row holds.
+struct PairRow {
+    int32_t lo, ka, kb;
+    int64_t start, a0, b0;
+};
+
+// Row tid of the workgroup's rows (the first is row0), both forms: the pair is the row itself, or is found among the nd
+// staged row_offsets.  What k_collate_pairs and k_plan_pairs both place a row with.
+__device__ __forceinline__ PairRow pair_row(const PairArgs& a, const int64_t* s_ro, int64_t d0, int32_t nd, int64_t row0, int tid) {
+    const bool win = a.rows != nullptr;
+    PairRow r;
+    r.lo = tid;
+    int64_t k = 0;
+    if (win) {
+        r.lo = staged_item_of_row(s_ro, nd, row0 + tid);
+        k = row0 + tid - s_ro[r.lo];
+    }
+    const int64_t p = d0 + r.lo;
+    const int64_t a0 = a.offs_a[p], b0 = a.offs_b[p];
+    const int64_t na = side_len(a0, a.offs_a[p + 1], a.r.cap_a, a.r.err);
+    const int64_t nb = side_len(b0, a.offs_b[p + 1], a.r.cap_b, a.r.err);
+    r.ka = 0, r.kb = 0;
+    r.start = 0;
+    const bool cut_b = a.strategy == HUTK_PAIR_ONLY_SECOND;
+    if (!win) pair_lengths(na, nb, a.R, a.strategy, r.ka, r.kb);
+    else {
+        int64_t C, step;
+        const int64_t n = cut_b ? nb : na;
+        const int64_t w = pair_window_count(n, cut_b ? na : nb, a.R, a.stride, C, step);
+        if (k < 0 || k >= w) note_error(a.r.err, HUTK_E_ARG);  // (a row_offsets that is not the scan of the counts)
+        else {
+            r.start = k * step;  // < n, or 0
+            const int32_t kn = n - r.start < C ? (int32_t)(n - r.start) : (int32_t)C;
+            const int32_t ko = a.R - (int32_t)C;
+            r.ka = cut_b ? ko : kn;
+            r.kb = cut_b ? kn : ko;
+        }
+    }
+    r.a0 = a0 + (cut_b ? 0 : r.start);
+    r.b0 = b0 + (cut_b ? r.start : 0);
+    return r;
+}
+
 // The planner, both forms.  Thread r places row r once: its pair (itself, or in the windows form found among the staged
 // row_offsets as k_collate_windows finds a document), both sides' offsets, ka, kb and the window's start go to LDS.
 // Whatever the offsets hold, every index stays inside the offsets arrays and the two id buffers.
@@ -683,44 +742,269 @@ __global__ __launch_bounds__(TB) void k_collate_pairs(const PairArgs a) {
         __syncthreads();
     }
     if (tid < t.nrows) {
-        int32_t lo = tid;
-        int64_t k = 0;
-        if (win) {
-            lo = staged_item_of_row(s_ro, nd, t.row0 + tid);
-            k = t.row0 + tid - s_ro[lo];
-        }
-        const int64_t p = d0 + lo;
-        const int64_t a0 = a.offs_a[p], b0 = a.offs_b[p];
-        const int64_t na = side_len(a0, a.offs_a[p + 1], a.r.cap_a, a.r.err);
-        const int64_t nb = side_len(b0, a.offs_b[p + 1], a.r.cap_b, a.r.err);
-        int32_t ka = 0, kb = 0;
-        int64_t start = 0;
-        const bool cut_b = a.strategy == HUTK_PAIR_ONLY_SECOND;
-        if (!win) pair_lengths(na, nb, a.R, a.strategy, ka, kb);
-        else {
-            int64_t C, step;
-            const int64_t n = cut_b ? nb : na;
-            const int64_t w = pair_window_count(n, cut_b ? na : nb, a.R, a.stride, C, step);
-            if (k < 0 || k >= w) note_error(a.r.err, HUTK_E_ARG);  // (a row_offsets that is not the scan of the counts)
-            else {
-                start = k * step;  // < n, or 0
-                const int32_t kn = n - start < C ? (int32_t)(n - start) : (int32_t)C;
-                const int32_t ko = a.R - (int32_t)C;
-                ka = cut_b ? ko : kn;
-                kb = cut_b ? kn : ko;
-            }
-        }
-        s_j[tid] = lo;
-        s_start[tid] = start;
-        s_ka[tid] = ka;
-        s_kb[tid] = kb;
-        s_srca[tid] = a0 + (cut_b ? 0 : start) - a.r.has_bos;
-        s_srcb[tid] = b0 + (cut_b ? start : 0) - (a.r.has_bos + ka + a.r.n_sep);
+        const PairRow r = pair_row(a, s_ro, d0, nd, t.row0, tid);
+        s_j[tid] = r.lo;
+        s_start[tid] = r.start;
+        s_ka[tid] = r.ka;
+        s_kb[tid] = r.kb;
+        s_srca[tid] = r.a0 - a.r.has_bos;
+        s_srcb[tid] = r.b0 - (a.r.has_bos + r.ka + a.r.n_sep);
     }
     __syncthreads();
     write_rows<W, VEC, true>(a.r, t, [&](int32_t rl) {
         return RowPlan{s_ka[rl], s_kb[rl], s_srca[rl], s_srcb[rl], d0 + s_j[rl], s_start[rl]};
     });
+}
+
+// ---- row plans --------------------------------------------------------------------------------------------------------
+// The geometry of a row as data: plan[r] = (item, start, src_a, ka, col_a, src_b, kb, col_b), eight int64.
+// Columns col_a .. col_a + ka - 1 of row r hold ids_a[src_a ..], columns col_b .. col_b + kb - 1 ids_b[src_b ..]; every
+// other column is bos, a separator, eos or padding.  A planner is the placement of its collate kernel, one thread per
+// row, with the row written as a plan instead of as elements.
+struct PlanOut {
+    int64_t* plan;
+    int32_t vec;  // plan is 16-byte aligned
+};
+
+// The plan of row `row` from what write_rows takes: the kept lengths, the first id of either side, (item, start)
+template <bool PAIR>
+__device__ __forceinline__ void store_plan(const PlanOut& o, const RowArgs& a, int64_t row, int64_t item, int64_t start,
+                                           int64_t src_a, int32_t ka, int64_t src_b, int32_t kb) {
+    const int32_t sl = ka + (PAIR ? kb : 0) + a.s;
+    const int64_t col_a = (a.pad_left ? a.L - sl : 0) + a.has_bos;
+    const int64_t col_b = col_a + ka + (PAIR ? a.n_sep : 0);
+    int64_t* p = o.plan + 8 * row;
+    if (!PAIR) src_b = 0, kb = 0;
+    if (o.vec) {
+        longlong2* q = reinterpret_cast<longlong2*>(p);
+        q[0] = make_longlong2(item, start);
+        q[1] = make_longlong2(src_a, ka);
+        q[2] = make_longlong2(col_a, src_b);
+        q[3] = make_longlong2(kb, col_b);
+    } else {
+        p[0] = item, p[1] = start, p[2] = src_a, p[3] = ka, p[4] = col_a, p[5] = src_b, p[6] = kb, p[7] = col_b;
+    }
+}
+
+// the 256 rows a workgroup of a planner places, as the tile that stage_items takes
+__device__ __forceinline__ RowTile plan_tile(int64_t n_rows) {
+    RowTile t{};
+    t.row0 = (int64_t)blockIdx.x * TB;
+    const int64_t left = n_rows - t.row0;
+    t.nrows = left < TB ? (int32_t)left : TB;
+    return t;
+}
+
+__global__ __launch_bounds__(TB) void k_plan_padded(const PadArgs a, const PlanOut o) {
+    const int64_t row = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (row >= a.n_docs) return;
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.r.cap_a) {  // the rows of offsets that do not fit the ids are empty
+        note_error(a.r.err, HUTK_E_ARG);
+        store_plan<false>(o, a.r, row, row, 0, 0, 0, 0, 0);
+        return;
+    }
+    const int64_t o0 = a.offs[row], o1 = a.offs[row + 1];
+    int64_t dl = o1 - o0;
+    if (dl < 0 || dl > a.r.cap_a) {
+        note_error(a.r.err, HUTK_E_ARG);
+        store_plan<false>(o, a.r, row, row, 0, 0, 0, 0, 0);
+        return;
+    }
+    const int32_t room = a.r.L - a.r.s;
+    const int32_t ka = dl > room ? room : (int32_t)dl;
+    const int64_t start = a.trunc_left ? dl - ka : 0;
+    store_plan<false>(o, a.r, row, row, start, o0 + start, ka, 0, 0);
+}
+
+__global__ __launch_bounds__(TB) void k_plan_windows(const WinArgs a, const PlanOut o) {
+    __shared__ int64_t s_ro[PAD_ROWS + 1], s_off[PAD_ROWS + 1];
+    __shared__ int64_t s_d0;
+    const int tid = threadIdx.x;
+    const RowTile t = plan_tile(a.n_rows);
+    if (t.nrows <= 0) return;
+    if (a.offs[0] != 0 || a.offs[a.n_docs] != a.r.cap_a || a.rows[0] != 0 || a.rows[a.n_docs] != a.n_rows) {
+        note_error(a.r.err, HUTK_E_ARG);
+        if (tid < t.nrows) store_plan<false>(o, a.r, t.row0 + tid, 0, 0, 0, 0, 0, 0);
+        return;
+    }
+    int32_t nd;
+    const int64_t d0 = stage_items(a.rows, a.n_docs, t, s_ro, &s_d0, nd);
+    for (int32_t i = tid; i <= nd; i += TB) s_off[i] = a.offs[d0 + i];
+    __syncthreads();
+    if (tid < t.nrows) {
+        int64_t start;
+        int32_t n;
+        const int32_t lo = window_row(s_ro, s_off, nd, t.row0 + tid, a.r.cap_a, a.C, a.step, a.r.err, start, n);
+        store_plan<false>(o, a.r, t.row0 + tid, d0 + lo, start, s_off[lo] + start, n, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(TB) void k_plan_pairs(const PairArgs a, const PlanOut o) {
+    __shared__ int64_t s_ro[PAD_ROWS + 1];
+    __shared__ int64_t s_d0;
+    const bool win = a.rows != nullptr;
+    const int tid = threadIdx.x;
+    const RowTile t = plan_tile(a.n_rows);
+    if (t.nrows <= 0) return;
+    if (win && (a.rows[0] != 0 || a.rows[a.n_pairs] != a.n_rows)) {
+        note_error(a.r.err, HUTK_E_ARG);
+        if (tid < t.nrows) store_plan<true>(o, a.r, t.row0 + tid, 0, 0, 0, 0, 0, 0);
+        return;
+    }
+    int64_t d0 = t.row0;
+    int32_t nd = t.nrows;
+    if (win) {
+        d0 = stage_items(a.rows, a.n_pairs, t, s_ro, &s_d0, nd);
+        __syncthreads();
+    }
+    if (tid < t.nrows) {
+        const PairRow r = pair_row(a, s_ro, d0, nd, t.row0, tid);
+        store_plan<true>(o, a.r, t.row0 + tid, d0 + r.lo, r.start, r.a0, r.ka, r.b0, r.kb);
+    }
+}
+
+// ---- the gather -------------------------------------------------------------------------------------------------------
+// out[r][c] = the record of the token that a planned row holds at column c, `fill` where it holds none: any per-token
+// array (spans, word ids, labels) in the rows' shape.  The tiling is that of the row writers (row_tile); the plans of a
+// workgroup's rows are staged in LDS once, clipped to the row, so that an element is four comparisons and at most one
+// load of REC bytes.  The plan is a caller's tensor: whatever it holds, a column outside [0, L) is never written and a
+// record outside values_a[0, n_a) / values_b[0, n_b) is never read.
+struct GatherArgs {
+    RowArgs r;  // (L, rows_per_block, col_chunks, err: what row_tile reads)
+    const int64_t* plan;
+    int64_t n_rows;
+    const void *va, *vb;
+    int64_t n_a, n_b;
+    int32_t f0, f1, f2, f3;  // the fill record (no array: a kernel argument indexed at run time lives in scratch)
+    void* out;
+};
+
+// one side of one plan, clipped: columns [lo, hi) of the row hold records src + (c - col); lo == hi: none
+__device__ __forceinline__ void clip_side(int64_t col, int64_t k, int32_t L, int32_t* err, int32_t& lo, int32_t& hi, int32_t& c0) {
+    lo = hi = c0 = 0;
+    if (k < 0) note_error(err, HUTK_E_ARG);
+    if (k <= 0) return;
+    if (col < 0 || col >= L || k > L - col) note_error(err, HUTK_E_ARG);  // (a planner never writes a side that leaves the row)
+    if (col >= L || col <= -(int64_t)L) return;
+    if (k > L) k = L;
+    const int64_t end = col + k;  // no overflow: |col| < L, k <= L
+    if (end <= 0) return;
+    lo = col < 0 ? 0 : (int32_t)col;
+    hi = end > L ? L : (int32_t)end;
+    c0 = (int32_t)col;
+}
+
+template <int REC>
+struct RecWord;  // the type a record is moved as on the wide path
+template <> struct RecWord<4> { using T = int32_t; };
+template <> struct RecWord<8> { using T = int2; };
+template <> struct RecWord<16> { using T = int4; };
+
+// WIDE: L * REC is a multiple of 16, out is 16-byte aligned and both value arrays are aligned to REC: a thread moves
+// 16 / REC records and stores 16 bytes.  Otherwise a thread moves one record dword by dword.
+template <int REC, bool WIDE>
+__global__ __launch_bounds__(TB) void k_rows_gather(const GatherArgs a) {
+    __shared__ int64_t s_srca[PAD_ROWS], s_srcb[PAD_ROWS];
+    __shared__ int32_t s_loa[PAD_ROWS], s_hia[PAD_ROWS], s_ca[PAD_ROWS], s_lob[PAD_ROWS], s_hib[PAD_ROWS], s_cb[PAD_ROWS];
+    const RowTile t = row_tile(a.r, a.n_rows);
+    if (t.nrows <= 0) return;
+    if (threadIdx.x < t.nrows) {
+        const int tid = threadIdx.x;
+        const int64_t* p = a.plan + 8 * (t.row0 + tid);
+        const bool first = t.c0 == 0;  // (of the workgroups of one long row, the first reports what is wrong with its plan)
+        int32_t lo, hi, c0;
+        clip_side(p[4], p[3], a.r.L, first ? a.r.err : nullptr, lo, hi, c0);
+        s_srca[tid] = p[2], s_loa[tid] = lo, s_hia[tid] = hi, s_ca[tid] = c0;
+        const int32_t lo_a = lo, hi_a = hi;
+        clip_side(p[7], p[6], a.r.L, first ? a.r.err : nullptr, lo, hi, c0);
+        s_srcb[tid] = p[5], s_lob[tid] = lo, s_hib[tid] = hi, s_cb[tid] = c0;
+        if (first && lo_a < hi_a && lo < hi && lo < hi_a && lo_a < hi) note_error(a.r.err, HUTK_E_ARG);  // (sides that overlap: A wins)
+    }
+    __syncthreads();
+    constexpr int V = WIDE ? 16 / REC : 1;  // records per thread
+    constexpr int D = REC / 4;              // dwords per record
+    const int32_t fill[4] = {a.f0, a.f1, a.f2, a.f3};  // (indexed by constants only)
+    for (int32_t i = threadIdx.x * V; i < t.total; i += TB * V) {
+        const int32_t rl = t.one_row ? 0 : i / a.r.L;
+        const int32_t c = t.one_row ? t.c0 + i : i - rl * a.r.L;
+        const int32_t lo_a = s_loa[rl], hi_a = s_hia[rl], lo_b = s_lob[rl], hi_b = s_hib[rl];
+        int32_t v[V * D];
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+#pragma unroll
+            for (int w = 0; w < D; w++) v[e * D + w] = fill[w];
+            const int32_t col = c + e;
+            const bool in_a = col >= lo_a && col < hi_a;
+            if (!in_a && !(col >= lo_b && col < hi_b)) continue;
+            const int64_t src = in_a ? s_srca[rl] : s_srcb[rl], n = in_a ? a.n_a : a.n_b;
+            const int64_t d = col - (in_a ? s_ca[rl] : s_cb[rl]);  // >= 0: col >= lo >= the side's first column
+            if (src >= n || src + d < 0 || src + d >= n) {  // (no overflow: src < n and 0 <= d < L)
+                note_error(a.r.err, HUTK_E_ARG);
+                continue;
+            }
+            const void* base = in_a ? a.va : a.vb;
+            if constexpr (WIDE) {
+                using T = typename RecWord<REC>::T;
+                const T x = static_cast<const T*>(base)[src + d];
+                if constexpr (REC == 4) v[e] = x;
+                else if constexpr (REC == 8) v[2 * e] = x.x, v[2 * e + 1] = x.y;
+                else v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+            } else {
+                const int32_t* x = static_cast<const int32_t*>(base) + (src + d) * D;
+#pragma unroll
+                for (int w = 0; w < D; w++) v[w] = x[w];
+            }
+        }
+        const int64_t at = (t.row0 + rl) * (int64_t)a.r.L + c;  // in records
+        if constexpr (WIDE) {
+            *reinterpret_cast<int4*>(static_cast<char*>(a.out) + at * REC) = make_int4(v[0], v[1], v[2], v[3]);
+        } else {
+            int32_t* q = static_cast<int32_t*>(a.out) + at * D;
+#pragma unroll
+            for (int w = 0; w < D; w++) q[w] = v[w];
+        }
+    }
+}
+
+// ---- answer positions -------------------------------------------------------------------------------------------------
+// The tokens of the named side of row r are j in [src, src + k) with non-decreasing spans (a_j, b_j); the answer (s, e)
+// of the row's item lies in the row iff k > 0, a_src <= s and b_{src + k - 1} >= e, and then starts at the column of
+// max j: a_j <= s and ends at that of min j: b_j >= e.  One wavefront per row, two searches.
+struct AnsArgs {
+    const int64_t* plan;
+    int64_t n_rows;
+    const void* spans;
+    int64_t n_spans;
+    const void* answers;
+    int64_t n_items;
+    int32_t* out;
+    int32_t* err;
+    int32_t side_b;
+};
+
+template <class T>
+__global__ __launch_bounds__(TB) void k_rows_answers(const AnsArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+    if (row >= a.n_rows) return;  // (a whole wavefront)
+    const int64_t* p = a.plan + 8 * row;
+    const int64_t item = p[0], src = p[a.side_b ? 5 : 2], k = p[a.side_b ? 6 : 3], col = p[a.side_b ? 7 : 4];
+    int32_t c_start = -1, c_end = -1;
+    const bool sound = item >= 0 && item < a.n_items && (k <= 0 || (src >= 0 && src < a.n_spans && k <= a.n_spans - src &&
+                                                                    col >= 0 && col <= INT32_MAX - k));
+    if (!sound) {
+        if (lane == 0) note_error(a.err, HUTK_E_ARG);
+    } else if (k > 0) {
+        const T* ans = static_cast<const T*>(a.answers) + 2 * item;
+        const T* sp = static_cast<const T*>(a.spans) + 2 * src;
+        const int64_t s = ans[0], e = ans[1];
+        if (s < e) {  // ((-1, -1) or s >= e: no answer)
+            const int64_t js = hutk::wave_count_leading(k, [&](int64_t j) { return (int64_t)sp[2 * j] <= s; }) - 1;
+            const int64_t je = hutk::wave_count_leading(k, [&](int64_t j) { return (int64_t)sp[2 * j + 1] < e; });
+            if (js >= 0 && je < k) c_start = (int32_t)(col + js), c_end = (int32_t)(col + je);
+        }
+    }
+    if (lane == 0) a.out[2 * row] = c_start, a.out[2 * row + 1] = c_end;
 }
 
 bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
@@ -871,6 +1155,20 @@ int pair_sizes(const char* who, int64_t max_len, int64_t stride, int strategy, i
     if (stride < 0 || stride >= max_len - *s)
         return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": stride must be in 0 .. max_len - s - 1");
     *R = max_len - *s;
+    return HUTK_OK;
+}
+
+// what the three planners launch alike: one thread per row, d_err cleared first
+template <class Args, class Kernel>
+int launch_plan(const char* who, Kernel k, Args& a, int64_t n_rows, int64_t* d_plan, hipStream_t st) {
+    if (!aligned_to(d_plan, 8)) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": d_plan must be 8-byte aligned");
+    const int64_t blocks = (n_rows + TB - 1) / TB;
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, std::string(who) + ": the batch is too large for one launch");
+    if (a.r.err) HUTK_HIP_TRY(hipMemsetAsync(a.r.err, 0, sizeof(int32_t), st));
+    if (blocks == 0) return HUTK_OK;
+    const PlanOut o{d_plan, aligned_to(d_plan, 16)};
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(TB), 0, st, a, o);
+    HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }
 
@@ -1073,6 +1371,159 @@ int hutk_collate_pairs_device(const int32_t* d_ids_a, const int64_t* d_offsets_a
     with_width_vec(out_width, vec, [&](auto w, auto v) {
         hipLaunchKernelGGL((k_collate_pairs<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
     });
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+// ---- row plans, the gather and the answer positions ---------------------------------------------------------
+int hutk_padded_plan_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, int64_t max_len, int32_t bos_id,
+                            int32_t eos_id, int flags, int64_t* d_plan, int32_t* d_err, void* hip_stream) {
+    const int s = (bos_id != HUTK_NO_TOKEN) + (eos_id != HUTK_NO_TOKEN);
+    if (n_docs < 0 || n_ids < 0 || (flags & ~(HUTK_COLLATE_TRUNC_LEFT | HUTK_COLLATE_PAD_LEFT)))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_padded_plan_device: bad arguments");
+    if (max_len < 1 || max_len < s || max_len > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_padded_plan_device: max_len must be at least 1 and the number of "
+                                               "bos/eos tokens, and below 2^31");
+    if (int rc = device_present("hutk_padded_plan_device")) return rc;
+    if (n_docs == 0) return HUTK_OK;
+    if (!d_offsets || !d_plan) return hutk::api_set_error(HUTK_E_ARG, "hutk_padded_plan_device: a buffer is NULL");
+    PadArgs a;
+    a.r = row_args(max_len, s, bos_id, eos_id, 0, flags, nullptr, nullptr, nullptr, nullptr, nullptr, d_err);
+    a.r.cap_a = n_ids;
+    a.offs = d_offsets;
+    a.n_docs = n_docs;
+    a.trunc_left = (flags & HUTK_COLLATE_TRUNC_LEFT) != 0;
+    return launch_plan("hutk_padded_plan_device", k_plan_padded, a, n_docs, d_plan, (hipStream_t)hip_stream);
+}
+
+int hutk_windows_plan_device(const int64_t* d_offsets, const int64_t* d_row_offsets, int64_t n_docs, int64_t n_ids,
+                             int64_t n_rows, int64_t max_len, int64_t stride, int32_t bos_id, int32_t eos_id, int flags,
+                             int64_t* d_plan, int32_t* d_err, void* hip_stream) {
+    const int s = (bos_id != HUTK_NO_TOKEN) + (eos_id != HUTK_NO_TOKEN);
+    if (n_docs < 0 || n_ids < 0 || n_rows < 0 || (flags & ~HUTK_COLLATE_PAD_LEFT))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_windows_plan_device: bad arguments (of the flags, only "
+                                               "HUTK_COLLATE_PAD_LEFT applies)");
+    int64_t C, step;
+    if (int rc = window_sizes("hutk_windows_plan_device", max_len, stride, s, &C, &step)) return rc;
+    if (int rc = device_present("hutk_windows_plan_device")) return rc;
+    if (n_docs == 0) return HUTK_OK;
+    if (!d_offsets || !d_row_offsets || (n_rows > 0 && !d_plan))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_windows_plan_device: a buffer is NULL");
+    WinArgs a;
+    a.r = row_args(max_len, s, bos_id, eos_id, 0, flags, nullptr, nullptr, nullptr, nullptr, nullptr, d_err);
+    a.r.cap_a = n_ids;
+    a.offs = d_offsets;
+    a.rows = d_row_offsets;
+    a.n_docs = n_docs;
+    a.n_rows = n_rows;
+    a.C = (int32_t)C;
+    a.step = (int32_t)step;
+    return launch_plan("hutk_windows_plan_device", k_plan_windows, a, n_rows, d_plan, (hipStream_t)hip_stream);
+}
+
+int hutk_pair_plan_device(const int64_t* d_offsets_a, const int64_t* d_offsets_b, const int64_t* d_row_offsets,
+                          int64_t n_pairs, int64_t cap_a, int64_t cap_b, int64_t n_rows, int64_t max_len, int64_t stride,
+                          int strategy, int32_t bos_id, const int32_t* sep_ids, int n_sep, int32_t eos_id, int flags,
+                          int64_t* d_plan, int32_t* d_err, void* hip_stream) {
+    if (n_pairs < 0 || cap_a < 0 || cap_b < 0 || n_rows < 0 || (flags & ~HUTK_COLLATE_PAD_LEFT))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_plan_device: bad arguments (of the flags, only "
+                                               "HUTK_COLLATE_PAD_LEFT applies)");
+    int s;
+    int64_t R;
+    if (int rc = pair_sizes("hutk_pair_plan_device", max_len, stride, strategy, bos_id, sep_ids, n_sep, eos_id, &s, &R))
+        return rc;
+    if (d_row_offsets && strategy == HUTK_PAIR_LONGEST_FIRST)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_plan_device: with d_row_offsets the strategy must name the side "
+                                               "that is cut into windows (HUTK_PAIR_ONLY_FIRST or HUTK_PAIR_ONLY_SECOND)");
+    if (!d_row_offsets && n_rows != n_pairs)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_plan_device: without d_row_offsets n_rows must be n_pairs");
+    if (int rc = device_present("hutk_pair_plan_device")) return rc;
+    if (n_pairs == 0) return HUTK_OK;
+    if (!d_offsets_a || !d_offsets_b || (n_rows > 0 && !d_plan))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_pair_plan_device: a buffer is NULL");
+    PairArgs a;
+    a.r = row_args(max_len, s, bos_id, eos_id, 0, flags, nullptr, nullptr, nullptr, nullptr, nullptr, d_err);
+    a.r.cap_a = cap_a;
+    a.r.cap_b = cap_b;
+    a.r.n_sep = n_sep;
+    a.offs_a = d_offsets_a;
+    a.offs_b = d_offsets_b;
+    a.rows = d_row_offsets;
+    a.n_pairs = n_pairs;
+    a.n_rows = n_rows;
+    a.R = (int32_t)R;
+    a.stride = (int32_t)stride;
+    a.strategy = strategy;
+    return launch_plan("hutk_pair_plan_device", k_plan_pairs, a, n_rows, d_plan, (hipStream_t)hip_stream);
+}
+
+int hutk_rows_gather_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_values_a, int64_t n_a,
+                            const void* d_values_b, int64_t n_b, int rec_bytes, const void* fill, void* d_out,
+                            int32_t* d_err, void* hip_stream) {
+    if (n_rows < 0 || n_a < 0 || n_b < 0 || (rec_bytes != 4 && rec_bytes != 8 && rec_bytes != 16) || !fill)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_gather_device: bad arguments (rec_bytes is 4, 8 or 16)");
+    if (max_len < 1 || max_len > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_gather_device: max_len must be in 1 .. 2^31 - 1");
+    if (int rc = device_present("hutk_rows_gather_device")) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return HUTK_OK;
+    if (!d_plan || !d_out || (n_a > 0 && !d_values_a) || (n_b > 0 && !d_values_b))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_gather_device: a buffer is NULL");
+    const uintptr_t least = rec_bytes == 16 ? 8 : 4;  // a record is one or two int32 or int64
+    if (!aligned_to(d_plan, 8) || !aligned_to(d_out, least) || !aligned_to(d_values_a, least) || !aligned_to(d_values_b, least))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_gather_device: a buffer is not aligned to its elements");
+    GatherArgs a = {};
+    a.r.L = (int32_t)max_len;
+    a.r.err = d_err;
+    a.plan = d_plan;
+    a.n_rows = n_rows;
+    a.va = d_values_a;
+    a.vb = d_values_b;
+    a.n_a = n_a;
+    a.n_b = n_b;
+    int32_t f[4] = {0, 0, 0, 0};
+    memcpy(f, fill, (size_t)rec_bytes);
+    a.f0 = f[0], a.f1 = f[1], a.f2 = f[2], a.f3 = f[3];
+    a.out = d_out;
+    int64_t blocks;
+    bool vec;
+    if (int rc = row_grid("hutk_rows_gather_device", a.r, n_rows, &blocks, &vec)) return rc;
+    const bool wide = max_len * rec_bytes % 16 == 0 && aligned_to(d_out, 16) && aligned_to(d_values_a, (uintptr_t)rec_bytes) &&
+                      aligned_to(d_values_b, (uintptr_t)rec_bytes);
+    const dim3 grid((unsigned)blocks), block(TB);
+    auto launch = [&](auto rec) {
+        constexpr int REC = decltype(rec)::value;
+        if (wide) hipLaunchKernelGGL((k_rows_gather<REC, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_rows_gather<REC, false>), grid, block, 0, st, a);
+    };
+    if (rec_bytes == 4) launch(std::integral_constant<int, 4>{});
+    else if (rec_bytes == 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 16>{});
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_rows_answers_device(const int64_t* d_plan, int64_t n_rows, int side, const void* d_spans, int span_width,
+                             int64_t n_spans, const void* d_answers, int64_t n_items, int32_t* d_out, int32_t* d_err,
+                             void* hip_stream) {
+    if (n_rows < 0 || n_spans < 0 || n_items < 0 || (side != 0 && side != 1) || (span_width != 4 && span_width != 8))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_answers_device: bad arguments (side is 0 for A or 1 for B, "
+                                               "span_width 4 or 8)");
+    if (int rc = device_present("hutk_rows_answers_device")) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return HUTK_OK;
+    if (!d_plan || !d_out || (n_spans > 0 && !d_spans) || (n_items > 0 && !d_answers))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_answers_device: a buffer is NULL");
+    if (!aligned_to(d_plan, 8) || !aligned_to(d_spans, (uintptr_t)span_width) || !aligned_to(d_answers, (uintptr_t)span_width) ||
+        !aligned_to(d_out, 4))
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_rows_answers_device: a buffer is not aligned to its elements");
+    const int64_t blocks = (n_rows + TB / 64 - 1) / (TB / 64);
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_rows_answers_device: the batch is too large for one launch");
+    const AnsArgs a{d_plan, n_rows, d_spans, n_spans, d_answers, n_items, d_out, d_err, side};
+    if (span_width == 4) hipLaunchKernelGGL(k_rows_answers<int32_t>, dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    else hipLaunchKernelGGL(k_rows_answers<int64_t>, dim3((unsigned)blocks), dim3(TB), 0, st, a);
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }

@@ -782,6 +782,72 @@ int hutk_ctx_pretokenizer(const hutk_ctx* ctx);
 /* the chunk of text one workgroup splits (tests lay their cases out around it) */
 int hutk_debug_presplit_chunk_bytes(void);
 
+/* ---- row-aligned features: row plans, the gather, word ids, answer positions ---------------------------------
+ * ROW PLANS.  The geometry of the rows of a row layout as a device array, d_plan int64[n_rows][8] (8-byte aligned;
+ * written with 16-byte stores when 16-byte aligned):
+ *   d_plan[r] = {item, start, src_a, ka, col_a, src_b, kb, col_b}
+ * item and start are what d_row_map holds: the document or pair of row r and the first id of its window inside the cut
+ * side (padded rows and one-row pairs: item = r; start = 0, or under HUTK_COLLATE_TRUNC_LEFT the index of the first
+ * kept id inside the document).  Column c of row r with col_a <= c < col_a + ka holds d_ids_a[src_a + (c - col_a)],
+ * one with col_b <= c < col_b + kb holds d_ids_b[src_b + (c - col_b)]; every other column is bos, a separator, eos or
+ * padding.  col_a and col_b include the shift of HUTK_COLLATE_PAD_LEFT.  Layouts without a B side write kb = 0,
+ * src_b = 0 and col_b = col_a + ka.  Each planner takes the geometry arguments of its collate call and refuses what
+ * that call refuses, runs one thread per row, and places a row with the device functions its collate kernel places it
+ * with: the padded plan for the padded rows, the windows plan (d_row_offsets: from the windows rows call) for the
+ * windows, the pair plan for both forms of the pairs (d_row_offsets == NULL: row i is pair i and n_rows == n_pairs).
+ * *d_err receives HUTK_E_ARG for offsets outside their call's condition; the rows they describe are planned empty
+ * (ka = 0, or kb = 0), and with offsets or row_offsets whose ends do not fit every row is.  Nothing is read outside the
+ * offsets arrays.  n_docs == 0 / n_pairs == 0 writes nothing. */
+int hutk_padded_plan_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, int64_t max_len, int32_t bos_id,
+                            int32_t eos_id, int flags, int64_t* d_plan, int32_t* d_err, void* hip_stream);
+int hutk_windows_plan_device(const int64_t* d_offsets, const int64_t* d_row_offsets, int64_t n_docs, int64_t n_ids,
+                             int64_t n_rows, int64_t max_len, int64_t stride, int32_t bos_id, int32_t eos_id, int flags,
+                             int64_t* d_plan, int32_t* d_err, void* hip_stream);
+int hutk_pair_plan_device(const int64_t* d_offsets_a, const int64_t* d_offsets_b, const int64_t* d_row_offsets,
+                          int64_t n_pairs, int64_t cap_a, int64_t cap_b, int64_t n_rows, int64_t max_len, int64_t stride,
+                          int strategy, int32_t bos_id, const int32_t* sep_ids, int n_sep, int32_t eos_id, int flags,
+                          int64_t* d_plan, int32_t* d_err, void* hip_stream);
+
+/* THE GATHER.  Any per-token array in the rows' shape: d_out [n_rows][max_len] records of rec_bytes = 4, 8 or 16 (one
+ * int32 or int64 per token, or a span of two), d_out[r][c] = d_values_a[src_a + (c - col_a)] on the A columns of plan
+ * r, d_values_b[src_b + (c - col_b)] on its B columns, and *fill (one record on the HOST, copied into the launch) on
+ * every other column.  d_values_a holds n_a records, d_values_b n_b; both may be one array.  Buffers are aligned to
+ * their elements (4 bytes; 8 with rec_bytes 16); with max_len * rec_bytes a multiple of 16, d_out 16-byte aligned and
+ * the values aligned to rec_bytes a thread stores 16 bytes at once.  The plan is not trusted: a side is clipped to the
+ * columns [0, max_len), a negative ka or kb counts as 0, where both sides claim a column A holds it, and a record
+ * outside its array is not read and leaves fill; each of these gives HUTK_E_ARG in *d_err.  Nothing is written outside
+ * d_out.  n_rows == 0 writes nothing. */
+int hutk_rows_gather_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_values_a, int64_t n_a,
+                            const void* d_values_b, int64_t n_b, int rec_bytes, const void* fill, void* d_out,
+                            int32_t* d_err, void* hip_stream);
+
+/* WORD IDS.  d_word_ids int32[n_ids]: the word of its document each token starts in, counted from 0, from the word
+ * split of the packed text: d_word_bits as hutk_pretokenize_batch_device writes it, d_before the prefix counts of the
+ * counting call of hutk_pretokenize_starts_device, d_offsets int64[n_docs + 1] the text offsets, d_spans [n_ids][2] the
+ * BYTE spans of hutk_token_spans_device (span_width 4: int32, 8: int64), d_id_offsets int64[n_docs + 1].  With base the
+ * text offset of the token's document, word_id = (set bits at positions base .. base + span_start) - 1.  One pass over
+ * the ids, a search of the id offsets per tile of hutk_debug_word_ids_tile ids.  Verified, not trusted: a non-empty
+ * span with a word start strictly inside it sets d_status[document] (int32[n_docs], may be NULL; cleared first) to
+ * HUTK_DOC_SPAN_MISMATCH and *d_err to HUTK_E_UNSUPPORTED -- the ids were made under another split -- and the other
+ * documents stay exact.  d_id_offsets[0] != 0, d_id_offsets[n_docs] != n_ids, d_offsets[0] < 0 or d_offsets[n_docs] >
+ * n_bytes: HUTK_E_ARG in *d_err and nothing is written; a span outside its document's text: HUTK_E_ARG and -1. */
+int hutk_token_word_ids_device(const uint32_t* d_word_bits, const int64_t* d_before, const int64_t* d_offsets,
+                               int64_t n_docs, int64_t n_bytes, const void* d_spans, int span_width,
+                               const int64_t* d_id_offsets, int64_t n_ids, int32_t* d_word_ids, int32_t* d_status,
+                               int32_t* d_err, void* hip_stream);
+int hutk_debug_word_ids_tile(void);
+
+/* ANSWER POSITIONS.  d_out int32[n_rows][2]: the columns at which an answer starts and ends in every row, for
+ * extractive QA.  side 0 names the A side of the plan, 1 the B side; d_spans [n_spans][2] are the spans of that side's
+ * tokens (span_width 4 or 8), non-decreasing along a document; d_answers [n_items][2] of the same width holds (s, e) of
+ * item i in the spans' unit, (-1, -1) or any s >= e for none.  The tokens of row r are j in [src, src + k) with spans
+ * (a_j, b_j).  The answer lies in the row iff k > 0, a_src <= s and b_(src+k-1) >= e; then d_out[r] = {col + (max j:
+ * a_j <= s) - src, col + (min j: b_j >= e) - src}, otherwise {-1, -1}.  One wavefront per row, two searches.  An item
+ * outside [0, n_items), tokens outside [0, n_spans) or columns beyond int32: {-1, -1} and HUTK_E_ARG in *d_err. */
+int hutk_rows_answers_device(const int64_t* d_plan, int64_t n_rows, int side, const void* d_spans, int span_width,
+                             int64_t n_spans, const void* d_answers, int64_t n_items, int32_t* d_out, int32_t* d_err,
+                             void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,7 +108,8 @@ __global__ __launch_bounds__(WI_THREADS) void k_word_ids(const WordArgs A) {
         int32_t word = -1;
         if (!doc_ok || a < 0 || b < a || b > end - base) note_error(A.err, HUTK_E_ARG);  // (spans of another text)
         else {
-            const int64_t at = rank_incl(A, base + a);
+            // (an empty span at the document's end belongs to its last word: the bit at `end` is the next document's)
+            const int64_t at = a < end - base ? rank_incl(A, base + a) : rank_excl(A, base + a);
             word = (int32_t)(at - base_rank - 1);
             if (b > a + 1 && rank_incl(A, base + b - 1) != at) {  // a word starts strictly inside the token
                 if (A.status) A.status[doc] = HUTK_DOC_SPAN_MISMATCH;

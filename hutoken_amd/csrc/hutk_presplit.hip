@@ -289,6 +289,9 @@ int hutk_pretokenizer_create(hutk_pretokenizer** out, int device, const uint8_t*
     hipError_t e = h->d_blob.reserve((size_t)n_blob_bytes);
     if (e == hipSuccess) e = hipMemcpy(h->d_blob.p, blob, (size_t)n_blob_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = h->w_ok.reserve(2);
+    // (no split yet: a bitmap given to hutk_pretokenize_starts_device is the caller's own and counts as sound)
+    if (e == hipSuccess) e = hipMemset(h->w_ok.p, 1, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(h->w_ok.p + 1, 0, sizeof(int32_t));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         hutk_pretokenizer_destroy(h);

@@ -758,7 +758,8 @@ int hutk_debug_norm_chunk_bytes(void);
  * hutk_pretokenize_starts_device turns the bitmap into positions, in two calls on the same stream: d_starts == NULL
  * counts (d_before: n_bytes / 32 + 2 values; afterwards d_before[n_bytes / 32 + 1] - 1 is the number of words); with
  * d_starts (room for that many) it writes the ascending byte positions of the word starts and d_start_offsets[n_docs + 1],
- * the index of every document's first word. */
+ * the index of every document's first word.  Behind a split that refused its offsets neither call reads the bitmap; on a
+ * pre-tokeniser that has split nothing yet the bitmap is the caller's own and is counted as it is. */
 #define HUTK_PRESPLIT_NONE (-1)
 #define HUTK_PRESPLIT_GPT2 0
 #define HUTK_PRESPLIT_CL100K 1

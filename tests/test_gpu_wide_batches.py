@@ -5,17 +5,21 @@ The batch is R copies of one block of documents (tests/wide_cases.py: an odd len
 long words, a document boundary and a three-byte character straddle the place where each boundary falls).  The cases
 with special tokens and byte fallback use a block of about 1 MiB laid out by the same rule, with a marker or an unknown
 character across each boundary: specials_ref and fallback_ref walk the text byte by byte and id by id in Python, and the
-positions a batch reaches do not depend on the block's length.  The CPU references -- the oracle, decode_ref, spans_ref,
-norm_ref, specials_ref, decode_special_ref, fallback_ref -- run on the block once; the GPU's result for the batch is
-compared on the device, reshaped to [R, T], with the block's row, in slices, and never copied to the host.  A mismatch
+positions a batch reaches do not depend on the block's length.  The split presets (the split and its listing, the encode
+of a context with a preset, word ids) use that small block too, with a digit run, contractions and a whitespace run
+across each boundary: presplit_ref is a Python loop as well.  The CPU references -- the oracle, decode_ref, spans_ref,
+norm_ref, specials_ref, decode_special_ref, fallback_ref, presplit_ref, features_ref -- run on the block once; the
+GPU's result for the batch is compared on the device, reshaped to [R, T], with the block's row, in slices, and never copied to the host.  A mismatch
 names the copy, the byte position and the side of the boundary it is on.  Every case first asserts that the GPU on the
 block alone equals the reference, so that a failure of the batch is one of position.
 
 Memory: a case adds up what it allocates and what the context's workspace takes (include/hutoken_amd.h) and skips only
 when torch.cuda.mem_get_info() shows less than 1.25 x that free; the skip names both numbers.  Every case prints one
 line "WIDE | case | boundary | ran or skipped | bytes needed | bytes free | seconds" (pytest -s, or -rs for the skips).
-Measured on an MI355X: the file 99 s, tests/test_gpu_bigdoc.py 18 s.  The byte-fallback encode is 46 s of that (16 s at
+Measured on an MI355X: the file 118 s, tests/test_gpu_bigdoc.py 18 s.  The byte-fallback encode is 46 s of that (16 s at
 2^31, 30 s at 2^32, 9 s of the first for fallback_ref): it runs the token spans over the ids' CAPACITY, not their number.
+The split presets' WIDE lines add up to 1.8 s (test_split_presets, six lines), 5.6 s (test_encode_under_a_preset, four)
+and 4.8 s (test_word_ids, two).
 Needs a real MI355X."""
 import gc
 import importlib
@@ -651,3 +655,156 @@ def test_decode_fallback(oracle_mod, vl_files, boundary):
                        (text_b, to_b, dst_b), len(b.docs), boundary, "decode fallback VL")
     finally:
         ctx.close()
+
+
+# ---- 7. the split presets: hutk_pretokenize_batch_device / _starts_device, the word_bits branch of k_tiles, word ids -----
+_preset = {}
+
+
+def split_rows(preset):
+    """The small text block with the split piece over it (one from p - 9 to p + 12 at each boundary, one in every third
+    document) -> (bytes, where the pieces are, presplit_ref's word starts as positions in the block, their offsets)"""
+    b = small_block("text")
+    if "data" not in _preset:
+        _preset["data"] = W.with_split_piece(b)
+    if ("starts", preset) not in _preset:
+        _preset["starts", preset] = W.preset_words(_preset["data"][0], b.offs, preset)
+    return _preset["data"] + _preset["starts", preset]
+
+
+def preset_id_rows(oracle_mod, vg_files, preset):
+    """(ids, out_offsets) of the oracle under the whole-document pattern over the restatement's words of that block"""
+    if ("ids", preset) not in _preset:
+        data, _at, starts, so = split_rows(preset)
+        _preset["ids", preset] = W.preset_ids(oracle_mod, vg_files, data, small_block("text").offs, starts, so)
+    return _preset["ids", preset]
+
+
+@pytest.fixture(scope="module")
+def lc_ctype():
+    """the rule of tests/test_gpu_presplit.py: the whole-document pattern was checked under one LC_CTYPE"""
+    import json
+    import locale
+    import os
+    import helpers as H
+    with open(os.path.join(H.GOLDEN_DIR, "g9_regex_path.json")) as f:
+        want = json.load(f)["lc_ctype"]
+    if locale.setlocale(locale.LC_CTYPE, None) != want:
+        pytest.skip("POSIX regex matching depends on LC_CTYPE; the whole-document pattern was checked under " + want)
+
+
+@pytest.mark.parametrize("boundary", BOUNDARIES)
+@pytest.mark.parametrize("preset", ["gpt2", "cl100k", "qwen2"])
+def test_split_presets(preset, boundary):
+    """hutoken_amd.pretokenize_packed_device (the split, the count, the listing): word starts that are byte positions past
+    the boundary, a digit run, a contraction and a whitespace run around the place where it falls."""
+    import torch
+    import hutoken_amd
+    b = small_block("text")
+    data, at, starts_b, so_b = split_rows(preset)
+    p = b.p_lo if boundary == W.B31 else b.p_hi
+    assert p - 9 in at and bytes(data[p - 9:p + 12]) == W.SPLIT_PIECE
+    n, S_ = len(b.docs), len(starts_b)
+    R = W.copies_cross(b.L, boundary)
+    # text and offsets, the bitmap and its prefix counts (8 bytes per 32 of text), the starts and their copy less r * L
+    need = R * b.L + 16 * (R * n + 1) + R * b.L // 8 + R * b.L // 4 + 16 * R * S_ + SCRATCH
+    with Row("split %s" % preset, boundary, need):
+        starts, so = hutoken_amd.pretokenize_packed_device(dev(data), dev(b.offs), preset)  # the block alone
+        assert np.array_equal(so.cpu().numpy(), so_b) and np.array_equal(starts.cpu().numpy(), starts_b), \
+            "the block alone differs from presplit_ref (%s)" % preset
+        batch = Batch(b, R, data)
+        assert batch.n_bytes >= boundary + 2 ** 26
+        starts, so = hutoken_amd.pretokenize_packed_device(batch.bytes, batch.offs, preset)
+        what = "split %s" % preset
+        assert starts.numel() == R * S_, "%s: %d word starts, %d copies of %d expected" % (what, starts.numel(), R, S_)
+        rel = (starts.view(R, S_) - torch.arange(R, dtype=torch.int64, device=DEV)[:, None] * b.L).reshape(-1)
+        assert_rows(rel, dev(starts_b), R, what + ", starts less r * L", lambda r, j: r * b.L + int(starts_b[j]), b.L)
+        assert_offsets(so, so_b, R, what + ", start_offs", lambda r, d: batch.doc_start(r, d), b.L)
+        del starts, so, rel, batch
+
+
+@pytest.mark.parametrize("boundary", BOUNDARIES)
+@pytest.mark.parametrize("preset", ["gpt2", "cl100k"])
+def test_encode_under_a_preset(lc_ctype, oracle_mod, vg_files, monkeypatch, preset, boundary):
+    """hutk_encode_batch_device of a context with a split preset, VG, k_tiles: the word_bits branch reads the bitmap at
+    byte positions past the boundary.  Against the oracle's ids of the restatement's words."""
+    monkeypatch.setenv("HUTK_PTILES", "0")
+    PT = importlib.import_module("hutoken_amd.pretokenize")
+    b = small_block("text")
+    data, _at, _starts, _so = split_rows(preset)
+    ids_b, oo_b = preset_id_rows(oracle_mod, vg_files, preset)
+    n, T = len(b.docs), len(ids_b)
+    st_b = np.zeros(n, dtype=np.int32)  # (the block's longest word is far below the limit: no document is cut)
+    R = W.copies_cross(b.L, boundary)
+    ctx, _files = _context("VG")
+    try:
+        ctx.set_pretokenizer(PT.preset_index(preset), PT.table_blob())
+        # (the encode's need, the bitmap)
+        with Row("encode VG under %s" % preset, boundary, encode_need(ctx, R * b.L, R * n) + R * b.L // 8):
+            assert ctx.tile_kernel(R * b.L) == 0, "the batch would not be given the kernel this case is about"
+            ids, oo, st, err = encode(ctx, dev(data), dev(b.offs), n, b.L)  # the block alone
+            assert err == 0
+            assert_block_alone(b, (ids.cpu().numpy(), oo.cpu().numpy(), st.cpu().numpy()), (ids_b, oo_b, st_b))
+            del ids, oo, st
+            batch = Batch(b, R, data)
+            assert batch.n_bytes >= boundary + 2 ** 26
+            ids, oo, st, err = encode(ctx, batch.bytes, batch.offs, batch.n_docs, batch.n_bytes)
+            what = "VG under %s" % preset
+            assert err == 0, "%s: *d_err = %d" % (what, err)
+            assert_offsets(oo, oo_b, R, what + ", out_offsets", lambda r, d: batch.doc_start(r, d), b.L)
+            assert_rows(st, dev(st_b), R, what + ", status", lambda r, d: batch.doc_start(r, d), b.L)
+            assert_rows(ids[:R * T], dev(ids_b), R, what + ", ids",
+                        lambda r, j: batch.doc_start(r, int(np.searchsorted(oo_b, j, side="right")) - 1), b.L)
+            del ids, oo, st, batch
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("boundary", BOUNDARIES)
+def test_word_ids(vg_files, boundary):
+    """hutoken_amd.token_word_ids_device under gpt2 on the batch and its own ids: the split, the count, int32 byte spans
+    and the rank kernel (hutk_token_word_ids_device) at byte positions past the boundary; against features_ref.word_ids
+    of the block, from spans_ref's spans of the block's ids and presplit_ref's word starts."""
+    import features_ref as FR
+    import hutoken_amd as hutoken
+    b = small_block("text")
+    data, _at, starts_b, so_b = split_rows("gpt2")
+    vp, sp, _kw = vg_files
+    hutoken.initialize(vp, sp, is_byte_encoder=True, pretokenizer="gpt2")
+    ctx = hutoken.context()
+    n = len(b.docs)
+    R = W.copies_cross(b.L, boundary)
+    # the encode; the spans' workspace (as in test_token_spans) and int32 spans; the bitmap, its prefix counts at 8 bytes per
+    # 32 text bytes, int32 words and a status per document.  (4 ids a byte at the most: the capacity's bound)
+    cap = ctx.ids_capacity(R * b.L, R * n)
+    need = encode_need(ctx, R * b.L, R * n) + 5 * R * b.L + 8 * cap + R * b.L // 8 + R * b.L // 4 + 4 * cap + 4 * R * n + SCRATCH
+    with Row("word ids VG gpt2", boundary, need):
+        # the block alone: its ids, their spans and word ids by the restatement
+        ids, oo = hutoken.encode_packed_device(dev(data), dev(b.offs), check=True)
+        oo_b = oo.cpu().numpy()
+        T = int(oo_b[-1])
+        ids_b = ids[:T].cpu().numpy()
+        tt = W.RefTokenText(DC.shipped_vocab_ref(vg_files))
+        spans_b, span_st = S.batch(tt, data, b.offs, ids_b, oo_b, True, "byte", np.int64)
+        assert not span_st.any() and not (ids_b == -1).any()
+        words_b = np.zeros(T, dtype=np.int32)
+        for d in range(n):
+            rel = (starts_b[so_b[d]:so_b[d + 1]] - b.offs[d]).tolist()
+            w, mismatch = FR.word_ids(None, spans_b[oo_b[d]:oo_b[d + 1]].tolist(), rel)
+            assert not mismatch, d
+            words_b[oo_b[d]:oo_b[d + 1]] = w
+        got = hutoken.token_word_ids_device(dev(data), dev(b.offs), ids[:T], oo, check=True)
+        assert np.array_equal(got.cpu().numpy(), words_b), "the block alone differs from features_ref.word_ids"
+        del ids, oo, got
+        batch = Batch(b, R, data)
+        assert batch.n_bytes >= boundary + 2 ** 26
+        ids, oo = hutoken.encode_packed_device(batch.bytes, batch.offs, check=True)
+
+        def id_pos(r, j):
+            return batch.doc_start(r, int(np.searchsorted(oo_b, j, side="right")) - 1)
+        assert_offsets(oo, oo_b, R, "gpt2, out_offsets", lambda r, d: batch.doc_start(r, d), b.L)
+        assert_rows(ids[:R * T], dev(ids_b), R, "gpt2, ids", id_pos, b.L)
+        words = hutoken.token_word_ids_device(batch.bytes, batch.offs, ids[:R * T], oo, n_ids=R * T, check=True)
+        assert words.dtype.is_signed and words.element_size() == 4
+        assert_rows(words, dev(words_b), R, "word ids", id_pos, b.L)
+        del ids, oo, words, batch

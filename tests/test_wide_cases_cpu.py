@@ -201,6 +201,58 @@ def test_markers_and_unknown_characters_lie_across_both_boundaries(small):
         raw[int(c.offs[d]):int(c.offs[d + 1])].decode("utf-8")
 
 
+def test_split_piece_lies_across_both_boundaries(small):
+    """with_split_piece(): lengths and offsets stay; the boundary falls inside the digit run of a piece, and the presets'
+    word starts differ there as their patterns say: cl100k groups the digits in threes (a start on either side), qwen2
+    takes each alone, gpt2 has one word from the space in front of the run to its end."""
+    import presplit_ref as PR
+    b = small["text"]
+    data, at = W.with_split_piece(b)
+    n = len(W.SPLIT_PIECE)
+    assert len(data) == b.L and b.p_lo - 9 in at and b.p_hi - 9 in at and len(at) > len(b.docs) // 4
+    raw = data.tobytes()
+    assert all(raw[s:s + n] == W.SPLIT_PIECE for s in at) and (data != b.data).sum() <= len(at) * n
+    lo, hi = W.SPLIT_DIGITS
+    assert W.SPLIT_PIECE[lo:hi].isdigit() and hi - lo == 7 and lo < 9 < hi - 1 and W.SPLIT_PIECE[lo - 1:lo] == b" "
+    want = {"gpt2": [], "cl100k": [lo, lo + 3, lo + 6], "qwen2": list(range(lo, hi))}
+    for preset in PR.PRESETS:
+        starts, so = W.preset_words(data, b.offs, preset)
+        assert so[0] == 0 and so[-1] == len(starts) and len(so) == len(b.docs) + 1 and (np.diff(starts) > 0).all()
+        have = set(starts.tolist())
+        for p in (b.p_lo, b.p_hi):
+            s = p - 9  # where the piece begins
+            assert [q - s for q in range(s + lo, s + hi) if q in have] == want[preset], (preset, p)
+            assert s + 1 in have and s + lo - 1 in have and s + 18 in have  # 's, the space in front of the digits, 'll
+            inside = [q for q in range(s + lo + 1, s + hi) if q in have]
+            if preset == "gpt2":
+                assert not inside  # one word across the boundary
+            else:
+                assert [q for q in inside if q < p] and [q for q in inside if q >= p]  # a start on either side of it
+
+
+@pytest.mark.parametrize("preset", ["gpt2", "cl100k"])
+def test_preset_ids_are_periodic_and_drop_nothing(small, oracles, oracle_mod, preset):
+    """The reference of the encode under a preset: three copies give three times the block's ids, and the ids decode to
+    the block's bytes, those of the words that are not valid UTF-8 included."""
+    _orc, _is_byte, files = oracles["VG"]
+    b = small["text"]
+    data, _at = W.with_split_piece(b)
+    with pytest.raises(UnicodeDecodeError):
+        data.tobytes().decode("utf-8")
+    starts, so = W.preset_words(data, b.offs, preset)
+    ids, oo = W.preset_ids(oracle_mod, files, data, b.offs, starts, so)
+    assert oo[0] == 0 and oo[-1] == len(ids) and len(oo) == len(b.docs) + 1
+    text, to = DC.shipped_vocab_ref(files).decode_packed(ids, oo)
+    assert np.array_equal(text, data) and np.array_equal(to, b.offs)
+    data3, offs3 = np.tile(data, 3), W.repeated_offsets(b.offs, b.L, 3)
+    starts3, so3 = W.preset_words(data3, offs3, preset)
+    assert np.array_equal(starts3, (starts[None, :] + (np.arange(3) * b.L)[:, None]).reshape(-1))
+    assert np.array_equal(so3, W.repeated_offsets(so, len(starts), 3))
+    ids3, oo3 = W.preset_ids(oracle_mod, files, data3, offs3, starts3, so3)
+    zeros = np.zeros(len(b.docs), dtype=np.int32)
+    _assert_tripled((ids, oo, zeros), (ids3, oo3, np.tile(zeros, 3)))
+
+
 def test_specials_ref_is_periodic(small, oracles):
     orc = oracles["VG"][0]
     data, offs = W.marked(small["text"])[0], small["text"].offs

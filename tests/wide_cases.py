@@ -27,6 +27,8 @@ there to p_hi + 1500 are the first word of the next document (a prefix case in c
 
 marked() and with_unknowns() write special-token markers and characters no vocabulary here knows OVER a block's text
 (lengths and offsets stay): one across p_lo and one across p_hi, and into every third document that has room.
+with_split_piece() does the same with a piece of text on which the split presets differ (a digit run, contractions, a
+whitespace run); preset_words() and preset_ids() are the references of the split and of the encode under a preset.
 
 check_layout() asserts all of this from the block's bytes alone.  Nothing here touches the package under test except
 for hutoken_amd.synth's frozen corpora."""
@@ -372,6 +374,77 @@ def with_unknowns(block, ch=UNKNOWN, every=3):
     boundaries, so that its bytes lie on either side, and one in every third document."""
     assert block.kind == "chars"
     return _overwritten(block, ch, every, 1, True)
+
+
+SPLIT_PIECE = b"x's 1234567 \n\n  we'll"  # a contraction, a digit run that cl100k groups in threes, a whitespace run, a contraction
+SPLIT_DIGITS = (4, 11)                    # where the digits lie in it
+
+
+def with_split_piece(block, every=3):
+    """What the split presets treat differently over the text: the piece begins 9 bytes in front of p_lo and of p_hi, so
+    that the place where the boundary falls lies inside the digit run, between its fifth and sixth digit, with the
+    contractions and the whitespace run within a dozen bytes either side; and in every third document."""
+    return _overwritten(block, SPLIT_PIECE, every, 9, False)
+
+
+WHOLE = "(.|\n)+"  # the whole-document pattern of test_regex_path.py: the oracle then encodes a document as ONE word
+
+
+def preset_words(data, offs, preset):
+    """presplit_ref over every document -> (starts: int64, the word starts as positions in data; start_offs: int64[n + 1])"""
+    import presplit_ref as PR
+    raw, starts, so = np.asarray(data).tobytes(), [], [0]
+    for d in range(len(offs) - 1):
+        a, b = int(offs[d]), int(offs[d + 1])
+        starts += [a + p for p in PR.word_starts(raw[a:b], preset)]
+        so.append(len(starts))
+    return np.array(starts, dtype=np.int64), np.array(so, dtype=np.int64)
+
+
+def preset_ids(oracle_mod, files, data, offs, starts, start_offs):
+    """What tests/test_gpu_presplit.py::expected_ids builds, for documents of bytes: the oracle's ids under the
+    whole-document pattern of every word of preset_words as a document of its own -> (ids int32, out_offsets int64[n + 1]
+    per DOCUMENT).  POSIX's `.` passes over a byte that is no character of the locale, so the words that are not valid
+    UTF-8 (documents that end inside a character, a piece written over one) are encoded under LC_CTYPE "C", where every
+    byte is one; the others under the process's own, as expected_ids does."""
+    import locale
+    vp, sp, kw = files
+    raw = np.asarray(data).tobytes()
+    edges = np.concatenate((starts, [len(raw)])).tolist()
+    assert len(raw) == int(offs[-1])  # (a word ends where the next starts: the documents tile the block)
+    words = [raw[a:b] for a, b in zip(edges, edges[1:])]
+    ill = []
+    for i, w in enumerate(words):
+        try:
+            w.decode("utf-8")
+        except UnicodeDecodeError:
+            ill.append(i)
+    orc = oracle_mod.Oracle(vp, sp, kw["prefix"], kw["is_byte_encoder"], pattern=WHOLE)
+    try:
+        d, o = oracle_mod.pack(words)
+        ids, oo, _st = orc.encode_packed(d, o, 8)
+        ids, oo = np.asarray(ids, dtype=np.int32), np.asarray(oo, dtype=np.int64)
+        if ill:
+            keep = locale.setlocale(locale.LC_CTYPE, None)
+            locale.setlocale(locale.LC_CTYPE, "C")
+            try:
+                d, o = oracle_mod.pack([words[i] for i in ill])
+                ids_c, oo_c, _st = orc.encode_packed(d, o, 8)
+            finally:
+                locale.setlocale(locale.LC_CTYPE, keep)
+            ids_c = np.asarray(ids_c, dtype=np.int32)
+            parts, at = [], 0
+            for n, i in enumerate(ill):
+                parts += [ids[oo[at]:oo[i]], ids_c[oo_c[n]:oo_c[n + 1]]]
+                at = i + 1
+            parts.append(ids[oo[at]:])
+            lens = np.diff(oo)
+            lens[ill] = np.diff(np.asarray(oo_c, dtype=np.int64))
+            ids = np.concatenate(parts)
+            oo = np.concatenate(([0], np.cumsum(lens)))
+    finally:
+        orc.close()
+    return ids, oo[start_offs]
 
 
 def byte_table(vocab_path):

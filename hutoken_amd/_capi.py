@@ -76,6 +76,8 @@ SIGNATURES = {
     "hutk_packer_destroy": (None, [_vp]),
     "hutk_token_spans_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "hutk_token_spans": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "hutk_debug_span_tile_ids": (_i32, []),
+    "hutk_debug_span_chunk_bytes": (_i32, []),
     "hutk_ctx_set_special_tokens": (_i32, [_vp, _vp, _vp, _vp, _i64]),
     "hutk_ctx_special_token_count": (_i64, [_vp]),
     "hutk_special_ids_capacity": (_i64, [_vp, _i64, _i64]),

@@ -589,6 +589,9 @@ using namespace hutk;
 
 extern "C" {
 
+int hutk_debug_span_tile_ids(void) { return (int)span_tile_ids(); }
+int hutk_debug_span_chunk_bytes(void) { return SPAN_CHUNK_BYTES; }
+
 int hutk_token_spans_device(hutk_ctx* c, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
                             const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_ids, int unit, int out_width,
                             void* d_spans, int32_t* d_status, int32_t* d_err, void* hip_stream) {

@@ -492,6 +492,10 @@ int hutk_token_spans_device(hutk_ctx* ctx, const uint8_t* d_bytes, const int64_t
                             int out_width, void* d_spans, int32_t* d_status, int32_t* d_err, void* hip_stream);
 int hutk_token_spans(hutk_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, const int32_t* ids,
                      const int64_t* id_offsets, int unit, int out_width, void* spans, int32_t* status);
+/* For tests that size their batches by the kernels' own constants: the ids one workgroup takes, and the source bytes per
+ * chunk of the rank structure over the character starts (64-byte blocks inside it). */
+int hutk_debug_span_tile_ids(void);
+int hutk_debug_span_chunk_bytes(void);
 
 /* ---- special tokens --------------------------------------------------------------------------------------
  * Byte strings of the text that encode as ONE id each ("<|endoftext|>", chat-template markers), matched on the GPU.  The

@@ -200,7 +200,7 @@ def test_library_exports_the_span_symbols():
     header = open(os.path.join(H.ROOT, "include", "hutoken_amd.h")).read()
     declared = set(re.findall(r"\b(hutk_[a-z0-9_]+)\s*\(", header))
     lib = _capi.load()
-    for name in ("hutk_token_spans_device", "hutk_token_spans"):
+    for name in ("hutk_token_spans_device", "hutk_token_spans", "hutk_debug_span_tile_ids", "hutk_debug_span_chunk_bytes"):
         assert name in declared and name in _capi.EXPORTS and hasattr(lib, name), name
     for const, value in (("HUTK_SPANS_BYTES", 0), ("HUTK_SPANS_CHARS", 1)):
         assert re.search(r"#define %s %d\b" % (const, value), header)

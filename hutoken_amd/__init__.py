@@ -24,6 +24,11 @@ row, with `row_map` from rows back to documents.  `collate_pairs` / `batch_encod
 [bos] A sep B [eos] with token type ids and the longest_first / only_first / only_second truncation;
 `collate_pair_windows` / `batch_encode_pair_windows` cut the named side into overlapping windows instead.
 
+Training targets (not in the reference): `mask_tokens` corrupts collated rows for masked-LM training and gives the
+labels, by tokens or by whole words, with random numbers that are a stated function of (seed, row, column) or (seed, row,
+side, word); `lm_labels` gives the loss labels of causal-LM and prompt + answer rows; `batch_encode_mlm` is the list
+form -- one HIP pass each over rows that exist already (csrc/hutk_collate.hip, csrc/hutk_philox.h).
+
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
 `encode_with_offsets` are the list forms (csrc/hutk_spans.hip).
@@ -53,7 +58,7 @@ from . import _capi
 from . import pretokenize as _presplit_tables  # (the module; the package's name `pretokenize` is the function below)
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 
-__all__ = ["gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -1922,3 +1927,222 @@ def token_word_ids_device(d_bytes, d_offsets, ids, out_offsets, *, preset=None, 
                              "strictly inside it: the ids were made under another split (device-side error %d)"
                              % (which, _presplit_tables.PRESETS[pi], codes[1]))
     return words
+
+
+# ---- targets: masked-LM corruption and loss labels ---------------------------------------------------------
+_MLM_SIDES = {"a": _capi.MLM_SIDE_A, "b": _capi.MLM_SIDE_B, "both": _capi.MLM_SIDE_A | _capi.MLM_SIDE_B}
+_LOSS_ON = {"a": _capi.LABELS_A, "b": _capi.LABELS_B, "template": _capi.LABELS_TEMPLATE, "end": _capi.LABELS_END}
+
+
+def _rows_arg(name, t):
+    """input_ids of rows: [n_rows, L] with L >= 1, int32 or int64, contiguous -> (dtype name, element bytes)."""
+    if not _is_tensor(t):
+        raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+    dname = _dtype_name(t)
+    if dname not in ("int32", "int64"):
+        raise TypeError("%s must have dtype int32 or int64, not %s" % (name, t.dtype))
+    if t.dim() != 2 or t.shape[1] < 1 or not t.is_contiguous():
+        raise ValueError("%s must be contiguous and of shape [n_rows, L] with L >= 1" % name)
+    _length_arg("the row length of %s" % name, t.shape[1], 1)
+    return dname, 4 if dname == "int32" else 8
+
+
+def _rows_plan_arg(row_plan, input_ids):
+    _plan_arg(row_plan)
+    if row_plan.shape[0] != input_ids.shape[0]:
+        raise ValueError("row_plan must hold one row for every row of input_ids (%d), not %d" % (input_ids.shape[0], row_plan.shape[0]))
+
+
+def _fraction_arg(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError("%s must be a number in [0, 1], not %s" % (name, type(v).__name__))
+    if not 0 <= v <= 1:  # (NaN is refused too)
+        raise ValueError("%s must be in [0, 1], not %r" % (name, v))
+    return float(v)
+
+
+def _ignore_arg(ignore_index, dname):
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+        raise TypeError("ignore_index must be an int, not %s" % type(ignore_index).__name__)
+    bits = 31 if dname == "int32" else 63
+    if not -2**bits <= ignore_index < 2**bits:
+        raise ValueError("ignore_index must fit %s" % dname)
+    return ignore_index
+
+
+def _on_one_gpu(what, named):
+    """named: (name, tensor) -- all on the GPU and on the device of the first"""
+    for name, t in named:
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU: %s runs there and nowhere else" % (name, what))
+        if t.device != named[0][1].device:
+            raise ValueError("%s must be on the device of %s" % (name, named[0][0]))
+
+
+def _mlm_args(mask_id, vocab_size, seed, mlm_probability, mask_fraction, random_fraction):
+    """What mask_tokens checks of its numbers -> (mask_id, vocab_size, select_below, mask_below, random_below): a
+    probability p is the threshold int(p * 2**32) against a draw of 32 bits."""
+    mask_id = _token_arg("mask_id", mask_id, False)
+    p_select = _fraction_arg("mlm_probability", mlm_probability)
+    p_mask, p_random = _fraction_arg("mask_fraction", mask_fraction), _fraction_arg("random_fraction", random_fraction)
+    if p_mask + p_random > 1 + 1e-12:
+        raise ValueError("mask_fraction + random_fraction must not be above 1, not %r" % (p_mask + p_random,))
+    if vocab_size is None:
+        if p_random != 0:
+            raise ValueError("vocab_size=None is allowed only with random_fraction == 0")
+    elif isinstance(vocab_size, bool) or not isinstance(vocab_size, int):
+        raise TypeError("vocab_size must be an int or None, not %s" % type(vocab_size).__name__)
+    elif not 1 <= vocab_size <= 2**31:
+        raise ValueError("vocab_size must be in 1 .. 2**31, not %d" % vocab_size)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError("seed must be an int, not %s" % type(seed).__name__)
+    if not 0 <= seed < 2**64:
+        raise ValueError("seed must be in 0 .. 2**64 - 1, not %d" % seed)
+    mask_below = int(p_mask * 2**32)
+    random_below = min(2**32, max(mask_below, int((p_mask + p_random) * 2**32)))
+    return mask_id, 1 if vocab_size is None else vocab_size, int(p_select * 2**32), mask_below, random_below
+
+
+def mask_tokens(input_ids, row_plan, *, mask_id, vocab_size=None, seed, mlm_probability=0.15, mask_fraction=0.8,
+                random_fraction=0.1, word_ids=None, word_ids_b=None, sides="both", ignore_index=-100, inplace=False,
+                check=False):
+    """The masked-LM corruption of collated rows, one HIP pass: input_ids [n_rows, L] int32 or int64 on the GPU and the
+    row_plan of the collate_* call that made them -> (input_ids, labels), both of input_ids' shape and dtype.  Only the
+    columns that hold a token of a text (of side "a", "b" or "both": `sides`) can be selected -- never bos, a separator,
+    eos or padding.  A selected column keeps its id in labels and becomes mask_id with probability mask_fraction, a
+    random id below vocab_size with random_fraction, and stays otherwise; every other column is copied and gets
+    ignore_index.  vocab_size=None is allowed only with random_fraction == 0.  Token mode selects every eligible column
+    with mlm_probability; with word_ids (the flat int32 tensor of token_word_ids_device for the encode call the rows
+    were made from; word_ids_b: the B side's, None reads both sides from word_ids) every word is selected with
+    mlm_probability and all its tokens in the row with it, and a token whose word id is below 0 is protected.
+    The random numbers are Philox4x32-10 draws that depend on nothing but (seed, row, column) or (seed, row, side, word)
+    -- include/hutoken_amd.h states the rule in full, tests/targets_ref.py restates it in numpy -- so a row's outcome
+    does not depend on the batch around it, and the same seed gives the same result anywhere.  seed is an int in
+    0 .. 2**64 - 1 and has no default: there is no hidden state; pass a different one per step.  A probability p is the
+    threshold int(p * 2**32) against a draw of 32 bits.  inplace=True overwrites input_ids and returns it.  On the
+    current torch stream, never synchronises; check=True does and raises ValueError for a plan that points outside its
+    row or the word ids (nothing is read or written out of bounds either way)."""
+    dname, width = _rows_arg("input_ids", input_ids)
+    _rows_plan_arg(row_plan, input_ids)
+    mask_id, vocab, select_below, mask_below, random_below = _mlm_args(mask_id, vocab_size, seed, mlm_probability, mask_fraction,
+                                                                       random_fraction)
+    if sides not in _MLM_SIDES:
+        raise ValueError("sides must be 'a', 'b' or 'both', not %r" % (sides,))
+    _ignore_arg(ignore_index, dname)
+    if not isinstance(inplace, bool):
+        raise TypeError("inplace must be a bool, not %s" % type(inplace).__name__)
+    if word_ids is None and word_ids_b is not None:
+        raise ValueError("word_ids_b needs word_ids")
+    named = [("input_ids", input_ids), ("row_plan", row_plan)]
+    for name, t in (("word_ids", word_ids), ("word_ids_b", word_ids_b)):
+        if t is None:
+            continue
+        if not _is_tensor(t):
+            raise TypeError("%s must be a torch tensor, not %s" % (name, type(t).__name__))
+        if _dtype_name(t) != "int32":
+            raise TypeError("%s must have dtype int32, not %s" % (name, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be one-dimensional and contiguous" % name)
+        named.append((name, t))
+    _on_one_gpu("the corruption", named)
+    import torch
+    dev = input_ids.device
+    n_rows, L = input_ids.shape
+    out = input_ids if inplace else torch.empty_like(input_ids)
+    labels = torch.empty_like(input_ids)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    wa, wb = word_ids, word_ids_b
+    if wa is not None and wa.numel() == 0:  # (an empty tensor has no address, and no address means token mode)
+        wa = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_a = 0 if word_ids is None else word_ids.numel()
+
+    def call():
+        _capi.rows_mlm_device(row_plan.data_ptr(), n_rows, L, input_ids.data_ptr(), width,
+                              0 if wa is None else wa.data_ptr(), n_a,
+                              0 if wb is None or wb.numel() == 0 else wb.data_ptr(), 0 if wb is None else wb.numel(),
+                              seed, select_below, mask_below, random_below, mask_id, vocab,
+                              ignore_index, _MLM_SIDES[sides], out.data_ptr(), labels.data_ptr(), err.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+        return out, labels
+    _on_torch_stream(dev, call, used=tuple(t for _n, t in named) + (err,) + (() if wa is None else (wa,)))
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: mask_tokens: a row_plan that points outside its row or the word ids (device-side "
+                         "error %d)" % int(err.item()))
+    return out, labels
+
+
+def _loss_on_arg(loss_on):
+    if loss_on == "all":
+        return sum(_LOSS_ON.values())
+    if loss_on == "completion":
+        return _capi.LABELS_B | _capi.LABELS_END
+    if isinstance(loss_on, (tuple, list)) and loss_on and all(isinstance(x, str) and x in _LOSS_ON for x in loss_on):
+        flags = 0
+        for x in loss_on:
+            flags |= _LOSS_ON[x]
+        return flags
+    raise ValueError("loss_on must be 'all', 'completion' or a non-empty tuple drawn from ('a', 'b', 'template', 'end'), "
+                     "not %r" % (loss_on,))
+
+
+def lm_labels(input_ids, attention_mask, row_plan, *, loss_on="all", shift=False, ignore_index=-100, check=False):
+    """The loss labels of collated rows, one HIP pass: input_ids [n_rows, L] int32 or int64, attention_mask uint8 of the
+    same shape and the row_plan of the collate_* call that made them -> labels of input_ids' shape and dtype: the id on
+    the columns that carry loss, ignore_index on the others.  Padding never carries loss.  loss_on="all": every real
+    column; "completion": the B side and eos -- SFT on batch_encode_pairs(prompts, answers, ...), where the prompt, bos
+    and the separators carry none; or a tuple drawn from ("a", "b", "template", "end"), template being bos and the
+    separators, end being eos.  shift=True gives labels[r][c] = what column c predicts: the id of column c + 1 when that
+    one carries loss and column c is real, ignore_index otherwise (the last column predicts nothing) -- for a loss
+    that does not shift by itself.  On the current torch stream, never synchronises; check=True does and raises
+    ValueError for a plan that points outside its row."""
+    dname, width = _rows_arg("input_ids", input_ids)
+    if not _is_tensor(attention_mask):
+        raise TypeError("attention_mask must be a torch tensor, not %s" % type(attention_mask).__name__)
+    if _dtype_name(attention_mask) != "uint8":
+        raise TypeError("attention_mask must have dtype uint8, not %s" % attention_mask.dtype)
+    if tuple(attention_mask.shape) != tuple(input_ids.shape) or not attention_mask.is_contiguous():
+        raise ValueError("attention_mask must be contiguous and of the shape of input_ids")
+    _rows_plan_arg(row_plan, input_ids)
+    flags = _loss_on_arg(loss_on)
+    if not isinstance(shift, bool):
+        raise TypeError("shift must be a bool, not %s" % type(shift).__name__)
+    _ignore_arg(ignore_index, dname)
+    _on_one_gpu("the labelling", (("input_ids", input_ids), ("attention_mask", attention_mask), ("row_plan", row_plan)))
+    import torch
+    dev = input_ids.device
+    n_rows, L = input_ids.shape
+    labels = torch.empty_like(input_ids)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.rows_labels_device(row_plan.data_ptr(), n_rows, L, input_ids.data_ptr(), width, attention_mask.data_ptr(),
+                                 flags | (_capi.LABELS_SHIFT if shift else 0), ignore_index, labels.data_ptr(),
+                                 err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return labels
+    _on_torch_stream(dev, call, used=(input_ids, attention_mask, row_plan, err))
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: lm_labels: a row_plan that points outside its row (device-side error %d)"
+                         % int(err.item()))
+    return labels
+
+
+def batch_encode_mlm(texts, max_length=None, *, mask_id, seed, vocab_size=None, whole_word=False, mlm_probability=0.15,
+                     mask_fraction=0.8, random_fraction=0.1, normalize=None, **collate_kwargs):
+    """A list of str -> (input_ids, attention_mask, lengths, labels), a masked-LM training batch: encode_packed_device,
+    collate_padded with `collate_kwargs` and its plan, and mask_tokens in place on the rows.  whole_word=True selects
+    whole words by token_word_ids_device (the context needs a split preset).  mask_id, seed, vocab_size,
+    mlm_probability, mask_fraction, random_fraction: as mask_tokens; normalize: as batch_encode_padded."""
+    if not isinstance(whole_word, bool):
+        raise TypeError("whole_word must be a bool, not %s" % type(whole_word).__name__)
+    if "return_plan" in collate_kwargs:
+        raise TypeError("batch_encode_mlm returns no plan: use batch_encode_padded(return_plan=True) and mask_tokens")
+    if whole_word and _ctx is not None and _ctx.pretokenizer is None:
+        raise ValueError(_NO_PRESET)
+    _mlm_args(mask_id, vocab_size, seed, mlm_probability, mask_fraction, random_fraction)
+    ids, oo, d_bytes, d_offs = _texts_to_device(texts, with_text=True, normalize=normalize)
+    input_ids, mask, lengths, plan = collate_padded(ids, oo, max_length, return_plan=True, **collate_kwargs)
+    words = token_word_ids_device(d_bytes, d_offs, ids, oo) if whole_word else None
+    _out, labels = mask_tokens(input_ids, plan, mask_id=mask_id, vocab_size=vocab_size, seed=seed,
+                               mlm_probability=mlm_probability, mask_fraction=mask_fraction,
+                               random_fraction=random_fraction, word_ids=words, inplace=True)
+    return input_ids, mask, lengths, labels

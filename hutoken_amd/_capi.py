@@ -121,6 +121,9 @@ SIGNATURES = {
     "hutk_token_word_ids_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "hutk_debug_word_ids_tile": (_i32, []),
     "hutk_rows_answers_device": (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "hutk_rows_mlm_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, C.c_uint64, _i64, _i64, _i64, _s32, _i64,
+                                    _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hutk_rows_labels_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -131,6 +134,8 @@ SPANS_BYTES, SPANS_CHARS = 0, 1
 DECODE_SKIP_SPECIAL = 1  # HUTK_DECODE_SKIP_SPECIAL
 FB_SPECIAL, FB_SKIP_SPECIAL = 1, 2  # HUTK_FB_*
 NFC, NFD, NFKC, NFKD = 0, 1, 2, 3  # HUTK_NFC ..
+MLM_SIDE_A, MLM_SIDE_B = 1, 2  # HUTK_MLM_SIDE_*
+LABELS_A, LABELS_B, LABELS_TEMPLATE, LABELS_END, LABELS_SHIFT = 1, 2, 4, 8, 16  # HUTK_LABELS_*
 
 _lib = None
 
@@ -809,6 +814,22 @@ def rows_answers_device(d_plan, n_rows, side, d_spans, span_width, n_spans, d_an
     """hutk_rows_answers_device on raw device pointers (ints); side: 0 for A, 1 for B; asynchronous on `stream`."""
     raise_for(load().hutk_rows_answers_device(d_plan or None, n_rows, side, d_spans or None, span_width, n_spans,
                                               d_answers or None, n_items, d_out or None, d_err or None, stream or None))
+
+
+def rows_mlm_device(d_plan, n_rows, max_len, d_input_ids, width, d_words_a, n_a, d_words_b, n_b, seed, select_below,
+                    mask_below, random_below, mask_id, vocab_size, ignore_index, sides, d_out_ids, d_labels, d_err=0, stream=0):
+    """hutk_rows_mlm_device on raw device pointers (ints); d_words_a == 0: token mode; the thresholds are ints in
+    0 .. 2**32; asynchronous on `stream`."""
+    raise_for(load().hutk_rows_mlm_device(d_plan or None, n_rows, max_len, d_input_ids or None, width, d_words_a or None, n_a,
+                                          d_words_b or None, n_b, seed, select_below, mask_below, random_below, mask_id,
+                                          vocab_size, ignore_index, sides, d_out_ids or None, d_labels or None,
+                                          d_err or None, stream or None))
+
+
+def rows_labels_device(d_plan, n_rows, max_len, d_input_ids, width, d_mask, flags, ignore_index, d_labels, d_err=0, stream=0):
+    """hutk_rows_labels_device on raw device pointers (ints); flags: LABELS_*; asynchronous on `stream`."""
+    raise_for(load().hutk_rows_labels_device(d_plan or None, n_rows, max_len, d_input_ids or None, width, d_mask or None,
+                                             flags, ignore_index, d_labels or None, d_err or None, stream or None))
 
 
 class Packer(_Owner):

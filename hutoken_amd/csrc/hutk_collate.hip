@@ -17,7 +17,8 @@
 // the rows as a device array, the row plan, written by a planner per row layout that places a row with the device
 // functions its collate kernel places it with (k_plan_padded, k_plan_windows, k_plan_pairs); the gather of any
 // per-token array into the rows' shape by a plan (k_rows_gather); the columns of an answer in every row
-// (k_rows_answers).
+// (k_rows_answers); and the last stage before a training batch: the masked-LM corruption of
+// rows with its labels (k_rows_mlm, drawing from hutk_philox.h) and the loss labels of rows (k_rows_labels).
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets.  A workgroup of the row layouts stages the plan of its rows in LDS
@@ -31,6 +32,7 @@
 #include <type_traits>
 
 #include "hutk_host.h"
+#include "hutk_philox.h"
 #include "hutk_wave.h"
 
 namespace {
@@ -966,6 +968,202 @@ __global__ __launch_bounds__(TB) void k_rows_gather(const GatherArgs a) {
     }
 }
 
+// ---- targets: masked-LM corruption and loss labels ----------------------------------------------------------
+// Both read rows that exist already, [n_rows][L] elements of W bytes, with the rows' plan, and write rectangles of the
+// same shape at the same positions: an element is read and written by one thread.  The tiling is row_tile's, the plans
+// of a workgroup's rows are staged clipped as k_rows_gather stages them, and a plan is trusted as little as there.
+struct SidePlans {
+    int64_t srca[PAD_ROWS], srcb[PAD_ROWS];
+    int32_t loa[PAD_ROWS], hia[PAD_ROWS], ca[PAD_ROWS], lob[PAD_ROWS], hib[PAD_ROWS], cb[PAD_ROWS];
+    int32_t endb[PAD_ROWS];  // col_b + kb inside [0, L]: the template's columns in front of it are bos and separators
+};
+
+// Every thread of the workgroup must call it; the plans are visible when it returns.
+__device__ __forceinline__ void stage_plans(SidePlans& s, const int64_t* plan, const RowTile& t, int32_t L, int32_t* err) {
+    if (threadIdx.x < t.nrows) {
+        const int tid = threadIdx.x;
+        const int64_t* p = plan + 8 * (t.row0 + tid);
+        int32_t* e = t.c0 == 0 ? err : nullptr;  // (of the workgroups of one long row, the first reports what is wrong with its plan)
+        int32_t lo, hi, c0;
+        clip_side(p[4], p[3], L, e, lo, hi, c0);
+        s.srca[tid] = p[2], s.loa[tid] = lo, s.hia[tid] = hi, s.ca[tid] = c0;
+        const int32_t lo_a = lo, hi_a = hi;
+        clip_side(p[7], p[6], L, e, lo, hi, c0);
+        s.srcb[tid] = p[5], s.lob[tid] = lo, s.hib[tid] = hi, s.cb[tid] = c0;
+        if (lo_a < hi_a && lo < hi && lo < hi_a && lo_a < hi) note_error(e, HUTK_E_ARG);  // (sides that overlap: A wins)
+        const int64_t col = p[7] < -(int64_t)L ? -(int64_t)L : p[7] > L ? L : p[7];
+        const int64_t k = p[6] < 0 ? 0 : p[6] > 2 * (int64_t)L ? 2 * (int64_t)L : p[6];
+        const int64_t end = col + k;  // (what a planner writes is left as it is: 0 <= col_b, col_b + kb <= L)
+        s.endb[tid] = end < 0 ? 0 : end > L ? L : (int32_t)end;
+    }
+    __syncthreads();
+}
+
+template <int W>
+using elem_t = std::conditional_t<W == 4, int32_t, int64_t>;  // an element of the rows: ids of either width are moved whole
+
+template <int W>
+__device__ __forceinline__ void load4(const void* base, int64_t i, elem_t<W> (&v)[4]) {
+    if constexpr (W == 4) {
+        const int4 x = *reinterpret_cast<const int4*>(static_cast<const int32_t*>(base) + i);
+        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+    } else {
+        const longlong2* p = reinterpret_cast<const longlong2*>(static_cast<const int64_t*>(base) + i);
+        const longlong2 x = p[0], y = p[1];
+        v[0] = x.x, v[1] = x.y, v[2] = y.x, v[3] = y.y;
+    }
+}
+template <int W>
+__device__ __forceinline__ void put4(void* base, int64_t i, const elem_t<W> (&v)[4]) {
+    if constexpr (W == 4) store4<4>(base, i, v);
+    else {  // (store4<8> widens int32: a label or an id of 64 bits goes as it is)
+        longlong2* p = reinterpret_cast<longlong2*>(static_cast<int64_t*>(base) + i);
+        p[0] = make_longlong2(v[0], v[1]);
+        p[1] = make_longlong2(v[2], v[3]);
+    }
+}
+template <int W>
+__device__ __forceinline__ void put1(void* base, int64_t i, elem_t<W> v) {
+    if constexpr (W == 4) store1<4>(base, i, v);
+    else static_cast<int64_t*>(base)[i] = v;
+}
+
+struct MlmArgs {
+    RowArgs r;  // (L, rows_per_block, col_chunks, err: what row_tile reads)
+    const int64_t* plan;
+    int64_t n_rows;
+    const void* ids;
+    void *out, *labels;
+    const int32_t *wa, *wb;  // whole-word mode: the word of every token of either side
+    int64_t n_a, n_b;
+    uint64_t seed;
+    uint64_t select_below, mask_below, random_below;  // 0 .. 2^32, against draws of 32 bits
+    uint64_t vocab;
+    int64_t ignore;
+    int32_t mask_id, sides;
+};
+
+// out[r][c] = the id, mask_id or a random id; labels[r][c] = the id where the column was selected, ignore elsewhere.
+// Only a column of a side named in `sides` draws (hutk_philox.h: the draw is a function of seed, row and column, or of
+// seed, row, side and word; never of the tile, W, VEC or the batch).  WORDS: the word of the column's token is selected,
+// and a selected column then draws its kind and id; a word id below 0 protects its token.
+template <int W, bool VEC, bool WORDS>
+__global__ __launch_bounds__(TB) void k_rows_mlm(const MlmArgs a) {
+    __shared__ SidePlans s;
+    const RowTile t = row_tile(a.r, a.n_rows);
+    if (t.nrows <= 0) return;
+    stage_plans(s, a.plan, t, a.r.L, a.r.err);
+    constexpr int V = VEC ? 4 : 1;
+    using T = elem_t<W>;
+    for (int32_t i = threadIdx.x * V; i < t.total; i += TB * V) {
+        const int32_t rl = t.one_row ? 0 : i / a.r.L;
+        const int32_t c = t.one_row ? t.c0 + i : i - rl * a.r.L;
+        const int64_t row = t.row0 + rl;
+        const int64_t at = row * (int64_t)a.r.L + c;
+        T v[V], lab[V];
+        if constexpr (VEC) load4<W>(a.ids, at, v);
+        else v[0] = static_cast<const T*>(a.ids)[at];
+        const int32_t lo_a = s.loa[rl], hi_a = s.hia[rl], lo_b = s.lob[rl], hi_b = s.hib[rl];
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            lab[e] = (T)a.ignore;
+            const int32_t col = c + e;
+            const bool in_a = col >= lo_a && col < hi_a;
+            const bool in_b = !in_a && col >= lo_b && col < hi_b;
+            if (!((in_a && (a.sides & HUTK_MLM_SIDE_A)) || (in_b && (a.sides & HUTK_MLM_SIDE_B)))) continue;
+            hutk::Philox4 d;
+            if constexpr (WORDS) {
+                const int64_t src = in_a ? s.srca[rl] : s.srcb[rl], n = in_a ? a.n_a : a.n_b;
+                const int64_t k = col - (in_a ? s.ca[rl] : s.cb[rl]);  // >= 0: col >= lo >= the side's first column
+                if (src >= n || src + k < 0 || src + k >= n) {  // (no overflow: src < n and 0 <= k < L)
+                    note_error(a.r.err, HUTK_E_ARG);
+                    continue;
+                }
+                const int32_t word = (in_a ? a.wa : a.wb)[src + k];
+                if (word < 0) continue;
+                if (hutk::draw(a.seed, row, (uint32_t)word, in_a ? hutk::DRAW_WORD_A : hutk::DRAW_WORD_B).x >= a.select_below) continue;
+                d = hutk::draw(a.seed, row, (uint32_t)col, hutk::DRAW_COLUMN);
+            } else {
+                d = hutk::draw(a.seed, row, (uint32_t)col, hutk::DRAW_COLUMN);
+                if (d.x >= a.select_below) continue;
+            }
+            lab[e] = v[e];
+            if (d.y < a.mask_below) v[e] = a.mask_id;
+            else if (d.y < a.random_below) v[e] = hutk::draw_id(d.z, a.vocab);
+        }
+        if constexpr (VEC) {
+            put4<W>(a.out, at, v);
+            put4<W>(a.labels, at, lab);
+        } else {
+            put1<W>(a.out, at, v[0]);
+            put1<W>(a.labels, at, lab[0]);
+        }
+    }
+}
+
+struct LabelArgs {
+    RowArgs r;  // (L, rows_per_block, col_chunks, err: what row_tile reads)
+    const int64_t* plan;
+    int64_t n_rows;
+    const void* ids;
+    const uint8_t* mask;
+    void* labels;
+    int64_t ignore;
+    int32_t flags;
+};
+
+// labels[r][c] = ids[r][c] on a loss column, ignore elsewhere; with HUTK_LABELS_SHIFT the id and the question move one
+// column to the right: what column c predicts.  A loss column is a real one (mask != 0) of a kind named in flags: A, B,
+// the template in front of col_b + kb (bos, separators) or at and behind it (eos).  The neighbour behind a thread's
+// elements is read from global memory, so the end of a workgroup's columns is no special place.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_rows_labels(const LabelArgs a) {
+    __shared__ SidePlans s;
+    const RowTile t = row_tile(a.r, a.n_rows);
+    if (t.nrows <= 0) return;
+    stage_plans(s, a.plan, t, a.r.L, a.r.err);
+    constexpr int V = VEC ? 4 : 1;
+    using T = elem_t<W>;
+    const bool shift = (a.flags & HUTK_LABELS_SHIFT) != 0;
+    for (int32_t i = threadIdx.x * V; i < t.total; i += TB * V) {
+        const int32_t rl = t.one_row ? 0 : i / a.r.L;
+        const int32_t c = t.one_row ? t.c0 + i : i - rl * a.r.L;
+        const int64_t at = (t.row0 + rl) * (int64_t)a.r.L + c;
+        T v[V + 1], lab[V];
+        uint8_t m[V + 1];
+        if constexpr (VEC) {
+            T q[4];
+            load4<W>(a.ids, at, q);
+            const uchar4 x = *reinterpret_cast<const uchar4*>(a.mask + at);
+            v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
+            m[0] = x.x, m[1] = x.y, m[2] = x.z, m[3] = x.w;
+        } else {
+            v[0] = static_cast<const T*>(a.ids)[at];
+            m[0] = a.mask[at];
+        }
+        v[V] = 0;
+        m[V] = shift && c + V < a.r.L ? a.mask[at + V] : 0;  // (the row ends at L: its last column predicts nothing)
+        const int32_t lo_a = s.loa[rl], hi_a = s.hia[rl], lo_b = s.lob[rl], hi_b = s.hib[rl], end_b = s.endb[rl];
+        bool loss[V + 1];
+#pragma unroll
+        for (int e = 0; e <= V; e++) {
+            const int32_t col = c + e;
+            const bool in_a = col >= lo_a && col < hi_a;
+            const bool in_b = !in_a && col >= lo_b && col < hi_b;
+            const int kind = in_a ? HUTK_LABELS_A : in_b ? HUTK_LABELS_B : col < end_b ? HUTK_LABELS_TEMPLATE : HUTK_LABELS_END;
+            loss[e] = m[e] != 0 && (a.flags & kind) != 0;
+        }
+        if (loss[V]) v[V] = static_cast<const T*>(a.ids)[at + V];  // (shift only: m[V] is 0 without)
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+            if (shift) lab[e] = m[e] != 0 && loss[e + 1] ? v[e + 1] : (T)a.ignore;
+            else lab[e] = loss[e] ? v[e] : (T)a.ignore;
+        }
+        if constexpr (VEC) put4<W>(a.labels, at, lab);
+        else put1<W>(a.labels, at, lab[0]);
+    }
+}
+
 // ---- answer positions -------------------------------------------------------------------------------------------------
 // The tokens of the named side of row r are j in [src, src + k) with non-decreasing spans (a_j, b_j); the answer (s, e)
 // of the row's item lies in the row iff k > 0, a_src <= s and b_{src + k - 1} >= e, and then starts at the column of
@@ -1170,6 +1368,23 @@ int launch_plan(const char* who, Kernel k, Args& a, int64_t n_rows, int64_t* d_p
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(TB), 0, st, a, o);
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
+}
+
+// What the two target calls refuse alike before anything else: the shape of the rows and a fill that does not fit them
+int target_sizes(const char* who, int64_t n_rows, int64_t max_len, int width, int64_t ignore_index) {
+    if (n_rows < 0 || (width != 4 && width != 8))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": bad arguments (width is 4 or 8)");
+    if (max_len < 1 || max_len > INT32_MAX)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": max_len must be in 1 .. 2^31 - 1");
+    if (width == 4 && (ignore_index < INT32_MIN || ignore_index > INT32_MAX))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": ignore_index must fit the rows' width");
+    return HUTK_OK;
+}
+
+// a buffer of np bytes at p and one of nq bytes at q that share a byte
+bool overlap(const void* p, int64_t np, const void* q, int64_t nq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + (uintptr_t)nq && b < a + (uintptr_t)np;
 }
 
 }  // namespace
@@ -1524,6 +1739,120 @@ int hutk_rows_answers_device(const int64_t* d_plan, int64_t n_rows, int side, co
     const AnsArgs a{d_plan, n_rows, d_spans, n_spans, d_answers, n_items, d_out, d_err, side};
     if (span_width == 4) hipLaunchKernelGGL(k_rows_answers<int32_t>, dim3((unsigned)blocks), dim3(TB), 0, st, a);
     else hipLaunchKernelGGL(k_rows_answers<int64_t>, dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+// ---- targets: masked-LM corruption and loss labels ----------------------------------------------------------
+int hutk_rows_mlm_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_input_ids, int width,
+                         const int32_t* d_words_a, int64_t n_a, const int32_t* d_words_b, int64_t n_b, uint64_t seed,
+                         int64_t select_below, int64_t mask_below, int64_t random_below, int32_t mask_id,
+                         int64_t vocab_size, int64_t ignore_index, int sides, void* d_out_ids, void* d_labels,
+                         int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_rows_mlm_device";
+    constexpr int64_t ONE = (int64_t)1 << 32;
+    if (int rc = target_sizes(who, n_rows, max_len, width, ignore_index)) return rc;
+    const bool words = d_words_a != nullptr;
+    if (words && (n_a < 0 || n_b < 0)) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": bad arguments (negative counts)");
+    if (select_below < 0 || select_below > ONE || mask_below < 0 || mask_below > random_below || random_below > ONE)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": the thresholds must be 0 <= select_below <= 2^32 and "
+                                                                  "0 <= mask_below <= random_below <= 2^32");
+    if (vocab_size < 1 || vocab_size > ((int64_t)1 << 31))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": vocab_size must be in 1 .. 2^31");
+    if ((sides & ~(HUTK_MLM_SIDE_A | HUTK_MLM_SIDE_B)) || !sides)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": sides must be HUTK_MLM_SIDE_A, HUTK_MLM_SIDE_B or both");
+    MlmArgs a = {};
+    a.r.L = (int32_t)max_len;
+    a.r.err = d_err;
+    int64_t blocks;
+    bool vec;
+    if (int rc = row_grid(who, a.r, n_rows, &blocks, &vec)) return rc;
+    if (!aligned_to(d_err, 4)) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its elements");
+    if (n_rows > 0) {
+        if (!d_plan || !d_input_ids || !d_out_ids || !d_labels)
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+        if (!aligned_to(d_plan, 8) || !aligned_to(d_input_ids, (uintptr_t)width) || !aligned_to(d_out_ids, (uintptr_t)width) ||
+            !aligned_to(d_labels, (uintptr_t)width) || !aligned_to(d_words_a, 4) || !aligned_to(d_words_b, 4))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its elements");
+        const int64_t bytes = n_rows * max_len * width;  // (no overflow: row_grid has bounded the rows)
+        if (overlap(d_labels, bytes, d_input_ids, bytes) || overlap(d_labels, bytes, d_out_ids, bytes) ||
+            (d_out_ids != d_input_ids && overlap(d_out_ids, bytes, d_input_ids, bytes)))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": d_labels must not overlap d_input_ids or d_out_ids, and "
+                                                                      "d_out_ids must be d_input_ids or apart from it");
+    }
+    if (int rc = device_present(who)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return HUTK_OK;
+    a.plan = d_plan;
+    a.n_rows = n_rows;
+    a.ids = d_input_ids;
+    a.out = d_out_ids;
+    a.labels = d_labels;
+    a.wa = d_words_a;
+    a.wb = d_words_b ? d_words_b : d_words_a;
+    a.n_a = n_a;
+    a.n_b = d_words_b ? n_b : n_a;
+    a.seed = seed;
+    a.select_below = (uint64_t)select_below;
+    a.mask_below = (uint64_t)mask_below;
+    a.random_below = (uint64_t)random_below;
+    a.vocab = (uint64_t)vocab_size;
+    a.ignore = ignore_index;
+    a.mask_id = mask_id;
+    a.sides = sides;
+    vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_out_ids, 16) && aligned_to(d_labels, 16);
+    const dim3 grid((unsigned)blocks), block(TB);
+    with_width_vec(width, vec, [&](auto w, auto v) {
+        constexpr int W = decltype(w)::value;
+        constexpr bool VEC = decltype(v)::value;
+        if (words) hipLaunchKernelGGL((k_rows_mlm<W, VEC, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_rows_mlm<W, VEC, false>), grid, block, 0, st, a);
+    });
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_rows_labels_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_input_ids, int width,
+                            const uint8_t* d_mask, int flags, int64_t ignore_index, void* d_labels, int32_t* d_err,
+                            void* hip_stream) {
+    const char* who = "hutk_rows_labels_device";
+    constexpr int SELECTING = HUTK_LABELS_A | HUTK_LABELS_B | HUTK_LABELS_TEMPLATE | HUTK_LABELS_END;
+    if (int rc = target_sizes(who, n_rows, max_len, width, ignore_index)) return rc;
+    if ((flags & ~(SELECTING | HUTK_LABELS_SHIFT)) || !(flags & SELECTING))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": flags must hold HUTK_LABELS_* only, and one of A, B, "
+                                                                  "TEMPLATE and END at least");
+    LabelArgs a = {};
+    a.r.L = (int32_t)max_len;
+    a.r.err = d_err;
+    int64_t blocks;
+    bool vec;
+    if (int rc = row_grid(who, a.r, n_rows, &blocks, &vec)) return rc;
+    if (!aligned_to(d_err, 4)) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its elements");
+    if (n_rows > 0) {
+        if (!d_plan || !d_input_ids || !d_mask || !d_labels)
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+        if (!aligned_to(d_plan, 8) || !aligned_to(d_input_ids, (uintptr_t)width) || !aligned_to(d_labels, (uintptr_t)width))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its elements");
+        const int64_t bytes = n_rows * max_len * width;  // (no overflow: row_grid has bounded the rows)
+        if (overlap(d_labels, bytes, d_input_ids, bytes) || overlap(d_labels, bytes, d_mask, n_rows * max_len))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": d_labels must not overlap d_input_ids or d_mask");
+    }
+    if (int rc = device_present(who)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return HUTK_OK;
+    a.plan = d_plan;
+    a.n_rows = n_rows;
+    a.ids = d_input_ids;
+    a.mask = d_mask;
+    a.labels = d_labels;
+    a.ignore = ignore_index;
+    a.flags = flags;
+    vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_labels, 16) && aligned_to(d_mask, 4);
+    with_width_vec(width, vec, [&](auto w, auto v) {
+        hipLaunchKernelGGL((k_rows_labels<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    });
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;
 }

@@ -853,6 +853,66 @@ int hutk_rows_answers_device(const int64_t* d_plan, int64_t n_rows, int side, co
                              int64_t n_spans, const void* d_answers, int64_t n_items, int32_t* d_out, int32_t* d_err,
                              void* hip_stream);
 
+/* MASKED-LM CORRUPTION.  d_input_ids [n_rows][max_len] elements of `width` bytes (4: int32, 8: int64) are rows whose
+ * geometry d_plan holds; d_out_ids and d_labels are rectangles of the same shape and width.  A column is ELIGIBLE iff it
+ * lies in the A side of its row's plan and sides has HUTK_MLM_SIDE_A, or in the B side and sides has HUTK_MLM_SIDE_B:
+ * bos, separators, eos and padding never are.  Every draw is Philox4x32-10 (multipliers 0xD2511F53 and 0xCD9E8D57, key
+ * increments 0x9E3779B9 and 0xBB67AE85) with key = (low32(seed), high32(seed)) and counter = (low32(row), high32(row),
+ * unit, purpose), so it depends on nothing but (seed, row, unit, purpose): not on the batch a row sits in, the width
+ * or the alignment.  purpose 0 with unit = column is the column's draw (u0, u1, u2, .); purpose 1 / 2 with unit = word
+ * id is the draw of a word of side A / B (a B side counts its words from 0 again).
+ *   token mode (d_words_a == NULL; n_a and n_b are not read): an eligible column is selected iff u0 < select_below.
+ *   whole-word mode: d_words_a int32[n_a] and d_words_b int32[n_b] hold the word of every token of either side,
+ *     indexed like the side's ids (hutk_token_word_ids_device); d_words_b == NULL reads both sides from d_words_a.  The
+ *     word of column c of side X is d_words_x[src_x + (c - col_x)]; a word below 0 makes the column not eligible (the
+ *     caller's way to protect a token, no error); otherwise the column is selected iff the word's u0 < select_below,
+ *     and only a selected column makes its own draw for u1 and u2.
+ *   a selected column: u1 < mask_below gives mask_id, else u1 < random_below gives the id (uint64(u2) * vocab_size) >>
+ *     32, else the id stays; d_labels holds the original id.  Every other column: the id is copied and d_labels holds
+ *     ignore_index.
+ * The thresholds are integers in 0 .. 2^32 against draws of 32 bits (a probability p is int(p * 2^32)), with
+ * 0 <= mask_below <= random_below <= 2^32; 1 <= vocab_size <= 2^31.  d_out_ids == d_input_ids is allowed (an element is
+ * read and written by one thread); otherwise the three rectangles must not overlap.  Buffers are aligned to their
+ * elements; with max_len a multiple of 4 and all three rectangles 16-byte aligned a thread moves four columns with
+ * 16-byte loads and stores.  The plan is not trusted, as in the gather: a side is clipped to the columns [0, max_len), a
+ * negative ka or kb counts as 0, where both sides claim a column it is A's, a word outside its array is not read; each
+ * of these gives HUTK_E_ARG in *d_err (may be NULL) and the columns concerned are not eligible.  Nothing is written
+ * outside the two outputs.  Refused with HUTK_E_ARG before a device is looked for: width other than 4 or 8, max_len
+ * outside 1 .. 2^31 - 1, negative counts, thresholds outside their order or range, vocab_size outside 1 .. 2^31, sides
+ * with unknown bits or none, an ignore_index that does not fit width, and with n_rows > 0 a NULL or misaligned buffer
+ * or rectangles that overlap.  n_rows == 0 writes nothing.  Asynchronous on hip_stream; never synchronises. */
+#define HUTK_MLM_SIDE_A 1
+#define HUTK_MLM_SIDE_B 2
+int hutk_rows_mlm_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_input_ids, int width,
+                         const int32_t* d_words_a, int64_t n_a, const int32_t* d_words_b, int64_t n_b,
+                         uint64_t seed, int64_t select_below, int64_t mask_below, int64_t random_below,
+                         int32_t mask_id, int64_t vocab_size, int64_t ignore_index, int sides,
+                         void* d_out_ids, void* d_labels, int32_t* d_err, void* hip_stream);
+
+/* LOSS LABELS.  d_labels [n_rows][max_len] of `width` bytes from the rows d_input_ids, their attention mask d_mask
+ * uint8 [n_rows][max_len] and their plan.  real(c) = d_mask[r][c] != 0.  A real column is a LOSS column when it is in A
+ * and flags has HUTK_LABELS_A; in B and HUTK_LABELS_B; a template column in front of col_b + kb and
+ * HUTK_LABELS_TEMPLATE (bos and the separators); a template column at or behind col_b + kb and HUTK_LABELS_END (eos).
+ * A layout without a B side writes col_b = col_a + ka and kb = 0, so the same rules hold for it.
+ *   without HUTK_LABELS_SHIFT: d_labels[r][c] = loss(c) ? d_input_ids[r][c] : ignore_index;
+ *   with it:                   d_labels[r][c] = real(c) && c + 1 < max_len && loss(c + 1) ? d_input_ids[r][c + 1]
+ *                                                                                         : ignore_index
+ * (what column c predicts: the last column of a row and the last pad column in front of a left-padded row predict
+ * nothing).  With max_len a multiple of 4, d_input_ids and d_labels 16-byte aligned and d_mask 4-byte aligned a thread
+ * moves four columns at once.  The plan is treated as in hutk_rows_mlm_device: clipped, A in front of B, HUTK_E_ARG in
+ * *d_err for what does not fit the row, the columns concerned are template columns; col_b + kb is taken inside
+ * [0, max_len].  Refused with HUTK_E_ARG before a device is looked for: width, max_len, n_rows and ignore_index as
+ * there, flags with unknown bits or none of A, B, TEMPLATE and END, and with n_rows > 0 a NULL or misaligned buffer or
+ * d_labels overlapping an input.  n_rows == 0 writes nothing.  Asynchronous on hip_stream; never synchronises. */
+#define HUTK_LABELS_A 1
+#define HUTK_LABELS_B 2
+#define HUTK_LABELS_TEMPLATE 4
+#define HUTK_LABELS_END 8
+#define HUTK_LABELS_SHIFT 16
+int hutk_rows_labels_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_input_ids, int width,
+                            const uint8_t* d_mask, int flags, int64_t ignore_index, void* d_labels, int32_t* d_err,
+                            void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

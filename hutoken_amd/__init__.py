@@ -27,7 +27,10 @@ row, with `row_map` from rows back to documents.  `collate_pairs` / `batch_encod
 Training targets (not in the reference): `mask_tokens` corrupts collated rows for masked-LM training and gives the
 labels, by tokens or by whole words, with random numbers that are a stated function of (seed, row, column) or (seed, row,
 side, word); `lm_labels` gives the loss labels of causal-LM and prompt + answer rows; `batch_encode_mlm` is the list
-form -- one HIP pass each over rows that exist already (csrc/hutk_collate.hip, csrc/hutk_philox.h).
+form -- one HIP pass each over rows that exist already (csrc/hutk_collate.hip, csrc/hutk_philox.h).  `corrupt_spans`
+is the span corruption of T5-style encoder-decoder training: every noise span of a row becomes one sentinel, the row
+closes up, and the spans move behind their sentinels into a target row, with the lengths of both and, on request, the
+decoder's input; `batch_encode_span_corruption` is the list form.  One wavefront per row scans and compacts it.
 
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
@@ -58,7 +61,7 @@ from . import _capi
 from . import pretokenize as _presplit_tables  # (the module; the package's name `pretokenize` is the function below)
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 
-__all__ = ["mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -1979,6 +1982,14 @@ def _on_one_gpu(what, named):
             raise ValueError("%s must be on the device of %s" % (name, named[0][0]))
 
 
+def _seed_arg(seed):
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError("seed must be an int, not %s" % type(seed).__name__)
+    if not 0 <= seed < 2**64:
+        raise ValueError("seed must be in 0 .. 2**64 - 1, not %d" % seed)
+    return seed
+
+
 def _mlm_args(mask_id, vocab_size, seed, mlm_probability, mask_fraction, random_fraction):
     """What mask_tokens checks of its numbers -> (mask_id, vocab_size, select_below, mask_below, random_below): a
     probability p is the threshold int(p * 2**32) against a draw of 32 bits."""
@@ -1994,10 +2005,7 @@ def _mlm_args(mask_id, vocab_size, seed, mlm_probability, mask_fraction, random_
         raise TypeError("vocab_size must be an int or None, not %s" % type(vocab_size).__name__)
     elif not 1 <= vocab_size <= 2**31:
         raise ValueError("vocab_size must be in 1 .. 2**31, not %d" % vocab_size)
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise TypeError("seed must be an int, not %s" % type(seed).__name__)
-    if not 0 <= seed < 2**64:
-        raise ValueError("seed must be in 0 .. 2**64 - 1, not %d" % seed)
+    _seed_arg(seed)
     mask_below = int(p_mask * 2**32)
     random_below = min(2**32, max(mask_below, int((p_mask + p_random) * 2**32)))
     return mask_id, 1 if vocab_size is None else vocab_size, int(p_select * 2**32), mask_below, random_below
@@ -2146,3 +2154,191 @@ def batch_encode_mlm(texts, max_length=None, *, mask_id, seed, vocab_size=None, 
                                mlm_probability=mlm_probability, mask_fraction=mask_fraction,
                                random_fraction=random_fraction, word_ids=words, inplace=True)
     return input_ids, mask, lengths, labels
+
+
+# ---- targets: span corruption ---------------------------------------------------------------------------------
+_SPAN_LENGTHS = 32  # the lengths a span can be drawn with (SPAN_LEN_MAX of csrc/hutk_collate.hip)
+
+
+def _span_length_table(mean_span_length, max_span_length, span_length_probs):
+    """-> (len_below, tail): len_below[j] = int(P(len <= j + 1) * 2**32), the last entry forced to 2**32;
+    tail[j] = P(len > j) for j in 0 .. n_len - 1.  tests/span_ref.py restates this arithmetic."""
+    if span_length_probs is not None:
+        if isinstance(span_length_probs, (str, bytes)) or not hasattr(span_length_probs, "__len__"):
+            raise TypeError("span_length_probs must be a sequence of numbers or None, not %s" % type(span_length_probs).__name__)
+        probs = list(span_length_probs)
+        if not 1 <= len(probs) <= _SPAN_LENGTHS:
+            raise ValueError("span_length_probs must hold 1 .. %d probabilities, not %d" % (_SPAN_LENGTHS, len(probs)))
+        for x in probs:
+            if isinstance(x, bool) or not isinstance(x, (int, float)):
+                raise TypeError("span_length_probs must hold numbers, not %s" % type(x).__name__)
+            if not 0 <= x <= 1:  # (NaN is refused too)
+                raise ValueError("span_length_probs must hold numbers in [0, 1], not %r" % (x,))
+        probs = [float(x) for x in probs]
+        if abs(sum(probs) - 1.0) > 1e-9:
+            raise ValueError("span_length_probs must sum to 1, not %r" % (sum(probs),))
+    else:
+        if isinstance(mean_span_length, bool) or not isinstance(mean_span_length, (int, float)):
+            raise TypeError("mean_span_length must be a number, not %s" % type(mean_span_length).__name__)
+        if not 1 <= mean_span_length < float("inf"):
+            raise ValueError("mean_span_length must be at least 1 and finite, not %r" % (mean_span_length,))
+        if isinstance(max_span_length, bool) or not isinstance(max_span_length, int):
+            raise TypeError("max_span_length must be an int, not %s" % type(max_span_length).__name__)
+        if not 1 <= max_span_length <= _SPAN_LENGTHS:
+            raise ValueError("max_span_length must be in 1 .. %d, not %d" % (_SPAN_LENGTHS, max_span_length))
+        q = 1.0 - 1.0 / float(mean_span_length)  # P(len > j) = q**j in front of the cut
+        probs = [(1.0 - q) * q**j for j in range(max_span_length - 1)] + [q**(max_span_length - 1)]
+    len_below, tail, cum = [], [], 0.0
+    for x in probs:
+        tail.append(min(1.0, max(0.0, 1.0 - cum)))
+        cum += x
+        len_below.append(min(2**32, max(int(cum * 2**32), len_below[-1] if len_below else 0)))
+    len_below[-1] = 2**32
+    return len_below, tail
+
+
+def _span_density(p, tail):
+    """The asymptotic density of the merged process: a column is noise unless none of the n_len columns at and in
+    front of it started a span that reaches it."""
+    clear = 1.0
+    for t in tail:
+        clear *= 1.0 - p * t
+    return 1.0 - clear
+
+
+def _span_start_probability(noise_density, tail):
+    """p with _span_density(p, tail) == noise_density, by bisection (the density grows with p).  A density above what
+    p = 1 gives raises; with the tails _span_length_table makes (tail[0] == 1) that is a density above 1 only."""
+    if noise_density <= 0.0:
+        return 0.0
+    most = _span_density(1.0, tail)
+    if noise_density > most + 1e-12:
+        raise ValueError("noise_density %r cannot be reached: spans of these lengths give at most %r" % (noise_density, most))
+    if noise_density >= most:
+        return 1.0
+    lo, hi = 0.0, 1.0
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        if _span_density(mid, tail) < noise_density:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def _span_args(dname, sentinel_first, seed, noise_density, mean_span_length, max_span_length, span_length_probs, n_sentinels,
+               sentinel_step, target_eos_id, decoder_start_id, max_target_length, pad_id, ignore_index, sides):
+    """What corrupt_spans checks of its numbers, before any device call -> (start_below, len_below, eos, start, pad)."""
+    bits = 31 if dname == "int32" else 63
+    for name, v in (("sentinel_first", sentinel_first), ("n_sentinels", n_sentinels), ("sentinel_step", sentinel_step)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("%s must be an int, not %s" % (name, type(v).__name__))
+    _seed_arg(seed)
+    if sentinel_step not in (-1, 1):
+        raise ValueError("sentinel_step must be -1 or 1, not %d" % sentinel_step)
+    if n_sentinels < 0:
+        raise ValueError("n_sentinels must not be negative")
+    for v in (sentinel_first, sentinel_first + max(n_sentinels - 1, 0) * sentinel_step):
+        if not -2**bits <= v < 2**bits:
+            raise ValueError("the sentinels %d .. must fit %s: %d does not" % (sentinel_first, dname, v))
+    density = _fraction_arg("noise_density", noise_density)
+    len_below, tail = _span_length_table(mean_span_length, max_span_length, span_length_probs)
+    start_below = int(_span_start_probability(density, tail) * 2**32)
+    eos, start = _token_arg("target_eos_id", target_eos_id), _token_arg("decoder_start_id", decoder_start_id)
+    pad = _token_arg("pad_id", pad_id, False)
+    if max_target_length is not None:
+        _length_arg("max_target_length", max_target_length, 1)
+    _ignore_arg(ignore_index, dname)
+    if sides not in _MLM_SIDES:
+        raise ValueError("sides must be 'a', 'b' or 'both', not %r" % (sides,))
+    return start_below, len_below, eos, start, pad
+
+
+def corrupt_spans(input_ids, attention_mask, row_plan, *, sentinel_first, seed, noise_density=0.15, mean_span_length=3.0,
+                  max_span_length=10, span_length_probs=None, n_sentinels=100, sentinel_step=-1, target_eos_id=None,
+                  decoder_start_id=None, max_target_length=None, pad_id=0, ignore_index=-100, sides="both", check=False):
+    """The span corruption (T5-style) of collated rows, one HIP pass: input_ids [n_rows, L] int32 or int64, attention_mask
+    uint8 of the same shape and the row_plan of the collate_* call that made them ->
+    (input_ids, attention_mask, labels, input_lengths, target_lengths), and decoder_input_ids behind them when
+    decoder_start_id is given.  Every noise span of a row becomes ONE sentinel in the corrupted row -- sentinel_first,
+    then sentinel_first + sentinel_step and so on (T5 counts down from the top of the vocabulary: step -1) -- and the
+    row closes up: whatever side the input was padded on, the output is compact and padded on the right with pad_id,
+    with its mask and input_lengths int32 [n_rows].  labels [n_rows, max_target_length] (None: L) holds, for each span in
+    order, its sentinel and then its ids, then target_eos_id when given, then ignore_index; what does not fit is
+    dropped, and target_lengths int32 [n_rows] is the count before that, so target_lengths > max_target_length tells a
+    cut row.  decoder_input_ids is labels moved one column to the right behind decoder_start_id, with pad_id where
+    labels holds ignore_index.  Only the columns that hold a token of a text (of side "a", "b" or "both": `sides`) and
+    are real by the mask can be noise -- never bos, a separator, eos or padding.  Runs past the n_sentinels-th stay text.
+    What is drawn: every eligible column starts a span with probability p, of a length drawn from span_length_probs
+    (up to 32 probabilities of the lengths 1, 2, ..; they sum to 1) or, without it, from the geometric law
+    P(len > j) = (1 - 1 / mean_span_length)**j cut at max_span_length (at most 32) with the tail folded into the last
+    length; a span ends with its side at the latest.  mean_span_length is the mean of that law in front of the cut: the
+    drawn lengths have the mean (1 - q**max_span_length) / (1 - q) with q = 1 - 1 / mean_span_length, 2.95 for the
+    defaults, and spans that overlap or touch merge, so the runs come out longer than the drawn lengths.  p is found on
+    the host by bisection so that a column far from its side's start is noise with probability noise_density,
+    1 - prod_j (1 - p * P(len > j)) = noise_density; the few columns at a side's start see fewer predecessors and are
+    noise a little less often.  With p = 1 every eligible column starts a span, so every noise_density in [0, 1] can be
+    reached with any lengths; only a density outside [0, 1] is refused (ValueError).  The random
+    numbers are Philox4x32-10 draws that depend on nothing but (seed, row, column) -- include/hutoken_amd.h states the
+    rule in full, tests/span_ref.py restates it in numpy -- so a row's outcome does not depend on the batch around it.
+    seed is an int in 0 .. 2**64 - 1 and has no default: there is no hidden state; pass a different one per step.  On the
+    current torch stream, never synchronises; check=True does and raises ValueError for a plan that points outside its
+    row (nothing is read or written out of bounds either way)."""
+    dname, width = _rows_arg("input_ids", input_ids)
+    if not _is_tensor(attention_mask):
+        raise TypeError("attention_mask must be a torch tensor, not %s" % type(attention_mask).__name__)
+    if _dtype_name(attention_mask) != "uint8":
+        raise TypeError("attention_mask must have dtype uint8, not %s" % attention_mask.dtype)
+    if tuple(attention_mask.shape) != tuple(input_ids.shape) or not attention_mask.is_contiguous():
+        raise ValueError("attention_mask must be contiguous and of the shape of input_ids")
+    _rows_plan_arg(row_plan, input_ids)
+    start_below, len_below, eos, start, pad = _span_args(
+        dname, sentinel_first, seed, noise_density, mean_span_length, max_span_length, span_length_probs, n_sentinels,
+        sentinel_step, target_eos_id, decoder_start_id, max_target_length, pad_id, ignore_index, sides)
+    _on_one_gpu("the corruption", (("input_ids", input_ids), ("attention_mask", attention_mask), ("row_plan", row_plan)))
+    import torch
+    dev = input_ids.device
+    n_rows, L = input_ids.shape
+    L_tgt = L if max_target_length is None else max_target_length
+    out, out_mask = torch.empty_like(input_ids), torch.empty_like(attention_mask)
+    labels = torch.empty((n_rows, L_tgt), dtype=input_ids.dtype, device=dev)
+    dec = torch.empty_like(labels) if decoder_start_id is not None else None
+    in_lengths, tgt_lengths = (torch.empty(n_rows, dtype=torch.int32, device=dev) for _ in range(2))
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.rows_span_corrupt_device(row_plan.data_ptr(), n_rows, L, input_ids.data_ptr(), width, attention_mask.data_ptr(),
+                                       seed, start_below, len_below, sentinel_first, sentinel_step, n_sentinels, eos, start,
+                                       pad, ignore_index, _MLM_SIDES[sides], L_tgt, out.data_ptr(), out_mask.data_ptr(),
+                                       labels.data_ptr(), 0 if dec is None else dec.data_ptr(), in_lengths.data_ptr(),
+                                       tgt_lengths.data_ptr(), err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return (out, out_mask, labels, in_lengths, tgt_lengths) + (() if dec is None else (dec,))
+    res = _on_torch_stream(dev, call, used=(input_ids, attention_mask, row_plan, err))
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: corrupt_spans: a row_plan that points outside its row (device-side error %d)"
+                         % int(err.item()))
+    return res
+
+
+def batch_encode_span_corruption(texts, max_length=None, *, sentinel_first, seed, normalize=None, noise_density=0.15,
+                                 mean_span_length=3.0, max_span_length=10, span_length_probs=None, n_sentinels=100,
+                                 sentinel_step=-1, target_eos_id=None, decoder_start_id=None, max_target_length=None,
+                                 ignore_index=-100, sides="both", check=False, **collate_kwargs):
+    """A list of str -> corrupt_spans' (input_ids, attention_mask, labels, input_lengths, target_lengths[,
+    decoder_input_ids]), an encoder-decoder training batch: encode_packed_device, collate_padded with `collate_kwargs`
+    (its pad_id pads the corrupted rows too) and its plan, then corrupt_spans.  sentinel_first, seed and the
+    corruption's keywords: as corrupt_spans (a padded row has an A side only: sides="b" corrupts nothing); check=True is
+    handed to both collate_padded and corrupt_spans; normalize: as batch_encode_padded."""
+    if "return_plan" in collate_kwargs:
+        raise TypeError("batch_encode_span_corruption returns no plan: use batch_encode_padded(return_plan=True) and corrupt_spans")
+    pad_id = collate_kwargs.get("pad_id", 0)
+    _span_args(_out_width(collate_kwargs.get("dtype"))[1], sentinel_first, seed, noise_density, mean_span_length, max_span_length,
+               span_length_probs, n_sentinels, sentinel_step, target_eos_id, decoder_start_id, max_target_length, pad_id,
+               ignore_index, sides)
+    ids, oo = _texts_to_device(texts, normalize=normalize)
+    input_ids, mask, _lengths, plan = collate_padded(ids, oo, max_length, return_plan=True, check=check, **collate_kwargs)
+    return corrupt_spans(input_ids, mask, plan, sentinel_first=sentinel_first, seed=seed, noise_density=noise_density,
+                         mean_span_length=mean_span_length, max_span_length=max_span_length, span_length_probs=span_length_probs,
+                         n_sentinels=n_sentinels, sentinel_step=sentinel_step, target_eos_id=target_eos_id,
+                         decoder_start_id=decoder_start_id, max_target_length=max_target_length, pad_id=pad_id,
+                         ignore_index=ignore_index, sides=sides, check=check)

@@ -124,6 +124,8 @@ SIGNATURES = {
     "hutk_rows_mlm_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, C.c_uint64, _i64, _i64, _i64, _s32, _i64,
                                     _i64, _i32, _vp, _vp, _vp, _vp]),
     "hutk_rows_labels_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "hutk_rows_span_corrupt_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, C.c_uint64, _i64, _vp, _i32, _i64, _i32, _i64,
+                                             _s32, _s32, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -830,6 +832,21 @@ def rows_labels_device(d_plan, n_rows, max_len, d_input_ids, width, d_mask, flag
     """hutk_rows_labels_device on raw device pointers (ints); flags: LABELS_*; asynchronous on `stream`."""
     raise_for(load().hutk_rows_labels_device(d_plan or None, n_rows, max_len, d_input_ids or None, width, d_mask or None,
                                              flags, ignore_index, d_labels or None, d_err or None, stream or None))
+
+
+def rows_span_corrupt_device(d_plan, n_rows, max_len, d_input_ids, width, d_mask, seed, start_below, len_below, sentinel_first,
+                             sentinel_step, n_sentinels, target_eos_id, decoder_start_id, pad_id, ignore_index, sides,
+                             max_target_len, d_out_ids, d_out_mask, d_labels, d_decoder_ids, d_in_lengths, d_tgt_lengths,
+                             d_err=0, stream=0):
+    """hutk_rows_span_corrupt_device on raw device pointers (ints); len_below: a sequence of ints in 0 .. 2**32, the host
+    table; target_eos_id / decoder_start_id: NO_TOKEN for none; asynchronous on `stream`."""
+    table = (_i64 * len(len_below))(*len_below)
+    raise_for(load().hutk_rows_span_corrupt_device(d_plan or None, n_rows, max_len, d_input_ids or None, width, d_mask or None,
+                                                   seed, start_below, table, len(len_below), sentinel_first, sentinel_step,
+                                                   n_sentinels, target_eos_id, decoder_start_id, pad_id, ignore_index, sides,
+                                                   max_target_len, d_out_ids or None, d_out_mask or None, d_labels or None,
+                                                   d_decoder_ids or None, d_in_lengths or None, d_tgt_lengths or None,
+                                                   d_err or None, stream or None))
 
 
 class Packer(_Owner):

@@ -18,7 +18,9 @@
 // functions its collate kernel places it with (k_plan_padded, k_plan_windows, k_plan_pairs); the gather of any
 // per-token array into the rows' shape by a plan (k_rows_gather); the columns of an answer in every row
 // (k_rows_answers); and the last stage before a training batch: the masked-LM corruption of
-// rows with its labels (k_rows_mlm, drawing from hutk_philox.h) and the loss labels of rows (k_rows_labels).
+// rows with its labels (k_rows_mlm, drawing from hutk_philox.h), the loss labels of rows (k_rows_labels), and the span
+// corruption of rows into corrupted rows and target rows, a wavefront scanning and compacting its row
+// (k_rows_span_corrupt).
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets.  A workgroup of the row layouts stages the plan of its rows in LDS
@@ -1164,6 +1166,217 @@ __global__ __launch_bounds__(TB) void k_rows_labels(const LabelArgs a) {
     }
 }
 
+// ---- targets: span corruption ---------------------------------------------------------------------------------
+// The first row pass whose outputs are of another length than its input: every noise span of a row becomes one
+// sentinel in the corrupted row, and the spans move, each behind its sentinel, into a target row.  One wavefront per
+// row, four rows per workgroup, no LDS and no barrier: the wavefront walks its row in chunks of 256 columns, four
+// consecutive ones per lane, and carries four values from chunk to chunk -- the prefix maximum of the reaches, whether
+// the last column was noise, the count of run beginnings and the packed counts of kept columns and target elements.
+// Every __shfl is executed by all 64 lanes: the trip count depends on L alone and a row behind the last one leaves as a
+// whole wavefront.
+constexpr int SPAN_LEN_MAX = 32;                // lengths a span can be drawn with
+constexpr int SPAN_CHUNK = 64 * 4;              // columns a wavefront takes per trip
+
+struct SpanArgs {
+    const int64_t* plan;
+    int64_t n_rows;
+    const void* ids;
+    const uint8_t* mask;
+    void *out, *labels, *dec;  // dec: NULL without decoder_start_id
+    uint8_t* out_mask;
+    int32_t *in_len, *tgt_len, *err;
+    uint64_t seed;
+    uint64_t start_below;  // 0 .. 2^32, against a draw of 32 bits
+    int64_t sentinel_first, pad, ignore;
+    int32_t L, L_tgt;
+    int32_t n_cmp;   // the thresholds below 2^32 among len_below[0 .. n_len - 2]: the others no draw reaches
+    int32_t step, n_sent, eos, dec_start, sides;
+    uint32_t len_below[SPAN_LEN_MAX - 1];  // (indexed by constants only: the loop over it is unrolled)
+};
+
+__device__ __forceinline__ uint4 splat16(uint8_t v) {
+    const uint32_t x = v * 0x01010101u;
+    return make_uint4(x, x, x, x);
+}
+__device__ __forceinline__ uint4 splat16(int32_t v) { return make_uint4((uint32_t)v, (uint32_t)v, (uint32_t)v, (uint32_t)v); }
+__device__ __forceinline__ uint4 splat16(int64_t v) {
+    const uint32_t lo = (uint32_t)(uint64_t)v, hi = (uint32_t)((uint64_t)v >> 32);
+    return make_uint4(lo, hi, lo, hi);
+}
+
+// p[from .. to) = v by one wavefront: single elements up to the first 16-byte boundary, 16-byte stores, single elements
+// behind the last one.  p is aligned to its elements.
+template <class T>
+__device__ __forceinline__ void wave_fill(T* p, int64_t from, int64_t to, T v, int lane) {
+    if (from >= to) return;
+    constexpr int PER = 16 / (int)sizeof(T);
+    T* b = p + from;
+    const int64_t n = to - from;
+    int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(b) & 15)) & 15) / (int64_t)sizeof(T);  // < PER <= 16
+    if (head > n) head = n;
+    if (lane < head) b[lane] = v;
+    const int64_t nvec = (n - head) / PER;
+    const uint4 x = splat16(v);
+    for (int64_t i = lane; i < nvec; i += 64) *reinterpret_cast<uint4*>(b + head + i * PER) = x;
+    const int64_t done = head + nvec * PER;  // n - done < PER
+    if (lane < n - done) b[done + lane] = v;
+}
+
+// See include/hutoken_amd.h for the rule.  VEC: L % 4 == 0, ids 16-byte and mask 4-byte aligned: a lane loads its four
+// columns at once.  Sums: the run beginnings in 32 bits (at most (L + 1) / 2); the kept columns (at most L < 2^31) in
+// the upper and the target elements (noise columns plus runs plus eos: at most L + (L + 1) / 2 + 1 < 2^32) in the lower
+// half of one 64-bit word, so the lower half never carries into the upper one, for every L the call admits.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_rows_span_corrupt(const SpanArgs a) {
+    using T = elem_t<W>;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+    if (row >= a.n_rows) return;  // (a whole wavefront)
+    const uint32_t L = (uint32_t)a.L, LT = (uint32_t)a.L_tgt;
+    const int64_t* p = a.plan + 8 * row;
+    int32_t* e0 = lane == 0 ? a.err : nullptr;  // (one lane reports what is wrong with the row's plan)
+    int32_t lo_a, hi_a, lo_b, hi_b, first;
+    clip_side(p[4], p[3], a.L, e0, lo_a, hi_a, first);
+    clip_side(p[7], p[6], a.L, e0, lo_b, hi_b, first);
+    if (lo_a < hi_a && lo_b < hi_b && lo_b < hi_a && lo_a < hi_b) note_error(e0, HUTK_E_ARG);  // (sides that overlap: A wins)
+    const bool side_a = (a.sides & HUTK_MLM_SIDE_A) != 0, side_b = (a.sides & HUTK_MLM_SIDE_B) != 0;
+    const int64_t in0 = row * (int64_t)L, tg0 = row * (int64_t)LT;  // the row's first element in the rectangles
+    const uint32_t n_sent = (uint32_t)a.n_sent;
+
+    const auto label = [&](uint32_t at, T v) {  // target element `at` and what the decoder reads behind it
+        if (at >= LT) return;
+        put1<W>(a.labels, tg0 + at, v);
+        if (a.dec && at + 1 < LT) put1<W>(a.dec, tg0 + at + 1, v);
+    };
+
+    uint32_t c_max = 0, c_runs = 0;  // carried: the prefix maximum of reach, the run beginnings so far
+    bool c_noise = false;            // carried: noise0 of the column in front of the chunk
+    uint64_t c_kt = 0;               // carried: kept columns << 32 | target elements
+    for (uint32_t base = 0; base < L; base += SPAN_CHUNK) {
+        const uint32_t c0 = base + (uint32_t)lane * 4;  // (below 2^32: base < L < 2^31)
+        T v[4] = {0, 0, 0, 0};
+        uint8_t m[4] = {0, 0, 0, 0};
+        if constexpr (VEC) {
+            if (c0 < L) {  // (L % 4 == 0: all four or none)
+                load4<W>(a.ids, in0 + c0, v);
+                const uchar4 x = *reinterpret_cast<const uchar4*>(a.mask + in0 + c0);
+                m[0] = x.x, m[1] = x.y, m[2] = x.z, m[3] = x.w;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (c0 + e < L) v[e] = static_cast<const T*>(a.ids)[in0 + c0 + e], m[e] = a.mask[in0 + c0 + e];
+        }
+        // reach, and its inclusive maximum: in the lane, across the lanes, with the chunks before
+        uint32_t pm[4], lane_max = 0, end[4], len[4], u1[4];
+        bool elig[4], starts[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t c = c0 + e;
+            const bool in_a = (int64_t)c >= lo_a && (int64_t)c < hi_a;
+            const bool in_b = !in_a && (int64_t)c >= lo_b && (int64_t)c < hi_b;
+            elig[e] = m[e] != 0 && ((in_a && side_a) || (in_b && side_b));  // (m is 0 behind the row)
+            end[e] = (uint32_t)(in_a ? hi_a : hi_b);
+            starts[e] = false, len[e] = 1, u1[e] = 0;
+            if (elig[e]) {  // only an eligible column draws
+                const hutk::Philox4 d = hutk::draw(a.seed, row, c, hutk::DRAW_SPAN);
+                starts[e] = d.x < a.start_below;
+                u1[e] = d.y;
+            }
+        }
+        // The lengths: one walk through the table for the four columns, the same in every lane (j < n_cmp is uniform, and
+        // so is the question whether any lane starts a span at all).
+        if (__ballot(starts[0] || starts[1] || starts[2] || starts[3])) {
+#pragma unroll
+            for (int j = 0; j < SPAN_LEN_MAX - 1; j++) {
+                if (j < a.n_cmp) {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) len[e] += u1[e] >= a.len_below[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t c = c0 + e;
+            const uint32_t reach = !starts[e] ? 0 : c + len[e] < end[e] ? c + len[e] : end[e];
+            lane_max = lane_max > reach ? lane_max : reach;
+            pm[e] = lane_max;
+        }
+        const uint32_t upto = hutk::wave_incl_max(lane_max, lane);
+        uint32_t before = __shfl_up(upto, 1);
+        if (lane == 0 || before < c_max) before = c_max;
+        c_max = __shfl(upto, 63) > c_max ? __shfl(upto, 63) : c_max;
+        bool noise[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) noise[e] = elig[e] && (pm[e] > before ? pm[e] : before) > c0 + e;
+        // run beginnings and their numbers
+        const int left = __shfl_up((int)noise[3], 1);
+        const int last = __shfl((int)noise[3], 63);
+        bool prev = lane == 0 ? c_noise : left != 0;
+        c_noise = last != 0;
+        bool begin[4];
+        uint32_t runs[4], lane_runs = 0;  // inclusive, in the lane
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            begin[e] = noise[e] && !prev;
+            prev = noise[e];
+            lane_runs += begin[e];
+            runs[e] = lane_runs;
+        }
+        const uint32_t runs_upto = hutk::wave_incl(lane_runs, lane);
+        const uint32_t runs_before = runs_upto - lane_runs + c_runs;
+        c_runs += __shfl(runs_upto, 63);
+        // runs past the last sentinel stay text; kept columns and target elements
+        uint64_t kt[4], lane_kt = 0;  // exclusive, in the lane
+        uint32_t k[4];
+        bool keep[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            k[e] = runs_before + runs[e] - 1;  // the number of the run a noise column lies in
+            noise[e] = noise[e] && k[e] < n_sent;
+            begin[e] = begin[e] && noise[e];
+            keep[e] = m[e] != 0 && (!noise[e] || begin[e]);
+            kt[e] = lane_kt;
+            lane_kt += ((uint64_t)keep[e] << 32) + (noise[e] ? 1u + begin[e] : 0u);
+        }
+        const uint64_t kt_upto = hutk::wave_incl(lane_kt, lane);
+        const uint64_t kt_before = kt_upto - lane_kt + c_kt;
+        c_kt += __shfl(kt_upto, 63);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint64_t at = kt_before + kt[e];
+            const T sentinel = (T)(a.sentinel_first + (int64_t)k[e] * a.step);
+            if (keep[e]) {  // (fewer columns are kept in front of c than there are: inside the row)
+                put1<W>(a.out, in0 + (int64_t)(at >> 32), begin[e] ? sentinel : v[e]);
+                a.out_mask[in0 + (int64_t)(at >> 32)] = 1;
+            }
+            if (noise[e]) {
+                uint32_t t = (uint32_t)at;
+                if (begin[e]) label(t++, sentinel);
+                label(t, v[e]);
+            }
+        }
+    }
+    const uint32_t kept = (uint32_t)(c_kt >> 32);
+    uint32_t targets = (uint32_t)c_kt;
+    if (a.eos != HUTK_NO_TOKEN) {
+        if (lane == 0) label(targets, (T)a.eos);
+        targets++;
+    }
+    const uint32_t written = targets < LT ? targets : LT;
+    wave_fill(static_cast<T*>(a.out) + in0, kept, L, (T)a.pad, lane);
+    wave_fill(a.out_mask + in0, kept, L, (uint8_t)0, lane);
+    wave_fill(static_cast<T*>(a.labels) + tg0, written, LT, (T)a.ignore, lane);
+    if (a.dec) {
+        wave_fill(static_cast<T*>(a.dec) + tg0, (int64_t)written + 1, LT, (T)a.pad, lane);
+        if (lane == 0) put1<W>(a.dec, tg0, (T)a.dec_start);
+    }
+    if (lane == 0) {
+        a.in_len[row] = (int32_t)kept;
+        a.tgt_len[row] = targets > (uint32_t)INT32_MAX ? INT32_MAX : (int32_t)targets;
+    }
+}
+
 // ---- answer positions -------------------------------------------------------------------------------------------------
 // The tokens of the named side of row r are j in [src, src + k) with non-decreasing spans (a_j, b_j); the answer (s, e)
 // of the row's item lies in the row iff k > 0, a_src <= s and b_{src + k - 1} >= e, and then starts at the column of
@@ -1852,6 +2065,103 @@ int hutk_rows_labels_device(const int64_t* d_plan, int64_t n_rows, int64_t max_l
     vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_labels, 16) && aligned_to(d_mask, 4);
     with_width_vec(width, vec, [&](auto w, auto v) {
         hipLaunchKernelGGL((k_rows_labels<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    });
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+// ---- targets: span corruption ---------------------------------------------------------------------------------
+int hutk_rows_span_corrupt_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_input_ids, int width,
+                                  const uint8_t* d_mask, uint64_t seed, int64_t start_below, const int64_t* len_below,
+                                  int n_len, int64_t sentinel_first, int sentinel_step, int64_t n_sentinels,
+                                  int32_t target_eos_id, int32_t decoder_start_id, int64_t pad_id, int64_t ignore_index,
+                                  int sides, int64_t max_target_len, void* d_out_ids, uint8_t* d_out_mask, void* d_labels,
+                                  void* d_decoder_ids, int32_t* d_in_lengths, int32_t* d_tgt_lengths, int32_t* d_err,
+                                  void* hip_stream) {
+    const char* who = "hutk_rows_span_corrupt_device";
+    constexpr int64_t ONE = (int64_t)1 << 32;
+    const auto refuse = [&](const char* what) { return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": " + what); };
+    if (int rc = target_sizes(who, n_rows, max_len, width, ignore_index)) return rc;
+    if (max_target_len < 1 || max_target_len > INT32_MAX) return refuse("max_target_len must be in 1 .. 2^31 - 1");
+    if (start_below < 0 || start_below > ONE) return refuse("start_below must be in 0 .. 2^32");
+    if (!len_below || n_len < 1 || n_len > SPAN_LEN_MAX) return refuse("len_below must hold 1 .. 32 thresholds");
+    for (int j = 0; j < n_len; j++)
+        if (len_below[j] < (j ? len_below[j - 1] : 0) || len_below[j] > ONE)
+            return refuse("len_below must not decrease and must lie in 0 .. 2^32");
+    if (len_below[n_len - 1] != ONE) return refuse("the last entry of len_below must be 2^32");
+    if (sentinel_step != 1 && sentinel_step != -1) return refuse("sentinel_step must be -1 or +1");
+    if (n_sentinels < 0) return refuse("n_sentinels must not be negative");
+    const auto fits = [&](__int128 v) { return width == 4 ? v >= INT32_MIN && v <= INT32_MAX : v >= INT64_MIN && v <= INT64_MAX; };
+    const __int128 sentinel_last = (__int128)sentinel_first + (__int128)(n_sentinels ? n_sentinels - 1 : 0) * sentinel_step;
+    if (!fits(sentinel_first) || !fits(sentinel_last)) return refuse("the first and the last sentinel must fit the rows' width");
+    if (!fits(pad_id)) return refuse("pad_id must fit the rows' width");
+    if ((sides & ~(HUTK_MLM_SIDE_A | HUTK_MLM_SIDE_B)) || !sides)
+        return refuse("sides must be HUTK_MLM_SIDE_A, HUTK_MLM_SIDE_B or both");
+    if (!aligned_to(d_err, 4)) return refuse("a buffer is not aligned to its elements");
+    const bool dec = decoder_start_id != HUTK_NO_TOKEN;
+    if (!dec) d_decoder_ids = nullptr;
+    // four rows a workgroup; the row count is bounded first, so that neither the sum below nor a size in bytes overflows
+    constexpr int64_t MOST_ROWS = (int64_t)INT32_MAX * (TB / 64);
+    int64_t in_bytes = 0, tg_bytes = 0;
+    if (n_rows > MOST_ROWS || __builtin_mul_overflow(n_rows, max_len * width, &in_bytes) ||
+        __builtin_mul_overflow(n_rows, max_target_len * width, &tg_bytes))
+        return hutk::api_set_error(HUTK_E_UNSUPPORTED, std::string(who) + ": the batch is too large for one launch");
+    const int64_t blocks = (n_rows + TB / 64 - 1) / (TB / 64);  // <= INT32_MAX
+    if (n_rows > 0) {
+        if (!d_plan || !d_input_ids || !d_mask || !d_out_ids || !d_out_mask || !d_labels || !d_in_lengths || !d_tgt_lengths ||
+            (dec && !d_decoder_ids))
+            return refuse("a buffer is NULL");
+        const uintptr_t w = (uintptr_t)width;
+        if (!aligned_to(d_plan, 8) || !aligned_to(d_input_ids, w) || !aligned_to(d_out_ids, w) || !aligned_to(d_labels, w) ||
+            !aligned_to(d_decoder_ids, w) || !aligned_to(d_in_lengths, 4) || !aligned_to(d_tgt_lengths, 4))
+            return refuse("a buffer is not aligned to its elements");
+        struct Buf {
+            const void* p;
+            int64_t bytes;
+        };
+        const Buf in[] = {{d_plan, n_rows * 64}, {d_input_ids, in_bytes}, {d_mask, n_rows * max_len}};
+        const Buf out[] = {{d_out_ids, in_bytes},       {d_out_mask, n_rows * max_len}, {d_labels, tg_bytes}, {d_decoder_ids, dec ? tg_bytes : 0},
+                           {d_in_lengths, n_rows * 4}, {d_tgt_lengths, n_rows * 4},    {d_err, d_err ? 4 : 0}};
+        for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); i++) {
+            if (!out[i].bytes) continue;
+            for (const Buf& b : in)
+                if (overlap(out[i].p, out[i].bytes, b.p, b.bytes)) return refuse("an output must not overlap an input: there is no in-place form");
+            for (size_t j = 0; j < i; j++)
+                if (out[j].bytes && overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return refuse("the outputs must not overlap each other");
+        }
+    }
+    if (int rc = device_present(who)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_rows == 0) return HUTK_OK;
+    SpanArgs a = {};
+    a.plan = d_plan;
+    a.n_rows = n_rows;
+    a.ids = d_input_ids;
+    a.mask = d_mask;
+    a.out = d_out_ids;
+    a.labels = d_labels;
+    a.dec = d_decoder_ids;
+    a.out_mask = d_out_mask;
+    a.in_len = d_in_lengths;
+    a.tgt_len = d_tgt_lengths;
+    a.err = d_err;
+    a.seed = seed;
+    a.start_below = (uint64_t)start_below;
+    a.sentinel_first = sentinel_first;
+    a.pad = pad_id;
+    a.ignore = ignore_index;
+    a.L = (int32_t)max_len;
+    a.L_tgt = (int32_t)max_target_len;
+    for (int j = 0; j + 1 < n_len && len_below[j] < ONE; j++) a.len_below[a.n_cmp++] = (uint32_t)len_below[j];
+    a.step = sentinel_step;
+    a.n_sent = n_sentinels > INT32_MAX ? INT32_MAX : (int32_t)n_sentinels;  // (a row has fewer runs than columns)
+    a.eos = target_eos_id;
+    a.dec_start = decoder_start_id;
+    a.sides = sides;
+    const bool vec = max_len % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_mask, 4);
+    with_width_vec(width, vec, [&](auto w, auto v) {
+        hipLaunchKernelGGL((k_rows_span_corrupt<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
     });
     HUTK_HIP_TRY(hipGetLastError());
     return HUTK_OK;

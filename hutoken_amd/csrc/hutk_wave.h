@@ -1,5 +1,5 @@
-// hutk_wave.h -- the two primitives that the kernels of several files share: a search by one wavefront and the scan over
-// a workgroup of 256 threads.  Device code only; every function is inlined into its caller.
+// hutk_wave.h -- the primitives that the kernels of several files share: a search by one wavefront, its inclusive sum and
+// maximum scans, and the scan over a workgroup of 256 threads.  Device code only; every function is inlined into its caller.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +34,17 @@ __device__ __forceinline__ V wave_incl(V v, int lane) {
     for (int off = 1; off < 64; off <<= 1) {
         const V p = __shfl_up(v, off);
         if (lane >= off) v += p;
+    }
+    return v;
+}
+
+// inclusive maximum over the 64 lanes of a wavefront: lane i gets max(v of lanes 0 .. i)
+template <class V>
+__device__ __forceinline__ V wave_incl_max(V v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const V p = __shfl_up(v, off);
+        if (lane >= off && p > v) v = p;
     }
     return v;
 }

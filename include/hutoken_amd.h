@@ -913,6 +913,51 @@ int hutk_rows_labels_device(const int64_t* d_plan, int64_t n_rows, int64_t max_l
                             const uint8_t* d_mask, int flags, int64_t ignore_index, void* d_labels, int32_t* d_err,
                             void* hip_stream);
 
+/* SPAN CORRUPTION (T5-style).  d_input_ids [n_rows][max_len] elements of `width` bytes with their attention mask d_mask
+ * uint8 [n_rows][max_len] and their plan -> the corrupted rows d_out_ids / d_out_mask of the same shape, in which every
+ * noise span is ONE sentinel, and the target rows d_labels [n_rows][max_target_len] of the same width, in which the
+ * spans follow their sentinels.  A row's outcome depends on (seed, the row's number, its plan and its mask) alone: not on
+ * the batch, the width, the alignment or the tiling.  All numbers are exact integers; thresholds lie in 0 .. 2^32 and are
+ * compared with draws of 32 bits, as in hutk_rows_mlm_device, whose generator this is.
+ *   ELIGIBLE.  Column c is eligible iff it lies in a side of the clipped plan that `sides` names (HUTK_MLM_SIDE_*; the
+ *     clipping is that of hutk_rows_mlm_device: a negative length counts as 0, a column both sides claim is A's) and
+ *     d_mask[r][c] != 0.  side_end(c) is the clipped end of the side that holds c.
+ *   DRAW.  An eligible column draws with purpose 3 and unit = c: (u0, u1, ., .).  It starts a span iff u0 < start_below,
+ *     of the length len = 1 + #{ j in 0 .. n_len - 2 : u1 >= len_below[j] }; len_below is a HOST array of n_len
+ *     cumulative thresholds, 1 <= n_len <= 32, non-decreasing, the last one 2^32, copied into the launch.  Then
+ *     reach(c) = min(c + len, side_end(c)); for every column that starts nothing reach(c) = 0.
+ *   NOISE.  noise0(c) = eligible(c) && max{ reach(s) : s <= c } > c, a prefix maximum along the row: spans that overlap
+ *     or touch merge.  A run is a maximal run of noise0 columns; its number k is the count of runs that begin in front of
+ *     it in the row, across both sides.  noise(c) = noise0(c) && k(c) < n_sentinels: whole runs past the last sentinel
+ *     stay text.  sentinel(k) = sentinel_first + k * sentinel_step, the step being -1 or +1.
+ *   CORRUPTED ROW.  real(c) = d_mask[r][c] != 0; keep(c) = real(c) && (!noise(c) || c begins its run).  The kept columns
+ *     are written in order from column 0 of d_out_ids[r], a run's first column as its sentinel, every other one as its
+ *     id; bos, separators and eos are real and never noise.  Whatever side the input is padded on, the output is compact:
+ *     pad_id fills the rest, d_out_mask is 1 on the written columns and 0 behind, d_in_lengths[r] is their count.
+ *   TARGET ROW.  For each run in order sentinel(k) and then the run's ids; then target_eos_id unless it is
+ *     HUTK_NO_TOKEN; ignore_index fills the rest.  An element at a position >= max_target_len is dropped;
+ *     d_tgt_lengths[r] is the count before that, eos included (a caller sees truncation as d_tgt_lengths[r] >
+ *     max_target_len), and min(count, 2^31 - 1): the count passes that only with max_len above 1.43e9.
+ *   DECODER INPUT.  With decoder_start_id other than HUTK_NO_TOKEN, d_decoder_ids of the target's shape:
+ *     [r][0] = decoder_start_id, [r][p + 1] = d_labels[r][p] for p + 1 < max_target_len, pad_id where that is
+ *     ignore_index.  Without, d_decoder_ids is not looked at and may be NULL.
+ * One wavefront per row walks it in chunks of 256 columns; with max_len a multiple of 4, d_input_ids 16-byte and d_mask
+ * 4-byte aligned a lane loads four columns at once.  The plan is trusted as little as in hutk_rows_mlm_device: what does
+ * not fit the row gives HUTK_E_ARG in *d_err (may be NULL) and the columns concerned are not eligible; nothing is read
+ * outside the rows and nothing is written outside the outputs.  Refused with HUTK_E_ARG before a device is looked for:
+ * width other than 4 or 8, max_len or max_target_len outside 1 .. 2^31 - 1, n_rows < 0, start_below outside 0 .. 2^32, a
+ * table that is empty, longer than 32, decreasing or not ending at 2^32, a step other than -1 and +1, n_sentinels < 0, a
+ * first or last sentinel, a pad_id or an ignore_index that does not fit width, sides with unknown bits or none, and with
+ * n_rows > 0 a NULL or misaligned buffer or an output that overlaps an input or another output (there is no in-place
+ * form).  n_rows == 0 writes nothing.  Asynchronous on hip_stream; never synchronises. */
+int hutk_rows_span_corrupt_device(const int64_t* d_plan, int64_t n_rows, int64_t max_len, const void* d_input_ids, int width,
+                                  const uint8_t* d_mask, uint64_t seed, int64_t start_below, const int64_t* len_below,
+                                  int n_len, int64_t sentinel_first, int sentinel_step, int64_t n_sentinels,
+                                  int32_t target_eos_id, int32_t decoder_start_id, int64_t pad_id, int64_t ignore_index,
+                                  int sides, int64_t max_target_len, void* d_out_ids, uint8_t* d_out_mask, void* d_labels,
+                                  void* d_decoder_ids, int32_t* d_in_lengths, int32_t* d_tgt_lengths, int32_t* d_err,
+                                  void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

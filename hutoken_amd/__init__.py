@@ -32,6 +32,12 @@ is the span corruption of T5-style encoder-decoder training: every noise span of
 closes up, and the spans move behind their sentinels into a target row, with the lengths of both and, on request, the
 decoder's input; `batch_encode_span_corruption` is the list form.  One wavefront per row scans and compacts it.
 
+Chat (not in the reference): `ChatTemplate` holds what surrounds the turns of a conversation (role headers, end-of-turn
+markers, bos/eos; presets `chatml()` and `llama3()`); `render_chat_device` turns the turns' contents, encoded as one
+document each, into one sequence per conversation -- a ragged pair that every collation above takes unchanged -- with
+loss labels on the assistant turns only, turn ids and source indices; `batch_encode_chat` is the list form
+(csrc/hutk_collate.hip).
+
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
 `encode_with_offsets` are the list forms (csrc/hutk_spans.hip).
@@ -70,7 +76,8 @@ __all__ = ["corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_l
            "set_byte_fallback", "encode_fallback", "batch_encode_fallback", "encode_fallback_packed_device",
            "decode_fallback", "batch_decode_fallback", "normalize_packed_device", "normalize",
            "pretokenize_packed_device", "pretokenize", "set_pretokenizer",
-           "collate_pairs", "collate_pair_windows", "batch_encode_pairs", "batch_encode_pair_windows"]
+           "collate_pairs", "collate_pair_windows", "batch_encode_pairs", "batch_encode_pair_windows",
+           "ChatTemplate", "render_chat_device", "batch_encode_chat"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -2342,3 +2349,274 @@ def batch_encode_span_corruption(texts, max_length=None, *, sentinel_first, seed
                          n_sentinels=n_sentinels, sentinel_step=sentinel_step, target_eos_id=target_eos_id,
                          decoder_start_id=decoder_start_id, max_target_length=max_target_length, pad_id=pad_id,
                          ignore_index=ignore_index, sides=sides, check=check)
+
+
+# ---- chat: multi-turn conversations --------------------------------------------------------------------------------
+_CHATML_ROLES = ("system", "user", "assistant", "tool")
+_LLAMA3_ROLES = ("system", "user", "assistant", "ipython")
+
+
+def _part_arg(what, ids):
+    """A prefix or suffix -> tuple of at most 32 int32 values, none of them the C ABI's "absent"."""
+    if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple)):
+        raise TypeError("%s must be a list or tuple of ints, not %s" % (what, type(ids).__name__))
+    ids = tuple(ids)
+    if len(ids) > _capi.CHAT_MAX_PART:
+        raise ValueError("%s holds %d ids; at most %d" % (what, len(ids), _capi.CHAT_MAX_PART))
+    return tuple(_token_arg("an id of %s" % what, v, False) for v in ids)
+
+
+class ChatTemplate:
+    """What surrounds the turns of a conversation (hutk_chat_template, include/hutoken_amd.h): `roles` maps a role's name
+    to (prefix_ids, suffix_ids) or (prefix_ids, suffix_ids, n_loss_suffix) -- at most 16 roles, numbered in the dict's
+    order, parts of at most 32 ids, n_loss_suffix the number of leading suffix ids that carry loss (default: all) --
+    and bos_id / eos_id open and close every conversation (None: absent).  The rendered conversation is
+        [bos]  prefix[role] content suffix[role]  (every turn)  [eos, or the prefix of add_generation_prompt's role]
+    The table goes to a device when it is first used there (render_chat_device, batch_encode_chat)."""
+
+    def __init__(self, roles, *, bos_id=None, eos_id=None):
+        if not isinstance(roles, dict):
+            raise TypeError("roles must be a dict {name: (prefix_ids, suffix_ids[, n_loss_suffix])}, not %s" % type(roles).__name__)
+        if not 1 <= len(roles) <= _capi.CHAT_MAX_ROLES:
+            raise ValueError("a template holds 1 .. %d roles, not %d" % (_capi.CHAT_MAX_ROLES, len(roles)))
+        self.role_names, self.parts, self.suffix_loss = [], [], []
+        for name, spec in roles.items():
+            if not isinstance(name, str):
+                raise TypeError("a role's name must be a str, not %s" % type(name).__name__)
+            if not isinstance(spec, (list, tuple)) or len(spec) not in (2, 3):
+                raise TypeError("role %r must map to (prefix_ids, suffix_ids) or (prefix_ids, suffix_ids, n_loss_suffix)" % (name,))
+            pre, suf = _part_arg("the prefix of role %r" % (name,), spec[0]), _part_arg("the suffix of role %r" % (name,), spec[1])
+            n_loss = len(suf) if len(spec) == 2 else spec[2]
+            if isinstance(n_loss, bool) or not isinstance(n_loss, int):
+                raise TypeError("n_loss_suffix of role %r must be an int, not %s" % (name, type(n_loss).__name__))
+            if not 0 <= n_loss <= len(suf):
+                raise ValueError("n_loss_suffix of role %r must be in 0 .. %d (its suffix), not %d" % (name, len(suf), n_loss))
+            self.role_names.append(name)
+            self.parts.append((pre, suf))
+            self.suffix_loss.append(n_loss)
+        self.bos_id, self.eos_id = bos_id, eos_id
+        self._bos, self._eos = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id)
+        self._handles = {}
+
+    def role_index(self, name):
+        """The number of role `name`; ValueError for one the template does not hold."""
+        if name not in self.role_names:
+            raise ValueError("unknown role %r: the template holds %s" % (name, ", ".join(repr(r) for r in self.role_names)))
+        return self.role_names.index(name)
+
+    def _handle(self, device_index):
+        h = self._handles.get(device_index)
+        if h is None:
+            h = self._handles[device_index] = _capi.ChatTemplate(self.parts, self.suffix_loss, self._bos, self._eos, device_index)
+        return h
+
+    def _loss_mask(self, loss_roles):
+        if isinstance(loss_roles, str):
+            loss_roles = (loss_roles,)
+        if not isinstance(loss_roles, (list, tuple, set, frozenset)):
+            raise TypeError("loss_roles must be a sequence of role names, not %s" % type(loss_roles).__name__)
+        bits = 0
+        for name in loss_roles:
+            bits |= 1 << self.role_index(name)
+        return bits
+
+    def _gen_role(self, add_generation_prompt):
+        if add_generation_prompt is None or add_generation_prompt is False:
+            return -1
+        if not isinstance(add_generation_prompt, str):
+            raise TypeError("add_generation_prompt must be a role's name or None, not %s" % type(add_generation_prompt).__name__)
+        r = self.role_index(add_generation_prompt)
+        if self.eos_id is not None:
+            raise ValueError("a template with an eos_id has no generation prompt: the conversation is closed")
+        return r
+
+    def close(self):
+        for h in self._handles.values():
+            h.close()
+        self._handles = {}
+
+    @classmethod
+    def from_strings(cls, roles, *, bos=None, eos=None):
+        """`roles` maps a name to (prefix, suffix) or (prefix, suffix, n_loss_suffix) as STRINGS, encoded with
+        encode_special on the initialised context -- the markers must have been installed by set_special_tokens;
+        bos / eos: a string that encodes to exactly one id, or None."""
+        if not isinstance(roles, dict):
+            raise TypeError("roles must be a dict {name: (prefix, suffix[, n_loss_suffix])}, not %s" % type(roles).__name__)
+        texts = []
+        for name, spec in roles.items():
+            if not isinstance(spec, (list, tuple)) or len(spec) not in (2, 3) or not all(isinstance(s, str) for s in spec[:2]):
+                raise TypeError("role %r must map to (prefix, suffix) or (prefix, suffix, n_loss_suffix) with two strings" % (name,))
+            texts += [spec[0], spec[1]]
+        for what, s in (("bos", bos), ("eos", eos)):
+            if s is not None and not isinstance(s, str):
+                raise TypeError("%s must be a str or None, not %s" % (what, type(s).__name__))
+        ends = [(what, s) for what, s in (("bos", bos), ("eos", eos)) if s is not None]
+        rows = batch_encode_special(texts + [s for _what, s in ends])
+        ids = {}
+        for (what, s), row in zip(ends, rows[len(texts):]):
+            if len(row) != 1:
+                raise ValueError("%s marker %r does not encode to exactly one id (set_special_tokens installs it): %r" % (what, s, row))
+            ids[what] = row[0]
+        made = {name: (rows[2 * k], rows[2 * k + 1]) + tuple(spec[2:]) for k, (name, spec) in enumerate(roles.items())}
+        return cls(made, bos_id=ids.get("bos"), eos_id=ids.get("eos"))
+
+    @staticmethod
+    def _markers(markers):
+        for m in markers:
+            row = encode_special(m)
+            if len(row) != 1:
+                raise ValueError("marker %r does not encode to exactly one id (set_special_tokens installs it): %r" % (m, row))
+
+    @classmethod
+    def chatml(cls, roles=_CHATML_ROLES):
+        """ChatML: every turn is <|im_start|>{role}\\n content <|im_end|>\\n, with loss on <|im_end|> but not on the
+        newline behind it; no bos, no eos.  Both markers must encode to one id each."""
+        cls._markers(("<|im_start|>", "<|im_end|>"))
+        return cls.from_strings({r: ("<|im_start|>%s\n" % r, "<|im_end|>\n", 1) for r in roles})
+
+    @classmethod
+    def llama3(cls, roles=_LLAMA3_ROLES):
+        """Llama 3: <|begin_of_text|>, then every turn is <|start_header_id|>{role}<|end_header_id|>\\n\\n content
+        <|eot_id|>; no eos.  The four markers must encode to one id each."""
+        cls._markers(("<|begin_of_text|>", "<|start_header_id|>", "<|end_header_id|>", "<|eot_id|>"))
+        return cls.from_strings({r: ("<|start_header_id|>%s<|end_header_id|>\n\n" % r, "<|eot_id|>") for r in roles},
+                                bos="<|begin_of_text|>")
+
+
+def render_chat_device(ids, offsets, conv_offsets, roles, template, *, loss_roles=("assistant",), add_generation_prompt=None,
+                       ignore_index=-100, n_ids=None, return_turn_ids=False, return_source=False, check=False):
+    """The turns of conversations, encoded as one document each (ids int32, offsets int64[n_turns + 1] of an
+    encode_*_packed_device call), with roles int32[n_turns] (template.role_index) and conv_offsets int64[n_conv + 1] into
+    the turns (from 0 to n_turns), all device tensors -> (out_ids int32[capacity], out_offsets int64[n_conv + 1],
+    labels int32[capacity][, turn_ids int32[capacity]][, source int64[capacity]]): one sequence per conversation,
+        [bos]  prefix[role] content suffix[role]  (every turn)  tail
+    with tail the prefix of role `add_generation_prompt`, or the template's eos.  (out_ids, out_offsets) is a ragged pair
+    like the encode's: collate_padded, collate_windows and SequencePacker.add take it unchanged.  labels holds the id on
+    the content and the loss-carrying suffix ids of the turns of `loss_roles` and ignore_index elsewhere; turn_ids the
+    turn's index inside its conversation (-1 on bos and tail); source the index into `ids` on content tokens (-1
+    elsewhere), which carries token_spans_device or token_word_ids_device of the turns over: values[source].  The
+    per-token arrays reach rows through gather_rows with the plan of the collate call.  Only the first out_offsets[-1]
+    elements are written.  On the current torch stream; synchronises only to read offsets[-1] (not with n_ids=) and for
+    check=True, which raises ValueError for a role outside the template, offsets that do not describe ids or
+    conv_offsets that do not describe the turns."""
+    if not isinstance(template, ChatTemplate):
+        raise TypeError("template must be a ChatTemplate, not %s" % type(template).__name__)
+    bits = template._loss_mask(loss_roles)
+    gen = template._gen_role(add_generation_prompt)
+    _ignore_arg(ignore_index, "int32")
+    for name, v in (("return_turn_ids", return_turn_ids), ("return_source", return_source)):
+        if not isinstance(v, bool):
+            raise TypeError("%s must be a bool, not %s" % (name, type(v).__name__))
+
+    def sizes():
+        if offsets.numel() < 1 or conv_offsets.numel() < 1:
+            raise ValueError("offsets and conv_offsets must hold at least one entry")
+        if roles.numel() != offsets.numel() - 1:
+            raise ValueError("roles must hold one entry per turn (%d), not %d" % (offsets.numel() - 1, roles.numel()))
+    _device_tensors((("ids", ids, "int32"), ("offsets", offsets, "int64"), ("conv_offsets", conv_offsets, "int64"),
+                     ("roles", roles, "int32")), sizes)
+    _on_one_gpu("the render", (("ids", ids), ("offsets", offsets), ("conv_offsets", conv_offsets), ("roles", roles)))
+    if n_ids is not None:
+        if isinstance(n_ids, bool) or not isinstance(n_ids, int):
+            raise TypeError("n_ids must be an int or None")
+        if n_ids < 0 or n_ids > ids.numel():
+            raise ValueError("n_ids must be in 0 .. ids.numel()")
+    import torch
+    dev = ids.device
+    n_turns, n_conv = offsets.numel() - 1, conv_offsets.numel() - 1
+    n_ids = _n_ids(ids, offsets, n_ids)
+    h = template._handle(dev.index)
+    cap = h.ids_bound(n_conv, n_turns, n_ids, gen)
+    turn_offsets = torch.empty(n_turns + 1, dtype=torch.int64, device=dev)
+    out_offsets = torch.empty(n_conv + 1, dtype=torch.int64, device=dev)
+    out_ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    labels = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    turn_ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if return_turn_ids else None
+    source = torch.empty(max(cap, 1), dtype=torch.int64, device=dev) if return_source else None
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        h.offsets_device(offsets.data_ptr(), roles.data_ptr(), conv_offsets.data_ptr(), n_conv, n_turns, n_ids, gen,
+                         turn_offsets.data_ptr(), out_offsets.data_ptr(), err[0:].data_ptr(), stream)
+        h.render_device(ids.data_ptr(), offsets.data_ptr(), roles.data_ptr(), conv_offsets.data_ptr(), turn_offsets.data_ptr(),
+                        out_offsets.data_ptr(), n_conv, n_turns, n_ids, gen, bits, ignore_index, cap, out_ids.data_ptr(),
+                        labels.data_ptr(), 0 if turn_ids is None else turn_ids.data_ptr(),
+                        0 if source is None else source.data_ptr(), err[1:].data_ptr(), stream)
+    if check:
+        code = int(err.max().item())
+        if code:
+            raise ValueError("hutoken_amd: render_chat_device: device-side error %d (a role outside the template, offsets that do "
+                             "not describe ids, or conv_offsets that do not describe the turns)" % code)
+    res = (out_ids, out_offsets, labels)
+    if return_turn_ids:
+        res += (turn_ids,)
+    if return_source:
+        res += (source,)
+    return res
+
+
+def _chat_turns(conversations, template):
+    """list of conversations -> (contents, role numbers, conv_offsets) as lists; a turn is {"role", "content"} or
+    (role, content)."""
+    if not isinstance(template, ChatTemplate):
+        raise TypeError("template must be a ChatTemplate, not %s" % type(template).__name__)
+    if not isinstance(conversations, list):
+        raise TypeError("conversations must be a list of conversations (lists of turns), not %s" % type(conversations).__name__)
+    contents, roles, conv = [], [], [0]
+    for c in conversations:
+        if not isinstance(c, (list, tuple)):
+            raise TypeError("a conversation must be a list of turns, not %s" % type(c).__name__)
+        for turn in c:
+            if isinstance(turn, dict):
+                if "role" not in turn or "content" not in turn:
+                    raise TypeError("a turn must hold 'role' and 'content'")
+                role, content = turn["role"], turn["content"]
+            elif isinstance(turn, (list, tuple)) and len(turn) == 2:
+                role, content = turn
+            else:
+                raise TypeError("a turn must be a dict {'role', 'content'} or a (role, content) pair, not %s" % type(turn).__name__)
+            if not isinstance(content, str):
+                raise TypeError("a turn's content must be a str, not %s" % type(content).__name__)
+            roles.append(template.role_index(role))
+            contents.append(content)
+        conv.append(len(contents))
+    return contents, roles, conv
+
+
+def batch_encode_chat(conversations, max_length=None, *, template, loss_roles=("assistant",), add_generation_prompt=None,
+                      normalize=None, special=False, byte_fallback=False, truncation="right", padding_side="right", pad_id=0,
+                      dtype=None, ignore_index=-100, return_plan=False):
+    """A list of conversations -- each a list of {"role", "content"} dicts or (role, content) pairs -> (input_ids
+    [n_conv, L], attention_mask, lengths, labels [n_conv, L] of input_ids' dtype[, row_plan]): a supervised fine-tuning
+    batch with loss on the turns of `loss_roles` only.  A composition of existing calls on the initialised context's GPU:
+    ONE encode call over all contents, render_chat_device with `template`, collate_padded without bos and eos (the render
+    wrote them) and its plan, gather_rows of the labels with fill=ignore_index.  The contents are encoded plainly, so
+    that a marker's string inside a user's text does NOT become a control id; special=True encodes them with
+    encode_special, byte_fallback=True with the byte-fallback table.  add_generation_prompt="assistant" ends every row's
+    sequence with that role's prefix (for inference; no loss there).  An unknown role raises ValueError; normalize: as
+    batch_encode_padded; max_length, truncation, padding_side, pad_id, dtype: as collate_padded, whose truncation cuts
+    the rendered sequence as a whole."""
+    contents, roles, conv = _chat_turns(conversations, template)
+    template._loss_mask(loss_roles)  # (both raise before anything is encoded)
+    template._gen_role(add_generation_prompt)
+    _out_width(dtype)
+    _ignore_arg(ignore_index, "int32")
+    for name, v in (("special", special), ("byte_fallback", byte_fallback)):
+        if not isinstance(v, bool):
+            raise TypeError("%s must be a bool, not %s" % (name, type(v).__name__))
+    if byte_fallback:
+        ids, oo = _fallback_texts_to_device(contents, special, normalize)
+    elif special:
+        ids, oo = _special_texts_to_device(contents, normalize)
+    else:
+        ids, oo = _texts_to_device(contents, normalize=normalize)
+    import torch
+    dev = ids.device
+    d_roles = torch.tensor(roles, dtype=torch.int32, device=dev)
+    d_conv = torch.tensor(conv, dtype=torch.int64, device=dev)
+    out_ids, out_offsets, labels = render_chat_device(ids, oo, d_conv, d_roles, template, loss_roles=loss_roles,
+                                                      add_generation_prompt=add_generation_prompt, ignore_index=ignore_index)
+    input_ids, mask, lengths, plan = collate_padded(out_ids, out_offsets, max_length, pad_id=pad_id, truncation=truncation,
+                                                    padding_side=padding_side, dtype=dtype, return_plan=True)
+    row_labels = gather_rows(plan, input_ids.shape[1], labels, fill=ignore_index).to(input_ids.dtype)
+    return (input_ids, mask, lengths, row_labels, plan) if return_plan else (input_ids, mask, lengths, row_labels)

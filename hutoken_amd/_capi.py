@@ -126,6 +126,13 @@ SIGNATURES = {
     "hutk_rows_labels_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
     "hutk_rows_span_corrupt_device": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, C.c_uint64, _i64, _vp, _i32, _i64, _i32, _i64,
                                              _s32, _s32, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_chat_template_create": (_i32, [_pvp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _s32, _s32]),
+    "hutk_chat_template_destroy": (None, [_vp]),
+    "hutk_chat_ids_bound": (_i64, [_vp, _i64, _i64, _i64, _i32]),
+    "hutk_chat_offsets_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hutk_chat_render_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _u32, _s32, _i64,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_debug_chat_span": (_i32, []),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -138,6 +145,7 @@ FB_SPECIAL, FB_SKIP_SPECIAL = 1, 2  # HUTK_FB_*
 NFC, NFD, NFKC, NFKD = 0, 1, 2, 3  # HUTK_NFC ..
 MLM_SIDE_A, MLM_SIDE_B = 1, 2  # HUTK_MLM_SIDE_*
 LABELS_A, LABELS_B, LABELS_TEMPLATE, LABELS_END, LABELS_SHIFT = 1, 2, 4, 8, 16  # HUTK_LABELS_*
+CHAT_MAX_ROLES, CHAT_MAX_PART = 16, 32  # HUTK_CHAT_MAX_*
 
 _lib = None
 
@@ -882,6 +890,61 @@ class Packer(_Owner):
         raise_for(load().hutk_packer_flush_device(self._h, d_input_ids or None, d_position_ids or None,
                                                   d_segment_ids or None, C.byref(n), stream or None))
         return n.value
+
+
+def _i32_array(values):
+    """ints -> a ctypes int32 array the call may read (never of length 0); the C ABI checks the values."""
+    values = tuple(values)
+    return (_s32 * max(1, len(values)))(*values)
+
+
+class ChatTemplate(_Owner):
+    """Owns one hutk_chat_template (include/hutoken_amd.h): parts = [(prefix ids, suffix ids)] per role, suffix_loss a
+    list of ints or None, bos_id / eos_id NO_TOKEN when absent.  The ids must fit an int32 (the caller's check)."""
+    _destroy = "hutk_chat_template_destroy"
+
+    def __init__(self, parts, suffix_loss=None, bos_id=NO_TOKEN, eos_id=NO_TOKEN, device=-1, n_roles=None):
+        parts = [(tuple(p), tuple(s)) for p, s in parts]
+        pre, suf, po, so = [], [], [0], [0]
+        for p, s in parts:
+            pre += p
+            suf += s
+            po.append(len(pre))
+            so.append(len(suf))
+        h = C.c_void_p()
+        raise_for(load().hutk_chat_template_create(C.byref(h), int(device), len(parts) if n_roles is None else n_roles,
+                                                   _i32_array(pre), _i32_array(po), _i32_array(suf), _i32_array(so),
+                                                   None if suffix_loss is None else _i32_array(suffix_loss),
+                                                   int(bos_id), int(eos_id)))
+        self._h = h
+
+    def ids_bound(self, n_conv, n_turns, n_ids, gen_role=-1):
+        """hutk_chat_ids_bound (host only): an upper bound of the ids a render of these sizes writes."""
+        n = load().hutk_chat_ids_bound(self._h, n_conv, n_turns, n_ids, gen_role)
+        if n < 0:
+            raise_for(-n)
+        return n
+
+    def offsets_device(self, d_offsets, d_roles, d_conv_offsets, n_conv, n_turns, n_ids, gen_role, d_turn_offsets,
+                       d_out_offsets, d_err=0, stream=0):
+        """hutk_chat_offsets_device on raw device pointers (ints); asynchronous on `stream`."""
+        raise_for(load().hutk_chat_offsets_device(self._h, d_offsets or None, d_roles or None, d_conv_offsets or None, n_conv,
+                                                  n_turns, n_ids, gen_role, d_turn_offsets or None, d_out_offsets or None,
+                                                  d_err or None, stream or None))
+
+    def render_device(self, d_ids, d_offsets, d_roles, d_conv_offsets, d_turn_offsets, d_out_offsets, n_conv, n_turns, n_ids,
+                      gen_role, loss_roles, ignore_index, out_cap, d_out_ids, d_labels, d_turn_ids=0, d_src=0, d_err=0,
+                      stream=0):
+        """hutk_chat_render_device on raw device pointers (ints); asynchronous on `stream`."""
+        raise_for(load().hutk_chat_render_device(self._h, d_ids or None, d_offsets or None, d_roles or None,
+                                                 d_conv_offsets or None, d_turn_offsets or None, d_out_offsets or None,
+                                                 n_conv, n_turns, n_ids, gen_role, loss_roles, ignore_index, out_cap,
+                                                 d_out_ids or None, d_labels or None, d_turn_ids or None, d_src or None,
+                                                 d_err or None, stream or None))
+
+
+def chat_span():
+    return load().hutk_debug_chat_span()
 
 
 NORMALIZER_INFO = ["format_version", "unidata", "blob_bytes", "chunk_bytes", "pairs", "decomposition_words", "lead_bytes",

@@ -20,7 +20,10 @@
 // (k_rows_answers); and the last stage before a training batch: the masked-LM corruption of
 // rows with its labels (k_rows_mlm, drawing from hutk_philox.h), the loss labels of rows (k_rows_labels), and the span
 // corruption of rows into corrupted rows and target rows, a wavefront scanning and compacting its row
-// (k_rows_span_corrupt).
+// (k_rows_span_corrupt).  In front of the layouts stands the chat render:
+// the turns of conversations, one encoded document each, become one sequence per conversation with role headers,
+// end-of-turn markers, loss labels, turn ids and source indices -- a ragged pair again, which every layout above takes
+// (ChatTurns through the rows scan, k_chat_offsets, k_chat_render: the packed layout's shape).
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets.  A workgroup of the row layouts stages the plan of its rows in LDS
@@ -519,6 +522,295 @@ __device__ __forceinline__ int32_t staged_item_of_row(const int64_t* s_ro, int32
         else hi = mid;
     }
     return lo;
+}
+
+// ---- chat ---------------------------------------------------------------------------------------------------------
+// A render step between encode and collation (include/hutoken_amd.h): the turns of n_conv
+// conversations, one encoded document each, become one sequence per conversation,
+//     [bos]  prefix[role_t] content_t suffix[role_t]  (every turn t of the conversation)  tail
+// with the loss labels, the turn index and the source index of every token.  T, the exclusive scan of the turns' rendered
+// lengths, is one more instantiation of the rows scan (ChatTurns); the sequences' offsets follow from it in closed form,
+// out_offsets[i] = T[conv[i]] + i * fixed with fixed = [bos] + |tail| (k_chat_offsets).  So turn t of conversation i
+// begins at output position T[t] + i * fixed + [bos], and the fill has the packed layout's shape: a workgroup owns
+// CHAT_SPAN output positions, one wavefront finds the span's first conversation on out_offsets and then, among that
+// conversation's turns, the span's first turn on T; the starts of the sequences and of the turns inside the span are
+// marked in LDS (empty ones mark nothing, so that several at one place cannot collide) and one workgroup scan turns the
+// marks into "conversation of this position" and "turn of this position".
+constexpr int CHAT_SPAN = 2048;           // output positions per workgroup (8 per thread in the scan, 4 in the stores)
+constexpr int CHAT_PER = CHAT_SPAN / TB;
+
+// The template as the kernels read it: in global memory behind a handle, staged into LDS by every workgroup of the fill
+// (a kernel-argument array indexed at run time would live in scratch).  Words of 4 bytes throughout.
+struct ChatTable {
+    int32_t n_roles, bos, eos, max_part;  // bos / eos: HUTK_NO_TOKEN = absent; max_part: the largest |prefix| + |suffix|
+    int32_t plen[HUTK_CHAT_MAX_ROLES], slen[HUTK_CHAT_MAX_ROLES], sloss[HUTK_CHAT_MAX_ROLES];
+    int32_t prefix[HUTK_CHAT_MAX_ROLES][HUTK_CHAT_MAX_PART], suffix[HUTK_CHAT_MAX_ROLES][HUTK_CHAT_MAX_PART];
+};
+constexpr int CHAT_TABLE_WORDS = (int)(sizeof(ChatTable) / sizeof(int32_t));
+
+// "rendered length of turn t" for the rows scan.  A role outside the template or a length that cannot be is reported and
+// counts as 0: the turn is left out.
+struct ChatTurns {
+    const ChatTable* tab;
+    const int64_t* offs;
+    const int32_t* roles;
+    int64_t n_turns, n_ids;
+    __device__ int64_t operator()(int64_t t, int32_t* err) const {
+        if (t == 0 && (offs[0] != 0 || offs[n_turns] != n_ids)) note_error(err, HUTK_E_ARG);
+        const int32_t r = roles[t];
+        const int64_t n = offs[t + 1] - offs[t];
+        if (r < 0 || r >= tab->n_roles || n < 0 || n > n_ids) {
+            note_error(err, HUTK_E_ARG);
+            return 0;
+        }
+        return tab->plen[r] + n + tab->slen[r];
+    }
+};
+
+__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+struct ChatOffArgs {
+    const int64_t* conv;  // [n_conv + 1] into the turns
+    const int64_t* T;     // [n_turns + 1]
+    int64_t n_conv, n_turns, fixed;
+    int64_t* oo;          // [n_conv + 1]
+    int32_t* err;
+};
+
+// One thread per entry of out_offsets.  conv must rise from 0 to n_turns; an entry that does not is reported and read
+// as the nearest turn there is.
+__global__ __launch_bounds__(TB) void k_chat_offsets(const ChatOffArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i > a.n_conv) return;
+    const int64_t c = a.conv[i];
+    if (c < 0 || c > a.n_turns || (i == 0 && c != 0) || (i == a.n_conv && c != a.n_turns) || (i < a.n_conv && a.conv[i + 1] < c))
+        note_error(a.err, HUTK_E_ARG);
+    a.oo[i] = a.T[clamp_i64(c, 0, a.n_turns)] + i * a.fixed;
+}
+
+struct ChatArgs {
+    const ChatTable* tab;
+    const int32_t* ids;
+    const int64_t* offs;   // [n_turns + 1] into ids
+    const int32_t* roles;  // [n_turns]
+    const int64_t* conv;   // [n_conv + 1] into the turns
+    const int64_t* T;      // [n_turns + 1]: turn_offsets
+    const int64_t* oo;     // [n_conv + 1]: out_offsets
+    int64_t n_conv, n_turns, n_ids, out_cap;
+    int32_t gen_role, has_bos, tail_len, fixed;
+    uint32_t loss_roles;
+    int32_t ignore;
+    int32_t *out_ids, *labels, *turn_ids;  // turn_ids: may be NULL
+    int64_t* src;                          // may be NULL
+    int32_t* err;
+    int32_t wide;  // bit 0 out_ids, 1 labels, 2 turn_ids, 3 src: the pointer is 16-byte aligned
+};
+
+// up to four neighbouring elements at element index `at` (a multiple of 4): one 16-byte store where the array allows
+__device__ __forceinline__ void chat_store(int32_t* base, bool wide, int64_t at, int cnt, const int32_t (&v)[4]) {
+    if (wide && cnt == 4) *reinterpret_cast<int4*>(base + at) = make_int4(v[0], v[1], v[2], v[3]);
+    else
+        for (int e = 0; e < cnt; e++) base[at + e] = v[e];
+}
+__device__ __forceinline__ void chat_store(int64_t* base, bool wide, int64_t at, int cnt, const int64_t (&v)[4]) {
+    if (wide && cnt == 4) {
+        longlong2* p = reinterpret_cast<longlong2*>(base + at);
+        p[0] = make_longlong2(v[0], v[1]);
+        p[1] = make_longlong2(v[2], v[3]);
+    } else
+        for (int e = 0; e < cnt; e++) base[at + e] = v[e];
+}
+
+// Nothing is trusted: every index into conv, T, offs, roles, ids and the table is checked before it is used, the marks
+// lie inside the span by construction, and a position is written only below min(n_out, out_cap).  What does not fit is
+// reported with HUTK_E_ARG and leaves id 0, ignore_index, -1, -1 at its place.
+__global__ __launch_bounds__(TB) void k_chat_render(const ChatArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t s_t[CHAT_SPAN];  // marks (turn - t0 at its start), then their running maximum
+    __shared__ __attribute__((aligned(16))) int32_t s_c[CHAT_SPAN];  // the same for the conversations (conversation - i0)
+    __shared__ ChatTable s_tab;
+    __shared__ int32_t s_wt[TB / 64], s_wc[TB / 64];
+    __shared__ int64_t s_first[2];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (a.offs[0] != 0 || a.offs[a.n_turns] != a.n_ids) {  // nothing is read through offsets that do not fit the ids
+        if (blockIdx.x == 0 && tid == 0) note_error(a.err, HUTK_E_ARG);
+        return;
+    }
+    const int64_t n_out = a.oo[a.n_conv];
+    if (blockIdx.x == 0 && tid == 0) {
+        if (a.oo[0] != 0 || a.T[0] != 0 || n_out != a.T[a.n_turns] + a.n_conv * (int64_t)a.fixed) note_error(a.err, HUTK_E_ARG);
+        if (n_out > a.out_cap) note_error(a.err, HUTK_E_CAPACITY);
+    }
+    const int64_t x0 = (int64_t)blockIdx.x * CHAT_SPAN;
+    int64_t x1 = x0 + CHAT_SPAN;
+    if (x1 > n_out) x1 = n_out;
+    if (x1 > a.out_cap) x1 = a.out_cap;
+    if (x0 >= x1) return;
+    const int32_t n = (int32_t)(x1 - x0);
+
+    for (int i = tid; i < CHAT_TABLE_WORDS; i += TB) reinterpret_cast<int32_t*>(&s_tab)[i] = reinterpret_cast<const int32_t*>(a.tab)[i];
+    for (int i = tid; i < CHAT_SPAN; i += TB) s_t[i] = 0, s_c[i] = 0;
+    // The last conversation that begins at or before the span's start -- of several at one place (empty ones, without
+    // bos and tail) the last, the one the position belongs to -- and then the last of ITS turns that begins at or before
+    // it (the turn before its first when none does: the span starts on its bos).  The second search needs the first
+    // one's answer, so one wavefront does both.
+    if (tid < 64) {
+        int64_t i0 = hutk::wave_count_leading(a.n_conv, [&](int64_t i) { return a.oo[i] <= x0; }) - 1;
+        if (i0 < 0) i0 = 0;  // (out_offsets[0] != 0: reported above)
+        const int64_t c0 = clamp_i64(a.conv[i0], 0, a.n_turns), c1 = clamp_i64(a.conv[i0 + 1], c0, a.n_turns);
+        const int64_t y = x0 - i0 * a.fixed - a.has_bos;
+        const int64_t k = hutk::wave_count_leading(c1 - c0, [&](int64_t k) { return a.T[c0 + k] <= y; });
+        if (tid == 0) s_first[0] = i0, s_first[1] = c0 + k - 1;
+    }
+    __syncthreads();
+    const int64_t i0 = s_first[0], t0 = s_first[1];
+
+    // The starts inside the span: a wavefront per conversation, its lanes over the conversation's turns.  Empty turns
+    // and empty sequences mark nothing.
+    for (int64_t i = i0 + w; i < a.n_conv; i += TB / 64) {
+        const int64_t o = a.oo[i];
+        if (i > i0 && o >= x1) break;
+        const int64_t c0 = clamp_i64(a.conv[i], 0, a.n_turns), c1 = clamp_i64(a.conv[i + 1], c0, a.n_turns);
+        if (i > i0 && o > x0 && lane == 0 && a.oo[i + 1] > o) s_c[o - x0] = (int32_t)(i - i0);
+        const int64_t shift = i * a.fixed + a.has_bos;
+        for (int64_t t = (i == i0 ? t0 + 1 : c0) + lane; t < c1; t += 64) {
+            const int64_t Tt = a.T[t], S = Tt + shift;
+            if (S >= x1) break;
+            if (S > x0 && a.T[t + 1] > Tt) s_t[S - x0] = (int32_t)(t - t0);
+        }
+    }
+    __syncthreads();
+
+    // workgroup scan over the marks: the running maximum of both (they grow along the span)
+    {
+        int32_t dt[CHAT_PER], dc[CHAT_PER];
+        const int4 tl = *reinterpret_cast<const int4*>(&s_t[tid * CHAT_PER]), th = *reinterpret_cast<const int4*>(&s_t[tid * CHAT_PER + 4]);
+        const int4 cl = *reinterpret_cast<const int4*>(&s_c[tid * CHAT_PER]), ch = *reinterpret_cast<const int4*>(&s_c[tid * CHAT_PER + 4]);
+        dt[0] = tl.x; dt[1] = tl.y; dt[2] = tl.z; dt[3] = tl.w; dt[4] = th.x; dt[5] = th.y; dt[6] = th.z; dt[7] = th.w;
+        dc[0] = cl.x; dc[1] = cl.y; dc[2] = cl.z; dc[3] = cl.w; dc[4] = ch.x; dc[5] = ch.y; dc[6] = ch.z; dc[7] = ch.w;
+        int32_t mt = 0, mc = 0;
+#pragma unroll
+        for (int e = 0; e < CHAT_PER; e++) {
+            mt = dt[e] > mt ? dt[e] : mt;
+            mc = dc[e] > mc ? dc[e] : mc;
+            dt[e] = mt;
+            dc[e] = mc;
+        }
+        const int32_t tt = hutk::wave_incl_max(mt, lane), tc = hutk::wave_incl_max(mc, lane);
+        if (lane == 63) s_wt[w] = tt, s_wc[w] = tc;
+        int32_t et = __shfl_up(tt, 1), ec = __shfl_up(tc, 1);
+        if (lane == 0) et = 0, ec = 0;
+        __syncthreads();
+        for (int u = 0; u < w; u++) {
+            et = s_wt[u] > et ? s_wt[u] : et;
+            ec = s_wc[u] > ec ? s_wc[u] : ec;
+        }
+#pragma unroll
+        for (int e = 0; e < CHAT_PER; e++) {
+            dt[e] = dt[e] > et ? dt[e] : et;
+            dc[e] = dc[e] > ec ? dc[e] : ec;
+        }
+        *reinterpret_cast<int4*>(&s_t[tid * CHAT_PER]) = make_int4(dt[0], dt[1], dt[2], dt[3]);
+        *reinterpret_cast<int4*>(&s_t[tid * CHAT_PER + 4]) = make_int4(dt[4], dt[5], dt[6], dt[7]);
+        *reinterpret_cast<int4*>(&s_c[tid * CHAT_PER]) = make_int4(dc[0], dc[1], dc[2], dc[3]);
+        *reinterpret_cast<int4*>(&s_c[tid * CHAT_PER + 4]) = make_int4(dc[4], dc[5], dc[6], dc[7]);
+    }
+    __syncthreads();
+
+    // The elements, four neighbours per thread and consecutive threads on consecutive groups.  A thread reads what it
+    // needs of a conversation (five words) and of a turn (five words) when it meets another one, which among four
+    // neighbours is rare; a position is then a few comparisons against them and at most one id.
+    const int32_t n_roles = s_tab.n_roles;
+    for (int32_t p = tid * 4; p < n; p += TB * 4) {
+        int32_t vi[4], vl[4], vt[4];
+        int64_t vs[4];
+        int64_t ci = -1, ct = -2;           // the conversation and the turn held in registers
+        int64_t o = 0, c0 = 0, c1 = 0, A = 0, R = 0;            // conversation: its start, its turns, T at its first turn, its turns' length
+        int64_t ts = 0, tlen = 0, off0 = 0, nt = 0;             // turn: its start behind A, its rendered length, its ids
+        int32_t role = -1, pl = 0, sl = 0, sloss = 0;
+        bool loss = false;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            vi[e] = 0;
+            vl[e] = a.ignore;
+            vt[e] = -1;
+            vs[e] = -1;
+            if (p + e >= n) continue;
+            const int64_t x = x0 + p + e;
+            const int64_t i = i0 + s_c[p + e];
+            if (i != ci) {
+                ci = i;
+                o = a.oo[i];
+                c0 = clamp_i64(a.conv[i], 0, a.n_turns);
+                c1 = clamp_i64(a.conv[i + 1], c0, a.n_turns);
+                A = a.T[c0];
+                R = a.T[c1] - A;
+            }
+            const int64_t q = x - o;
+            if (q < 0) {
+                note_error(a.err, HUTK_E_ARG);
+                continue;
+            }
+            if (a.has_bos && q == 0) {
+                vi[e] = s_tab.bos;
+                continue;
+            }
+            const int64_t yy = q - a.has_bos;  // behind the bos: the turns, then the tail
+            if (yy >= R) {
+                const int64_t k = yy - R;
+                if (k < a.tail_len) vi[e] = a.gen_role >= 0 ? s_tab.prefix[a.gen_role][k] : s_tab.eos;
+                else note_error(a.err, HUTK_E_ARG);
+                continue;
+            }
+            const int64_t t = t0 + s_t[p + e];
+            if (t < c0 || t >= c1) {
+                note_error(a.err, HUTK_E_ARG);
+                continue;
+            }
+            if (t != ct) {
+                ct = t;
+                const int64_t Tt = a.T[t];
+                ts = Tt - A;
+                tlen = a.T[t + 1] - Tt;
+                off0 = a.offs[t];
+                nt = a.offs[t + 1] - off0;
+                role = a.roles[t];
+                if (role < 0 || role >= n_roles) role = -1;
+                else {
+                    pl = s_tab.plen[role];
+                    sl = s_tab.slen[role];
+                    sloss = s_tab.sloss[role];
+                    loss = (a.loss_roles >> role) & 1u;
+                }
+            }
+            const int64_t u = yy - ts;  // inside the turn: prefix, content, suffix
+            if (role < 0 || u < 0 || u >= tlen) {
+                note_error(a.err, HUTK_E_ARG);
+                continue;
+            }
+            vt[e] = (int32_t)(t - c0);
+            if (u < pl) vi[e] = s_tab.prefix[role][u];
+            else if (u - pl < nt) {
+                const int64_t idx = off0 + u - pl;
+                if (idx >= 0 && idx < a.n_ids) {
+                    vi[e] = a.ids[idx];
+                    vs[e] = idx;
+                    if (loss) vl[e] = vi[e];
+                } else note_error(a.err, HUTK_E_ARG);
+            } else {
+                const int64_t v = u - pl - nt;
+                if (v >= 0 && v < sl) {
+                    vi[e] = s_tab.suffix[role][v];
+                    if (loss && v < sloss) vl[e] = vi[e];
+                } else note_error(a.err, HUTK_E_ARG);
+            }
+        }
+        const int64_t at = x0 + p;
+        const int cnt = n - p < 4 ? n - p : 4;
+        chat_store(a.out_ids, a.wide & 1, at, cnt, vi);
+        chat_store(a.labels, a.wide & 2, at, cnt, vl);
+        if (a.turn_ids) chat_store(a.turn_ids, a.wide & 4, at, cnt, vt);
+        if (a.src) chat_store(a.src, a.wide & 8, at, cnt, vs);
+    }
 }
 
 // ---- windows ------------------------------------------------------------------------------------------------------
@@ -1602,6 +1894,31 @@ bool overlap(const void* p, int64_t np, const void* q, int64_t nq) {
 
 }  // namespace
 
+struct hutk_chat_template {
+    int device = 0;
+    ChatTable h = {};        // the table on the host, for the sizes
+    ChatTable* d = nullptr;  // and on the device: written once, read-only afterwards
+};
+
+namespace {
+
+// What the three chat calls refuse alike before anything else.  fixed = [bos] + |tail| and the tail's length come back.
+int chat_sizes(const char* who, const hutk_chat_template* t, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role,
+               int64_t* fixed, int32_t* tail_len) {
+    if (!t) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": the template is NULL");
+    if (n_conv < 0 || n_turns < 0 || n_ids < 0 || n_conv > INT32_MAX - 1 || n_turns > INT32_MAX - 1)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": counts must not be negative, n_conv and n_turns below 2^31 - 1");
+    if (gen_role < -1 || gen_role >= t->h.n_roles)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": gen_role must be -1 or a role of the template");
+    if (gen_role >= 0 && t->h.eos != HUTK_NO_TOKEN)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a generation prompt and an eos exclude each other");
+    *tail_len = gen_role >= 0 ? t->h.plen[gen_role] : t->h.eos != HUTK_NO_TOKEN;
+    *fixed = (t->h.bos != HUTK_NO_TOKEN) + *tail_len;
+    return HUTK_OK;
+}
+
+}  // namespace
+
 struct hutk_packer {
     int device = 0;
     int64_t L = 0;
@@ -2312,5 +2629,173 @@ void hutk_packer_destroy(hutk_packer* p) {
     if (p->carry) (void)hipFree(p->carry);
     delete p;
 }
+
+int hutk_chat_template_create(hutk_chat_template** out, int device, int n_roles, const int32_t* prefix_ids,
+                              const int32_t* prefix_offsets, const int32_t* suffix_ids, const int32_t* suffix_offsets,
+                              const int32_t* suffix_loss, int32_t bos_id, int32_t eos_id) {
+    const char* who = "hutk_chat_template_create";
+    if (!out) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": out is NULL");
+    *out = nullptr;
+    if (n_roles < 1 || n_roles > HUTK_CHAT_MAX_ROLES || !prefix_offsets || !suffix_offsets)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": n_roles must be in 1 .. 16 and the offsets given");
+    ChatTable h = {};
+    h.n_roles = n_roles;
+    h.bos = bos_id;
+    h.eos = eos_id;
+    for (int side = 0; side < 2; side++) {
+        const int32_t* offs = side ? suffix_offsets : prefix_offsets;
+        const int32_t* ids = side ? suffix_ids : prefix_ids;
+        if (offs[0] != 0) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": the parts' offsets must be a scan from 0");
+        for (int r = 0; r < n_roles; r++) {
+            const int64_t len = (int64_t)offs[r + 1] - offs[r];
+            if (len < 0 || len > HUTK_CHAT_MAX_PART)
+                return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a part holds 0 .. 32 ids, and the offsets must not decrease");
+            if (len > 0 && !ids) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a part's ids are NULL");
+            (side ? h.slen : h.plen)[r] = (int32_t)len;
+            for (int k = 0; k < len; k++) {
+                const int32_t id = ids[offs[r] + k];
+                if (id == HUTK_NO_TOKEN) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a part must not hold HUTK_NO_TOKEN");
+                (side ? h.suffix : h.prefix)[r][k] = id;
+            }
+        }
+    }
+    for (int r = 0; r < n_roles; r++) {
+        h.sloss[r] = suffix_loss ? suffix_loss[r] : h.slen[r];
+        if (h.sloss[r] < 0 || h.sloss[r] > h.slen[r])
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": suffix_loss must be in 0 .. the suffix's length");
+        if (h.plen[r] + h.slen[r] > h.max_part) h.max_part = h.plen[r] + h.slen[r];
+    }
+    if (device == -2) {  // the table on the host only, as a context's: the sizes, and the checks of the two device calls
+        hutk_chat_template* t = new hutk_chat_template();
+        t->device = -2;
+        t->h = h;
+        *out = t;
+        return HUTK_OK;
+    }
+    int n = 0;
+    if (int rc = device_present(who, &n)) return rc;
+    if (device < 0) HUTK_HIP_TRY(hipGetDevice(&device));
+    if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, std::string(who) + ": no such device");
+    HUTK_HIP_TRY(hipSetDevice(device));
+    hutk_chat_template* t = new hutk_chat_template();
+    t->device = device;
+    t->h = h;
+    hipError_t e = hipMalloc((void**)&t->d, sizeof(ChatTable));
+    if (e == hipSuccess) e = hipMemcpy(t->d, &t->h, sizeof(ChatTable), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hutk_chat_template_destroy(t);
+        return hutk::api_set_error(e == hipErrorOutOfMemory ? HUTK_E_MEMORY : HUTK_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    *out = t;
+    return HUTK_OK;
+}
+
+void hutk_chat_template_destroy(hutk_chat_template* t) {
+    if (!t) return;
+    if (t->d) {
+        (void)hipSetDevice(t->device);
+        (void)hipDeviceSynchronize();  // nothing is freed under a running kernel
+        (void)hipFree(t->d);
+    }
+    delete t;
+}
+
+int64_t hutk_chat_ids_bound(const hutk_chat_template* t, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role) {
+    int64_t fixed;
+    int32_t tail_len;
+    if (chat_sizes("hutk_chat_ids_bound", t, n_conv, n_turns, n_ids, gen_role, &fixed, &tail_len)) return -HUTK_E_ARG;
+    return n_ids + n_turns * t->h.max_part + n_conv * fixed;
+}
+
+int hutk_chat_offsets_device(const hutk_chat_template* t, const int64_t* d_offsets, const int32_t* d_roles,
+                             const int64_t* d_conv_offsets, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role,
+                             int64_t* d_turn_offsets, int64_t* d_out_offsets, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_chat_offsets_device";
+    int64_t fixed;
+    int32_t tail_len;
+    if (int rc = chat_sizes(who, t, n_conv, n_turns, n_ids, gen_role, &fixed, &tail_len)) return rc;
+    if (!d_out_offsets || (n_conv > 0 && (!d_offsets || !d_conv_offsets || !d_turn_offsets || (n_turns > 0 && !d_roles))))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(d_out_offsets, 8) || !aligned_to(d_offsets, 8) || !aligned_to(d_conv_offsets, 8) || !aligned_to(d_turn_offsets, 8) ||
+        !aligned_to(d_roles, 4) || !aligned_to(d_err, 4))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+    if (int rc = device_present(who)) return rc;
+    if (!t->d) return hutk::api_set_error(HUTK_E_DEVICE, std::string(who) + ": host-only template: no device to render on");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HUTK_HIP_TRY(hipSetDevice(t->device));
+    if (n_conv == 0) {
+        if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+        HUTK_HIP_TRY(hipMemsetAsync(d_out_offsets, 0, sizeof(int64_t), st));
+        if (d_turn_offsets) HUTK_HIP_TRY(hipMemsetAsync(d_turn_offsets, 0, sizeof(int64_t), st));
+        return HUTK_OK;
+    }
+    const ChatTurns turns{t->d, d_offsets, d_roles, n_turns, n_ids};
+    if (int rc = rows_scan(turns, n_turns, d_turn_offsets, d_err, st)) return rc;
+    const ChatOffArgs a{d_conv_offsets, d_turn_offsets, n_conv, n_turns, fixed, d_out_offsets, d_err};
+    hipLaunchKernelGGL(k_chat_offsets, dim3((unsigned)((n_conv + 1 + TB - 1) / TB)), dim3(TB), 0, st, a);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_chat_render_device(const hutk_chat_template* t, const int32_t* d_ids, const int64_t* d_offsets,
+                            const int32_t* d_roles, const int64_t* d_conv_offsets, const int64_t* d_turn_offsets,
+                            const int64_t* d_out_offsets, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role,
+                            uint32_t loss_roles, int32_t ignore_index, int64_t out_cap, int32_t* d_out_ids,
+                            int32_t* d_labels, int32_t* d_turn_ids, int64_t* d_src, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_chat_render_device";
+    int64_t fixed;
+    int32_t tail_len;
+    if (int rc = chat_sizes(who, t, n_conv, n_turns, n_ids, gen_role, &fixed, &tail_len)) return rc;
+    if (out_cap < 0 || (t->h.n_roles < 32 && (loss_roles >> t->h.n_roles) != 0))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": out_cap must not be negative and loss_roles name roles of the template");
+    if (n_conv > 0 && (!d_offsets || !d_conv_offsets || !d_turn_offsets || !d_out_offsets || (n_turns > 0 && !d_roles) ||
+                       (n_ids > 0 && !d_ids) || (out_cap > 0 && (!d_out_ids || !d_labels))))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(d_offsets, 8) || !aligned_to(d_conv_offsets, 8) || !aligned_to(d_turn_offsets, 8) || !aligned_to(d_out_offsets, 8) ||
+        !aligned_to(d_src, 8) || !aligned_to(d_ids, 4) || !aligned_to(d_roles, 4) || !aligned_to(d_out_ids, 4) ||
+        !aligned_to(d_labels, 4) || !aligned_to(d_turn_ids, 4) || !aligned_to(d_err, 4))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+    if (int rc = device_present(who)) return rc;
+    if (!t->d) return hutk::api_set_error(HUTK_E_DEVICE, std::string(who) + ": host-only template: no device to render on");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HUTK_HIP_TRY(hipSetDevice(t->device));
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_conv == 0) return HUTK_OK;
+    // n_out is on the device only: as many workgroups as the capacity holds spans (one that finds its span behind n_out
+    // returns at once), at least the one that reports a capacity of nothing
+    int64_t blocks = (out_cap + CHAT_SPAN - 1) / CHAT_SPAN;
+    if (blocks < 1) blocks = 1;
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, std::string(who) + ": the batch is too large for one launch");
+    ChatArgs a = {};
+    a.tab = t->d;
+    a.ids = d_ids;
+    a.offs = d_offsets;
+    a.roles = d_roles;
+    a.conv = d_conv_offsets;
+    a.T = d_turn_offsets;
+    a.oo = d_out_offsets;
+    a.n_conv = n_conv;
+    a.n_turns = n_turns;
+    a.n_ids = n_ids;
+    a.out_cap = out_cap;
+    a.gen_role = gen_role;
+    a.has_bos = t->h.bos != HUTK_NO_TOKEN;
+    a.tail_len = tail_len;
+    a.fixed = (int32_t)fixed;
+    a.loss_roles = loss_roles;
+    a.ignore = ignore_index;
+    a.out_ids = d_out_ids;
+    a.labels = d_labels;
+    a.turn_ids = d_turn_ids;
+    a.src = d_src;
+    a.err = d_err;
+    a.wide = (aligned_to(d_out_ids, 16) ? 1 : 0) | (aligned_to(d_labels, 16) ? 2 : 0) | (aligned_to(d_turn_ids, 16) ? 4 : 0) |
+             (aligned_to(d_src, 16) ? 8 : 0);
+    hipLaunchKernelGGL(k_chat_render, dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_debug_chat_span(void) { return CHAT_SPAN; }
 
 }  // extern "C"

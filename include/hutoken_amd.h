@@ -452,6 +452,70 @@ int hutk_collate_pairs_device(const int32_t* d_ids_a, const int64_t* d_offsets_a
                               int flags, int out_width, void* d_input_ids, uint8_t* d_mask, uint8_t* d_token_types,
                               int32_t* d_lengths, int64_t* d_row_map, int32_t* d_err, void* hip_stream);
 
+/* ---- chat: multi-turn conversations with assistant-only labels -----------------------------------------------
+ * A render step between encode and collation.  The turns' contents are encoded as one document each by one encode
+ * call; the render makes of them one sequence per conversation, a new ragged pair (d_out_ids, d_out_offsets) that
+ * every layout above takes unchanged, plus per-token arrays ragged along the same offsets.  Inputs, on one device:
+ *   d_ids int32, d_offsets int64[n_turns + 1]    the encode call's pair (offsets[0] == 0, offsets[n_turns] == n_ids)
+ *   d_roles int32[n_turns]                       the role of every turn, 0 .. n_roles - 1
+ *   d_conv_offsets int64[n_conv + 1]             into the turns: [0] == 0, non-decreasing, [n_conv] == n_turns
+ * A TEMPLATE holds for each role r < n_roles <= HUTK_CHAT_MAX_ROLES a prefix and a suffix of 0 .. HUTK_CHAT_MAX_PART ids
+ * each, suffix_loss[r] <= |suffix_r| (NULL: all of it), the number of leading suffix ids that carry loss, and bos_id /
+ * eos_id (HUTK_NO_TOKEN = absent).  The sequence of conversation i with the turns t = co[i] .. co[i + 1] - 1 is
+ *     [bos]  prefix[role_t] content_t suffix[role_t]  (for every t, in order)  tail
+ * where tail is prefix[gen_role] with a generation prompt (gen_role >= 0), otherwise [eos]; asking for both is
+ * HUTK_E_ARG.  A conversation without turns is [bos] tail.  With len(t) = |prefix| + n_t + |suffix| and T the exclusive
+ * scan of len over all turns:
+ *   d_turn_offsets int64[n_turns + 1] = T
+ *   d_out_offsets[i] = T[co[i]] + i * fixed, fixed = [bos] + |tail|; n_out = d_out_offsets[n_conv]
+ *   d_out_ids int32[n_out]     the sequences
+ *   d_labels int32[n_out]      the id on the content and on the first suffix_loss[r] suffix ids of every turn whose
+ *                              role's bit is set in loss_roles; ignore_index everywhere else: prefixes, the other
+ *                              roles, bos, the generation prompt, eos
+ *   d_turn_ids int32[n_out]    (may be NULL) the turn's index inside its conversation on the tokens of its prefix,
+ *                              content and suffix, -1 on bos and tail
+ *   d_src int64[n_out]         (may be NULL) the index into d_ids on content tokens, -1 elsewhere: what carries any
+ *                              per-token array of the encode call (spans, word ids) over to the rendered stream
+ *   the template    create copies the parts (HOST arrays: ids of all roles end to end, offsets int32[n_roles + 1]) into
+ *                   a small table on `device` (-1: the current one), read-only afterwards: calls on one handle need
+ *                   no serialisation among themselves.  destroy waits for the device first.  device == -2 keeps the
+ *                   table on the host only, as a context's: the bound and every check below work, the two device calls
+ *                   then end with HUTK_E_DEVICE.
+ *   the ids bound   host only: n_ids + n_turns * max_r(|prefix_r| + |suffix_r|) + n_conv * fixed, at least n_out for any
+ *                   roles; -HUTK_E_ARG for sizes the other calls refuse.
+ *   the offsets call  writes d_turn_offsets (the rows scan of the windows: count, scan, write, sharing its per-device
+ *                   buffer and its rule) and d_out_offsets (one launch).  *d_err receives HUTK_E_ARG for a role outside
+ *                   [0, n_roles) or a turn length below 0 or above n_ids -- the turn then counts as rendered length 0,
+ *                   it is left out and everything else is as stated -- and for d_offsets whose ends are not 0 and n_ids
+ *                   or d_conv_offsets that do not rise from 0 to n_turns.  n_conv == 0 writes d_out_offsets[0] = 0.
+ *   the render call writes the four per-token arrays.  *d_err receives HUTK_E_ARG for the above and for turn or out
+ *                   offsets that are not what the offsets call writes; the outputs are then undefined, but nothing is
+ *                   read outside the inputs or written outside out_cap elements (every index is range-checked).
+ *                   n_out > out_cap: HUTK_E_CAPACITY in *d_err, and nothing is written at or behind out_cap.
+ * All calls are asynchronous on hip_stream and never synchronise; *d_err (may be NULL) is cleared by each call.
+ * Refused with HUTK_E_ARG before a device is looked for: n_roles outside 1 .. 16, a part longer than 32 ids or holding
+ * HUTK_NO_TOKEN, part offsets that are not a scan from 0, suffix_loss[r] outside its suffix, a NULL template, gen_role
+ * outside -1 .. n_roles - 1, gen_role >= 0 with an eos, loss_roles bits at or above n_roles, negative counts (n_conv
+ * and n_turns: below 2^31 - 1), and with work to do (n_conv > 0) a NULL required buffer or one not aligned to its
+ * element type.  16-byte alignment of an output gets it 16-byte stores. */
+#define HUTK_CHAT_MAX_ROLES 16
+#define HUTK_CHAT_MAX_PART 32
+typedef struct hutk_chat_template hutk_chat_template;
+int hutk_chat_template_create(hutk_chat_template** out, int device, int n_roles, const int32_t* prefix_ids,
+                              const int32_t* prefix_offsets, const int32_t* suffix_ids, const int32_t* suffix_offsets,
+                              const int32_t* suffix_loss, int32_t bos_id, int32_t eos_id);
+void hutk_chat_template_destroy(hutk_chat_template* t);
+int64_t hutk_chat_ids_bound(const hutk_chat_template* t, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role);
+int hutk_chat_offsets_device(const hutk_chat_template* t, const int64_t* d_offsets, const int32_t* d_roles,
+                             const int64_t* d_conv_offsets, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role,
+                             int64_t* d_turn_offsets, int64_t* d_out_offsets, int32_t* d_err, void* hip_stream);
+int hutk_chat_render_device(const hutk_chat_template* t, const int32_t* d_ids, const int64_t* d_offsets,
+                            const int32_t* d_roles, const int64_t* d_conv_offsets, const int64_t* d_turn_offsets,
+                            const int64_t* d_out_offsets, int64_t n_conv, int64_t n_turns, int64_t n_ids, int gen_role,
+                            uint32_t loss_roles, int32_t ignore_index, int64_t out_cap, int32_t* d_out_ids,
+                            int32_t* d_labels, int32_t* d_turn_ids, int64_t* d_src, int32_t* d_err, void* hip_stream);
+int hutk_debug_chat_span(void);
+
 /* ---- token spans (offset mapping) ----------------------------------------------------------------------
  * Which stretch of its document each id covers: from the packed text (d_bytes, d_offsets) and the ragged pair that
  * hutk_encode_batch_device wrote for it (d_ids, d_id_offsets; n_ids as in the collation calls: d_id_offsets[n_docs] ==

@@ -67,7 +67,7 @@ from . import _capi
 from . import pretokenize as _presplit_tables  # (the module; the package's name `pretokenize` is the function below)
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 
-__all__ = ["corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -1121,6 +1121,44 @@ def batch_encode_pair_windows(texts_a, texts_b, max_length, stride=0, *, normali
                                text, return_offsets_mapping, offsets_unit, return_word_ids)
 
 
+_PACKER_ROWS = ("input_ids", "position_ids", "segment_ids")
+
+
+def _channel_specs(channels):
+    """SequencePacker(channels=...): {name: (dtype, fill[, per])} -> [(name, dtype name, width, per, fill)], in the
+    mapping's order.  Checked without a device."""
+    if channels is None:
+        return []
+    if not isinstance(channels, dict):
+        raise TypeError("channels must be a dict of name -> (dtype, fill[, per]), not %s" % type(channels).__name__)
+    if len(channels) > _capi.PACKER_MAX_CHANNELS:
+        raise ValueError("a packer carries at most %d channels, not %d" % (_capi.PACKER_MAX_CHANNELS, len(channels)))
+    specs = []
+    for name, spec in channels.items():
+        if not isinstance(name, str) or not name:
+            raise TypeError("a channel's name must be a non-empty str, not %r" % (name,))
+        if name in _PACKER_ROWS:
+            raise ValueError("a channel cannot be named %r: that is one of the packer's own outputs" % name)
+        if not isinstance(spec, (tuple, list)) or len(spec) not in (2, 3):
+            raise TypeError("channel %r must be given as (dtype, fill) or (dtype, fill, per)" % name)
+        try:
+            width, dname = _out_width(spec[0])
+        except ValueError:
+            raise ValueError("channel %r: dtype must be torch.int32 or torch.int64, not %r" % (name, spec[0])) from None
+        if spec[0] is None:
+            raise ValueError("channel %r: dtype must be torch.int32 or torch.int64, not None" % name)
+        fill, per = spec[1], spec[2] if len(spec) == 3 else 1
+        if isinstance(fill, bool) or not isinstance(fill, int):
+            raise TypeError("channel %r: fill must be an int, not %s" % (name, type(fill).__name__))
+        bits = 31 if dname == "int32" else 63
+        if not -2**bits <= fill < 2**bits:
+            raise ValueError("channel %r: fill must fit %s" % (name, dname))
+        if isinstance(per, bool) or per not in (1, 2):
+            raise ValueError("channel %r: per (the elements of a record) must be 1 or 2, not %r" % (name, per))
+        specs.append((name, dname, width, per, fill))
+    return specs
+
+
 class SequencePacker:
     """Packs documents into rows of `seq_len` tokens for pretraining (hutk_packer_*, include/hutoken_amd.h).
 
@@ -1129,17 +1167,27 @@ class SequencePacker:
         input_ids [rows, seq_len] (dtype), position_ids int32 (0 at every document start and row start),
         segment_ids int32 (1, 2, 3 .. per row, for masking attention at document boundaries)
     and keeps the unfinished row on the device for the next call; flush() returns it padded with pad_id (position 0,
-    segment 0) and empties the stream.  The rows do not depend on how the documents are split over add() calls."""
+    segment 0) and empties the stream.  The rows do not depend on how the documents are split over add() calls.
 
-    def __init__(self, seq_len, *, eos_id=None, bos_id=None, pad_id=0, dtype=None, device=None):
+    channels={"labels": ("int64", -100), "spans": ("int32", 0, 2)}: name -> (dtype, fill[, per]), at most four.  A
+    channel is a per-token array along the ids' offsets (labels and turn ids of render_chat_device, token spans, word
+    ids) that the packer moves with the ids, carry included: add(..., channels={name: tensor}) then returns one more
+    [rows, seq_len] tensor per channel ([rows, seq_len, 2] with per == 2) holding the token's value, and `fill` where
+    the packer put bos, eos or padding."""
+
+    _channels = ()  # (name, dtype name, width, per, fill) of each channel
+
+    def __init__(self, seq_len, *, eos_id=None, bos_id=None, pad_id=0, dtype=None, device=None, channels=None):
         bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
         self.seq_len = _length_arg("seq_len", seq_len, 1)
         self._width, self._dname = _out_width(dtype)
+        self._channels = _channel_specs(channels)
         if device is not None and (isinstance(device, bool) or not isinstance(device, int)):
             device = getattr(device, "index", device)  # a torch.device
             if device is not None and not isinstance(device, int):
                 raise TypeError("device must be an int, a torch.device or None")
-        self._p = _capi.Packer(self.seq_len, bos, eos, pad, self._width, _default_device(device))
+        self._p = _capi.Packer(self.seq_len, bos, eos, pad, self._width, _default_device(device),
+                               channels=[(width, per, fill) for _n, _d, width, per, fill in self._channels])
         self._device = None
 
     @property
@@ -1150,25 +1198,66 @@ class SequencePacker:
     def _rows(self, n, dev):
         import torch
         shape = (n, self.seq_len)
-        return {"input_ids": torch.empty(shape, dtype=getattr(torch, self._dname), device=dev),
-                "position_ids": torch.empty(shape, dtype=torch.int32, device=dev),
-                "segment_ids": torch.empty(shape, dtype=torch.int32, device=dev)}
+        out = {"input_ids": torch.empty(shape, dtype=getattr(torch, self._dname), device=dev),
+               "position_ids": torch.empty(shape, dtype=torch.int32, device=dev),
+               "segment_ids": torch.empty(shape, dtype=torch.int32, device=dev)}
+        for name, dname, _width, per, _fill in self._channels:
+            out[name] = torch.empty(shape + ((2,) if per == 2 else ()), dtype=getattr(torch, dname), device=dev)
+        return out
 
-    def add(self, ids, offsets, n_ids=None, check=False):
-        """Device tensors of encode_packed_device -> the complete rows (possibly zero), on the current torch stream."""
+    def _channel_args(self, n_ids, channels):
+        """add(channels=...): exactly the declared names, each a contiguous tensor of the declared dtype, [m] or [m, 2]
+        by the declared record, with m >= n_ids (when n_ids is given) -> the tensors in the declared order.  No device
+        is needed for any of it."""
+        given = {} if channels is None else channels
+        if not isinstance(given, dict):
+            raise TypeError("channels must be a dict of name -> tensor, not %s" % type(given).__name__)
+        names = [c[0] for c in self._channels]
+        missing, extra = [n for n in names if n not in given], [n for n in given if n not in names]
+        if missing or extra:
+            raise ValueError("add() needs exactly the packer's channels %r: missing %r, not declared %r" % (names, missing, extra))
+        for name, dname, _width, per, _fill in self._channels:
+            t = given[name]
+            if not _is_tensor(t):
+                raise TypeError("channel %r must be a torch tensor, not %s" % (name, type(t).__name__))
+            if _dtype_name(t) != dname:
+                raise TypeError("channel %r must have dtype %s, not %s" % (name, dname, t.dtype))
+            if not ((t.dim() == 1 and per == 1) or (t.dim() == 2 and per == 2 and t.shape[1] == 2)) or not t.is_contiguous():
+                raise ValueError("channel %r must be contiguous and of shape %s" % (name, "[m, 2]" if per == 2 else "[m]"))
+            if isinstance(n_ids, int) and t.shape[0] < n_ids:
+                raise ValueError("channel %r holds %d records, fewer than n_ids = %d" % (name, t.shape[0], n_ids))
+        return [given[n] for n in names]
+
+    def add(self, ids, offsets, n_ids=None, check=False, channels=None):
+        """Device tensors of encode_packed_device -> the complete rows (possibly zero), on the current torch stream.
+        channels: name -> tensor for every channel the packer was made with (see the class); only the first n_ids
+        records of each are read."""
+        vals = self._channel_args(n_ids, channels)
         _ragged_args(ids, offsets, n_ids)
+        for (name, *_rest), t in zip(self._channels, vals):
+            if not t.is_cuda or t.device != ids.device:
+                raise ValueError("channel %r must be on the device of ids" % name)
         import torch
         dev = ids.device
         n_docs = offsets.numel() - 1
         n_ids = _n_ids(ids, offsets, n_ids)
+        for (name, *_rest), t in zip(self._channels, vals):
+            if t.shape[0] < n_ids:
+                raise ValueError("channel %r holds %d records, fewer than n_ids = %d" % (name, t.shape[0], n_ids))
         n = self._p.rows(n_docs, n_ids)
         out = self._rows(n, dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         self._device = dev
+        stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            got = self._p.add(ids.data_ptr(), offsets.data_ptr(), n_docs, n_ids, out["input_ids"].data_ptr(),
-                              out["position_ids"].data_ptr(), out["segment_ids"].data_ptr(), n, err.data_ptr(),
-                              torch.cuda.current_stream(dev).cuda_stream)
+            if self._channels:
+                got = self._p.add_channels(ids.data_ptr(), offsets.data_ptr(), n_docs, n_ids, [t.data_ptr() for t in vals],
+                                           out["input_ids"].data_ptr(), out["position_ids"].data_ptr(),
+                                           out["segment_ids"].data_ptr(), [out[c[0]].data_ptr() for c in self._channels],
+                                           n, err.data_ptr(), stream)
+            else:
+                got = self._p.add(ids.data_ptr(), offsets.data_ptr(), n_docs, n_ids, out["input_ids"].data_ptr(),
+                                  out["position_ids"].data_ptr(), out["segment_ids"].data_ptr(), n, err.data_ptr(), stream)
         assert got == n
         if check:
             _raise_device_error(err, "SequencePacker.add")
@@ -1176,7 +1265,10 @@ class SequencePacker:
 
     def add_texts(self, texts, normalize=None):
         """A list of str: encoded with the initialised context (encode_packed_device), then add().  normalize: as
-        batch_encode_padded."""
+        batch_encode_padded.  A packer with channels refuses: texts carry none."""
+        if self._channels:
+            raise ValueError("add_texts: the packer has channels %r and texts carry none; encode, build the channels and "
+                             "call add()" % [c[0] for c in self._channels])
         ids, oo = _texts_to_device(texts, normalize=normalize)
         return self.add(ids, oo)
 
@@ -1187,9 +1279,14 @@ class SequencePacker:
         dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
         out = self._rows(n, dev)
         if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
             with torch.cuda.device(dev):
-                self._p.flush(out["input_ids"].data_ptr(), out["position_ids"].data_ptr(),
-                              out["segment_ids"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                if self._channels:
+                    self._p.flush_channels(out["input_ids"].data_ptr(), out["position_ids"].data_ptr(),
+                                           out["segment_ids"].data_ptr(), [out[c[0]].data_ptr() for c in self._channels], stream)
+                else:
+                    self._p.flush(out["input_ids"].data_ptr(), out["position_ids"].data_ptr(),
+                                  out["segment_ids"].data_ptr(), stream)
         return out
 
     def close(self):
@@ -2138,6 +2235,85 @@ def lm_labels(input_ids, attention_mask, row_plan, *, loss_on="all", shift=False
     if check and int(err.item()):
         raise ValueError("hutoken_amd: lm_labels: a row_plan that points outside its row (device-side error %d)"
                          % int(err.item()))
+    return labels
+
+
+def _segments_arg(segment_ids):
+    """segment_ids of packed rows: int32 [n_rows, L] with L >= 1, contiguous."""
+    if not _is_tensor(segment_ids):
+        raise TypeError("segment_ids must be a torch tensor, not %s" % type(segment_ids).__name__)
+    if _dtype_name(segment_ids) != "int32":
+        raise TypeError("segment_ids must have dtype int32, not %s" % segment_ids.dtype)
+    if segment_ids.dim() != 2 or segment_ids.shape[1] < 1 or not segment_ids.is_contiguous():
+        raise ValueError("segment_ids must be contiguous and of shape [n_rows, L] with L >= 1")
+
+
+def packed_cu_seqlens(segment_ids, *, cap=None, check=False):
+    """cu_seqlens for varlen attention from the segment_ids of packed rows (SequencePacker.add, .flush, or both
+    concatenated), one stream compaction in HIP: segment_ids int32 [n_rows, L] -> (cu_seqlens int32 [cap + 1],
+    info int32 [2] = (n_seq, max_seqlen), both on the device).  Flat element r * L + c starts a sequence when c == 0 or
+    its segment differs from the one before it in the row, so the sequences are the pieces of documents in each row and
+    a padding run is one of its own (its labels are ignore_index).  cu_seqlens holds the rising starts and then
+    n_rows * L in every remaining slot: the surplus sequences have length zero.  With a given `cap` the call never
+    synchronises; cap below n_seq writes the first cap starts, info[0] still holds
+    the true count, and check=True raises ValueError naming both.  cap=None reads the count once -- the one
+    synchronisation -- and returns cu_seqlens of exactly n_seq + 1 entries.  On the current torch stream."""
+    _segments_arg(segment_ids)
+    if cap is not None:
+        if isinstance(cap, bool) or not isinstance(cap, int):
+            raise TypeError("cap must be an int or None, not %s" % type(cap).__name__)
+        if cap < 0 or cap >= _INT32_MAX:
+            raise ValueError("cap must be in 0 .. 2**31 - 2")
+    n_rows, L = segment_ids.shape
+    if n_rows * L > _INT32_MAX:
+        raise ValueError("segment_ids must hold fewer than 2**31 elements: cu_seqlens is int32")
+    if not segment_ids.is_cuda:
+        raise ValueError("segment_ids must be on the GPU: packed_cu_seqlens runs there and nowhere else")
+    import torch
+    dev = segment_ids.device
+    room = n_rows * L if cap is None else cap  # (no more sequences than elements)
+    cu = torch.empty(room + 1, dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.packed_cu_seqlens_device(segment_ids.data_ptr(), n_rows, L, room, cu.data_ptr(), info.data_ptr(),
+                                       err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return cu, info
+    _on_torch_stream(dev, call, used=(segment_ids, err))
+    if cap is None:
+        return cu[:int(info[0].item()) + 1], info
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: packed_cu_seqlens: cap = %d is below the %d sequences of the rows" % (cap, int(info[0].item())))
+    return cu, info
+
+
+def packed_lm_labels(values, segment_ids, *, shift=False, ignore_index=-100):
+    """The loss labels of packed rows, one HIP pass: values [n_rows, L] int32 or int64 -- the rows' input_ids for plain
+    causal LM, or a packed `labels` channel (SequencePacker(channels=...)) where everything off the assistant's turns is
+    ignore_index already -- and the rows' segment_ids -> labels of values' shape and dtype.  shift=False: the value on
+    every real column (segment != 0), ignore_index on padding.  shift=True: what column c predicts, values[r][c + 1], when
+    column c + 1 is in the row and of the same, real segment; ignore_index otherwise, so that no column predicts across
+    a document boundary, a row end or into padding -- lm_labels(shift=True) for the packed layout.  On the current torch
+    stream, never synchronises."""
+    dname, width = _rows_arg("values", values)
+    _segments_arg(segment_ids)
+    if tuple(segment_ids.shape) != tuple(values.shape):
+        raise ValueError("segment_ids must be of the shape of values")
+    if not isinstance(shift, bool):
+        raise TypeError("shift must be a bool, not %s" % type(shift).__name__)
+    _ignore_arg(ignore_index, dname)
+    _on_one_gpu("the labelling", (("values", values), ("segment_ids", segment_ids)))
+    import torch
+    dev = values.device
+    n_rows, L = values.shape
+    labels = torch.empty_like(values)
+
+    def call():
+        _capi.packed_labels_device(values.data_ptr(), width, segment_ids.data_ptr(), n_rows, L, shift, ignore_index,
+                                   labels.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return labels
+    _on_torch_stream(dev, call, used=(values, segment_ids))
     return labels
 
 

@@ -74,6 +74,13 @@ SIGNATURES = {
     "hutk_packer_flush_device": (_i32, [_vp, _vp, _vp, _vp, _pi64, _vp]),
     "hutk_packer_pending": (_i64, [_vp]),
     "hutk_packer_destroy": (None, [_vp]),
+    "hutk_packer_create_channels": (_i32, [_pvp, _i64, _s32, _s32, _s32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "hutk_packer_channel_count": (_i32, [_vp]),
+    "hutk_packer_add_channels_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _vp, _vp]),
+    "hutk_packer_flush_channels_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64, _vp]),
+    "hutk_packed_cu_seqlens_device": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_packed_labels_device": (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp]),
+    "hutk_debug_cu_tile": (_i32, []),
     "hutk_token_spans_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "hutk_token_spans": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "hutk_debug_span_tile_ids": (_i32, []),
@@ -146,6 +153,7 @@ NFC, NFD, NFKC, NFKD = 0, 1, 2, 3  # HUTK_NFC ..
 MLM_SIDE_A, MLM_SIDE_B = 1, 2  # HUTK_MLM_SIDE_*
 LABELS_A, LABELS_B, LABELS_TEMPLATE, LABELS_END, LABELS_SHIFT = 1, 2, 4, 8, 16  # HUTK_LABELS_*
 CHAT_MAX_ROLES, CHAT_MAX_PART = 16, 32  # HUTK_CHAT_MAX_*
+PACKER_MAX_CHANNELS = 4  # HUTK_PACKER_MAX_CHANNELS
 
 _lib = None
 
@@ -861,11 +869,44 @@ class Packer(_Owner):
     """Owns one hutk_packer (include/hutoken_amd.h): raw device pointers (ints) in, rows written asynchronously."""
     _destroy = "hutk_packer_destroy"
 
-    def __init__(self, seq_len, bos_id=NO_TOKEN, eos_id=NO_TOKEN, pad_id=0, out_width=4, device=-1):
+    def __init__(self, seq_len, bos_id=NO_TOKEN, eos_id=NO_TOKEN, pad_id=0, out_width=4, device=-1, channels=()):
+        """channels: (width, per, fill) of each per-token array the packer moves with the ids (hutk_packer_create_channels;
+        the C ABI checks them)."""
         h = C.c_void_p()
-        raise_for(load().hutk_packer_create(C.byref(h), int(seq_len), int(bos_id), int(eos_id), int(pad_id),
-                                            int(out_width), int(device)))
+        channels = [tuple(c) for c in channels]
+        if channels:
+            n = len(channels)
+            raise_for(load().hutk_packer_create_channels(
+                C.byref(h), int(seq_len), int(bos_id), int(eos_id), int(pad_id), int(out_width), int(device), n,
+                (C.c_int * n)(*(c[0] for c in channels)), (C.c_int * n)(*(c[1] for c in channels)),
+                (_i64 * n)(*(c[2] for c in channels))))
+        else:
+            raise_for(load().hutk_packer_create(C.byref(h), int(seq_len), int(bos_id), int(eos_id), int(pad_id),
+                                                int(out_width), int(device)))
         self._h = h
+
+    @property
+    def channel_count(self):
+        return load().hutk_packer_channel_count(self._h)
+
+    def add_channels(self, d_ids, d_offsets, n_docs, n_ids, d_values, d_input_ids, d_position_ids, d_segment_ids,
+                     d_channel_rows, rows_cap, d_err=0, stream=0):
+        """hutk_packer_add_channels_device: d_values / d_channel_rows are sequences of device pointers (ints), one per
+        channel -> the number of rows written."""
+        n = C.c_int64(0)
+        raise_for(load().hutk_packer_add_channels_device(self._h, d_ids or None, d_offsets or None, n_docs, n_ids,
+                                                         _pointer_array(d_values), d_input_ids or None, d_position_ids or None,
+                                                         d_segment_ids or None, _pointer_array(d_channel_rows), rows_cap,
+                                                         C.byref(n), d_err or None, stream or None))
+        return n.value
+
+    def flush_channels(self, d_input_ids, d_position_ids, d_segment_ids, d_channel_rows, stream=0):
+        """hutk_packer_flush_channels_device -> 0 or 1 rows written."""
+        n = C.c_int64(0)
+        raise_for(load().hutk_packer_flush_channels_device(self._h, d_input_ids or None, d_position_ids or None,
+                                                           d_segment_ids or None, _pointer_array(d_channel_rows), C.byref(n),
+                                                           stream or None))
+        return n.value
 
     def rows(self, n_docs, n_ids):
         """Rows the next add() with these sizes writes."""
@@ -890,6 +931,28 @@ class Packer(_Owner):
         raise_for(load().hutk_packer_flush_device(self._h, d_input_ids or None, d_position_ids or None,
                                                   d_segment_ids or None, C.byref(n), stream or None))
         return n.value
+
+
+def _pointer_array(pointers):
+    """device pointers (ints; 0: NULL) -> a host array of them the call may read, or NULL for an empty sequence"""
+    pointers = tuple(pointers)
+    return (_vp * len(pointers))(*(p or None for p in pointers)) if pointers else None
+
+
+def packed_cu_seqlens_device(d_segment_ids, n_rows, seq_len, cap, d_cu_seqlens, d_info, d_err=0, stream=0):
+    """hutk_packed_cu_seqlens_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_packed_cu_seqlens_device(d_segment_ids or None, n_rows, seq_len, cap, d_cu_seqlens or None,
+                                                   d_info or None, d_err or None, stream or None))
+
+
+def packed_labels_device(d_values, width, d_segment_ids, n_rows, seq_len, shift, ignore_index, d_labels, stream=0):
+    """hutk_packed_labels_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_packed_labels_device(d_values or None, width, d_segment_ids or None, n_rows, seq_len,
+                                               1 if shift else 0, ignore_index, d_labels or None, stream or None))
+
+
+def cu_tile():
+    return load().hutk_debug_cu_tile()
 
 
 def _i32_array(values):

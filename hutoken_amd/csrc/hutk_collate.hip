@@ -23,7 +23,11 @@
 // (k_rows_span_corrupt).  In front of the layouts stands the chat render:
 // the turns of conversations, one encoded document each, become one sequence per conversation with role headers,
 // end-of-turn markers, loss labels, turn ids and source indices -- a ragged pair again, which every layout above takes
-// (ChatTurns through the rows scan, k_chat_offsets, k_chat_render: the packed layout's shape).
+// (ChatTurns through the rows scan, k_chat_offsets, k_chat_render: the packed layout's shape).  Behind the packed layout
+// stand the packed rows for training: per-token channels that the packer moves along with the ids
+// (k_collate_packed_ch, k_collate_flush_ch: siblings that share the packed kernels' body), cu_seqlens from the segment
+// ids (CuStarts through the rows count and scan, k_cu_write, k_cu_gaps) and the loss labels of packed rows
+// (k_packed_labels).
 //
 // All are one pass: every id is read once, every output element is written once, with 16-byte stores where the row
 // length allows.  No element searches the offsets.  A workgroup of the row layouts stages the plan of its rows in LDS
@@ -248,8 +252,119 @@ __device__ __forceinline__ int64_t last_doc_le(const PackArgs& a, int64_t x) {
     return hutk::wave_count_leading(a.n_docs, [&](int64_t j) { return a.P + a.offs[j] + j * a.s <= x; }) - 1;
 }
 
-template <int W, bool VEC>
-__global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
+// A channel: a per-token array that lies along the offsets like the ids, records of 1 or 2 elements of 4 or 8 bytes, so
+// 1, 2 or 4 dwords (include/hutoken_amd.h, PACKED CHANNELS).  The kernels move records as dwords
+// and know the element width only for the alignment of a read from the caller's array; the packer's own carry is
+// aligned to the record.
+struct PackChan {
+    const void* values;  // [n_ids] records, read at the index the id is read at
+    void* rows;          // [rows][L] records
+    const void* c_car;   // the carry this call consumes (P records)
+    void* n_car;         // the carry it leaves
+    int32_t f0, f1, f2, f3;  // the fill record (no array: PackArgs' note)
+    int32_t words;       // dwords per record: 1, 2, 4
+    int32_t w8;          // elements of 8 bytes (words 2: one of them; words 4: two)
+};
+struct PackChans {
+    int32_t n;
+    PackChan c[HUTK_PACKER_MAX_CHANNELS];
+};
+
+// A record in registers is an int4 of which the first WORDS components count.  Record i of a caller's array (aligned
+// to its elements only) and of the packer's carry (aligned to the record):
+template <int WORDS>
+__device__ __forceinline__ int4 chan_load(const void* base, int64_t i, bool w8) {
+    int4 r = make_int4(0, 0, 0, 0);
+    const int32_t* p = static_cast<const int32_t*>(base) + i * WORDS;
+    if constexpr (WORDS == 1) r.x = p[0];
+    else if (w8) {
+        const int2 x = reinterpret_cast<const int2*>(p)[0];
+        r.x = x.x, r.y = x.y;
+        if constexpr (WORDS == 4) {
+            const int2 y = reinterpret_cast<const int2*>(p)[1];
+            r.z = y.x, r.w = y.y;
+        }
+    } else {
+        r.x = p[0], r.y = p[1];
+        if constexpr (WORDS == 4) r.z = p[2], r.w = p[3];
+    }
+    return r;
+}
+template <int WORDS>
+__device__ __forceinline__ void chan_store(void* base, int64_t i, bool w8, int4 r) {
+    int32_t* p = static_cast<int32_t*>(base) + i * WORDS;
+    if constexpr (WORDS == 1) p[0] = r.x;
+    else if (w8) {
+        reinterpret_cast<int2*>(p)[0] = make_int2(r.x, r.y);
+        if constexpr (WORDS == 4) reinterpret_cast<int2*>(p)[1] = make_int2(r.z, r.w);
+    } else {
+        p[0] = r.x, p[1] = r.y;
+        if constexpr (WORDS == 4) p[2] = r.z, p[3] = r.w;
+    }
+}
+template <int WORDS>
+__device__ __forceinline__ int4 carry_load(const void* base, int64_t i) {
+    if constexpr (WORDS == 1) return make_int4(static_cast<const int32_t*>(base)[i], 0, 0, 0);
+    else if constexpr (WORDS == 2) {
+        const int2 x = static_cast<const int2*>(base)[i];
+        return make_int4(x.x, x.y, 0, 0);
+    } else return static_cast<const int4*>(base)[i];
+}
+template <int WORDS>
+__device__ __forceinline__ void carry_store(void* base, int64_t i, int4 r) {
+    if constexpr (WORDS == 1) static_cast<int32_t*>(base)[i] = r.x;
+    else if constexpr (WORDS == 2) static_cast<int2*>(base)[i] = make_int2(r.x, r.y);
+    else static_cast<int4*>(base)[i] = r;
+}
+
+// where a record comes from: src >= 0 the index the id was read at, -1 the fill (bos, eos, behind the stream's end,
+// offsets that do not describe the ids), <= -2 slot -2 - src of the consumed carry
+template <int WORDS>
+__device__ __forceinline__ int4 chan_record(const PackChan& c, int64_t src) {
+    if (src >= 0) return chan_load<WORDS>(c.values, src, c.w8 != 0);
+    if (src < -1) return carry_load<WORDS>(c.c_car, -2 - src);
+    return make_int4(c.f0, c.f1, c.f2, c.f3);
+}
+
+// The records of one channel behind the elements a thread has just placed.  They go where the ids went: to the rows at
+// element `at` (four of them as WORDS 16-byte stores) or, behind the last whole row, to the new carry.
+template <int WORDS>
+__device__ __forceinline__ void chan_emit4(const PackChan& c, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t at,
+                                           int64_t out_end, int64_t total) {
+    const int4 r0 = chan_record<WORDS>(c, s0), r1 = chan_record<WORDS>(c, s1), r2 = chan_record<WORDS>(c, s2),
+               r3 = chan_record<WORDS>(c, s3);
+    if (at < out_end) {
+        int4* o = static_cast<int4*>(c.rows) + (at >> 2) * WORDS;  // (at is a multiple of 4 on this path)
+        if constexpr (WORDS == 1) o[0] = make_int4(r0.x, r1.x, r2.x, r3.x);
+        else if constexpr (WORDS == 2) {
+            o[0] = make_int4(r0.x, r0.y, r1.x, r1.y);
+            o[1] = make_int4(r2.x, r2.y, r3.x, r3.y);
+        } else o[0] = r0, o[1] = r1, o[2] = r2, o[3] = r3;
+    } else {
+        const int64_t t = at - out_end;
+        if (at < total) carry_store<WORDS>(c.n_car, t, r0);
+        if (at + 1 < total) carry_store<WORDS>(c.n_car, t + 1, r1);
+        if (at + 2 < total) carry_store<WORDS>(c.n_car, t + 2, r2);
+        if (at + 3 < total) carry_store<WORDS>(c.n_car, t + 3, r3);
+    }
+}
+template <int WORDS>
+__device__ __forceinline__ void chan_emit1(const PackChan& c, int64_t s0, int64_t at, int64_t out_end, int64_t total) {
+    const int4 r = chan_record<WORDS>(c, s0);
+    if (at < out_end) chan_store<WORDS>(c.rows, at, c.w8 != 0, r);
+    else if (at < total) carry_store<WORDS>(c.n_car, at - out_end, r);
+}
+template <int WORDS, bool VEC>
+__device__ __forceinline__ void chan_emit(const PackChan& c, const int64_t (&src)[VEC ? 4 : 1], int64_t at, int64_t out_end,
+                                          int64_t total) {
+    if constexpr (VEC) chan_emit4<WORDS>(c, src[0], src[1], src[2], src[3], at, out_end, total);
+    else chan_emit1<WORDS>(c, src[0], at, out_end, total);
+}
+
+// k_collate_packed and its sibling with channels, k_collate_packed_ch, share this body: CH = false compiles every line
+// about channels away, so the kernel that the plain add call launches is what it was.
+template <int W, bool VEC, bool CH>
+__device__ __forceinline__ void collate_packed_body(const PackArgs& a, const PackChans* ch) {
     __shared__ __attribute__((aligned(16))) int32_t s_d[SPAN + 4];  // marks (document - j0 at its sequence start), then their running maximum
     __shared__ __attribute__((aligned(16))) int32_t s_c[SPAN];  // (1 + where the position's sequence starts in the span) << 16 | starts so far
     __shared__ int32_t s_wmax[TB / 64], s_wcnt[TB / 64], s_wpos[TB / 64];
@@ -261,6 +376,12 @@ __global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
     }
     const int tid = threadIdx.x;
     const int64_t blk = blockIdx.x;
+    if constexpr (CH) {
+        // Offsets that decrease describe no ids either.  The ids' rows come out of the range-checked reads whatever the
+        // offsets say, but a channel row is only as good as its offsets: every workgroup looks at its share of them.
+        for (int64_t j = blk * TB + tid; j < a.n_docs; j += (int64_t)gridDim.x * TB)
+            if (a.offs[j + 1] < a.offs[j]) note_error(a.err, HUTK_E_ARG);
+    }
     int64_t k0, x0, x1;  // first row, first and one-past-last stream position of this workgroup
     if (a.spans_per_row > 1) {
         k0 = blk / a.spans_per_row;
@@ -379,17 +500,20 @@ __global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
         const int64_t row_start = row_start0 + (int64_t)rl * a.L;
         const int32_t seg_base = rl == 0 ? 1 + pre : 1 - (s_c[rl * Li] & 0xFFFF);
         int32_t vi[V], vp[V], vs[V];
+        int64_t src[V];  // (CH only) where the element's channel records come from: chan_emit
 #pragma unroll
         for (int e = 0; e < V; e++) {
             const int64_t gp = x0 + i + e;
             vi[e] = 0;
             vp[e] = 0;
             vs[e] = 0;
+            if constexpr (CH) src[e] = -1;
             if (gp >= x1) continue;  // (only behind the stream's end: whole rows are multiples of V)
             if (gp < a.P) {
                 vi[e] = a.c_ids[gp];
                 vp[e] = a.c_pos[gp];
                 vs[e] = a.c_seg[gp];
+                if constexpr (CH) src[e] = -2 - gp;
                 continue;
             }
             // No offsets are read here: the sequence's start is where its mark stood (or b_j0 for the one that reaches into
@@ -410,8 +534,10 @@ __global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
             else if (last) vi[e] = a.eos;
             else {
                 const int64_t idx = gp - a.P - j * a.s - a.has_bos;
-                if (idx >= 0 && idx < a.n_ids) vi[e] = a.ids[idx];
-                else note_error(a.err, HUTK_E_ARG);
+                if (idx >= 0 && idx < a.n_ids) {
+                    vi[e] = a.ids[idx];
+                    if constexpr (CH) src[e] = idx;
+                } else note_error(a.err, HUTK_E_ARG);
             }
             vp[e] = (int32_t)(gp - (b > row_start ? b : row_start));
             vs[e] = seg_base + (cc & 0xFFFF);
@@ -438,7 +564,28 @@ __global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
                 }
             }
         }
+        if constexpr (CH) {
+#pragma unroll
+            for (int k = 0; k < HUTK_PACKER_MAX_CHANNELS; k++) {
+                if (k < ch->n) {
+                    const PackChan c = ch->c[k];
+                    if (c.words == 1) chan_emit<1, VEC>(c, src, at, out_end, a.total);
+                    else if (c.words == 2) chan_emit<2, VEC>(c, src, at, out_end, a.total);
+                    else chan_emit<4, VEC>(c, src, at, out_end, a.total);
+                }
+            }
+        }
     }
+}
+
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_packed(const PackArgs a) {
+    collate_packed_body<W, VEC, false>(a, nullptr);
+}
+
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_collate_packed_ch(const PackArgs a, const PackChans ch) {
+    collate_packed_body<W, VEC, true>(a, &ch);
 }
 
 // the carry as one padded row
@@ -450,6 +597,26 @@ __global__ __launch_bounds__(TB) void k_collate_flush(const int32_t* c_ids, cons
         store1<W>(out, c, in ? c_ids[c] : pad);
         if (pos) pos[c] = in ? c_pos[c] : 0;
         if (seg) seg[c] = in ? c_seg[c] : 0;
+    }
+}
+
+// and its channels: carry first, then fill
+template <int WORDS>
+__device__ __forceinline__ void chan_flush(const PackChan& ch, int64_t c, bool in) {
+    chan_store<WORDS>(ch.rows, c, ch.w8 != 0, in ? carry_load<WORDS>(ch.c_car, c) : make_int4(ch.f0, ch.f1, ch.f2, ch.f3));
+}
+
+__global__ __launch_bounds__(TB) void k_collate_flush_ch(const PackChans ch, int64_t P, int64_t L) {
+    for (int64_t c = (int64_t)blockIdx.x * TB + threadIdx.x; c < L; c += (int64_t)gridDim.x * TB) {
+#pragma unroll
+        for (int k = 0; k < HUTK_PACKER_MAX_CHANNELS; k++) {
+            if (k < ch.n) {
+                const PackChan h = ch.c[k];
+                if (h.words == 1) chan_flush<1>(h, c, c < P);
+                else if (h.words == 2) chan_flush<2>(h, c, c < P);
+                else chan_flush<4>(h, c, c < P);
+            }
+        }
     }
 }
 
@@ -1458,6 +1625,115 @@ __global__ __launch_bounds__(TB) void k_rows_labels(const LabelArgs a) {
     }
 }
 
+// ---- packed rows for training ---------------------------------------------------------------------------
+// cu_seqlens is a stream compaction of the flat elements that start a sequence: the rows scan with "element" as the
+// item counts them per workgroup (k_rows_count<CuStarts>) and scans the workgroups' counts; the write differs, since
+// what is kept is the element's index at its rank, not a rank per element (k_cu_write).  The gaps between neighbouring
+// entries of what was written give max_seqlen (k_cu_gaps: a maximum per workgroup, one atomic each).
+constexpr int CU_TILE = 2048;  // elements per workgroup of the count (times a whole number above WIN_BLOCKS * CU_TILE elements)
+
+struct CuStarts {
+    const int32_t* seg;
+    int64_t L;
+    __device__ __forceinline__ int64_t operator()(int64_t f, int32_t*) const {
+        return f % L == 0 || seg[f] != seg[f - 1];
+    }
+};
+
+struct CuArgs {
+    int32_t* cu;    // [cap + 1]; NULL: count only
+    int32_t* info;  // (n_seq, max_seqlen)
+    int64_t cap, total;
+};
+
+__global__ __launch_bounds__(TB) void k_cu_write(const ScanArgs a, const CuStarts starts, const CuArgs o) {
+    __shared__ int64_t s_part[TB / 64];
+    const int64_t lo = (int64_t)blockIdx.x * a.per_block;
+    const int64_t hi = lo + a.per_block < a.n ? lo + a.per_block : a.n;
+    const int64_t n_seq = a.sums[gridDim.x];
+    int64_t base = a.sums[blockIdx.x];
+    for (int64_t at = lo; at < hi; at += TB) {  // (uniform: every thread meets the barriers of the scan)
+        const int64_t i = at + threadIdx.x;
+        const int64_t w = i < hi ? starts(i, nullptr) : 0;
+        int64_t total;
+        const int64_t k = base + hutk::block_excl(w, s_part, total);
+        if (w && o.cu && k < o.cap) o.cu[k] = (int32_t)i;
+        base += total;
+    }
+    // behind the starts: the total in every slot up to and including slot cap
+    if (o.cu)
+        for (int64_t k = (n_seq < o.cap ? n_seq : o.cap) + (int64_t)blockIdx.x * TB + threadIdx.x; k <= o.cap; k += (int64_t)gridDim.x * TB)
+            o.cu[k] = (int32_t)o.total;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        o.info[0] = (int32_t)n_seq;
+        o.info[1] = 0;
+        if (o.cu && n_seq > o.cap) note_error(a.err, HUTK_E_CAPACITY);
+    }
+}
+
+// info[1] = the largest cu[k + 1] - cu[k] over the sequences written, k < min(n_seq, cap)
+__global__ __launch_bounds__(TB) void k_cu_gaps(const CuArgs o) {
+    __shared__ int32_t s_max[TB / 64];
+    const int64_t n_seq = o.info[0];
+    const int64_t m = n_seq < o.cap ? n_seq : o.cap;
+    int32_t mine = 0;
+    for (int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x; k < m; k += (int64_t)gridDim.x * TB) {
+        const int32_t g = o.cu[k + 1] - o.cu[k];
+        mine = g > mine ? g : mine;
+    }
+    const int lane = threadIdx.x & 63;
+    mine = __shfl(hutk::wave_incl_max(mine, lane), 63);
+    if (lane == 0) s_max[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int u = 1; u < TB / 64; u++) mine = s_max[u] > mine ? s_max[u] : mine;
+        if (mine > 0) atomicMax(&o.info[1], mine);
+    }
+}
+
+struct PackedLabelArgs {
+    const void* values;
+    const int32_t* seg;
+    void* labels;
+    int64_t n, L;  // elements, row length
+    int64_t ignore;
+    int32_t shift;
+};
+
+// labels[f] = values[f] on a real column (segment != 0), or with shift what the column predicts: values[f + 1] when that
+// column is in the same row and of the same, real segment.  One elementwise pass; the neighbour behind a thread's V
+// elements is read from global memory, so the end of a workgroup's elements is no special place.
+template <int W, bool VEC>
+__global__ __launch_bounds__(TB) void k_packed_labels(const PackedLabelArgs a) {
+    constexpr int V = VEC ? 4 : 1;
+    using T = elem_t<W>;
+    const int64_t at = ((int64_t)blockIdx.x * TB + threadIdx.x) * V;
+    if (at >= a.n) return;
+    const int64_t c = at % a.L;  // (VEC: L % 4 == 0, the V elements share a row)
+    T v[V + 1], lab[V];
+    int32_t sg[V + 1];
+    if constexpr (VEC) {
+        T q[4];
+        load4<W>(a.values, at, q);
+        const int4 x = *reinterpret_cast<const int4*>(a.seg + at);
+        v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
+        sg[0] = x.x, sg[1] = x.y, sg[2] = x.z, sg[3] = x.w;
+    } else {
+        v[0] = static_cast<const T*>(a.values)[at];
+        sg[0] = a.seg[at];
+    }
+    const bool next = a.shift && c + V < a.L;  // (the row ends at L: its last column predicts nothing)
+    sg[V] = next ? a.seg[at + V] : 0;
+    v[V] = next && sg[V] != 0 ? static_cast<const T*>(a.values)[at + V] : 0;
+#pragma unroll
+    for (int e = 0; e < V; e++) {
+        if (a.shift) lab[e] = sg[e] != 0 && sg[e + 1] == sg[e] ? v[e + 1] : (T)a.ignore;
+        else lab[e] = sg[e] != 0 ? v[e] : (T)a.ignore;
+    }
+    if constexpr (VEC) put4<W>(a.labels, at, lab);
+    else put1<W>(a.labels, at, lab[0]);
+}
+
 // ---- targets: span corruption ---------------------------------------------------------------------------------
 // The first row pass whose outputs are of another length than its input: every noise span of a row becomes one
 // sentinel in the corrupted row, and the spans move, each behind its sentinel, into a target row.  One wavefront per
@@ -1930,9 +2206,59 @@ struct hutk_packer {
     hipEvent_t ev = nullptr;     // behind the last kernel of the last call
     bool ev_recorded = false;
     std::mutex mu;
+    // channels: the width, the record size and the fill of each, and one carry of [2][L] records for all
+    int n_ch = 0;
+    int ch_width[HUTK_PACKER_MAX_CHANNELS] = {}, ch_per[HUTK_PACKER_MAX_CHANNELS] = {};
+    int64_t ch_fill[HUTK_PACKER_MAX_CHANNELS] = {};
+    int64_t ch_at[HUTK_PACKER_MAX_CHANNELS] = {};  // where the channel's two halves begin in ch_carry, a multiple of 16
+    char* ch_carry = nullptr;
     int s() const { return (bos != HUTK_NO_TOKEN) + (eos != HUTK_NO_TOKEN); }
     int32_t* half(int h, int which) const { return carry + ((int64_t)h * 3 + which) * L; }
+    int64_t ch_rec(int c) const { return (int64_t)ch_width[c] * ch_per[c]; }
+    char* ch_half(int h, int c) const { return ch_carry + ch_at[c] + h * L * ch_rec(c); }
 };
+
+namespace {
+
+// What the kernels read of the packer's channels: the caller's arrays (NULL where the call has none: flush reads no
+// values), the halves of the carry the call consumes and leaves, and the fill as the dwords of a record.
+PackChans pack_chans(const hutk_packer* p, const void* const* d_values, void* const* d_rows) {
+    PackChans ch = {};
+    ch.n = p->n_ch;
+    for (int c = 0; c < p->n_ch; c++) {
+        PackChan& k = ch.c[c];
+        k.values = d_values ? d_values[c] : nullptr;
+        k.rows = d_rows ? d_rows[c] : nullptr;
+        k.c_car = p->ch_half(p->cur, c);
+        k.n_car = p->ch_half(p->cur ^ 1, c);
+        k.w8 = p->ch_width[c] == 8;
+        k.words = (int32_t)(p->ch_rec(c) / 4);
+        const int32_t lo = (int32_t)(uint32_t)(uint64_t)p->ch_fill[c], hi = (int32_t)(uint32_t)((uint64_t)p->ch_fill[c] >> 32);
+        if (k.w8) k.f0 = lo, k.f1 = hi, k.f2 = lo, k.f3 = hi;
+        else k.f0 = k.f1 = k.f2 = k.f3 = lo;
+    }
+    return ch;
+}
+
+// The pointers of a call with channels: every one given and aligned to its elements.  *wide: all rows 16-byte aligned.
+int chan_pointers(const char* who, const hutk_packer* p, const void* const* d_values, bool need_values, void* const* d_rows,
+                  bool need_rows, bool* wide) {
+    *wide = true;
+    if (p->n_ch == 0) return HUTK_OK;
+    if ((need_values && !d_values) || (need_rows && !d_rows))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": the packer has channels: d_values and d_channel_rows must be given");
+    for (int c = 0; c < p->n_ch; c++) {
+        if ((need_values && !d_values[c]) || (need_rows && !d_rows[c]))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a channel's buffer is NULL");
+        if ((need_values && !aligned_to(d_values[c], (uintptr_t)p->ch_width[c])) ||
+            (need_rows && !aligned_to(d_rows[c], (uintptr_t)p->ch_width[c])))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a channel's buffer is not aligned to its elements");
+        if (need_rows && !aligned_to(d_rows[c], 16)) *wide = false;
+    }
+    return HUTK_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -2486,14 +2812,29 @@ int hutk_rows_span_corrupt_device(const int64_t* d_plan, int64_t n_rows, int64_t
 
 int hutk_packer_create(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32_t eos_id, int32_t pad_id,
                        int out_width, int device) {
-    if (!out) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_create: out is NULL");
+    return hutk_packer_create_channels(out, seq_len, bos_id, eos_id, pad_id, out_width, device, 0, nullptr, nullptr, nullptr);
+}
+
+int hutk_packer_create_channels(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32_t eos_id, int32_t pad_id,
+                                int out_width, int device, int n_channels, const int* widths, const int* per,
+                                const int64_t* fills) {
+    const std::string who = n_channels ? "hutk_packer_create_channels" : "hutk_packer_create";
+    if (!out) return hutk::api_set_error(HUTK_E_ARG, who + ": out is NULL");
     *out = nullptr;
     if (seq_len < 1 || seq_len > INT32_MAX || (out_width != 4 && out_width != 8))
-        return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_create: seq_len must be in 1 .. 2^31 - 1 and out_width 4 or 8");
+        return hutk::api_set_error(HUTK_E_ARG, who + ": seq_len must be in 1 .. 2^31 - 1 and out_width 4 or 8");
+    if (n_channels < 0 || n_channels > HUTK_PACKER_MAX_CHANNELS || (n_channels > 0 && (!widths || !per || !fills)))
+        return hutk::api_set_error(HUTK_E_ARG, who + ": n_channels must be in 0 .. HUTK_PACKER_MAX_CHANNELS, with widths, per and fills");
+    for (int c = 0; c < n_channels; c++) {
+        if ((widths[c] != 4 && widths[c] != 8) || (per[c] != 1 && per[c] != 2))
+            return hutk::api_set_error(HUTK_E_ARG, who + ": a channel's width must be 4 or 8 and its per 1 or 2");
+        if (widths[c] == 4 && (fills[c] < INT32_MIN || fills[c] > INT32_MAX))
+            return hutk::api_set_error(HUTK_E_ARG, who + ": a channel's fill must fit its width");
+    }
     int n = 0;
-    if (int rc = device_present("hutk_packer_create", &n)) return rc;
+    if (int rc = device_present(who.c_str(), &n)) return rc;
     if (device < 0) HUTK_HIP_TRY(hipGetDevice(&device));
-    if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, "hutk_packer_create: no such device");
+    if (device >= n) return hutk::api_set_error(HUTK_E_DEVICE, who + ": no such device");
     HUTK_HIP_TRY(hipSetDevice(device));
     hutk_packer* p = new hutk_packer();
     p->device = device;
@@ -2502,16 +2843,28 @@ int hutk_packer_create(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32
     p->eos = eos_id;
     p->pad = pad_id;
     p->width = out_width;
+    p->n_ch = n_channels;
+    int64_t ch_bytes = 0;
+    for (int c = 0; c < n_channels; c++) {
+        p->ch_width[c] = widths[c];
+        p->ch_per[c] = per[c];
+        p->ch_fill[c] = fills[c];
+        p->ch_at[c] = ch_bytes;
+        ch_bytes += (2 * seq_len * p->ch_rec(c) + 15) / 16 * 16;
+    }
     hipError_t e = hipMalloc((void**)&p->carry, (size_t)seq_len * 6 * sizeof(int32_t));
+    if (e == hipSuccess && ch_bytes) e = hipMalloc((void**)&p->ch_carry, (size_t)ch_bytes);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         hutk_packer_destroy(p);
         return hutk::api_set_error(e == hipErrorOutOfMemory ? HUTK_E_MEMORY : HUTK_E_DEVICE,
-                                   std::string("hutk_packer_create: ") + hipGetErrorString(e));
+                                   who + ": " + hipGetErrorString(e));
     }
     *out = p;
     return HUTK_OK;
 }
+
+int hutk_packer_channel_count(const hutk_packer* p) { return p ? p->n_ch : -1; }
 
 int64_t hutk_packer_rows(const hutk_packer* p, int64_t n_docs, int64_t n_ids) {
     if (!p || n_docs < 0 || n_ids < 0) return -1;
@@ -2520,19 +2873,27 @@ int64_t hutk_packer_rows(const hutk_packer* p, int64_t n_docs, int64_t n_ids) {
 
 int64_t hutk_packer_pending(const hutk_packer* p) { return p ? p->pending : -1; }
 
-int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs,
-                           int64_t n_ids, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
-                           int64_t rows_cap, int64_t* n_rows, int32_t* d_err, void* hip_stream) {
+// the two add calls; `plain`: the one without channels, which a packer that has some refuses
+static int packer_add(const std::string& who, bool plain, hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets,
+                      int64_t n_docs, int64_t n_ids, const void* const* d_values, void* d_input_ids, int32_t* d_position_ids,
+                      int32_t* d_segment_ids, void* const* d_channel_rows, int64_t rows_cap, int64_t* n_rows, int32_t* d_err,
+                      void* hip_stream) {
     if (!p || n_docs < 0 || n_ids < 0 || rows_cap < 0 || n_docs > INT32_MAX - 1)
-        return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_add_device: bad arguments");
+        return hutk::api_set_error(HUTK_E_ARG, who + ": bad arguments");
     std::lock_guard<std::mutex> lock(p->mu);
+    if (plain && p->n_ch)
+        return hutk::api_set_error(HUTK_E_ARG, who + ": the packer has channels, whose carry this call would lose: use "
+                                                     "hutk_packer_add_channels_device");
     const int s = p->s();
     const int64_t total = p->pending + n_ids + n_docs * s;
     const int64_t rows = total / p->L;
     if (rows > rows_cap)
-        return hutk::api_set_error(HUTK_E_CAPACITY, "hutk_packer_add_device: rows_cap is below hutk_packer_rows()");
+        return hutk::api_set_error(HUTK_E_CAPACITY, who + ": rows_cap is below hutk_packer_rows()");
     if ((n_docs > 0 && !d_offsets) || (n_ids > 0 && !d_ids) || (rows > 0 && !d_input_ids))
-        return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_add_device: a buffer is NULL");
+        return hutk::api_set_error(HUTK_E_ARG, who + ": a buffer is NULL");
+    bool wide = true;
+    if (n_docs > 0)
+        if (int rc = chan_pointers(who.c_str(), p, d_values, n_ids > 0, d_channel_rows, rows > 0, &wide)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     HUTK_HIP_TRY(hipSetDevice(p->device));
     if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
@@ -2573,14 +2934,22 @@ int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* 
         a.spans_per_row = 1;
         blocks = (rows_all + a.rows_per_block - 1) / a.rows_per_block;
     }
-    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_packer_add_device: the batch is too large for one launch");
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, who + ": the batch is too large for one launch");
     if (blocks > 0) {
         if (p->ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, p->ev, 0));
         const bool vec = p->L % 4 == 0 && aligned_to(d_input_ids, 16) && aligned_to(d_position_ids, 16) &&
-                         aligned_to(d_segment_ids, 16);
-        with_width_vec(p->width, vec, [&](auto w, auto v) {
-            hipLaunchKernelGGL((k_collate_packed<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
-        });
+                         aligned_to(d_segment_ids, 16) && wide;
+        if (p->n_ch == 0) {
+            with_width_vec(p->width, vec, [&](auto w, auto v) {
+                hipLaunchKernelGGL((k_collate_packed<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a);
+            });
+        } else {
+            // (with no complete row the kernel stores to the carry only: the rows' pointers are never used)
+            const PackChans ch = pack_chans(p, n_ids > 0 ? d_values : nullptr, rows > 0 ? d_channel_rows : nullptr);
+            with_width_vec(p->width, vec, [&](auto w, auto v) {
+                hipLaunchKernelGGL((k_collate_packed_ch<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0, st, a, ch);
+            });
+        }
         HUTK_HIP_TRY(hipGetLastError());
         HUTK_HIP_TRY(hipEventRecord(p->ev, st));
         p->ev_recorded = true;
@@ -2590,15 +2959,35 @@ int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* 
     return HUTK_OK;
 }
 
-int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
-                             int64_t* n_rows, void* hip_stream) {
-    if (!p) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_flush_device: bad arguments");
+int hutk_packer_add_device(hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs,
+                           int64_t n_ids, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                           int64_t rows_cap, int64_t* n_rows, int32_t* d_err, void* hip_stream) {
+    return packer_add("hutk_packer_add_device", true, p, d_ids, d_offsets, n_docs, n_ids, nullptr, d_input_ids, d_position_ids,
+                      d_segment_ids, nullptr, rows_cap, n_rows, d_err, hip_stream);
+}
+
+int hutk_packer_add_channels_device(hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs,
+                                    int64_t n_ids, const void* const* d_values, void* d_input_ids,
+                                    int32_t* d_position_ids, int32_t* d_segment_ids, void* const* d_channel_rows,
+                                    int64_t rows_cap, int64_t* n_rows, int32_t* d_err, void* hip_stream) {
+    return packer_add("hutk_packer_add_channels_device", false, p, d_ids, d_offsets, n_docs, n_ids, d_values, d_input_ids,
+                      d_position_ids, d_segment_ids, d_channel_rows, rows_cap, n_rows, d_err, hip_stream);
+}
+
+static int packer_flush(const std::string& who, bool plain, hutk_packer* p, void* d_input_ids, int32_t* d_position_ids,
+                        int32_t* d_segment_ids, void* const* d_channel_rows, int64_t* n_rows, void* hip_stream) {
+    if (!p) return hutk::api_set_error(HUTK_E_ARG, who + ": bad arguments");
     std::lock_guard<std::mutex> lock(p->mu);
+    if (plain && p->n_ch)
+        return hutk::api_set_error(HUTK_E_ARG, who + ": the packer has channels, whose carry this call would lose: use "
+                                                     "hutk_packer_flush_channels_device");
     if (p->pending == 0) {
         if (n_rows) *n_rows = 0;
         return HUTK_OK;
     }
-    if (!d_input_ids) return hutk::api_set_error(HUTK_E_ARG, "hutk_packer_flush_device: d_input_ids is NULL");
+    if (!d_input_ids) return hutk::api_set_error(HUTK_E_ARG, who + ": d_input_ids is NULL");
+    bool wide;
+    if (int rc = chan_pointers(who.c_str(), p, nullptr, false, d_channel_rows, true, &wide)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     HUTK_HIP_TRY(hipSetDevice(p->device));
     if (p->ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, p->ev, 0));
@@ -2611,12 +3000,27 @@ int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_posit
     else
         hipLaunchKernelGGL((k_collate_flush<8>), grid, block, 0, st, p->half(p->cur, 0), p->half(p->cur, 1),
                            p->half(p->cur, 2), p->pending, p->L, p->pad, d_input_ids, d_position_ids, d_segment_ids);
+    if (p->n_ch)
+        hipLaunchKernelGGL(k_collate_flush_ch, grid, block, 0, st, pack_chans(p, nullptr, d_channel_rows), p->pending, p->L);
     HUTK_HIP_TRY(hipGetLastError());
     HUTK_HIP_TRY(hipEventRecord(p->ev, st));
     p->ev_recorded = true;
     p->pending = 0;
     if (n_rows) *n_rows = 1;
     return HUTK_OK;
+}
+
+int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                             int64_t* n_rows, void* hip_stream) {
+    return packer_flush("hutk_packer_flush_device", true, p, d_input_ids, d_position_ids, d_segment_ids, nullptr, n_rows,
+                        hip_stream);
+}
+
+int hutk_packer_flush_channels_device(hutk_packer* p, void* d_input_ids, int32_t* d_position_ids,
+                                      int32_t* d_segment_ids, void* const* d_channel_rows, int64_t* n_rows,
+                                      void* hip_stream) {
+    return packer_flush("hutk_packer_flush_channels_device", false, p, d_input_ids, d_position_ids, d_segment_ids,
+                        d_channel_rows, n_rows, hip_stream);
 }
 
 void hutk_packer_destroy(hutk_packer* p) {
@@ -2627,8 +3031,91 @@ void hutk_packer_destroy(hutk_packer* p) {
         (void)hipEventDestroy(p->ev);
     }
     if (p->carry) (void)hipFree(p->carry);
+    if (p->ch_carry) (void)hipFree(p->ch_carry);
     delete p;
 }
+
+// ---- packed rows for training ---------------------------------------------------------------------------
+int hutk_packed_cu_seqlens_device(const int32_t* d_segment_ids, int64_t n_rows, int64_t seq_len, int64_t cap,
+                                  int32_t* d_cu_seqlens, int32_t* d_info, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_packed_cu_seqlens_device";
+    if (n_rows < 0 || seq_len < 1 || seq_len > INT32_MAX || n_rows > INT32_MAX / seq_len)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": n_rows * seq_len must be below 2^31 (the starts are int32), seq_len at least 1");
+    if (cap < 0 || cap > INT32_MAX - 1) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": cap must be in 0 .. 2^31 - 2");
+    if (!d_info || (n_rows > 0 && !d_segment_ids))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(d_segment_ids, 4) || !aligned_to(d_cu_seqlens, 4) || !aligned_to(d_info, 4) || !aligned_to(d_err, 4))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its elements");
+    if (int rc = device_present(who)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    const int64_t n = n_rows * seq_len;
+    if (n == 0) {
+        HUTK_HIP_TRY(hipMemsetAsync(d_info, 0, 2 * sizeof(int32_t), st));
+        if (d_cu_seqlens) HUTK_HIP_TRY(hipMemsetAsync(d_cu_seqlens, 0, (size_t)(cap + 1) * sizeof(int32_t), st));
+        return HUTK_OK;
+    }
+    ScanArgs a;
+    a.n = n;
+    a.per_block = (n + (int64_t)WIN_BLOCKS * CU_TILE - 1) / ((int64_t)WIN_BLOCKS * CU_TILE) * CU_TILE;
+    const int64_t blocks = (n + a.per_block - 1) / a.per_block;
+    const CuStarts starts{d_segment_ids, seq_len};
+    const CuArgs o{d_cu_seqlens, d_info, cap, n};
+    std::lock_guard<std::mutex> lock(g_win_mu);
+    WinScratch* w;
+    if (int rc = scratch_for(st, &w)) return rc;
+    a.sums = w->sums;
+    a.row_offs = nullptr;
+    a.err = d_err;
+    const dim3 grid((unsigned)blocks), block(TB);
+    hipLaunchKernelGGL(k_rows_count<CuStarts>, grid, block, 0, st, a, starts);
+    hutk::launch_scan_i64(w->sums, blocks, st);
+    hipLaunchKernelGGL(k_cu_write, grid, block, 0, st, a, starts, o);
+    if (d_cu_seqlens && cap > 0) {
+        const int64_t most = cap < n ? cap : n;  // sequences that can have been written
+        int64_t gb = (most + TB - 1) / TB;
+        if (gb > 1024) gb = 1024;
+        hipLaunchKernelGGL(k_cu_gaps, dim3((unsigned)gb), block, 0, st, o);
+    }
+    return scratch_used(w, st);
+}
+
+int hutk_packed_labels_device(const void* d_values, int width, const int32_t* d_segment_ids, int64_t n_rows,
+                              int64_t seq_len, int shift, int64_t ignore_index, void* d_labels, void* hip_stream) {
+    const char* who = "hutk_packed_labels_device";
+    if (int rc = target_sizes(who, n_rows, seq_len, width, ignore_index)) return rc;
+    if (n_rows > INT64_MAX / 8 / seq_len) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": the rows are too large");
+    const int64_t n = n_rows * seq_len;
+    if (n > 0) {
+        if (!d_values || !d_segment_ids || !d_labels) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+        if (!aligned_to(d_values, (uintptr_t)width) || !aligned_to(d_labels, (uintptr_t)width) || !aligned_to(d_segment_ids, 4))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its elements");
+        if (overlap(d_labels, n * width, d_values, n * width) || overlap(d_labels, n * width, d_segment_ids, n * 4))
+            return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": d_labels must not overlap d_values or d_segment_ids");
+    }
+    if (int rc = device_present(who)) return rc;
+    if (n == 0) return HUTK_OK;
+    const bool vec = seq_len % 4 == 0 && aligned_to(d_values, 16) && aligned_to(d_labels, 16) && aligned_to(d_segment_ids, 16);
+    const int64_t per = TB * (vec ? 4 : 1);
+    const int64_t blocks = (n + per - 1) / per;
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, std::string(who) + ": the batch is too large for one launch");
+    PackedLabelArgs a;
+    a.values = d_values;
+    a.seg = d_segment_ids;
+    a.labels = d_labels;
+    a.n = n;
+    a.L = seq_len;
+    a.ignore = ignore_index;
+    a.shift = shift != 0;
+    with_width_vec(width, vec, [&](auto w, auto v) {
+        hipLaunchKernelGGL((k_packed_labels<decltype(w)::value, decltype(v)::value>), dim3((unsigned)blocks), dim3(TB), 0,
+                           (hipStream_t)hip_stream, a);
+    });
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_debug_cu_tile(void) { return CU_TILE; }
 
 int hutk_chat_template_create(hutk_chat_template** out, int device, int n_roles, const int32_t* prefix_ids,
                               const int32_t* prefix_offsets, const int32_t* suffix_ids, const int32_t* suffix_offsets,

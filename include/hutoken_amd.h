@@ -369,6 +369,71 @@ int hutk_packer_flush_device(hutk_packer* p, void* d_input_ids, int32_t* d_posit
 int64_t hutk_packer_pending(const hutk_packer* p);
 void hutk_packer_destroy(hutk_packer* p);
 
+/* PACKED CHANNELS.  A channel is a per-token array that lies along the same offsets as the ids: n_ids records of `per`
+ * (1 or 2) elements of `width` (4 or 8) bytes -- the chat render's labels and turn ids, the [n_ids][2] of
+ * hutk_token_spans_device, word ids.  A packer made by the create call below moves up to HUTK_PACKER_MAX_CHANNELS of them
+ * along with the ids, so that channel c of every row element is, on top of the PACKED definition above:
+ *   - for a stream position that holds document id number idx of the call, values_c[idx] (with per == 2 both elements of
+ *     the record);
+ *   - for a position the packer inserted (bos, eos) and for the padding of a flushed row, the channel's fill (an int64
+ *     that must fit the width; with per == 2 it fills both elements);
+ *   - carried tokens keep their channel values: the packer owns a carry per channel, two halves of seq_len * per
+ *     elements of the channel's width, beside the carry of ids, positions and segments.
+ * So the channel rows, like the id rows, depend on the order of the documents only, not on how they were split over the
+ * add calls.  d_values and d_channel_rows are HOST arrays of n_channels DEVICE pointers: d_values[c] holds n_ids records,
+ * d_channel_rows[c] receives [n_rows][seq_len] records (the flush call: one row).  With n_channels == 0 the create call
+ * is hutk_packer_create and the two calls are the add and flush calls above.  On a packer that has channels those
+ * older two return HUTK_E_ARG and consume nothing: they would lose the channels' carry.
+ * The create call refuses, with HUTK_E_ARG and before any device call, n_channels outside 0 .. HUTK_PACKER_MAX_CHANNELS,
+ * a width other than 4 or 8, a per other than 1 or 2 and a fill that does not fit its width.  A channel is read at the
+ * index the id is read at, under the same range check: offsets that do not describe the ids set HUTK_E_ARG in *d_err
+ * and nothing is read outside d_values[c][0 .. n_ids).  Alignment: that of the element; 16 bytes on every output gets
+ * the wide path.
+ *
+ * Worked example: seq_len 4, eos 99, pad 0, documents [10,11,12], [], [20..25], [30], one channel equal to the ids, int64,
+ * fill -100.  Three complete rows and the flushed one:
+ *   ids        10 11 12 99   | 99 20 21 22     | 23 24 25 99     | 30 99 0 0
+ *   segments   1 1 1 1       | 1 2 2 2         | 1 1 1 1         | 1 1 0 0
+ *   channel    10 11 12 -100 | -100 20 21 22   | 23 24 25 -100   | 30 -100 -100 -100 */
+#define HUTK_PACKER_MAX_CHANNELS 4
+int hutk_packer_create_channels(hutk_packer** out, int64_t seq_len, int32_t bos_id, int32_t eos_id, int32_t pad_id,
+                                int out_width, int device, int n_channels, const int* widths, const int* per,
+                                const int64_t* fills);
+int hutk_packer_channel_count(const hutk_packer* p);
+int hutk_packer_add_channels_device(hutk_packer* p, const int32_t* d_ids, const int64_t* d_offsets, int64_t n_docs,
+                                    int64_t n_ids, const void* const* d_values, void* d_input_ids,
+                                    int32_t* d_position_ids, int32_t* d_segment_ids, void* const* d_channel_rows,
+                                    int64_t rows_cap, int64_t* n_rows, int32_t* d_err, void* hip_stream);
+int hutk_packer_flush_channels_device(hutk_packer* p, void* d_input_ids, int32_t* d_position_ids,
+                                      int32_t* d_segment_ids, void* const* d_channel_rows, int64_t* n_rows,
+                                      void* hip_stream);
+
+/* PACKED ROWS FOR TRAINING.  Two passes over rows the packer wrote (from add, from flush, or both concatenated).
+ *
+ * The cu_seqlens call: d_segment_ids int32 [n_rows][L].  Flat element f = r * L + c starts a sequence when c == 0 or
+ * seg[r][c] != seg[r][c - 1]; nothing else is looked at, so any int32 values are safe input.  (Segment numbers are dense
+ * per row and 0 on padding: the sequences are the pieces of documents in each row, and a padding run is a sequence of
+ * its own.)  d_cu_seqlens int32 [cap + 1] receives the rising starts, then n_rows * L in every remaining slot up to and
+ * including slot cap: the surplus sequences have length zero.  d_info int32 [2] receives (n_seq, max_seqlen), max_seqlen
+ * being the largest difference of two neighbouring entries of d_cu_seqlens.  cap < n_seq: HUTK_E_CAPACITY in *d_err, the
+ * first cap starts are written (slot cap holds n_rows * L) and d_info[0] still holds the true n_seq.  n_rows * L >= 2^31:
+ * HUTK_E_ARG, on the host and before anything else (the starts are int32: what varlen attention kernels take).
+ * n_rows == 0: all zeros.  Never synchronises.  In the example above, the four rows and cap 8:
+ * cu_seqlens = 0 4 5 8 12 14 16 16 16, info = (6, 4).
+ *
+ * The labels call: d_values [n_rows][L] of `width` 4 or 8 -- the input ids for plain causal LM, or a packed labels channel
+ * whose columns off the loss are ignore_index already -- and d_segment_ids.  shift == 0: labels[r][c] = values[r][c]
+ * where seg[r][c] != 0, ignore_index elsewhere.  shift != 0: labels[r][c] = values[r][c + 1] when c + 1 < L and
+ * seg[r][c + 1] == seg[r][c] != 0, ignore_index elsewhere: no column predicts across a document boundary, a row end or
+ * into padding.  d_labels has the width of d_values and must not overlap it or d_segment_ids; ignore_index must fit the
+ * width.  In the example, ids and shift, i for ignore_index:  11 12 99 i | i 21 22 i | 24 25 99 i | 99 i i i.
+ * hutk_debug_cu_tile: the elements a workgroup of the cu_seqlens count takes (tests place edges there). */
+int hutk_packed_cu_seqlens_device(const int32_t* d_segment_ids, int64_t n_rows, int64_t seq_len, int64_t cap,
+                                  int32_t* d_cu_seqlens, int32_t* d_info, int32_t* d_err, void* hip_stream);
+int hutk_packed_labels_device(const void* d_values, int width, const int32_t* d_segment_ids, int64_t n_rows,
+                              int64_t seq_len, int shift, int64_t ignore_index, void* d_labels, void* hip_stream);
+int hutk_debug_cu_tile(void);
+
 /* WINDOWS.  A long document becomes several overlapping rows instead of one truncated row (what other tokenizers call
  * stride with overflowing tokens, truncation on the right).  With C = max_len - s (the document ids a row holds) and
  * step = C - stride (0 <= stride < C), a document of n ids gives w(n) rows: 1 when n <= C (an empty document too),

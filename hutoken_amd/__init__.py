@@ -38,6 +38,12 @@ document each, into one sequence per conversation -- a ragged pair that every co
 loss labels on the assistant turns only, turn ids and source indices; `batch_encode_chat` is the list form
 (csrc/hutk_collate.hip).
 
+Fill-in-the-middle (not in the reference): `fim_device` cuts the documents of a ragged pair into prefix / middle /
+suffix and re-orders them behind three sentinel ids, PSM or SPM, with random numbers that are a stated function of
+(seed, document) -- a ragged pair again, with loss labels, parts and source indices; `fim_cut_text_device` and
+`fim_pieces_device` are the character-level form, which cuts the packed text BEFORE it is encoded so that no token
+straddles a cut; `batch_encode_fim` is the list form (csrc/hutk_fim.h, csrc/hutk_collate.hip).
+
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
 `encode_with_offsets` are the list forms (csrc/hutk_spans.hip).
@@ -77,7 +83,8 @@ __all__ = ["packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_enco
            "decode_fallback", "batch_decode_fallback", "normalize_packed_device", "normalize",
            "pretokenize_packed_device", "pretokenize", "set_pretokenizer",
            "collate_pairs", "collate_pair_windows", "batch_encode_pairs", "batch_encode_pair_windows",
-           "ChatTemplate", "render_chat_device", "batch_encode_chat"]
+           "ChatTemplate", "render_chat_device", "batch_encode_chat",
+           "fim_device", "fim_cut_text_device", "fim_pieces_device", "batch_encode_fim"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -2792,6 +2799,232 @@ def batch_encode_chat(conversations, max_length=None, *, template, loss_roles=("
     d_conv = torch.tensor(conv, dtype=torch.int64, device=dev)
     out_ids, out_offsets, labels = render_chat_device(ids, oo, d_conv, d_roles, template, loss_roles=loss_roles,
                                                       add_generation_prompt=add_generation_prompt, ignore_index=ignore_index)
+    input_ids, mask, lengths, plan = collate_padded(out_ids, out_offsets, max_length, pad_id=pad_id, truncation=truncation,
+                                                    padding_side=padding_side, dtype=dtype, return_plan=True)
+    row_labels = gather_rows(plan, input_ids.shape[1], labels, fill=ignore_index).to(input_ids.dtype)
+    return (input_ids, mask, lengths, row_labels, plan) if return_plan else (input_ids, mask, lengths, row_labels)
+
+
+# ---- fill-in-the-middle (csrc/hutk_fim.h, csrc/hutk_collate.hip) ----------------------------------
+_FIM_LOSS_BITS = dict({name: 1 << i for i, name in enumerate(_capi.FIM_PARTS)}, end=32)  # HUTK_FIM_PART_*, HUTK_FIM_LOSS_END
+
+
+def _fim_loss_arg(loss_on):
+    """loss_on -> loss_parts of hutk_fim_render_device"""
+    if loss_on == "all":
+        return 31
+    if loss_on == "middle":
+        return _FIM_LOSS_BITS["middle"] | _FIM_LOSS_BITS["end"] | _FIM_LOSS_BITS["plain"]
+    if isinstance(loss_on, (tuple, list, set, frozenset)) and all(isinstance(x, str) and x in _FIM_LOSS_BITS for x in loss_on):
+        bits = 0
+        for x in loss_on:
+            bits |= _FIM_LOSS_BITS[x]
+        return bits
+    raise ValueError("loss_on must be 'all', 'middle' or a tuple drawn from ('plain', 'prefix', 'middle', 'suffix', 'sentinel', "
+                     "'end'), not %r" % (loss_on,))
+
+
+def _fim_sentinel_args(prefix_id, suffix_id, middle_id, end_id):
+    return (_token_arg("prefix_id", prefix_id, False), _token_arg("suffix_id", suffix_id, False),
+            _token_arg("middle_id", middle_id, False), _token_arg("end_id", end_id))
+
+
+def _fim_draw_args(seed, fim_rate, spm_rate, first_doc):
+    """-> (seed, fim_below, spm_below, first_doc): a probability p is the threshold int(p * 2**32) against a draw of 32 bits"""
+    _seed_arg(seed)
+    fim_below, spm_below = int(_fraction_arg("fim_rate", fim_rate) * 2**32), int(_fraction_arg("spm_rate", spm_rate) * 2**32)
+    if isinstance(first_doc, bool) or not isinstance(first_doc, int):
+        raise TypeError("first_doc must be an int, not %s" % type(first_doc).__name__)
+    if not 0 <= first_doc < 2**62:
+        raise ValueError("first_doc must be in 0 .. 2**62 - 1, not %d" % first_doc)
+    return seed, fim_below, spm_below, first_doc
+
+
+def _fim_output_args(ignore_index, return_labels, return_parts, return_source, check):
+    _ignore_arg(ignore_index, "int32")
+    for name, v in (("return_labels", return_labels), ("return_parts", return_parts), ("return_source", return_source),
+                    ("check", check)):
+        if not isinstance(v, bool):
+            raise TypeError("%s must be a bool, not %s" % (name, type(v).__name__))
+
+
+def _fim_render(who, ids, n_ids, n_docs, plan_call, used, kinds, sentinels, loss_bits, ignore_index, return_labels,
+                return_parts, return_source, check):
+    """What fim_device and fim_pieces_device share: the outputs, plan_call(out_offsets, plan, kinds, err, stream) and the
+    render behind it on the current torch stream, the check."""
+    import torch
+    dev = ids.device
+    pre, suf, mid, end = sentinels
+    cap = _capi.fim_ids_bound(n_docs, n_ids, end != _capi.NO_TOKEN)
+    out_offsets = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    plan = torch.empty((max(n_docs, 1), 4), dtype=torch.int64, device=dev)
+    if kinds is None:
+        kinds = torch.empty(max(n_docs, 1), dtype=torch.int32, device=dev)
+    out_ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    labels = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if return_labels else None
+    parts = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if return_parts else None
+    source = torch.empty(max(cap, 1), dtype=torch.int64, device=dev) if return_source else None
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+    res = (out_ids, out_offsets) + tuple(t for t in (labels, parts, source) if t is not None)
+
+    def call():
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        plan_call(out_offsets.data_ptr(), plan.data_ptr(), kinds.data_ptr(), err[0:].data_ptr(), stream)
+        _capi.fim_render_device(ids.data_ptr(), plan.data_ptr(), kinds.data_ptr(), out_offsets.data_ptr(), n_docs, n_ids, pre,
+                                suf, mid, end, loss_bits, ignore_index, cap, out_ids.data_ptr(),
+                                0 if labels is None else labels.data_ptr(), 0 if parts is None else parts.data_ptr(),
+                                0 if source is None else source.data_ptr(), err[1:].data_ptr(), stream)
+        return res
+    _on_torch_stream(dev, call, used=tuple(used) + (ids, plan, kinds, err))
+    if check:
+        code = int(err.max().item())
+        if code:
+            raise ValueError("hutoken_amd: %s: device-side error %d (offsets that do not describe ids, or kinds outside 0 .. 2)"
+                             % (who, code))
+    return res
+
+
+def fim_device(ids, offsets, *, prefix_id, suffix_id, middle_id, end_id=None, seed, fim_rate=0.5, spm_rate=0.5, first_doc=0,
+               loss_on="all", ignore_index=-100, n_ids=None, return_labels=False, return_parts=False, return_source=False,
+               check=False):
+    """Fill-in-the-middle at token level, on the GPU: the ragged pair of an encode_*_packed_device call (ids int32, offsets
+    int64[n_docs + 1]) -> (out_ids int32[capacity], out_offsets int64[n_docs + 1][, labels int32[capacity]][, parts
+    int32[capacity]][, source int64[capacity]]).  Document number first_doc + i is transformed with probability fim_rate:
+    cut at two places drawn uniformly from its n + 1 gaps into prefix / middle / suffix and written as
+        PSM  prefix_id prefix suffix_id suffix middle_id middle [end_id]
+        SPM  prefix_id suffix_id suffix middle_id prefix middle [end_id]     (with probability spm_rate)
+    and copied unchanged otherwise.  (out_ids, out_offsets) is a ragged pair like the encode's: collate_padded,
+    collate_windows and SequencePacker.add take it unchanged, the packer with channels={"labels": labels}.  labels holds
+    the id where `loss_on` names the position and ignore_index elsewhere: "all", "middle" (the middle, the end sentinel
+    and plain documents) or a tuple drawn from ("plain", "prefix", "middle", "suffix", "sentinel", "end"); parts the
+    part of every position (0 plain, 1 prefix, 2 middle, 3 suffix, 4 sentinel); source the index into `ids` on document
+    tokens and -1 on sentinels, which carries token_spans_device or token_word_ids_device over: values[source].
+    The random numbers are Philox4x32-10 draws that depend on nothing but (seed, first_doc + i) -- include/hutoken_amd.h
+    states the rule in full, tests/fim_ref.py restates it in numpy -- so a document's outcome does not depend on the batch
+    around it.  seed is an int in 0 .. 2**64 - 1 and has no default: there is no hidden state.  Only the first
+    out_offsets[-1] elements are written.  On the current torch stream; synchronises only to read offsets[-1] (not with
+    n_ids=) and for check=True, which raises ValueError for offsets that do not describe ids."""
+    sentinels = _fim_sentinel_args(prefix_id, suffix_id, middle_id, end_id)
+    seed, fim_below, spm_below, first_doc = _fim_draw_args(seed, fim_rate, spm_rate, first_doc)
+    bits = _fim_loss_arg(loss_on)
+    _fim_output_args(ignore_index, return_labels, return_parts, return_source, check)
+    _ragged_args(ids, offsets, n_ids)
+    n_docs = offsets.numel() - 1
+    n_ids = _n_ids(ids, offsets, n_ids)
+    has_end = sentinels[3] != _capi.NO_TOKEN
+
+    def plan_call(d_out_offsets, d_plan, d_kinds, d_err, stream):
+        _capi.fim_plan_tokens_device(offsets.data_ptr(), n_docs, n_ids, seed, first_doc, fim_below, spm_below, has_end,
+                                     d_out_offsets, d_plan, d_kinds, d_err, stream)
+    return _fim_render("fim_device", ids, n_ids, n_docs, plan_call, (offsets,), None, sentinels, bits, ignore_index,
+                       return_labels, return_parts, return_source, check)
+
+
+def fim_cut_text_device(d_bytes, d_offsets, *, seed, fim_rate=0.5, spm_rate=0.5, first_doc=0, check=False):
+    """Fill-in-the-middle at character level, first step: the packed text of encode_packed_device (uint8 bytes, int64
+    offsets[n_docs + 1], device tensors) -> (piece_offsets int64[3 n_docs + 1], kinds int32[n_docs]).  Every document is
+    cut by the draw of fim_device over its BYTES, each cut moved back to the start of its UTF-8 character, into three
+    pieces prefix / middle / suffix (a plain document: whole, empty, empty).  No byte is copied: encode the same
+    d_bytes with piece_offsets -- ONE encode call over 3 n_docs documents -- and give its (ids, offsets) and `kinds` to
+    fim_pieces_device.  No token then straddles a cut.  On the current torch stream, never synchronises; check=True
+    does and raises ValueError for offsets that do not describe d_bytes."""
+    seed, fim_below, spm_below, first_doc = _fim_draw_args(seed, fim_rate, spm_rate, first_doc)
+    if not isinstance(check, bool):
+        raise TypeError("check must be a bool, not %s" % type(check).__name__)
+    _packed_text_args(d_bytes, d_offsets)
+    import torch
+    dev = d_bytes.device
+    n_docs, n_bytes = d_offsets.numel() - 1, d_bytes.numel()
+    pieces = torch.empty(3 * n_docs + 1, dtype=torch.int64, device=dev)
+    kinds = torch.empty(max(n_docs, 1), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.fim_cut_text_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, seed, first_doc, fim_below,
+                                  spm_below, pieces.data_ptr(), kinds.data_ptr(), err.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream)
+        return pieces, kinds
+    _on_torch_stream(dev, call, used=(d_bytes, d_offsets, err))
+    if check:
+        _raise_device_error(err, "fim_cut_text_device")
+    return pieces, kinds[:n_docs]
+
+
+def fim_pieces_device(ids, offsets, kinds, *, prefix_id, suffix_id, middle_id, end_id=None, loss_on="all", ignore_index=-100,
+                      n_ids=None, return_labels=False, return_parts=False, return_source=False, check=False):
+    """Fill-in-the-middle at character level, second step: (ids int32, offsets int64[3 n_docs + 1]) of ONE encode call over
+    the pieces of fim_cut_text_device and its `kinds` int32[n_docs] -> what fim_device returns, with the same keywords
+    less the rates and the seed: nothing is drawn here.  Document i is the pieces 3i (prefix), 3i + 1 (middle) and 3i + 2
+    (suffix); source indexes `ids`, the pieces' ids."""
+    sentinels = _fim_sentinel_args(prefix_id, suffix_id, middle_id, end_id)
+    bits = _fim_loss_arg(loss_on)
+    _fim_output_args(ignore_index, return_labels, return_parts, return_source, check)
+
+    def sizes():
+        if offsets.numel() < 1 or (offsets.numel() - 1) % 3:
+            raise ValueError("offsets must hold 3 n_docs + 1 entries, not %d" % offsets.numel())
+        if kinds.numel() != (offsets.numel() - 1) // 3:
+            raise ValueError("kinds must hold one entry per document (%d), not %d" % ((offsets.numel() - 1) // 3, kinds.numel()))
+    _device_tensors((("ids", ids, "int32"), ("offsets", offsets, "int64"), ("kinds", kinds, "int32")), sizes)
+    _on_one_gpu("the render", (("ids", ids), ("offsets", offsets), ("kinds", kinds)))
+    if n_ids is not None:
+        if isinstance(n_ids, bool) or not isinstance(n_ids, int):
+            raise TypeError("n_ids must be an int or None")
+        if n_ids < 0 or n_ids > ids.numel():
+            raise ValueError("n_ids must be in 0 .. ids.numel()")
+    n_docs = (offsets.numel() - 1) // 3
+    n_ids = _n_ids(ids, offsets, n_ids)
+    has_end = sentinels[3] != _capi.NO_TOKEN
+    if n_docs == 0:
+        import torch
+        kinds = torch.zeros(1, dtype=torch.int32, device=ids.device)  # (an empty tensor has no address)
+
+    def plan_call(d_out_offsets, d_plan, d_kinds, d_err, stream):
+        _capi.fim_plan_pieces_device(offsets.data_ptr(), d_kinds, n_docs, n_ids, has_end, d_out_offsets, d_plan, d_err, stream)
+    return _fim_render("fim_pieces_device", ids, n_ids, n_docs, plan_call, (offsets,), kinds, sentinels, bits, ignore_index,
+                       return_labels, return_parts, return_source, check)
+
+
+def batch_encode_fim(texts, max_length=None, *, prefix_id, suffix_id, middle_id, end_id=None, seed, level="char", fim_rate=0.5,
+                     spm_rate=0.5, first_doc=0, loss_on="all", ignore_index=-100, normalize=None, truncation="right",
+                     padding_side="right", pad_id=0, dtype=None, return_plan=False):
+    """A list of str -> (input_ids [n_docs, L], attention_mask, lengths, labels [n_docs, L] of input_ids' dtype[,
+    row_plan]): a fill-in-the-middle pretraining batch.  A composition of existing calls on the initialised context's GPU:
+    the upload (and normalize_packed_device), then with level="char" fim_cut_text_device, ONE encode call over the 3
+    n_docs pieces and fim_pieces_device -- no token straddles a cut -- or with level="token" one encode call over the
+    texts and fim_device; then collate_padded without bos and eos and its plan, and gather_rows of the labels with
+    fill=ignore_index.  The sentinels, seed, fim_rate, spm_rate, first_doc and loss_on: as fim_device; max_length,
+    truncation, padding_side, pad_id, dtype: as collate_padded, whose truncation cuts the rendered sequence as a whole."""
+    sentinels = dict(prefix_id=prefix_id, suffix_id=suffix_id, middle_id=middle_id, end_id=end_id)
+    _fim_sentinel_args(**sentinels)
+    _fim_draw_args(seed, fim_rate, spm_rate, first_doc)
+    _fim_loss_arg(loss_on)
+    _ignore_arg(ignore_index, "int32")
+    _out_width(dtype)
+    if level not in ("char", "token"):
+        raise ValueError("level must be 'char' or 'token', not %r" % (level,))
+    draw = dict(seed=seed, fim_rate=fim_rate, spm_rate=spm_rate, first_doc=first_doc)
+    common = dict(sentinels, loss_on=loss_on, ignore_index=ignore_index, return_labels=True)
+    if level == "token":
+        ids, oo = _texts_to_device(texts, normalize=normalize)
+        out_ids, out_offsets, labels = fim_device(ids, oo, **draw, **common)
+    else:
+        _normalize_arg(normalize)
+        if _ctx is None:
+            raise RuntimeError(_NOT_INIT)
+        if not isinstance(texts, list):
+            raise TypeError("Invalid arguments. Expected a list of strings.")
+        import torch
+        data, offs = _pack(texts)
+        dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
+        d_bytes = torch.from_numpy(data.copy()).to(dev)  # (a copy: _pack's array is a read-only view of a bytes object)
+        d_offs = torch.from_numpy(offs).to(dev)
+        with torch.cuda.device(dev):
+            if normalize is not None:
+                d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, normalize)
+            pieces, kinds = fim_cut_text_device(d_bytes, d_offs, **draw)
+            ids, oo = _on_torch_stream(dev, lambda: _encode_device("plain", d_bytes, pieces, 0, True), used=(d_bytes, pieces))
+            out_ids, out_offsets, labels = fim_pieces_device(ids, oo, kinds, **common)
     input_ids, mask, lengths, plan = collate_padded(out_ids, out_offsets, max_length, pad_id=pad_id, truncation=truncation,
                                                     padding_side=padding_side, dtype=dtype, return_plan=True)
     row_labels = gather_rows(plan, input_ids.shape[1], labels, fill=ignore_index).to(input_ids.dtype)

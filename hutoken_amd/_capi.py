@@ -140,6 +140,15 @@ SIGNATURES = {
     "hutk_chat_render_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _u32, _s32, _i64,
                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "hutk_debug_chat_span": (_i32, []),
+    "hutk_fim_ids_bound": (_i64, [_i64, _i64, _i32]),
+    "hutk_fim_cut_text_device": (_i32, [_vp, _vp, _i64, _i64, C.c_uint64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_fim_plan_tokens_device": (_i32, [_vp, _i64, _i64, C.c_uint64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_fim_plan_pieces_device": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hutk_fim_render_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _s32, _s32, _s32, _s32, _u32, _s32, _i64, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "hutk_debug_fim_span": (_i32, []),
+    "hutk_debug_fim_decide": (_i32, [C.c_uint64, _i64, _i64, _i64, _i64, _pi64]),
+    "hutk_debug_fim_locate": (_i32, [_i64, _i64, _i64, _i32, _i32, _i64, _pi64]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -154,6 +163,8 @@ MLM_SIDE_A, MLM_SIDE_B = 1, 2  # HUTK_MLM_SIDE_*
 LABELS_A, LABELS_B, LABELS_TEMPLATE, LABELS_END, LABELS_SHIFT = 1, 2, 4, 8, 16  # HUTK_LABELS_*
 CHAT_MAX_ROLES, CHAT_MAX_PART = 16, 32  # HUTK_CHAT_MAX_*
 PACKER_MAX_CHANNELS = 4  # HUTK_PACKER_MAX_CHANNELS
+FIM_PLAIN, FIM_PSM, FIM_SPM = 0, 1, 2  # HUTK_FIM_*: the kinds
+FIM_PARTS = ("plain", "prefix", "middle", "suffix", "sentinel")  # HUTK_FIM_PART_*: a part's number is its index here
 
 _lib = None
 
@@ -1008,6 +1019,65 @@ class ChatTemplate(_Owner):
 
 def chat_span():
     return load().hutk_debug_chat_span()
+
+
+def fim_ids_bound(n_docs, n_ids, has_end):
+    """hutk_fim_ids_bound (host only): an upper bound of the ids a fill-in-the-middle render of these sizes writes."""
+    n = load().hutk_fim_ids_bound(n_docs, n_ids, 1 if has_end else 0)
+    if n < 0:
+        raise_for(-n)
+    return n
+
+
+def fim_cut_text_device(d_bytes, d_offsets, n_docs, n_bytes, seed, first_doc, fim_below, spm_below, d_piece_offsets, d_kinds,
+                        d_err=0, stream=0):
+    """hutk_fim_cut_text_device on raw device pointers (ints); the thresholds are ints in 0 .. 2**32; asynchronous on
+    `stream`."""
+    raise_for(load().hutk_fim_cut_text_device(d_bytes or None, d_offsets or None, n_docs, n_bytes, seed, first_doc, fim_below,
+                                              spm_below, d_piece_offsets or None, d_kinds or None, d_err or None,
+                                              stream or None))
+
+
+def fim_plan_tokens_device(d_offsets, n_docs, n_ids, seed, first_doc, fim_below, spm_below, has_end, d_out_offsets, d_plan,
+                           d_kinds, d_err=0, stream=0):
+    """hutk_fim_plan_tokens_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_fim_plan_tokens_device(d_offsets or None, n_docs, n_ids, seed, first_doc, fim_below, spm_below,
+                                                 1 if has_end else 0, d_out_offsets or None, d_plan or None, d_kinds or None,
+                                                 d_err or None, stream or None))
+
+
+def fim_plan_pieces_device(d_piece_id_offsets, d_kinds, n_docs, n_ids, has_end, d_out_offsets, d_plan, d_err=0, stream=0):
+    """hutk_fim_plan_pieces_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_fim_plan_pieces_device(d_piece_id_offsets or None, d_kinds or None, n_docs, n_ids,
+                                                 1 if has_end else 0, d_out_offsets or None, d_plan or None, d_err or None,
+                                                 stream or None))
+
+
+def fim_render_device(d_ids, d_plan, d_kinds, d_out_offsets, n_docs, n_ids, pre_id, suf_id, mid_id, end_id, loss_parts,
+                      ignore_index, out_cap, d_out_ids, d_labels=0, d_parts=0, d_src=0, d_err=0, stream=0):
+    """hutk_fim_render_device on raw device pointers (ints); end_id NO_TOKEN: none; asynchronous on `stream`."""
+    raise_for(load().hutk_fim_render_device(d_ids or None, d_plan or None, d_kinds or None, d_out_offsets or None, n_docs,
+                                            n_ids, pre_id, suf_id, mid_id, end_id, loss_parts, ignore_index, out_cap,
+                                            d_out_ids or None, d_labels or None, d_parts or None, d_src or None,
+                                            d_err or None, stream or None))
+
+
+def fim_span():
+    return load().hutk_debug_fim_span()
+
+
+def fim_decide(seed, doc, length, fim_below, spm_below):
+    """hutk_debug_fim_decide (host only) -> (kind, lo, hi)"""
+    out = (_i64 * 3)()
+    raise_for(load().hutk_debug_fim_decide(seed, doc, length, fim_below, spm_below, out))
+    return out[0], out[1], out[2]
+
+
+def fim_locate(n, lo, hi, kind, has_end, p):
+    """hutk_debug_fim_locate (host only) -> (part, index inside the document or the sentinel's number)"""
+    out = (_i64 * 2)()
+    raise_for(load().hutk_debug_fim_locate(n, lo, hi, kind, 1 if has_end else 0, p, out))
+    return out[0], out[1]
 
 
 NORMALIZER_INFO = ["format_version", "unidata", "blob_bytes", "chunk_bytes", "pairs", "decomposition_words", "lead_bytes",

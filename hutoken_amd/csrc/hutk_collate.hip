@@ -23,7 +23,10 @@
 // (k_rows_span_corrupt).  In front of the layouts stands the chat render:
 // the turns of conversations, one encoded document each, become one sequence per conversation with role headers,
 // end-of-turn markers, loss labels, turn ids and source indices -- a ragged pair again, which every layout above takes
-// (ChatTurns through the rows scan, k_chat_offsets, k_chat_render: the packed layout's shape).  Behind the packed layout
+// (ChatTurns through the rows scan, k_chat_offsets, k_chat_render: the packed layout's shape).  Beside it stands the
+// fill-in-the-middle render (the rule is hutk_fim.h): a document is cut into prefix / middle /
+// suffix, at tokens or -- on the packed text, before the encode -- at characters, and re-ordered behind three sentinels,
+// a ragged pair again (k_fim_cut, FimDocs through the rows scan, k_fim_plan, k_fim_render).  Behind the packed layout
 // stand the packed rows for training: per-token channels that the packer moves along with the ids
 // (k_collate_packed_ch, k_collate_flush_ch: siblings that share the packed kernels' body), cu_seqlens from the segment
 // ids (CuStarts through the rows count and scan, k_cu_write, k_cu_gaps) and the loss labels of packed rows
@@ -40,6 +43,7 @@
 #include <string>
 #include <type_traits>
 
+#include "hutk_fim.h"
 #include "hutk_host.h"
 #include "hutk_philox.h"
 #include "hutk_wave.h"
@@ -976,6 +980,260 @@ __global__ __launch_bounds__(TB) void k_chat_render(const ChatArgs a) {
         chat_store(a.out_ids, a.wide & 1, at, cnt, vi);
         chat_store(a.labels, a.wide & 2, at, cnt, vl);
         if (a.turn_ids) chat_store(a.turn_ids, a.wide & 4, at, cnt, vt);
+        if (a.src) chat_store(a.src, a.wide & 8, at, cnt, vs);
+    }
+}
+
+// ---- fill-in-the-middle ---------------------------------------------------------------------------------------------
+// A render step between encode and collation, like the chat render (include/hutoken_amd.h): a
+// document is cut into prefix / middle / suffix and re-ordered behind three sentinels (hutk_fim.h holds the rule).  The
+// cuts are drawn per document at token level (FimDocs with kinds_in == NULL), or were drawn on the packed text before
+// the encode (k_fim_cut) and are read back from the offsets of the 3 n_docs encoded pieces (kinds_in given).
+// out_offsets, the exclusive scan of the rendered lengths, is one more instantiation of the rows scan (FimDocs); the
+// plan row (src0, n, lo, hi) and the kind of every document are written by one thread each (k_fim_plan); the fill has
+// the chat render's shape with ONE level of search: a workgroup owns FIM_SPAN output positions, one wavefront finds the
+// span's first document on out_offsets, the documents that start inside the span are marked in LDS (empty ones mark
+// nothing) and one workgroup scan turns the marks into "document of this position".
+constexpr int FIM_SPAN = 2048;  // output positions per workgroup (8 per thread in the scan, 4 in the stores)
+constexpr int FIM_PER = FIM_SPAN / TB;
+
+struct FimDoc {
+    int32_t kind;
+    int64_t src0, n, lo, hi;
+};
+
+// Document i as the plan sees it, and "rendered length of document i" for the rows scan.  What cannot be (offsets that
+// decrease or leave the ids, a kind outside 0 .. 2) is reported and gives a plain document of no ids: it is left out.
+struct FimDocs {
+    const int64_t* offs;      // tokens: [n_docs + 1] into the ids; pieces: [3 n_docs + 1]
+    const int32_t* kinds_in;  // NULL: token level, the cuts are drawn here
+    int64_t n_docs, n_ids, first_doc;
+    uint64_t seed, fim_below, spm_below;
+    int32_t E;
+    __device__ FimDoc doc(int64_t i, int32_t* err) const {
+        FimDoc d{hutk::FIM_PLAIN, 0, 0, 0, 0};
+        if (!kinds_in) {
+            if (i == 0 && (offs[0] != 0 || offs[n_docs] != n_ids)) note_error(err, HUTK_E_ARG);
+            const int64_t a = offs[i], n = offs[i + 1] - a;
+            if (a < 0 || n < 0 || a > n_ids || n > n_ids - a) {
+                note_error(err, HUTK_E_ARG);
+                return d;
+            }
+            const hutk::FimCut c = hutk::fim_decide(seed, first_doc + i, n, fim_below, spm_below);
+            return FimDoc{c.kind, a, n, c.lo, c.hi};
+        }
+        if (i == 0 && (offs[0] != 0 || offs[3 * n_docs] != n_ids)) note_error(err, HUTK_E_ARG);
+        const int64_t a = offs[3 * i], b = offs[3 * i + 1], c = offs[3 * i + 2], e = offs[3 * i + 3];
+        const int32_t kind = kinds_in[i];
+        if (a < 0 || b < a || c < b || e < c || e > n_ids || kind < hutk::FIM_PLAIN || kind > hutk::FIM_SPM) {
+            note_error(err, HUTK_E_ARG);
+            return d;
+        }
+        return FimDoc{kind, a, e - a, b - a, c - a};
+    }
+    __device__ int64_t operator()(int64_t i, int32_t* err) const {
+        const FimDoc d = doc(i, err);
+        return hutk::fim_length(d.n, d.kind, E);
+    }
+};
+
+// One thread per document: its plan row and, at token level, its kind.  (The scan in front of it has reported what is
+// wrong with a document.)
+__global__ __launch_bounds__(TB) void k_fim_plan(const FimDocs docs, int64_t* plan, int32_t* kinds_out) {
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= docs.n_docs) return;
+    const FimDoc d = docs.doc(i, nullptr);
+    plan[4 * i] = d.src0;
+    plan[4 * i + 1] = d.n;
+    plan[4 * i + 2] = d.lo;
+    plan[4 * i + 3] = d.hi;
+    if (kinds_out) kinds_out[i] = d.kind;
+}
+
+struct FimCutArgs {
+    const uint8_t* bytes;
+    const int64_t* offs;  // [n_docs + 1] into the bytes
+    int64_t n_docs, n_bytes, first_doc;
+    uint64_t seed, fim_below, spm_below;
+    int64_t* pieces;  // [3 n_docs + 1]
+    int32_t* kinds;   // [n_docs]
+    int32_t* err;
+};
+
+// a cut of a document of `len` bytes at `base`, moved back to the start of its UTF-8 character: at most three steps
+__device__ __forceinline__ int64_t fim_char_start(const uint8_t* base, int64_t len, int64_t pos) {
+#pragma unroll
+    for (int step = 0; step < 3; step++) {
+        if (pos <= 0 || pos >= len || (base[pos] & 0xC0) != 0x80) break;
+        pos--;
+    }
+    return pos;
+}
+
+// The text cut, one thread per document: the draw, at most six byte reads, four stores.  A document whose offsets cannot
+// be is reported and counted as plain with length 0.
+__global__ __launch_bounds__(TB) void k_fim_cut(const FimCutArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= a.n_docs) return;
+    if (i == 0) {
+        if (a.offs[0] != 0 || a.offs[a.n_docs] != a.n_bytes) note_error(a.err, HUTK_E_ARG);
+        a.pieces[3 * a.n_docs] = a.n_bytes;
+    }
+    int64_t s = a.offs[i], len = a.offs[i + 1] - s;
+    if (s < 0 || len < 0 || s > a.n_bytes || len > a.n_bytes - s) {
+        note_error(a.err, HUTK_E_ARG);
+        s = clamp_i64(s, 0, a.n_bytes);
+        len = 0;
+    }
+    const hutk::FimCut c = hutk::fim_decide(a.seed, a.first_doc + i, len, a.fim_below, a.spm_below);
+    int64_t lo = c.lo, hi = c.hi;
+    if (c.kind != hutk::FIM_PLAIN) {
+        lo = fim_char_start(a.bytes + s, len, lo);
+        hi = fim_char_start(a.bytes + s, len, hi);
+    }
+    a.pieces[3 * i] = s;
+    a.pieces[3 * i + 1] = s + lo;
+    a.pieces[3 * i + 2] = s + hi;
+    a.kinds[i] = c.kind;
+}
+
+struct FimArgs {
+    const int32_t* ids;
+    const int64_t* plan;   // [n_docs][4]: src0, n, lo, hi
+    const int32_t* kinds;  // [n_docs]
+    const int64_t* oo;     // [n_docs + 1]: out_offsets
+    int64_t n_docs, n_ids, out_cap;
+    int32_t pre, suf, mid, end, E;
+    uint32_t loss_parts;
+    int32_t ignore;
+    int32_t *out_ids, *labels, *parts;  // labels, parts: may be NULL
+    int64_t* src;                       // may be NULL
+    int32_t* err;
+    int32_t wide;  // bit 0 out_ids, 1 labels, 2 parts, 3 src: the pointer is 16-byte aligned
+};
+
+// A plan row and a kind that fit the ids: 0 <= lo <= hi <= n, the document inside ids[0, n_ids), a kind of 0 .. 2.
+__device__ __forceinline__ bool fim_doc_fits(const FimDoc& d, int64_t n_ids) {
+    return d.kind >= hutk::FIM_PLAIN && d.kind <= hutk::FIM_SPM && d.lo >= 0 && d.lo <= d.hi && d.hi <= d.n && d.src0 >= 0 &&
+           d.src0 <= n_ids && d.n <= n_ids - d.src0;
+}
+
+// Nothing is trusted: every index into out_offsets, the plan, the kinds and the ids is checked before it is used, the
+// marks lie inside the span by construction, and a position is written only below min(n_out, out_cap).  What does not
+// fit is reported with HUTK_E_ARG and leaves id 0, ignore_index, part -1, source -1 at its place.
+__global__ __launch_bounds__(TB) void k_fim_render(const FimArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t s_d[FIM_SPAN];  // marks (document - i0 at its start), then their running maximum
+    __shared__ int32_t s_w[TB / 64];
+    __shared__ int64_t s_first;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t n_out = a.oo[a.n_docs];
+    if (blockIdx.x == 0 && tid == 0) {
+        if (a.oo[0] != 0) note_error(a.err, HUTK_E_ARG);
+        if (n_out > a.out_cap) note_error(a.err, HUTK_E_CAPACITY);
+    }
+    const int64_t x0 = (int64_t)blockIdx.x * FIM_SPAN;
+    int64_t x1 = x0 + FIM_SPAN;
+    if (x1 > n_out) x1 = n_out;
+    if (x1 > a.out_cap) x1 = a.out_cap;
+    if (x0 >= x1) return;
+    const int32_t n = (int32_t)(x1 - x0);
+
+    for (int i = tid; i < FIM_SPAN; i += TB) s_d[i] = 0;
+    // the last document that begins at or before the span's start: of several at one place (empty ones) the last, the
+    // one the position belongs to
+    if (tid < 64) {
+        const int64_t i0 = hutk::wave_count_leading(a.n_docs, [&](int64_t i) { return a.oo[i] <= x0; }) - 1;
+        if (tid == 0) s_first = i0 < 0 ? 0 : i0;  // (out_offsets[0] != 0: reported above)
+    }
+    __syncthreads();
+    const int64_t i0 = s_first;
+
+    // The starts inside the span, a thread per document.  Empty sequences mark nothing.  Here every document that starts
+    // in (x0, x1] is also held against out_offsets: its rendered length must be the distance to the next start.
+    for (int64_t i = i0 + 1 + tid; i < a.n_docs; i += TB) {
+        const int64_t o = a.oo[i];
+        if (o > x1) break;
+        const int64_t len = a.oo[i + 1] - o;
+        const int32_t kind = a.kinds[i];
+        if (kind < hutk::FIM_PLAIN || kind > hutk::FIM_SPM || len != hutk::fim_length(a.plan[4 * i + 1], kind, a.E)) note_error(a.err, HUTK_E_ARG);
+        if (o > x0 && o < x1 && len > 0) s_d[o - x0] = (int32_t)(i - i0);
+    }
+    __syncthreads();
+
+    // workgroup scan over the marks: their running maximum (they grow along the span)
+    {
+        int32_t d[FIM_PER];
+        const int4 dl = *reinterpret_cast<const int4*>(&s_d[tid * FIM_PER]), dh = *reinterpret_cast<const int4*>(&s_d[tid * FIM_PER + 4]);
+        d[0] = dl.x; d[1] = dl.y; d[2] = dl.z; d[3] = dl.w; d[4] = dh.x; d[5] = dh.y; d[6] = dh.z; d[7] = dh.w;
+        int32_t m = 0;
+#pragma unroll
+        for (int e = 0; e < FIM_PER; e++) {
+            m = d[e] > m ? d[e] : m;
+            d[e] = m;
+        }
+        const int32_t t = hutk::wave_incl_max(m, lane);
+        if (lane == 63) s_w[w] = t;
+        int32_t before = __shfl_up(t, 1);
+        if (lane == 0) before = 0;
+        __syncthreads();
+        for (int u = 0; u < w; u++) before = s_w[u] > before ? s_w[u] : before;
+#pragma unroll
+        for (int e = 0; e < FIM_PER; e++) d[e] = d[e] > before ? d[e] : before;
+        *reinterpret_cast<int4*>(&s_d[tid * FIM_PER]) = make_int4(d[0], d[1], d[2], d[3]);
+        *reinterpret_cast<int4*>(&s_d[tid * FIM_PER + 4]) = make_int4(d[4], d[5], d[6], d[7]);
+    }
+    __syncthreads();
+
+    // The elements, four neighbours per thread and consecutive threads on consecutive groups.  A thread reads a
+    // document's two offsets, plan row and kind when it meets another document, which among four neighbours is rare; a
+    // position is then a few comparisons (fim_locate) and at most one id.
+    for (int32_t p = tid * 4; p < n; p += TB * 4) {
+        int32_t vi[4], vl[4], vp[4];
+        int64_t vs[4];
+        int64_t ci = -1, o = 0, len = 0;  // the document held in registers: its start and its rendered length
+        FimDoc d{0, 0, 0, 0, 0};
+        bool fits = false;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            vi[e] = 0;
+            vl[e] = a.ignore;
+            vp[e] = -1;
+            vs[e] = -1;
+            if (p + e >= n) continue;
+            const int64_t i = i0 + s_d[p + e];
+            if (i != ci) {
+                ci = i;
+                fits = i >= 0 && i < a.n_docs;
+                if (fits) {
+                    o = a.oo[i];
+                    d = FimDoc{a.kinds[i], a.plan[4 * i], a.plan[4 * i + 1], a.plan[4 * i + 2], a.plan[4 * i + 3]};
+                    fits = fim_doc_fits(d, a.n_ids);
+                    len = fits ? hutk::fim_length(d.n, d.kind, a.E) : 0;
+                    if (fits && a.oo[i + 1] - o != len) note_error(a.err, HUTK_E_ARG);  // (out_offsets is not the scan)
+                }
+            }
+            const int64_t q = x0 + p + e - o;
+            const hutk::FimPlace at = fits ? hutk::fim_locate(d.n, d.lo, d.hi, d.kind, a.E, q) : hutk::FimPlace{-1, -1};
+            if (at.part < 0) {
+                note_error(a.err, HUTK_E_ARG);
+                continue;
+            }
+            if (at.part == hutk::FIM_PART_SENTINEL) {
+                vi[e] = at.v == hutk::FIM_PRE ? a.pre : at.v == hutk::FIM_SUF ? a.suf : at.v == hutk::FIM_MID ? a.mid : a.end;
+            } else {
+                const int64_t idx = d.src0 + at.v;  // (inside the ids: the document is, and v < n)
+                vi[e] = a.ids[idx];
+                vs[e] = idx;
+            }
+            vp[e] = at.part;
+            const bool end_loss = at.part == hutk::FIM_PART_SENTINEL && at.v == hutk::FIM_END && (a.loss_parts & HUTK_FIM_LOSS_END);
+            if (((a.loss_parts >> at.part) & 1u) || end_loss) vl[e] = vi[e];
+        }
+        const int64_t at = x0 + p;
+        const int cnt = n - p < 4 ? n - p : 4;
+        chat_store(a.out_ids, a.wide & 1, at, cnt, vi);
+        if (a.labels) chat_store(a.labels, a.wide & 2, at, cnt, vl);
+        if (a.parts) chat_store(a.parts, a.wide & 4, at, cnt, vp);
         if (a.src) chat_store(a.src, a.wide & 8, at, cnt, vs);
     }
 }
@@ -2193,6 +2451,37 @@ int chat_sizes(const char* who, const hutk_chat_template* t, int64_t n_conv, int
     return HUTK_OK;
 }
 
+// What the fill-in-the-middle calls refuse alike before anything else (a call without a draw passes 0 for the last three)
+int fim_sizes(const char* who, int64_t n_docs, int64_t n_ids, int64_t first_doc, int64_t fim_below, int64_t spm_below) {
+    constexpr int64_t ONE = (int64_t)1 << 32;
+    if (n_docs < 0 || n_ids < 0 || n_docs > INT32_MAX - 1)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": counts must not be negative, n_docs below 2^31 - 1");
+    if (first_doc < 0 || first_doc > INT64_MAX - n_docs)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": first_doc must not be negative, first_doc + n_docs below 2^63");
+    if (fim_below < 0 || fim_below > ONE || spm_below < 0 || spm_below > ONE)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": the thresholds must lie in 0 .. 2^32");
+    return HUTK_OK;
+}
+
+// What the two plan calls do alike: the rows scan over "rendered length of document i", then the plan rows
+int fim_plan(const char* who, FimDocs& docs, int64_t n_docs, int64_t n_ids, int has_end, int64_t* d_out_offsets,
+             int64_t* d_plan, int32_t* d_kinds_out, int32_t* d_err, hipStream_t st) {
+    if (!d_out_offsets || (n_docs > 0 && (!docs.offs || !d_plan || (!docs.kinds_in && !d_kinds_out))))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(docs.offs, 8) || !aligned_to(d_out_offsets, 8) || !aligned_to(d_plan, 8) || !aligned_to(d_kinds_out, 4) ||
+        !aligned_to(d_err, 4))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+    if (int rc = device_present(who)) return rc;
+    docs.n_docs = n_docs;
+    docs.n_ids = n_ids;
+    docs.E = has_end ? 1 : 0;
+    if (int rc = rows_scan(docs, n_docs, d_out_offsets, d_err, st)) return rc;  // (clears *d_err; n_docs == 0: out_offsets[0] = 0)
+    if (n_docs == 0) return HUTK_OK;
+    hipLaunchKernelGGL(k_fim_plan, dim3((unsigned)((n_docs + TB - 1) / TB)), dim3(TB), 0, st, docs, d_plan, d_kinds_out);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
 }  // namespace
 
 struct hutk_packer {
@@ -3284,5 +3573,131 @@ int hutk_chat_render_device(const hutk_chat_template* t, const int32_t* d_ids, c
 }
 
 int hutk_debug_chat_span(void) { return CHAT_SPAN; }
+
+int64_t hutk_fim_ids_bound(int64_t n_docs, int64_t n_ids, int has_end) {
+    if (fim_sizes("hutk_fim_ids_bound", n_docs, n_ids, 0, 0, 0)) return -HUTK_E_ARG;
+    return n_ids + (3 + (has_end ? 1 : 0)) * n_docs;
+}
+
+int hutk_fim_cut_text_device(const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes, uint64_t seed,
+                             int64_t first_doc, int64_t fim_below, int64_t spm_below, int64_t* d_piece_offsets,
+                             int32_t* d_kinds, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_fim_cut_text_device";
+    if (int rc = fim_sizes(who, n_docs, n_bytes, first_doc, fim_below, spm_below)) return rc;
+    if (n_docs == 0 && n_bytes != 0) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": bytes without documents");
+    if (!d_piece_offsets || (n_docs > 0 && (!d_offsets || !d_kinds || (n_bytes > 0 && !d_bytes))))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(d_offsets, 8) || !aligned_to(d_piece_offsets, 8) || !aligned_to(d_kinds, 4) || !aligned_to(d_err, 4))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+    if (int rc = device_present(who)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_docs == 0) {
+        HUTK_HIP_TRY(hipMemsetAsync(d_piece_offsets, 0, sizeof(int64_t), st));
+        return HUTK_OK;
+    }
+    const FimCutArgs a{d_bytes, d_offsets, n_docs, n_bytes, first_doc, seed, (uint64_t)fim_below, (uint64_t)spm_below,
+                       d_piece_offsets, d_kinds, d_err};
+    hipLaunchKernelGGL(k_fim_cut, dim3((unsigned)((n_docs + TB - 1) / TB)), dim3(TB), 0, st, a);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_fim_plan_tokens_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, uint64_t seed, int64_t first_doc,
+                                int64_t fim_below, int64_t spm_below, int has_end, int64_t* d_out_offsets, int64_t* d_plan,
+                                int32_t* d_kinds, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_fim_plan_tokens_device";
+    if (int rc = fim_sizes(who, n_docs, n_ids, first_doc, fim_below, spm_below)) return rc;
+    FimDocs docs = {};
+    docs.offs = d_offsets;
+    docs.first_doc = first_doc;
+    docs.seed = seed;
+    docs.fim_below = (uint64_t)fim_below;
+    docs.spm_below = (uint64_t)spm_below;
+    return fim_plan(who, docs, n_docs, n_ids, has_end, d_out_offsets, d_plan, d_kinds, d_err, (hipStream_t)hip_stream);
+}
+
+int hutk_fim_plan_pieces_device(const int64_t* d_piece_id_offsets, const int32_t* d_kinds, int64_t n_docs, int64_t n_ids,
+                                int has_end, int64_t* d_out_offsets, int64_t* d_plan, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_fim_plan_pieces_device";
+    if (int rc = fim_sizes(who, n_docs, n_ids, 0, 0, 0)) return rc;
+    if (n_docs > 0 && !d_kinds) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(d_kinds, 4)) return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+    FimDocs docs = {};
+    docs.offs = d_piece_id_offsets;
+    docs.kinds_in = d_kinds;
+    return fim_plan(who, docs, n_docs, n_ids, has_end, d_out_offsets, d_plan, nullptr, d_err, (hipStream_t)hip_stream);
+}
+
+int hutk_fim_render_device(const int32_t* d_ids, const int64_t* d_plan, const int32_t* d_kinds, const int64_t* d_out_offsets,
+                           int64_t n_docs, int64_t n_ids, int32_t pre_id, int32_t suf_id, int32_t mid_id, int32_t end_id,
+                           uint32_t loss_parts, int32_t ignore_index, int64_t out_cap, int32_t* d_out_ids, int32_t* d_labels,
+                           int32_t* d_parts, int64_t* d_src, int32_t* d_err, void* hip_stream) {
+    const char* who = "hutk_fim_render_device";
+    if (int rc = fim_sizes(who, n_docs, n_ids, 0, 0, 0)) return rc;
+    if (pre_id == HUTK_NO_TOKEN || suf_id == HUTK_NO_TOKEN || mid_id == HUTK_NO_TOKEN)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": pre_id, suf_id and mid_id must not be HUTK_NO_TOKEN");
+    if (out_cap < 0 || (loss_parts >> 6) != 0)
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": out_cap must not be negative and loss_parts name parts 0 .. 4 and HUTK_FIM_LOSS_END");
+    if (n_docs > 0 && (!d_plan || !d_kinds || !d_out_offsets || (n_ids > 0 && !d_ids) || (out_cap > 0 && !d_out_ids)))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is NULL");
+    if (!aligned_to(d_plan, 8) || !aligned_to(d_out_offsets, 8) || !aligned_to(d_src, 8) || !aligned_to(d_ids, 4) ||
+        !aligned_to(d_kinds, 4) || !aligned_to(d_out_ids, 4) || !aligned_to(d_labels, 4) || !aligned_to(d_parts, 4) ||
+        !aligned_to(d_err, 4))
+        return hutk::api_set_error(HUTK_E_ARG, std::string(who) + ": a buffer is not aligned to its element type");
+    if (int rc = device_present(who)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_err) HUTK_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int32_t), st));
+    if (n_docs == 0) return HUTK_OK;
+    // n_out is on the device only: as many workgroups as the capacity holds spans (one that finds its span behind n_out
+    // returns at once), at least the one that reports a capacity of nothing
+    int64_t blocks = (out_cap + FIM_SPAN - 1) / FIM_SPAN;
+    if (blocks < 1) blocks = 1;
+    if (blocks > INT32_MAX) return hutk::api_set_error(HUTK_E_UNSUPPORTED, std::string(who) + ": the batch is too large for one launch");
+    FimArgs a = {};
+    a.ids = d_ids;
+    a.plan = d_plan;
+    a.kinds = d_kinds;
+    a.oo = d_out_offsets;
+    a.n_docs = n_docs;
+    a.n_ids = n_ids;
+    a.out_cap = out_cap;
+    a.pre = pre_id;
+    a.suf = suf_id;
+    a.mid = mid_id;
+    a.end = end_id;
+    a.E = end_id != HUTK_NO_TOKEN;
+    a.loss_parts = loss_parts;
+    a.ignore = ignore_index;
+    a.out_ids = d_out_ids;
+    a.labels = d_labels;
+    a.parts = d_parts;
+    a.src = d_src;
+    a.err = d_err;
+    a.wide = (aligned_to(d_out_ids, 16) ? 1 : 0) | (aligned_to(d_labels, 16) ? 2 : 0) | (aligned_to(d_parts, 16) ? 4 : 0) |
+             (aligned_to(d_src, 16) ? 8 : 0);
+    hipLaunchKernelGGL(k_fim_render, dim3((unsigned)blocks), dim3(TB), 0, st, a);
+    HUTK_HIP_TRY(hipGetLastError());
+    return HUTK_OK;
+}
+
+int hutk_debug_fim_span(void) { return FIM_SPAN; }
+
+int hutk_debug_fim_decide(uint64_t seed, int64_t doc, int64_t len, int64_t fim_below, int64_t spm_below, int64_t out3[3]) {
+    constexpr int64_t ONE = (int64_t)1 << 32;
+    if (!out3 || fim_below < 0 || fim_below > ONE || spm_below < 0 || spm_below > ONE)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_debug_fim_decide: out3 is NULL or a threshold lies outside 0 .. 2^32");
+    const hutk::FimCut c = hutk::fim_decide(seed, doc, len, (uint64_t)fim_below, (uint64_t)spm_below);
+    out3[0] = c.kind, out3[1] = c.lo, out3[2] = c.hi;
+    return HUTK_OK;
+}
+
+int hutk_debug_fim_locate(int64_t n, int64_t lo, int64_t hi, int kind, int has_end, int64_t p, int64_t out2[2]) {
+    if (!out2 || kind < hutk::FIM_PLAIN || kind > hutk::FIM_SPM || lo < 0 || lo > hi || hi > n)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_debug_fim_locate: out2 is NULL, a kind outside 0 .. 2 or cuts that are not 0 <= lo <= hi <= n");
+    const hutk::FimPlace at = hutk::fim_locate(n, lo, hi, kind, has_end ? 1 : 0, p);
+    out2[0] = at.part, out2[1] = at.v;
+    return HUTK_OK;
+}
 
 }  // extern "C"

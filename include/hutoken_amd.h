@@ -581,6 +581,98 @@ int hutk_chat_render_device(const hutk_chat_template* t, const int32_t* d_ids, c
                             int32_t* d_labels, int32_t* d_turn_ids, int64_t* d_src, int32_t* d_err, void* hip_stream);
 int hutk_debug_chat_span(void);
 
+/* ---- fill-in-the-middle (FIM): PSM and SPM, cut at tokens or at characters ----------------------------------------
+ * A render step between encode and collation, of the chat render's shape: a document is cut into prefix / middle /
+ * suffix and re-ordered behind three sentinel ids, so that a left-to-right model learns to infill (Bavarian et al. 2022).
+ * A ragged pair (d_ids, d_offsets) goes in and a new ragged pair (d_out_ids, d_out_offsets) comes out, which every layout
+ * above takes unchanged, plus per-token arrays along the same offsets.  THE RULE (csrc/hutk_fim.h holds it as code,
+ * tests/fim_ref.py restates it in numpy):
+ *   CONSTANTS.  The sentinels pre_id, suf_id, mid_id are required; end_id is optional (HUTK_NO_TOKEN = absent) and is
+ *     appended behind the middle of transformed documents only; E = 1 with an end_id, else 0.  Kinds: 0 plain, 1 PSM,
+ *     2 SPM.  Parts: 0 plain, 1 prefix, 2 middle, 3 suffix, 4 sentinel; loss_parts is a mask of 1 << part, and
+ *     HUTK_FIM_LOSS_END (1 << 5) in it names the end sentinel alone, for loss on the middle and what closes it.
+ *   DRAW.  Document number d = first_doc + i draws (u0, u1, u2, u3) = draw(seed, d, 0, DRAW_FIM) with DRAW_FIM = 4:
+ *     Philox4x32-10 with key (low32(seed), high32(seed)) and counter (low32(d), high32(d), 0, 4) (csrc/hutk_philox.h).
+ *     With len the document's length it is TRANSFORMED iff u0 < fim_below and 1 <= len < 2^31, and SPM iff transformed
+ *     and u1 < spm_below, else PSM.  a = (uint64(u2) * (len + 1)) >> 32, b = (uint64(u3) * (len + 1)) >> 32,
+ *     lo = min(a, b), hi = max(a, b), so 0 <= lo <= hi <= len.  The thresholds are integers in 0 .. 2^32, as in
+ *     hutk_rows_mlm_device: a probability p is int(p * 2^32).  A plain document has lo = hi = len.
+ *   TOKEN LEVEL.  len is the document's id count n.  With its ids x[0..n): prefix = x[0..lo), middle = x[lo..hi),
+ *     suffix = x[hi..n); P = lo, M = hi - lo, S = n - hi.
+ *       plain  x unchanged: n outputs of part 0.
+ *       PSM    pre prefix suf suffix mid middle [end]: position 0 is pre, 1 .. P is x[p - 1], P + 1 is suf,
+ *              P + 2 .. P + S + 1 is x[hi + p - P - 2], P + S + 2 is mid, the M positions behind it are x[lo + ..], the
+ *              last is end.
+ *       SPM    pre suf suffix mid prefix middle [end] (the paper's variant 2, what Megatron and bigcode call SPM):
+ *              0 is pre, 1 is suf, 2 .. S + 1 is the suffix, S + 2 is mid, the P positions behind it are the prefix, the
+ *              M positions behind those the middle, the last is end.
+ *     A transformed document has n + 3 + E outputs, and d_out_offsets is the exclusive scan of the outputs.  Per token:
+ *       d_out_ids int32   the id
+ *       d_labels int32    (may be NULL) the id where loss_parts has the position's part (or HUTK_FIM_LOSS_END, on the
+ *                         end sentinel), else ignore_index
+ *       d_parts int32     (may be NULL) the part
+ *       d_src int64       (may be NULL) the index into d_ids on document tokens, -1 on sentinels: the chat render's
+ *                         source
+ *     Example: x = 10 11 12 13 14, lo = 1, hi = 3, sentinels 1 / 2 / 3, end 4:
+ *       PSM  1 10 2 13 14 3 11 12 4   source -1 0 -1 3 4 -1 1 2 -1
+ *       SPM  1 2 13 14 3 10 11 12 4   source -1 -1 3 4 -1 0 1 2 -1
+ *   CHARACTER LEVEL.  hutk_fim_cut_text_device cuts the packed text (d_bytes, d_offsets int64[n_docs + 1]) before it is
+ *     encoded, so that no token straddles a cut.  len is the document's byte count; lo and hi come from the same draw;
+ *     each cut then moves back to a UTF-8 character start: while 0 < pos < len, bytes[pos] is in 0x80 .. 0xBF and fewer
+ *     than three steps were taken, pos -= 1.  It writes d_piece_offsets int64[3 n_docs + 1] -- the document's start,
+ *     start + lo, start + hi for each document, then the end of the text -- and d_kinds int32[n_docs].  The bytes are not
+ *     copied: the same d_bytes is encoded with the new offsets as 3 n_docs documents by ONE encode call.  A plain
+ *     document is the pieces (whole, empty, empty), so its ids are those of the unsplit document.
+ *     hutk_fim_plan_pieces_device then reads lo / hi / n of document i from the ids' offsets [3i .. 3i + 3] and the
+ *     kind from d_kinds; it draws nothing.  The render is the same call as at token level.
+ * The calls:
+ *   the ids bound   host only: n_ids + (3 + E) * n_docs, at least n_out; -HUTK_E_ARG for sizes the other calls refuse.
+ *   the text cut    one launch.  *d_err receives HUTK_E_ARG for offsets whose ends are not 0 and n_bytes or that
+ *                   decrease; such a document counts as plain with length 0.  n_docs == 0 writes
+ *                   d_piece_offsets[0] = 0 only (n_bytes must then be 0: HUTK_E_ARG otherwise).
+ *   the plan calls  write d_out_offsets int64[n_docs + 1] (the rows scan of the windows: count, scan, write, sharing
+ *                   its per-device buffer and its rule), d_plan int64[n_docs][4] = (src0, n, lo, hi) with src0 the
+ *                   document's first id, and at token level d_kinds.  *d_err receives HUTK_E_ARG for offsets that do not
+ *                   describe the ids and, from pieces, a kind outside 0 .. 2; such a document counts as plain with no
+ *                   ids.  n_docs == 0 writes d_out_offsets[0] = 0 only.
+ *   the render      writes the per-token arrays.  Nothing is trusted: *d_err receives HUTK_E_ARG for a plan row that is
+ *                   not 0 <= lo <= hi <= n with src0 + n <= n_ids, a kind outside 0 .. 2, and d_out_offsets that are
+ *                   not the scan of the rendered lengths; what does not fit leaves id 0, ignore_index, part -1,
+ *                   source -1 at its place, and nothing is read outside the inputs.  n_out > out_cap: HUTK_E_CAPACITY
+ *                   in *d_err, and nothing is written at or behind out_cap.
+ * All device calls are asynchronous on hip_stream and never synchronise; *d_err (may be NULL) is cleared by each call.
+ * Refused with HUTK_E_ARG before a device is looked for: negative counts, n_docs at or above 2^31 - 1, a negative
+ * first_doc, thresholds outside 0 .. 2^32, a required sentinel equal to HUTK_NO_TOKEN, loss_parts with bits above
+ * 1 << 5, a negative out_cap, and with work to do (n_docs > 0) a NULL required buffer or one not aligned to its element
+ * type.  16-byte alignment of an output gets it 16-byte stores.  hutk_debug_fim_decide -> out3 = (kind, lo, hi) and
+ * hutk_debug_fim_locate -> out2 = (part, the index inside the document or the sentinel's number 0 pre / 1 suf / 2 mid /
+ * 3 end; part -1 for a p outside the document) are host only and call the two functions of csrc/hutk_fim.h. */
+#define HUTK_FIM_PLAIN 0
+#define HUTK_FIM_PSM 1
+#define HUTK_FIM_SPM 2
+#define HUTK_FIM_PART_PLAIN 0
+#define HUTK_FIM_PART_PREFIX 1
+#define HUTK_FIM_PART_MIDDLE 2
+#define HUTK_FIM_PART_SUFFIX 3
+#define HUTK_FIM_PART_SENTINEL 4
+#define HUTK_FIM_LOSS_END 32
+int64_t hutk_fim_ids_bound(int64_t n_docs, int64_t n_ids, int has_end);
+int hutk_fim_cut_text_device(const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes, uint64_t seed,
+                             int64_t first_doc, int64_t fim_below, int64_t spm_below, int64_t* d_piece_offsets,
+                             int32_t* d_kinds, int32_t* d_err, void* hip_stream);
+int hutk_fim_plan_tokens_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, uint64_t seed, int64_t first_doc,
+                                int64_t fim_below, int64_t spm_below, int has_end, int64_t* d_out_offsets, int64_t* d_plan,
+                                int32_t* d_kinds, int32_t* d_err, void* hip_stream);
+int hutk_fim_plan_pieces_device(const int64_t* d_piece_id_offsets, const int32_t* d_kinds, int64_t n_docs, int64_t n_ids,
+                                int has_end, int64_t* d_out_offsets, int64_t* d_plan, int32_t* d_err, void* hip_stream);
+int hutk_fim_render_device(const int32_t* d_ids, const int64_t* d_plan, const int32_t* d_kinds, const int64_t* d_out_offsets,
+                           int64_t n_docs, int64_t n_ids, int32_t pre_id, int32_t suf_id, int32_t mid_id, int32_t end_id,
+                           uint32_t loss_parts, int32_t ignore_index, int64_t out_cap, int32_t* d_out_ids, int32_t* d_labels,
+                           int32_t* d_parts, int64_t* d_src, int32_t* d_err, void* hip_stream);
+int hutk_debug_fim_span(void);
+int hutk_debug_fim_decide(uint64_t seed, int64_t doc, int64_t len, int64_t fim_below, int64_t spm_below, int64_t out3[3]);
+int hutk_debug_fim_locate(int64_t n, int64_t lo, int64_t hi, int kind, int has_end, int64_t p, int64_t out2[2]);
+
 /* ---- token spans (offset mapping) ----------------------------------------------------------------------
  * Which stretch of its document each id covers: from the packed text (d_bytes, d_offsets) and the ragged pair that
  * hutk_encode_batch_device wrote for it (d_ids, d_id_offsets; n_ids as in the collation calls: d_id_offsets[n_docs] ==

@@ -19,6 +19,90 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
+_C_CLASSES = {"int": "int32", "int32_t": "int32", "uint32_t": "uint32", "int64_t": "int64", "uint64_t": "uint64",
+              "size_t": "uint64", "float": "float", "void": "void"}
+
+
+def _c_class(decl, is_return=False):
+    """The class of one parameter (or return type) of a prototype: what a caller has to pass in that place."""
+    decl = decl.strip()
+    if "*" in decl or "[" in decl:
+        base = decl.split("*")[0].replace("const", "").split()
+        return "string" if base == ["char"] else "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    assert words, "an empty declaration"
+    if not is_return and len(words) > 1:
+        words = words[:-1]  # (the parameter's name)
+    assert len(words) == 1 and words[0] in _C_CLASSES, "a type this test does not know: %r" % decl
+    return _C_CLASSES[words[0]]
+
+
+def _ctypes_class(t):
+    import ctypes as C
+    if t is None:
+        return "void"
+    if t is C.c_char_p:
+        return "string"
+    if t is C.c_void_p or issubclass(t, C._Pointer):
+        return "pointer"
+    if t is C.c_float:
+        return "float"
+    assert issubclass(t, C._SimpleCData) and t._type_ in "iIlLqQ", "a ctypes type this test does not know: %r" % t
+    return ("uint" if t._type_ in "ILQ" else "int") + str(8 * C.sizeof(t))
+
+
+def header_prototypes():
+    """name -> (class of the return type, [class of every parameter]) of every hutk_* prototype of the header"""
+    header = open(os.path.join(H.ROOT, "include", "hutoken_amd.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ \t]*?[ \t*]+)\b(hutk_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header):
+        assert name not in protos, name
+        ret = ret.replace("extern", "").strip()
+        params = [p for p in (q.strip() for q in params.split(",")) if p]
+        args = [] if params in ([], ["void"]) else [_c_class(p) for p in params]
+        protos[name] = (_c_class(ret, is_return=True), args)
+    return protos
+
+
+def test_signatures_have_the_headers_types():
+    """Every place of every ctypes signature is of the class the header declares: pointer, C string, 32-bit or 64-bit,
+    signed or unsigned, float, void.  An int32 where the header says int64_t passes every small test and truncates
+    a batch past 2^31; the test above compares names only."""
+    import ctypes as C
+    assert C.sizeof(C.c_int) == 4 and C.sizeof(C.c_size_t) == 8
+    protos = header_prototypes()
+    assert sorted(protos) == sorted(_capi.SIGNATURES), "the parser and the table do not list the same functions"
+    wrong = []
+    for name, (ret, args) in sorted(protos.items()):
+        restype, argtypes = _capi.SIGNATURES[name]
+        got = (_ctypes_class(restype), [_ctypes_class(t) for t in argtypes])
+        if got[0] != ret:
+            wrong.append("%s returns %s, the table has %s" % (name, ret, got[0]))
+        if len(got[1]) != len(args):
+            wrong.append("%s takes %d arguments, the table has %d" % (name, len(args), len(got[1])))
+            continue
+        wrong += ["%s, argument %d: the header has %s, the table %s" % (name, i, a, g)
+                  for i, (a, g) in enumerate(zip(args, got[1])) if a != g]
+    assert not wrong, "\n".join(wrong)
+
+
+def test_the_signature_parser_tells_the_classes_apart():
+    """(the check of the check: a width, a sign or a count that differs is seen)"""
+    import ctypes as C
+    assert [_c_class(p) for p in ("const hutk_ctx* ctx", "const char* path", "int64_t n", "int flags", "uint32_t a3", "size_t n",
+                                  "uint64_t seed", "float p", "const int64_t* d_offsets", "hutk_ctx** out", "double* out10")] \
+        == ["pointer", "string", "int64", "int32", "uint32", "uint64", "uint64", "float", "pointer", "pointer", "pointer"]
+    assert [_ctypes_class(t) for t in (C.c_void_p, C.c_char_p, C.c_int64, C.c_int, C.c_int32, C.c_uint32, C.c_size_t, C.c_uint64,
+                                       C.c_float, C.POINTER(C.c_int64), None)] \
+        == ["pointer", "string", "int64", "int32", "int32", "uint32", "uint64", "uint64", "float", "pointer", "void"]
+    protos = header_prototypes()
+    assert protos["hutk_ids_capacity"] == ("int64", ["pointer", "int64", "int64"])
+    assert protos["hutk_host_alloc"] == ("pointer", ["uint64"]) and protos["hutk_last_error"] == ("string", [])
+    assert protos["hutk_ctx_destroy"] == ("void", ["pointer"])
+
+
 def test_header_cites_reference_interfaces():
     header = open(os.path.join(H.ROOT, "include", "hutoken_amd.h")).read()
     for cite in ("src/lib.c:185-571", "src/lib.c:779-794", "src/lib.c:668-720", "include/hutoken/core.h:11"):

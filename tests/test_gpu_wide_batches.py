@@ -21,9 +21,7 @@ Measured on an MI355X: the file 118 s, tests/test_gpu_bigdoc.py 18 s.  The byte-
 The split presets' WIDE lines add up to 1.8 s (test_split_presets, six lines), 5.6 s (test_encode_under_a_preset, four)
 and 4.8 s (test_word_ids, two).
 Needs a real MI355X."""
-import gc
 import importlib
-import time
 
 import numpy as np
 import pytest
@@ -35,6 +33,7 @@ import norm_ref as NR
 import spans_ref as S
 import specials_ref as SR
 import wide_cases as W
+from wide_cases import Row
 
 pytestmark = pytest.mark.gpu
 
@@ -70,33 +69,6 @@ def dev(x):
 def stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
-
-
-class Row:
-    """One case at one boundary: the memory rule in front of it, one line of the table behind it."""
-
-    def __init__(self, name, boundary, need):
-        self.name, self.boundary, self.need = name, "2^31" if boundary == W.B31 else "2^32", int(need)
-
-    def __enter__(self):
-        import torch
-        gc.collect()
-        torch.cuda.empty_cache()
-        self.free = torch.cuda.mem_get_info()[0]
-        if self.free < 1.25 * self.need:
-            print("WIDE | %s | %s | skipped | %d | %d | -" % (self.name, self.boundary, self.need, self.free))
-            pytest.skip("%s at %s needs 1.25 x %d bytes of device memory, %d are free" % (self.name, self.boundary, self.need, self.free))
-        self.t0 = time.time()
-        return self
-
-    def __exit__(self, kind, exc, tb):
-        import torch
-        torch.cuda.synchronize()
-        took = time.time() - self.t0
-        gc.collect()
-        torch.cuda.empty_cache()
-        print("WIDE | %s | %s | %s | %d | %d | %.1f" % (self.name, self.boundary, "ran" if kind is None else "ran, FAILED", self.need,
-                                                      self.free, took))
 
 
 def assert_rows(got, row, R, what, where, per_copy=L):

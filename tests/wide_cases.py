@@ -30,11 +30,15 @@ marked() and with_unknowns() write special-token markers and characters no vocab
 with_split_piece() does the same with a piece of text on which the split presets differ (a digit run, contractions, a
 whitespace run); preset_words() and preset_ids() are the references of the split and of the encode under a preset.
 
-check_layout() asserts all of this from the block's bytes alone.  Nothing here touches the package under test except
-for hutoken_amd.synth's frozen corpora."""
+check_layout() asserts all of this from the block's bytes alone.  Row is the memory rule and the table line of a wide
+case, shared with tests/test_gpu_wide_rows.py.  Nothing here touches the package under test except for
+hutoken_amd.synth's frozen corpora."""
+import gc
 import random
+import time
 
 import numpy as np
+import pytest
 
 import helpers as H
 
@@ -494,6 +498,33 @@ def encode_workspace(n_bytes, n_docs, units_per_item):
     ordinary vocabulary files, about 60 + 12 x (units per item) where an item can become several units."""
     per = 18 if units_per_item <= 1 else 60 + 12 * units_per_item
     return per * n_bytes + 64 * n_docs
+
+
+class Row:
+    """One case at one boundary: the memory rule in front of it, one line of the table behind it."""
+
+    def __init__(self, name, boundary, need):
+        self.name, self.boundary, self.need = name, "2^31" if boundary == B31 else "2^32", int(need)
+
+    def __enter__(self):
+        import torch
+        gc.collect()
+        torch.cuda.empty_cache()
+        self.free = torch.cuda.mem_get_info()[0]
+        if self.free < 1.25 * self.need:
+            print("WIDE | %s | %s | skipped | %d | %d | -" % (self.name, self.boundary, self.need, self.free))
+            pytest.skip("%s at %s needs 1.25 x %d bytes of device memory, %d are free" % (self.name, self.boundary, self.need, self.free))
+        self.t0 = time.time()
+        return self
+
+    def __exit__(self, kind, exc, tb):
+        import torch
+        torch.cuda.synchronize()
+        took = time.time() - self.t0
+        gc.collect()
+        torch.cuda.empty_cache()
+        print("WIDE | %s | %s | %s | %d | %d | %.1f" % (self.name, self.boundary, "ran" if kind is None else "ran, FAILED", self.need,
+                                                      self.free, took))
 
 
 def assert_rows(got, row, R, what, where, L, slice_elems=2 ** 28):

@@ -44,6 +44,13 @@ suffix and re-orders them behind three sentinel ids, PSM or SPM, with random num
 `fim_pieces_device` are the character-level form, which cuts the packed text BEFORE it is encoded so that no token
 straddles a cut; `batch_encode_fim` is the list form (csrc/hutk_fim.h, csrc/hutk_collate.hip).
 
+Best-fit packing (not in the reference): `pack_best_fit` lays the documents of a ragged pair into rows of `seq_len`
+tokens WITHOUT cutting any that fits a row -- only a longer one is cut, every `seq_len` tokens, and the pieces are packed
+best-fit-decreasing (Ding et al. 2024) -- with position and segment ids, lengths and, on request, the source index of
+every element and the place of every document; `gather_source` moves any per-token array (labels, turn ids, spans, word
+ids) along such a source array, the chat render's and fill-in-the-middle's too; `batch_encode_best_fit` is the list form.
+The plan is made on the GPU, never on the host (csrc/hutk_bestfit.hip).
+
 Offset mapping (not in the reference): `token_spans_device` turns the same device arrays plus the packed text into the
 [start, end) of every token in its document, in characters or bytes; `batch_encode_with_offsets` and
 `encode_with_offsets` are the list forms (csrc/hutk_spans.hip).
@@ -84,7 +91,8 @@ __all__ = ["packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_enco
            "pretokenize_packed_device", "pretokenize", "set_pretokenizer",
            "collate_pairs", "collate_pair_windows", "batch_encode_pairs", "batch_encode_pair_windows",
            "ChatTemplate", "render_chat_device", "batch_encode_chat",
-           "fim_device", "fim_cut_text_device", "fim_pieces_device", "batch_encode_fim"]
+           "fim_device", "fim_cut_text_device", "fim_pieces_device", "batch_encode_fim",
+           "pack_best_fit", "gather_source", "batch_encode_best_fit"]
 
 _NOT_INIT = ("Vocabulary is not initialized for encoding. "
              "Call 'initialize_encode' function first.")
@@ -2322,6 +2330,128 @@ def packed_lm_labels(values, segment_ids, *, shift=False, ignore_index=-100):
         return labels
     _on_torch_stream(dev, call, used=(values, segment_ids))
     return labels
+
+
+def pack_best_fit(ids, offsets, seq_len, *, bos_id=None, eos_id=None, pad_id=0, dtype=None, n_ids=None, n_rows=None,
+                  check=False, return_source=False, return_doc_map=False):
+    """Device tensors of encode_packed_device in, rows of WHOLE documents out, on the current torch stream (Ding et al.
+    2024, "Fewer Truncations Improve Language Modeling"): -> dict of input_ids [n_rows, seq_len] of `dtype` (torch.int32,
+    the default, or torch.int64), position_ids and segment_ids int32 [n_rows, seq_len], lengths int32 [n_rows] (the filled
+    columns) and, on request, source int64 [n_rows, seq_len] -- the index into ids of the token at that element, -1 for
+    bos, eos and padding: what gather_source takes -- and doc_map int64 [n_docs, 4] = (whole_row, n_whole, row, col).
+    Document i's sequence is [bos_id] + its ids + [eos_id] (those given).  Only a sequence longer than seq_len is cut:
+    every seq_len tokens of it are a row of their own (the first rows of the result, in document order, segment 1), and
+    what remains of it, like every shorter sequence, is an item.  The items are packed best-fit-decreasing: taken by
+    (length descending, document ascending), each into the open row with the least room that still holds it (the lowest
+    such row), else into a new row.  Inside a row segment_ids count the items 1, 2, .. and are 0 on the padding behind
+    the last one; position_ids restart at 0 with every item (SequencePacker's rule), so packed_lm_labels and
+    packed_cu_seqlens take these rows as they are.  A call packs what it is given: nothing is carried to the next one.
+    n_rows=None reads the number of rows once -- the one synchronisation (and one more for offsets[-1] without n_ids=);
+    a given n_rows is the capacity of the result and the call then reads nothing back: rows behind the last real one are
+    padding with length 0, and a capacity below the number of rows is a device-side error.  (The kernels' scratch is one
+    buffer per device; a call that needs more of it than any call before waits for the device once, before its first
+    kernel, while the buffer grows.)  check=True synchronises and raises
+    ValueError on such an error (7: n_rows is too small; 4: offsets that do not describe ids).  seq_len above 65536 is
+    refused."""
+    bos, eos, pad = _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
+    s = (bos != _capi.NO_TOKEN) + (eos != _capi.NO_TOKEN)
+    _length_arg("seq_len", seq_len, max(1, s))
+    if seq_len > 65536:
+        raise ValueError("seq_len must be at most 65536 for best-fit packing")
+    width, dname = _out_width(dtype)
+    _n_rows_arg(n_rows)
+    _ragged_args(ids, offsets, n_ids)
+    import torch
+    dev = ids.device
+    n_docs = offsets.numel() - 1
+    n_ids = _n_ids(ids, offsets, n_ids)
+    doc_map = torch.empty((n_docs, 4), dtype=torch.int64, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # one word per call
+
+    def call():
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cap = n_rows
+        if cap is None:
+            bound = _capi.bestfit_rows_bound(n_docs, n_ids, seq_len, s)
+            _capi.bestfit_plan_device(offsets.data_ptr(), n_docs, n_ids, seq_len, bos, eos, bound, doc_map.data_ptr(),
+                                      info.data_ptr(), err[0:].data_ptr(), stream)
+            cap = int(info[0].item())  # the one synchronisation; pass n_rows= to avoid it
+            if cap < 0 or cap > bound:
+                raise ValueError("hutoken_amd: pack_best_fit: offsets that do not describe ids (%d rows)" % cap)
+        else:
+            _capi.bestfit_plan_device(offsets.data_ptr(), n_docs, n_ids, seq_len, bos, eos, cap, doc_map.data_ptr(),
+                                      info.data_ptr(), err[0:].data_ptr(), stream)
+        out = torch.empty((cap, seq_len), dtype=getattr(torch, dname), device=dev)
+        pos = torch.empty((cap, seq_len), dtype=torch.int32, device=dev)
+        seg = torch.empty((cap, seq_len), dtype=torch.int32, device=dev)
+        lengths = torch.empty(cap, dtype=torch.int32, device=dev)
+        source = torch.empty((cap, seq_len), dtype=torch.int64, device=dev) if return_source else None
+        _capi.bestfit_rows_device(ids.data_ptr(), offsets.data_ptr(), doc_map.data_ptr(), n_docs, n_ids, seq_len, bos, eos,
+                                  pad, width, cap, out.data_ptr(), pos.data_ptr(), seg.data_ptr(), lengths.data_ptr(),
+                                  0 if source is None else source.data_ptr(), err[1:].data_ptr(), stream)
+        return (out, pos, seg, lengths) + (() if source is None else (source,))
+    res = _on_torch_stream(dev, call, used=(ids, offsets, doc_map, info, err))
+    if check:
+        codes = err.tolist()
+        if codes[0] or codes[1]:
+            raise ValueError("hutoken_amd: pack_best_fit: device-side error %d (7: n_rows is below the number of rows; 4: "
+                             "offsets that do not describe ids)" % (codes[0] or codes[1]))
+    out = {"input_ids": res[0], "position_ids": res[1], "segment_ids": res[2], "lengths": res[3]}
+    if return_source:
+        out["source"] = res[4]
+    if return_doc_map:
+        out["doc_map"] = doc_map
+    return out
+
+
+def gather_source(source, values, fill, *, check=False):
+    """Any per-token array along a `source` array: source int64 of any shape (pack_best_fit(return_source=True), the
+    chat render's or fill-in-the-middle's source) and values, a device tensor [n] or [n, 2] of int32 or int64 indexed like
+    the ids the source points into (labels, turn ids, spans, word ids) -> a tensor of source's shape (with a trailing 2 for
+    [n, 2]) and values' dtype: values[source] where source >= 0, `fill` (an int: it fills both halves of a pair)
+    elsewhere.  One elementwise HIP pass on the current torch stream, never synchronises (it has no scratch); a source at or above
+    len(values) gives `fill` and a device-side error that check=True raises as ValueError."""
+    if not _is_tensor(source):
+        raise TypeError("source must be a torch tensor, not %s" % type(source).__name__)
+    if _dtype_name(source) != "int64":
+        raise TypeError("source must have dtype int64, not %s" % source.dtype)
+    if not source.is_contiguous():
+        raise ValueError("source must be contiguous")
+    dname, rec = _records_arg("values", values)
+    per = 2 if values.dim() == 2 else 1
+    if isinstance(fill, bool) or not isinstance(fill, int):
+        raise TypeError("fill must be an int, not %s" % type(fill).__name__)
+    bits = 31 if dname == "int32" else 63
+    if not -2**bits <= fill < 2**bits:
+        raise ValueError("fill must fit %s" % dname)
+    _on_one_gpu("the gather", (("source", source), ("values", values)))
+    import torch
+    dev = source.device
+    out = torch.empty(tuple(source.shape) + ((2,) if per == 2 else ()), dtype=values.dtype, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def call():
+        _capi.rows_gather_source_device(source.data_ptr(), source.numel(), values.data_ptr(), values.shape[0], rec // per, per,
+                                        fill, out.data_ptr(), err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out
+    _on_torch_stream(dev, call, used=(source, values, err))
+    if check and int(err.item()):
+        raise ValueError("hutoken_amd: gather_source: a source at or above the %d values (device-side error %d)"
+                         % (values.shape[0], int(err.item())))
+    return out
+
+
+def batch_encode_best_fit(texts, seq_len, *, bos_id=None, eos_id=None, pad_id=0, dtype=None, return_source=False,
+                          return_doc_map=False, normalize=None):
+    """A list of str: encoded with the initialised context (encode_packed_device), then pack_best_fit.  normalize: as
+    batch_encode_padded."""
+    _token_arg("bos_id", bos_id), _token_arg("eos_id", eos_id), _token_arg("pad_id", pad_id, False)
+    _length_arg("seq_len", seq_len, max(1, (bos_id is not None) + (eos_id is not None)))
+    _out_width(dtype)
+    ids, oo = _texts_to_device(texts, normalize=normalize)
+    return pack_best_fit(ids, oo, seq_len, bos_id=bos_id, eos_id=eos_id, pad_id=pad_id, dtype=dtype, check=True,
+                         return_source=return_source, return_doc_map=return_doc_map)
 
 
 def batch_encode_mlm(texts, max_length=None, *, mask_id, seed, vocab_size=None, whole_word=False, mlm_probability=0.15,

@@ -81,6 +81,12 @@ SIGNATURES = {
     "hutk_packed_cu_seqlens_device": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hutk_packed_labels_device": (_i32, [_vp, _i32, _vp, _i64, _i64, _i32, _i64, _vp, _vp]),
     "hutk_debug_cu_tile": (_i32, []),
+    "hutk_bestfit_rows_bound": (_i64, [_i64, _i64, _i64, _i32]),
+    "hutk_bestfit_plan_device": (_i32, [_vp, _i64, _i64, _i64, _s32, _s32, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_bestfit_rows_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _s32, _s32, _s32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "hutk_rows_gather_source_device": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp]),
+    "hutk_debug_bestfit_tile": (_i32, []),
     "hutk_token_spans_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "hutk_token_spans": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "hutk_debug_span_tile_ids": (_i32, []),
@@ -964,6 +970,39 @@ def packed_labels_device(d_values, width, d_segment_ids, n_rows, seq_len, shift,
 
 def cu_tile():
     return load().hutk_debug_cu_tile()
+
+
+def bestfit_rows_bound(n_docs, n_ids, seq_len, s):
+    """hutk_bestfit_rows_bound (host only): an upper bound of the rows best-fit packing gives."""
+    n = load().hutk_bestfit_rows_bound(n_docs, n_ids, seq_len, s)
+    if n < 0:
+        raise_for(-n)
+    return n
+
+
+def bestfit_plan_device(d_offsets, n_docs, n_ids, seq_len, bos_id, eos_id, rows_cap, d_doc_map, d_info, d_err=0, stream=0):
+    """hutk_bestfit_plan_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_bestfit_plan_device(d_offsets or None, n_docs, n_ids, seq_len, bos_id, eos_id, rows_cap,
+                                              d_doc_map or None, d_info or None, d_err or None, stream or None))
+
+
+def bestfit_rows_device(d_ids, d_offsets, d_doc_map, n_docs, n_ids, seq_len, bos_id, eos_id, pad_id, out_width, rows_cap,
+                        d_input_ids, d_position_ids, d_segment_ids, d_lengths, d_source=0, d_err=0, stream=0):
+    """hutk_bestfit_rows_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_bestfit_rows_device(d_ids or None, d_offsets or None, d_doc_map or None, n_docs, n_ids, seq_len,
+                                              bos_id, eos_id, pad_id, out_width, rows_cap, d_input_ids or None,
+                                              d_position_ids or None, d_segment_ids or None, d_lengths or None,
+                                              d_source or None, d_err or None, stream or None))
+
+
+def rows_gather_source_device(d_source, n, d_values, n_values, width, per, fill, d_out, d_err=0, stream=0):
+    """hutk_rows_gather_source_device on raw device pointers (ints); asynchronous on `stream`."""
+    raise_for(load().hutk_rows_gather_source_device(d_source or None, n, d_values or None, n_values, width, per, fill,
+                                                    d_out or None, d_err or None, stream or None))
+
+
+def bestfit_tile():
+    return load().hutk_debug_bestfit_tile()
 
 
 def _i32_array(values):

@@ -434,6 +434,76 @@ int hutk_packed_labels_device(const void* d_values, int width, const int32_t* d_
                               int64_t seq_len, int shift, int64_t ignore_index, void* d_labels, void* hip_stream);
 int hutk_debug_cu_tile(void);
 
+/* BEST FIT.  Rows of whole documents: only a sequence longer than a row is cut, and the pieces are packed
+ * best-fit-decreasing (Ding et al. 2024, "Fewer Truncations Improve Language Modeling").  Inputs as above: d_ids int32,
+ * d_offsets int64 [n_docs + 1]; L = seq_len; bos_id / eos_id / pad_id as for the packer, s the number of bos/eos given.
+ * Document i has n_i ids; its sequence is [bos] ids [eos], m_i = n_i + s tokens.
+ *   WHOLE ROWS.  A sequence is cut every L tokens: w_i = m_i div L whole rows and, when m_i mod L > 0, one ITEM of length
+ *     l_i = m_i mod L, the sequence's tail.  m_i == 0 (an empty document, s == 0) gives nothing.  Output rows 0 .. W - 1,
+ *     W = sum of w_i, are the whole rows in document order: segment 1, positions 0 .. L - 1.
+ *   BINS.  The items are taken in the order (length descending, document number ascending).  Each goes into the open bin
+ *     whose remaining room is the smallest that is still >= l; among bins of equal room into the lowest-numbered one; when
+ *     none fits a new bin opens with room L.  The item's column is L - room before it is placed, its segment id the number
+ *     of items already in the bin plus 1, its positions 0 .. l - 1 (the packer's rule: 0 at every document start and every
+ *     row start).  Bin b is output row W + b.  Behind a bin's last item: pad_id, position 0, segment 0.
+ *     n_rows = W + B.  The rows depend on the documents and their order only.
+ * Outputs, R = rows_cap rows: d_input_ids [R][L] of out_width 4 or 8, d_position_ids and d_segment_ids int32 [R][L],
+ * d_lengths int32 [R] (the filled columns), d_source int64 [R][L] (may be NULL): the index into d_ids of the token at that
+ * element, -1 for bos, eos and padding.  Rows from n_rows up to R are all padding, length 0.
+ * d_doc_map int64 [n_docs][4] = (whole_row, n_whole, row, col): the document's first whole row (-1 when n_whole == 0)
+ * and where its item starts (-1, -1 when it has none).  d_info int64 [2] = (n_rows, W).
+ *
+ * Worked example: L 8, eos 99, pad 0, documents A = 10..14, B = [], C = 20..28, D = 30 31 32, E = 40, F = 50..56;
+ * m = 6, 1, 10, 4, 2, 8.  Whole rows: C's first eight tokens (row 0), F with its eos (row 1).  Items in order: A 6, D 4,
+ * C 2 (28 99), E 2, B 1.
+ *   row 0   ids 20 21 22 23 24 25 26 27   segments 1 1 1 1 1 1 1 1   positions 0..7            length 8
+ *   row 1   ids 50 51 52 53 54 55 56 99   segments 1 1 1 1 1 1 1 1   positions 0..7            length 8
+ *   row 2   ids 10 11 12 13 14 99 28 99   segments 1 1 1 1 1 1 2 2   positions 0 1 2 3 4 5 0 1  length 8
+ *   row 3   ids 30 31 32 99 40 99 99 0    segments 1 1 1 1 2 2 3 0   positions 0 1 2 3 0 1 0 0  length 7
+ *   source of row 2: 0 1 2 3 4 -1 13 -1; of row 3: 14 15 16 -1 17 -1 -1 -1.
+ *   doc_map: A (-1,0,2,0)  B (-1,0,3,6)  C (0,1,2,6)  D (-1,0,3,0)  E (-1,0,3,4)  F (1,1,-1,-1);  info = (4, 2).
+ *
+ * the rows bound  host only, no synchronisation: at least n_rows for any offsets that describe n_ids ids.  T = n_ids +
+ *                 s * n_docs tokens in all.  Two bins are never both at most half full (the item that opened the later
+ *                 one did not fit the earlier one), so all bins but one hold more than L / 2: B <= 2 * (T - W * L) / L + 1
+ *                 and n_rows <= 2 * T div L + 1.  And W <= T div L, B <= n_docs.  The bound is the smaller of
+ *                 2 * T div L + 1 and T div L + n_docs; 0 for n_docs == 0; -HUTK_E_ARG for bad arguments.
+ * the plan call   documents -> d_doc_map, d_info.  rows_cap < n_rows: HUTK_E_CAPACITY in *d_err (d_info still holds the
+ *                 true counts; the call itself writes nothing that rows_cap sizes).  Offsets that do not describe the ids:
+ *                 HUTK_E_ARG in *d_err, the documents they name are taken as empty.  n_docs == 0: info = (0, 0).
+ * the rows call   d_doc_map + ids -> the five row arrays, R = rows_cap rows, every element written exactly once.  It
+ *                 trusts nothing: a doc_map row that is not what the offsets give (n_whole, whole_row), that points
+ *                 outside the R rows or the row's columns, or that shares its place with another one, and offsets that
+ *                 do not describe the ids, set HUTK_E_ARG in *d_err; what it cannot place is left out (the place
+ *                 holds padding), and every write stays inside the outputs.  So after a plan that reported
+ *                 HUTK_E_CAPACITY the rows call writes the rows below rows_cap and reports HUTK_E_ARG.  Items that
+ *                 overlap without sharing their first column are not told apart from good ones: the later start wins.
+ * the gather      d_out[e] = d_source[e] >= 0 ? d_values[d_source[e]] : fill over n elements: records of `per` (1 or 2)
+ *                 elements of `width` (4 or 8) bytes, as the packer's channels -- labels, turn ids, spans, word ids --
+ *                 along the source array of these rows, of the chat render or of fill-in-the-middle.  A source at or
+ *                 above n_values: the fill, and HUTK_E_ARG in *d_err.  fill must fit the width.
+ * All device calls are asynchronous on hip_stream.  Their scratch is one buffer per device that grows at a call larger
+ * than any before it, and growing it waits for the device: the one synchronisation there can be.  The plan call makes the
+ * buffer large enough for the rows call of rows_cap rows that follows it, so a pair of calls waits at most once, in front
+ * of the plan, and a loop over batches of a steady size does not wait after its first pass.  Refused with HUTK_E_ARG before a device is looked for: seq_len < 1, < s, >= 2^31
+ * or above 65536 (the length classes are ranked by 16 bits), negative counts, a width other than 4 or 8, a per other
+ * than 1 or 2.  Alignment: that of the element; 16 bytes on every output (and L % 4 == 0) gets the wide path.
+ * hutk_debug_bestfit_tile: the documents a workgroup of the plan's ranking pass owns at least, T = 4 wavefronts x 64.  A
+ * wavefront owns a contiguous run of per_wave documents and walks it in chunks of 64: per_wave = 64 while n_docs <= 64 *
+ * max(1, 2^21 div L), otherwise ceil(n_docs / max(1, 2^21 div L)) rounded up to a multiple of 64 (the rows call's
+ * document passes: the same with 4096 wavefronts and runs of 128 at least).  Tests place edges at multiples of T / 4, T and per_wave. */
+int64_t hutk_bestfit_rows_bound(int64_t n_docs, int64_t n_ids, int64_t seq_len, int s);
+int hutk_bestfit_plan_device(const int64_t* d_offsets, int64_t n_docs, int64_t n_ids, int64_t seq_len, int32_t bos_id,
+                             int32_t eos_id, int64_t rows_cap, int64_t* d_doc_map, int64_t* d_info, int32_t* d_err,
+                             void* hip_stream);
+int hutk_bestfit_rows_device(const int32_t* d_ids, const int64_t* d_offsets, const int64_t* d_doc_map, int64_t n_docs,
+                             int64_t n_ids, int64_t seq_len, int32_t bos_id, int32_t eos_id, int32_t pad_id, int out_width,
+                             int64_t rows_cap, void* d_input_ids, int32_t* d_position_ids, int32_t* d_segment_ids,
+                             int32_t* d_lengths, int64_t* d_source, int32_t* d_err, void* hip_stream);
+int hutk_rows_gather_source_device(const int64_t* d_source, int64_t n, const void* d_values, int64_t n_values, int width,
+                                   int per, int64_t fill, void* d_out, int32_t* d_err, void* hip_stream);
+int hutk_debug_bestfit_tile(void);
+
 /* WINDOWS.  A long document becomes several overlapping rows instead of one truncated row (what other tokenizers call
  * stride with overflowing tokens, truncation on the right).  With C = max_len - s (the document ids a row holds) and
  * step = C - stride (0 <= stride < C), a document of n ids gives w(n) rows: 1 when n <= C (an empty document too),

@@ -67,6 +67,13 @@ installs the ids of the vocabulary's `<0x00>`..`<0xFF>` lines (or 256 ids of the
 covers, `decode_fallback` / `batch_decode_fallback` / `decode_packed_device(byte_fallback=True)` turn such ids back into
 the raw bytes (csrc/hutk_fallback.hip).  Every other function ignores the table.
 
+WordPiece (not in the reference, whose only encoder is BPE): `WordPiece` holds a BERT-family vocabulary (a vocab.txt
+with "##" pieces) and encodes on the GPU as `tokenizers` does with BertNormalizer, BertPreTokenizer and
+models.WordPiece: `encode_packed_device` gives the same ragged (ids, offsets) pair as the function of that name, and
+word ids on request, so every collate_*, SequencePacker.add and mask_tokens takes it unchanged; `batch_encode` and
+`encode` are the list forms, `from_file` and `from_tokenizer` the other constructors (csrc/hutk_wordpiece.hip, DESIGN.md
+section 8m).  It needs no initialised context.
+
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
 the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
@@ -79,8 +86,9 @@ import traceback
 from . import _capi
 from . import pretokenize as _presplit_tables  # (the module; the package's name `pretokenize` is the function below)
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
+from . import wordpiece as _wp_tables
 
-__all__ = ["packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -1778,6 +1786,147 @@ def normalize(texts, form="NFC"):
     out, oo = normalize_packed_device(d_bytes, torch.from_numpy(offs).to(dev), form)
     raw, bounds = out.cpu().numpy().tobytes(), oo.tolist()
     return [raw[bounds[i]:bounds[i + 1]].decode("utf-8", "surrogateescape") for i in range(len(chunks))]
+
+
+# ---- WordPiece (hutk_wordpiece.hip) ----
+class WordPiece:
+    """A WordPiece vocabulary and BERT's normaliser and word split, encoding on the GPU what the `tokenizers` package
+    encodes with models.WordPiece behind normalizers.BertNormalizer and pre_tokenizers.BertPreTokenizer.
+
+    vocab: the tokens in id order (a list of str; of two equal ones the later id wins).  unk_token must be one of them.
+    strip_accents=None means "as lowercase".  device: a torch device, an index, or None for the current one; the
+    tables are uploaded at the first call that needs the GPU, once.  Needs no initialised context.
+
+    Left out: token spans over the original text, decoding, and matching "[MASK]"-style special strings inside text
+    (they are split like any other text: "[", "mask", "]")."""
+
+    def __init__(self, vocab, unk_token="[UNK]", continuing_subword_prefix="##", max_input_chars_per_word=100, lowercase=True,
+                 strip_accents=None, clean_text=True, handle_chinese_chars=True, device=None):
+        if isinstance(vocab, (str, bytes)) or not hasattr(vocab, "__iter__"):
+            raise TypeError("vocab must be a list of str (one token per id), not %s" % type(vocab).__name__)
+        vocab = list(vocab)
+        for i, t in enumerate(vocab):
+            if not isinstance(t, str):
+                raise TypeError("vocab[%d] must be a str, not %s" % (i, type(t).__name__))
+            if not t:
+                raise ValueError("vocab[%d] is empty" % i)
+        for name, v in (("unk_token", unk_token), ("continuing_subword_prefix", continuing_subword_prefix)):
+            if not isinstance(v, str):
+                raise TypeError("%s must be a str, not %s" % (name, type(v).__name__))
+        if isinstance(max_input_chars_per_word, bool) or not isinstance(max_input_chars_per_word, int):
+            raise TypeError("max_input_chars_per_word must be an int")
+        if not 0 <= max_input_chars_per_word <= 1 << 20:
+            raise ValueError("max_input_chars_per_word must lie in 0 .. 2**20")
+        self._flags = _wp_tables.flags_of(lowercase, strip_accents, clean_text, handle_chinese_chars)
+        if not vocab:
+            raise ValueError("vocab is empty")
+        if len(continuing_subword_prefix.encode("utf-8")) > 16:
+            raise ValueError("continuing_subword_prefix is longer than 16 bytes")
+        self._ids = {t: i for i, t in enumerate(vocab)}  # (the later id wins)
+        if unk_token not in self._ids:
+            raise ValueError("unk_token %r is not in the vocabulary" % (unk_token,))
+        if "\x00" in unk_token or "\x00" in continuing_subword_prefix:
+            raise ValueError("unk_token and continuing_subword_prefix must not hold U+0000")
+        if device is not None and not isinstance(device, int) and not hasattr(device, "index"):
+            raise TypeError("device must be a torch device, an int or None")
+        self._vocab = vocab
+        self.unk_token, self.continuing_subword_prefix = unk_token, continuing_subword_prefix
+        self.max_input_chars_per_word = max_input_chars_per_word
+        self._device = device
+        self._handles = {}
+
+    @classmethod
+    def from_file(cls, path, **options):
+        """A vocab.txt: one token a line, the id is the line number."""
+        with open(path, "rb") as f:
+            raw = f.read().decode("utf-8")
+        lines = raw.split("\n")
+        if lines and lines[-1] == "":
+            lines.pop()
+        return cls([t[:-1] if t.endswith("\r") else t for t in lines], **options)
+
+    @classmethod
+    def from_tokenizer(cls, tok, device=None):
+        """From a `tokenizers.Tokenizer` or a `transformers` fast tokenizer whose model is WordPiece behind a
+        BertNormalizer and a BertPreTokenizer: their options and the vocabulary.  Anything else: ValueError."""
+        from . import hf
+        lines, options = hf.wordpiece_options(tok)
+        return cls(lines, device=device, **options)
+
+    @property
+    def vocab_size(self):
+        return len(self._vocab)
+
+    def token_to_id(self, token):
+        return self._ids.get(token)
+
+    def id_to_token(self, i):
+        return self._vocab[i] if 0 <= i < len(self._vocab) else None
+
+    def _handle(self, dev):
+        h = self._handles.get(dev.index)
+        if h is None:
+            strip = self._flags & _wp_tables.STRIP_ACCENTS
+            h = self._handles[dev.index] = _capi.WordPiece(
+                _wp_tables.table_blob(), _norm_tables.table_blob() if strip else None,
+                [t.encode("utf-8", "surrogateescape") for t in self._vocab], self.unk_token.encode("utf-8"),
+                self.continuing_subword_prefix.encode("utf-8"), self.max_input_chars_per_word, self._flags, dev.index)
+        return h
+
+    def encode_packed_device(self, d_bytes, d_offsets, check=True, return_word_ids=False):
+        """Device tensors in (uint8 bytes, int64 offsets[n + 1]), device tensors out: (ids int32, out_offsets int64[n + 1])
+        -- the pair every collate_* function and SequencePacker.add take -- and with return_word_ids the index of every
+        id's word in its document (int32, what `tokenizers` calls word_ids; mask_tokens(word_ids=) takes it).  Runs on
+        the current torch stream.  ids is a view of a buffer of the capacity bound; its length is read from the device,
+        which is the call's one synchronisation.  check=True: offsets that do not describe d_bytes raise ValueError."""
+        _packed_text_args(d_bytes, d_offsets)
+        import torch
+        dev = d_bytes.device
+        h = self._handle(dev)
+        n_docs, n_bytes = d_offsets.numel() - 1, d_bytes.numel()
+        cap = h.ids_capacity(n_bytes, n_docs)
+
+        def call():
+            ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            oo = torch.zeros(n_docs + 1, dtype=torch.int64, device=dev)
+            wi = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if return_word_ids else None
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            h.batch_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap, oo.data_ptr(),
+                           wi.data_ptr() if return_word_ids else 0, err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return (ids, oo, err, wi) if return_word_ids else (ids, oo, err)
+
+        res = _on_torch_stream(dev, call, used=(d_bytes, d_offsets))
+        ids, oo, err = res[:3]
+        code = int(err.item()) if check else 0
+        if code:
+            raise ValueError("hutoken_amd: WordPiece.encode_packed_device: device-side error %d (offsets that do not "
+                             "describe d_bytes)" % code)
+        total = int(oo[n_docs].item())
+        return (ids[:total], oo, res[3][:total]) if return_word_ids else (ids[:total], oo)
+
+    def batch_encode(self, texts):
+        """A list of str -> a list of lists of ids, encoded on the GPU."""
+        import numpy as np
+        import torch
+        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+            raise TypeError("Invalid arguments. Expected a list of strings.")
+        chunks = [t.encode("utf-8", "surrogateescape") for t in texts]
+        offs = np.zeros(len(chunks) + 1, dtype=np.int64)
+        if chunks:
+            np.cumsum(np.fromiter(map(len, chunks), dtype=np.int64, count=len(chunks)), out=offs[1:])
+        d = self._device
+        dev = torch.device("cuda", torch.cuda.current_device() if d is None else d if isinstance(d, int) else
+                           (d.index if d.index is not None else torch.cuda.current_device()))
+        d_bytes = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()).to(dev)
+        ids, oo = self.encode_packed_device(d_bytes, torch.from_numpy(offs).to(dev))
+        flat, bounds = ids.tolist(), oo.tolist()
+        return [flat[bounds[i]:bounds[i + 1]] for i in range(len(chunks))]
+
+    def encode(self, text):
+        """One str -> its list of ids."""
+        if not isinstance(text, str):
+            raise TypeError("Invalid arguments. Expected a string.")
+        return self.batch_encode([text])[0]
 
 
 # ---- split presets (hutk_presplit.hip, DESIGN.md section 4d) ----

@@ -155,6 +155,14 @@ SIGNATURES = {
     "hutk_debug_fim_span": (_i32, []),
     "hutk_debug_fim_decide": (_i32, [C.c_uint64, _i64, _i64, _i64, _i64, _pi64]),
     "hutk_debug_fim_locate": (_i32, [_i64, _i64, _i64, _i32, _i32, _i64, _pi64]),
+    "hutk_wordpiece_create": (_i32, [_pvp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _str, _str, _s32, _u32]),
+    "hutk_wordpiece_destroy": (None, [_vp]),
+    "hutk_wordpiece_info": (_i32, [_vp, _vp]),
+    "hutk_wordpiece_ids_capacity": (_i64, [_vp, _i64, _i64]),
+    "hutk_wordpiece_encode_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_wordpiece_encode_batch": (_i32, [_vp, _vp, _vp, _i64, _pvp, _pvp, _pvp]),
+    "hutk_debug_wordpiece_chunk_bytes": (_i32, []),
+    "hutk_debug_wordpiece_bucket": (_i64, [_vp, _vp, _i64, _i32]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -170,6 +178,7 @@ LABELS_A, LABELS_B, LABELS_TEMPLATE, LABELS_END, LABELS_SHIFT = 1, 2, 4, 8, 16  
 CHAT_MAX_ROLES, CHAT_MAX_PART = 16, 32  # HUTK_CHAT_MAX_*
 PACKER_MAX_CHANNELS = 4  # HUTK_PACKER_MAX_CHANNELS
 FIM_PLAIN, FIM_PSM, FIM_SPM = 0, 1, 2  # HUTK_FIM_*: the kinds
+WP_CLEAN_TEXT, WP_CJK, WP_STRIP_ACCENTS, WP_LOWERCASE = 1, 2, 4, 8  # HUTK_WP_*
 FIM_PARTS = ("plain", "prefix", "middle", "suffix", "sentinel")  # HUTK_FIM_PART_*: a part's number is its index here
 
 _lib = None
@@ -1203,3 +1212,79 @@ class Pretokenizer(_Owner):
 
 def presplit_chunk_bytes():
     return load().hutk_debug_presplit_chunk_bytes()
+
+
+WORDPIECE_INFO = ["format_version", "unidata", "blob_bytes", "chunk_bytes", "vocab_size", "table_slots", "flags", "unk_id"]
+
+
+class WordPiece(_Owner):
+    """Owns one hutk_wordpiece (WordPiece encoding on the GPU, include/hutoken_amd.h): the class tables of
+    hutoken_amd.wordpiece, the vocabulary's table and, with WP_STRIP_ACCENTS, a normaliser, on one device."""
+    _destroy = "hutk_wordpiece_destroy"
+
+    def __init__(self, tables, norm_blob, lines, unk_token, prefix, max_input_chars_per_word, flags, device=-1):
+        """lines: the vocabulary, a list of bytes; unk_token, prefix: bytes"""
+        import numpy as np
+        h = C.c_void_p()
+        tb = (C.c_uint8 * max(len(tables), 1)).from_buffer_copy(bytes(tables) or b"\0")
+        nb = (C.c_uint8 * max(len(norm_blob), 1)).from_buffer_copy(bytes(norm_blob) or b"\0") if norm_blob else None
+        offs = np.zeros(len(lines) + 1, dtype=np.int64)
+        if lines:
+            np.cumsum(np.fromiter(map(len, lines), dtype=np.int64, count=len(lines)), out=offs[1:])
+        data = np.frombuffer(b"".join(lines) or b"\0", dtype=np.uint8)
+        raise_for(load().hutk_wordpiece_create(C.byref(h), int(device), C.cast(tb, C.c_void_p), len(tables),
+                                               C.cast(nb, C.c_void_p) if nb is not None else None, len(norm_blob) if norm_blob else 0,
+                                               data.ctypes.data, offs.ctypes.data, len(lines), bytes(unk_token), bytes(prefix),
+                                               int(max_input_chars_per_word), int(flags)))
+        self._h = h
+
+    def info(self):
+        import numpy as np
+        out = np.zeros(8, dtype=np.int64)
+        raise_for(load().hutk_wordpiece_info(self._h, out.ctypes.data))
+        return dict(zip(WORDPIECE_INFO, out.tolist()))
+
+    def ids_capacity(self, n_bytes, n_docs):
+        return load().hutk_wordpiece_ids_capacity(self._h, n_bytes, n_docs)
+
+    def bucket(self, piece, continuation):
+        """hutk_debug_wordpiece_bucket: the slot the probe of `piece` (bytes) starts at"""
+        buf = (C.c_uint8 * max(len(piece), 1)).from_buffer_copy(bytes(piece) or b"\0")
+        return load().hutk_debug_wordpiece_bucket(self._h, C.cast(buf, C.c_void_p), len(piece), 1 if continuation else 0)
+
+    def batch_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets, d_word_ids=0, d_err=0, stream=0):
+        """hutk_wordpiece_encode_batch_device on raw device pointers (ints).  Asynchronous on `stream`, never synchronises."""
+        raise_for(load().hutk_wordpiece_encode_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                            d_ids or None, ids_cap, d_out_offsets or None, d_word_ids or None,
+                                                            d_err or None, stream or None))
+
+    def batch(self, data, offsets, word_ids=False):
+        """Host numpy buffers in and out (hutk_wordpiece_encode_batch): -> (ids int32, out_offsets int64[n + 1]) and, with
+        word_ids, the word ids (int32)."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if n < 0:
+            raise TypeError("offsets must hold at least one entry")
+        if int(offsets[n]) > len(data):
+            raise TypeError("offsets point outside data")
+        L = load()
+        ids, oo, wi = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        raise_for(L.hutk_wordpiece_encode_batch(self._h, data.ctypes.data if len(data) else None, offsets.ctypes.data, n,
+                                                C.byref(ids), C.byref(oo), C.byref(wi) if word_ids else None))
+        try:
+            r_oo = np.frombuffer((C.c_int64 * (n + 1)).from_address(oo.value), dtype=np.int64).copy()
+            total = int(r_oo[n])
+            r_ids = np.frombuffer((C.c_int32 * max(total, 1)).from_address(ids.value), dtype=np.int32)[:total].copy()
+            r_wi = np.frombuffer((C.c_int32 * max(total, 1)).from_address(wi.value), dtype=np.int32)[:total].copy() if word_ids else None
+        finally:
+            L.hutk_host_free(ids)
+            L.hutk_host_free(oo)
+            if word_ids:
+                L.hutk_host_free(wi)
+        return (r_ids, r_oo, r_wi) if word_ids else (r_ids, r_oo)
+
+
+def wordpiece_chunk_bytes():
+    return load().hutk_debug_wordpiece_chunk_bytes()

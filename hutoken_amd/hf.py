@@ -210,3 +210,38 @@ def export(reference, **options):
                 is_byte_encoder=1 if byte_level else options.get("is_byte_encoder", 0),
                 merges_file_path=_merges_file(tok, folder, reference), tokenizer=tok,
                 normalizer=normalizer_form(tok), pretokenizer=pretokenizer_preset(tok))
+
+
+def wordpiece_options(tok):
+    """What hutoken_amd.WordPiece.from_tokenizer reads from a `tokenizers.Tokenizer` or a `transformers` fast tokenizer:
+    -> (vocabulary lines in id order, keyword options).  Accepted is a model WordPiece behind a BertNormalizer and a
+    BertPreTokenizer; anything else raises ValueError naming what was found.  Nothing is read from disk or network."""
+    js = _backend_json(tok)
+    if js is None and hasattr(tok, "to_str"):
+        js = json.loads(tok.to_str())
+    if js is None:
+        raise ValueError("from_tokenizer needs a tokenizers.Tokenizer or a transformers fast tokenizer, not %s" % type(tok).__name__)
+
+    def kind(node):
+        return "none" if node is None else str(node.get("type"))
+
+    model, norm, pre = js.get("model") or {}, js.get("normalizer"), js.get("pre_tokenizer")
+    if kind(model) != "WordPiece":
+        raise ValueError("from_tokenizer: the model is %s, not WordPiece" % kind(model))
+    if kind(norm) != "BertNormalizer":
+        raise ValueError("from_tokenizer: the normalizer is %s, not BertNormalizer" % kind(norm))
+    if kind(pre) != "BertPreTokenizer":
+        raise ValueError("from_tokenizer: the pre-tokenizer is %s, not BertPreTokenizer" % kind(pre))
+    vocab = model.get("vocab") or {}
+    ids = sorted(vocab.values())
+    if ids != list(range(len(ids))):
+        raise ValueError("from_tokenizer: the vocabulary's ids are not 0 .. %d without gaps" % (len(ids) - 1))
+    lines = [None] * len(ids)
+    for t, i in vocab.items():
+        lines[i] = t
+    return lines, dict(unk_token=model.get("unk_token", "[UNK]"),
+                       continuing_subword_prefix=model.get("continuing_subword_prefix", "##"),
+                       max_input_chars_per_word=model.get("max_input_chars_per_word", 100),
+                       lowercase=bool(norm.get("lowercase", True)), strip_accents=norm.get("strip_accents"),
+                       clean_text=bool(norm.get("clean_text", True)),
+                       handle_chinese_chars=bool(norm.get("handle_chinese_chars", True)))

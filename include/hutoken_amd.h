@@ -1249,6 +1249,98 @@ int hutk_rows_span_corrupt_device(const int64_t* d_plan, int64_t n_rows, int64_t
                                   void* d_decoder_ids, int32_t* d_in_lengths, int32_t* d_tgt_lengths, int32_t* d_err,
                                   void* hip_stream);
 
+/* ---- WordPiece: BERT's normaliser, word split and greedy longest match ------------------------------------------
+ * The encoder of BERT-family vocabularies (a vocab.txt with "##" continuation pieces) on the device
+ * (hutk_wordpiece.hip, hutk_wordpiece.h): the pair (uint8 bytes, int64 offsets[n_docs + 1]) in,
+ * the ragged (int32 ids, int64 out_offsets[n_docs + 1]) of hutk_encode_batch_device out, so every collation, packing
+ * and target call takes the result as it is.  The reference has no counterpart; the contract is the `tokenizers`
+ * package: models.WordPiece behind normalizers.BertNormalizer and pre_tokenizers.BertPreTokenizer.  A document is
+ * normalised, split into words, and every word is matched; documents are independent.
+ *
+ * NORMALISER, character by character, in this order (flags HUTK_WP_*):
+ *   1. HUTK_WP_CLEAN_TEXT drops U+0000, U+FFFD and every character of category Cc, Cf or Co except \t \n \r (a dropped
+ *      character joins its neighbours: "a" U+200B "b" is the word "ab"; Cn is not dropped), then maps every White_Space
+ *      character that remains (25 code points, U+00A0, U+2028 and U+2029 among them) to ' '.  U+000B, U+000C and U+0085
+ *      are Cc: they are dropped, they do not become spaces.
+ *   2. HUTK_WP_CJK makes a word of every code point of 4E00-9FFF, 3400-4DBF, 20000-2A6DF, 2A700-2B73F, 2B740-2B81F,
+ *      2B920-2CEAF, F900-FAFF, 2F800-2FA1F.  The sixth range starts at 2B920 as in `tokenizers`, not at 2B820 as in
+ *      Google's BERT.
+ *   3. HUTK_WP_STRIP_ACCENTS applies NFD (the normaliser above, on the same stream) and drops every character of
+ *      category Mn.  Hangul syllables therefore become jamo.
+ *   4. HUTK_WP_LOWERCASE maps every character on its own (Python's "".join(c.lower() for c in s)): no final-sigma rule,
+ *      and U+0130 without HUTK_WP_STRIP_ACCENTS becomes 'i' + U+0307, two characters.
+ *   A byte that strict UTF-8 rejects is not covered by `tokenizers`, which takes str.  It is one character of class
+ *   "word" that stays as it is, as in the normaliser above; a sequence that a document's end cuts short is such bytes.
+ * SPLIT.  Whitespace separates words and is dropped.  A punctuation character (ASCII 33-47, 58-64, 91-96, 123-126, or
+ *   category P*) is a word of its own, and under HUTK_WP_CJK so is every CJK character.  Everything else runs together.
+ * MATCH.  A word of more than max_input_chars_per_word characters (of the normalised word, not bytes) is one unk id.
+ *   Otherwise from start = 0 the longest end on a character boundary such that word[start:end] is in the vocabulary is
+ *   taken -- from the second piece on prefix + word[start:end] is looked up -- its id is emitted and the match goes on
+ *   at end.  If no end matches at some start the whole word is one unk id and the pieces found so far are discarded:
+ *   with "a" in the vocabulary and "##a" not, "aaa" is unk.  The id of a line is its number; of two equal lines the later
+ *   id wins.  An empty or all-blank document gives no ids.
+ * The classes and the lower-case mapping come from the Unicode data of the tables' builder (Python's unicodedata);
+ * `tokenizers` carries tables of other versions, so the two differ on recently assigned characters (463 code points
+ * with Unicode 13.0 against tokenizers 0.22.2, none below U+07FD).
+ *
+ * TABLES.  One blob, built by hutoken_amd/wordpiece.py and written to a file by `python -m hutoken_amd.wordpiece
+ * --write FILE`.  Format (little-endian 32-bit words; offsets in bytes from the blob's start, multiples of 4):
+ *   header, 32 words: 0 magic 0x43505748 ("HWPC")  1 format version (1)  2 Unicode version major << 16 | minor << 8 | patch
+ *     3 size of the blob  4, 5 stage one: offset, entries (uint16[0x110000 >> 7]: block of code point c = stage1[c >> 7])
+ *     6, 7 class blocks: offset, blocks (128 code points a block, one word a code point: bits 0..2 the class under
+ *          HUTK_WP_CLEAN_TEXT -- 0 word, 1 space, 2 punctuation, 3 CJK, 4 dropped, 5 nonspacing mark | bits 3..23 the
+ *          lower-case mapping's first character less the code point, modulo 2^21 | bits 24..26 the class without HUTK_WP_CLEAN_TEXT | bits 27..31 the
+ *          index of the mapping's second character, 0: none)
+ *     8, 9 second characters: offset, entries (uint32, entry 0 unused)   10 block shift (7)
+ *     16..19 the largest characters-out / bytes-in of one code point through the normaliser, rounded up, for the settings
+ *          lowercase | strip_accents << 1       20..23 the largest bytes-out / bytes-in, times 16, rounded up, likewise
+ *   hutk_wordpiece_create checks the magic, the version, every offset, index and code point before anything reads
+ *   through the blob: HUTK_E_VALUE with a message otherwise.
+ *
+ * hutk_wordpiece_create: a handle on one device (device < 0: the current one); it needs no hutk_ctx.  tables: the blob
+ *   above; norm_blob: the normaliser's blob, needed with HUTK_WP_STRIP_ACCENTS and ignored (may be NULL) without;
+ *   the vocabulary as n_vocab lines, line i being vocab_bytes[vocab_offsets[i] .. vocab_offsets[i + 1]).  HUTK_E_VALUE:
+ *   an empty line, an unk_token that is no line, a prefix of more than 16 bytes, a max_input_chars_per_word outside
+ *   0 .. 2^20, no line or 2^30 and more.  A line of more than 4 * max_input_chars_per_word bytes can never match and is
+ *   kept for its id alone.  The table is built on the host and uploaded once: open addressing over (piece bytes, initial
+ *   or continuation), 16 bytes a slot, a load of at most one half, continuation pieces stored without the prefix, all
+ *   keys in one byte blob; a slot counts as a hit only after its bytes have been compared.
+ * hutk_wordpiece_info: out8 = format version, Unicode version word, blob bytes, chunk bytes, vocabulary lines, table
+ *   slots, flags, the unk id.
+ * hutk_wordpiece_ids_capacity: an id covers at least one character of the normalised text, so n_bytes times header word
+ *   16 + setting bounds the ids of any batch of n_bytes bytes (1 with the Unicode data seen so far: n_bytes itself).
+ * hutk_wordpiece_encode_batch_device: asynchronous on hip_stream, never synchronises (growing the handle's workspace for
+ *   a batch larger than any before may wait once).  d_ids[ids_cap], d_out_offsets[n_docs + 1]; d_word_ids (int32 per id,
+ *   may be NULL): the index of the id's word in its document, what `tokenizers` calls word_ids.  d_err (may be NULL) takes
+ *   the first device-side error: HUTK_E_ARG for offsets that do not rise from 0 to n_bytes (the kernels refuse before they
+ *   read through them, and nothing else is written), HUTK_E_CAPACITY for an ids_cap below the total (no id is written).
+ *   The text is cut into chunks of hutk_debug_wordpiece_chunk_bytes() bytes; a word may cross any number of chunk edges
+ *   and have any length in bytes: its cost is bounded by max_input_chars_per_word characters walked and as many trips.
+ *   Alignment of every buffer: that of its element type.  Calls on one handle are serialised.
+ * hutk_wordpiece_encode_batch: host arrays in; the work is done on the GPU; *out_ids ((*out_offsets)[n_docs] entries),
+ *   *out_offsets (n_docs + 1 entries) and, when out_word_ids is not NULL, *out_word_ids are allocated here and given
+ *   back with hutk_host_free.
+ * hutk_debug_wordpiece_bucket: the slot the probe of the piece starts at (tests build pieces that share one); -1 on bad
+ *   arguments. */
+#define HUTK_WP_CLEAN_TEXT 1u
+#define HUTK_WP_CJK 2u
+#define HUTK_WP_STRIP_ACCENTS 4u
+#define HUTK_WP_LOWERCASE 8u
+typedef struct hutk_wordpiece hutk_wordpiece;
+int hutk_wordpiece_create(hutk_wordpiece** out, int device, const uint8_t* tables, int64_t n_table_bytes, const uint8_t* norm_blob,
+                          int64_t n_norm_bytes, const uint8_t* vocab_bytes, const int64_t* vocab_offsets, int64_t n_vocab,
+                          const char* unk_token, const char* prefix, int32_t max_input_chars_per_word, uint32_t flags);
+void hutk_wordpiece_destroy(hutk_wordpiece* h);
+int hutk_wordpiece_info(const hutk_wordpiece* h, int64_t* out8);
+int64_t hutk_wordpiece_ids_capacity(const hutk_wordpiece* h, int64_t n_bytes, int64_t n_docs);
+int hutk_wordpiece_encode_batch_device(hutk_wordpiece* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs,
+                                       int64_t n_bytes, int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets,
+                                       int32_t* d_word_ids, int32_t* d_err, void* hip_stream);
+int hutk_wordpiece_encode_batch(hutk_wordpiece* h, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int32_t** out_ids,
+                                int64_t** out_offsets, int32_t** out_word_ids);
+int hutk_debug_wordpiece_chunk_bytes(void);
+int64_t hutk_debug_wordpiece_bucket(const hutk_wordpiece* h, const uint8_t* bytes, int64_t len, int continuation);
+
 #ifdef __cplusplus
 }
 #endif

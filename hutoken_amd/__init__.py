@@ -74,6 +74,13 @@ word ids on request, so every collate_*, SequencePacker.add and mask_tokens take
 `encode` are the list forms, `from_file` and `from_tokenizer` the other constructors (csrc/hutk_wordpiece.hip, DESIGN.md
 section 8m).  It needs no initialised context.
 
+Unigram (not in the reference either): `Unigram` holds a SentencePiece-style Unigram vocabulary -- (piece, score) pairs
+and an unk id, as T5, mT5, ALBERT, XLNet, XLM-R, mBART and Pegasus use -- and encodes on the GPU as `tokenizers` does with
+models.Unigram behind a Metaspace pre-tokenizer: the Metaspace word split (or T5's whitespace split in front of it), then
+the best path over every word's piece lattice in f64.  The methods and constructors are WordPiece's
+(`encode_packed_device` with word ids on request, `batch_encode`, `encode`, `from_file` for a tokenizer.json,
+`from_tokenizer`); csrc/hutk_unigram.hip, DESIGN.md section 8n.  It needs no initialised context.
+
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
 the batch-fed trainer and a writer of GPT-2-shaped (mode="bytes") or
@@ -88,7 +95,7 @@ from . import pretokenize as _presplit_tables  # (the module; the package's name
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 from . import wordpiece as _wp_tables
 
-__all__ = ["WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["Unigram", "WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -1927,6 +1934,181 @@ class WordPiece:
         if not isinstance(text, str):
             raise TypeError("Invalid arguments. Expected a string.")
         return self.batch_encode([text])[0]
+
+
+# ---- Unigram (hutk_unigram.hip) ----
+class Unigram:
+    """A Unigram vocabulary (SentencePiece's language model: T5, mT5, ALBERT, XLNet, XLM-R, mBART, Pegasus) behind a
+    Metaspace word split, encoding on the GPU what the `tokenizers` package encodes with models.Unigram(vocab, unk_id,
+    byte_fallback=False) behind pre_tokenizers.Metaspace -- id for id and word id for word id.
+
+    vocab: the (piece, score) pairs in id order (of two equal pieces the later id, with its own score, is found); unk_id
+    is required.  prepend_scheme: "always" ("first" is read as "always") or "never".  whitespace_split=True is T5's
+    shape, Sequence[WhitespaceSplit, Metaspace]; it needs prepend_scheme "always".  collapse_spaces=True is the
+    normaliser step Replace(" {2,}", " ") of XLM-R and ALBERT.  device: a torch device, an index, or None for the
+    current one; the table is uploaded at the first call that needs the GPU, once.  Needs no initialised context.
+
+    Left out: SentencePiece's precompiled normaliser (nmt_nfkc and its kin), byte_fallback, sampling and n-best, decoding,
+    token spans over the source text, special strings inside text, and binary .model files."""
+
+    def __init__(self, vocab, unk_id, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False, device=None):
+        import math
+        if isinstance(vocab, (str, bytes, dict)) or not hasattr(vocab, "__iter__"):
+            raise TypeError("vocab must be a list of (piece, score) pairs in id order, not %s" % type(vocab).__name__)
+        vocab = list(vocab)
+        pieces, scores = [], []
+        for i, entry in enumerate(vocab):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+                raise TypeError("vocab[%d] must be a (piece, score) pair" % i)
+            t, sc = entry
+            if not isinstance(t, str):
+                raise TypeError("vocab[%d]: the piece must be a str, not %s" % (i, type(t).__name__))
+            if isinstance(sc, bool) or not isinstance(sc, (int, float)):
+                raise TypeError("vocab[%d]: the score must be a float, not %s" % (i, type(sc).__name__))
+            if not t:
+                raise ValueError("vocab[%d] is empty" % i)
+            if not math.isfinite(sc):
+                raise ValueError("vocab[%d]: the score is not finite" % i)
+            if len(t.encode("utf-8", "surrogateescape")) - 2 * t.count("\u2581") > 256:
+                raise ValueError("vocab[%d] is longer than 256 bytes" % i)
+            pieces.append(t)
+            scores.append(float(sc))
+        if isinstance(unk_id, bool) or not isinstance(unk_id, int):
+            raise TypeError("unk_id must be an int (the reference raises at the first unknown character without one; here it is required)")
+        for name, v in (("whitespace_split", whitespace_split), ("collapse_spaces", collapse_spaces)):
+            if not isinstance(v, bool):
+                raise TypeError("%s must be a bool, not %s" % (name, type(v).__name__))
+        if not isinstance(prepend_scheme, str):
+            raise TypeError("prepend_scheme must be a str")
+        if prepend_scheme not in ("always", "first", "never"):
+            raise ValueError("prepend_scheme must be \"always\", \"first\" or \"never\", not %r" % (prepend_scheme,))
+        if not pieces:
+            raise ValueError("vocab is empty")
+        if not 0 <= unk_id < len(pieces):
+            raise ValueError("unk_id %d is no id of the vocabulary" % unk_id)
+        if whitespace_split and prepend_scheme == "never":
+            raise ValueError("whitespace_split needs prepend_scheme \"always\"")
+        if device is not None and not isinstance(device, int) and (isinstance(device, str) or not hasattr(device, "index")):
+            raise TypeError("device must be a torch device, an int or None")
+        self._pieces, self._scores, self.unk_id = pieces, scores, unk_id
+        self._ids = {t: i for i, t in enumerate(pieces)}  # (the later id wins)
+        self.prepend_scheme, self.whitespace_split, self.collapse_spaces = prepend_scheme, whitespace_split, collapse_spaces
+        self._flags = ((0 if prepend_scheme == "never" else _capi.UG_PREPEND) | (_capi.UG_WHITESPACE_SPLIT if whitespace_split else 0)
+                       | (_capi.UG_COLLAPSE_SPACES if collapse_spaces else 0))
+        self.normalize = None  # the default of the list forms' normalize= (from_tokenizer sets it)
+        self._device = device
+        self._handles = {}
+
+    @classmethod
+    def from_file(cls, path, **options):
+        """A tokenizer.json-style JSON file: the whole file, or its "model" object (type "Unigram", vocab, unk_id)."""
+        import json
+        with open(path, "rb") as f:
+            obj = json.loads(f.read().decode("utf-8"))
+        model = obj.get("model", obj) if isinstance(obj, dict) else None
+        if not isinstance(model, dict) or model.get("type", "Unigram") != "Unigram" or "vocab" not in model:
+            raise ValueError("%s holds no Unigram model (an object with type \"Unigram\", vocab and unk_id)" % path)
+        if model.get("byte_fallback"):
+            raise ValueError("%s: byte_fallback is not supported" % path)
+        if model.get("unk_id") is None:
+            raise ValueError("%s: the model has no unk_id" % path)
+        return cls([(p, s) for p, s in model["vocab"]], model["unk_id"], **options)
+
+    @classmethod
+    def from_tokenizer(cls, tok, assume_normalized=False, device=None):
+        """From a `tokenizers.Tokenizer` or a `transformers` fast tokenizer whose model is Unigram behind a Metaspace
+        pre-tokenizer (hf.unigram_options lists what is accepted).  Anything else: ValueError naming the step; with
+        assume_normalized=True the normaliser steps that cannot be reproduced are dropped and the caller vouches for
+        the text.  A normalisation form (NFC .. NFKD) becomes the instance's `normalize` default."""
+        from . import hf
+        vocab, options = hf.unigram_options(tok, assume_normalized=assume_normalized)
+        form = options.pop("normalize")
+        unk_id = options.pop("unk_id")
+        self = cls(vocab, unk_id, device=device, **options)
+        self.normalize = form
+        return self
+
+    @property
+    def vocab_size(self):
+        return len(self._pieces)
+
+    def token_to_id(self, token):
+        return self._ids.get(token)
+
+    def id_to_token(self, i):
+        return self._pieces[i] if 0 <= i < len(self._pieces) else None
+
+    def _handle(self, dev):
+        h = self._handles.get(dev.index)
+        if h is None:
+            h = self._handles[dev.index] = _capi.Unigram([t.encode("utf-8", "surrogateescape") for t in self._pieces], self._scores,
+                                                         self.unk_id, self._flags, dev.index)
+        return h
+
+    def encode_packed_device(self, d_bytes, d_offsets, check=True, return_word_ids=False):
+        """Device tensors in (uint8 bytes, int64 offsets[n + 1]), device tensors out: (ids int32, out_offsets int64[n + 1])
+        -- the pair every collate_* function and SequencePacker.add take -- and with return_word_ids the index of every
+        id's word in its document (int32, what `tokenizers` calls word_ids; mask_tokens(word_ids=) takes it).  Runs on
+        the current torch stream.  ids is a view of a buffer of the capacity bound (n_bytes + n_docs); its length is read
+        from the device, which is the call's one synchronisation.  check=True: offsets that do not describe d_bytes raise
+        ValueError."""
+        _packed_text_args(d_bytes, d_offsets)
+        import torch
+        dev = d_bytes.device
+        h = self._handle(dev)
+        n_docs, n_bytes = d_offsets.numel() - 1, d_bytes.numel()
+        cap = h.ids_capacity(n_bytes, n_docs)
+
+        def call():
+            ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            oo = torch.zeros(n_docs + 1, dtype=torch.int64, device=dev)
+            wi = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if return_word_ids else None
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            h.batch_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap, oo.data_ptr(),
+                           wi.data_ptr() if return_word_ids else 0, err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return (ids, oo, err, wi) if return_word_ids else (ids, oo, err)
+
+        res = _on_torch_stream(dev, call, used=(d_bytes, d_offsets))
+        ids, oo, err = res[:3]
+        code = int(err.item()) if check else 0
+        if code:
+            raise ValueError("hutoken_amd: Unigram.encode_packed_device: device-side error %d (offsets that do not "
+                             "describe d_bytes)" % code)
+        total = int(oo[n_docs].item())
+        return (ids[:total], oo, res[3][:total]) if return_word_ids else (ids[:total], oo)
+
+    def batch_encode(self, texts, normalize=None):
+        """A list of str -> a list of lists of ids, encoded on the GPU.  normalize="NFC" (.. "NFKD"): the packed text is
+        put into that form on the GPU first (None: the instance's default, which from_tokenizer sets)."""
+        import numpy as np
+        import torch
+        from .normalize import form_index  # (by module name: after a reload of the package its attribute `normalize` is the function)
+        form = self.normalize if normalize is None else normalize
+        if form is not None:
+            form_index(form)
+        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+            raise TypeError("Invalid arguments. Expected a list of strings.")
+        chunks = [t.encode("utf-8", "surrogateescape") for t in texts]
+        offs = np.zeros(len(chunks) + 1, dtype=np.int64)
+        if chunks:
+            np.cumsum(np.fromiter(map(len, chunks), dtype=np.int64, count=len(chunks)), out=offs[1:])
+        d = self._device
+        dev = torch.device("cuda", torch.cuda.current_device() if d is None else d if isinstance(d, int) else
+                           (d.index if d.index is not None else torch.cuda.current_device()))
+        d_bytes = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()).to(dev)
+        d_offs = torch.from_numpy(offs).to(dev)
+        if form is not None:
+            with torch.cuda.device(dev):
+                d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, form)
+        ids, oo = self.encode_packed_device(d_bytes, d_offs)
+        flat, bounds = ids.tolist(), oo.tolist()
+        return [flat[bounds[i]:bounds[i + 1]] for i in range(len(chunks))]
+
+    def encode(self, text, normalize=None):
+        """One str -> its list of ids."""
+        if not isinstance(text, str):
+            raise TypeError("Invalid arguments. Expected a string.")
+        return self.batch_encode([text], normalize=normalize)[0]
 
 
 # ---- split presets (hutk_presplit.hip, DESIGN.md section 4d) ----

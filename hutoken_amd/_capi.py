@@ -163,6 +163,14 @@ SIGNATURES = {
     "hutk_wordpiece_encode_batch": (_i32, [_vp, _vp, _vp, _i64, _pvp, _pvp, _pvp]),
     "hutk_debug_wordpiece_chunk_bytes": (_i32, []),
     "hutk_debug_wordpiece_bucket": (_i64, [_vp, _vp, _i64, _i32]),
+    "hutk_unigram_create": (_i32, [_pvp, _i32, _vp, _vp, _vp, _i64, _i64, _u32]),
+    "hutk_unigram_destroy": (None, [_vp]),
+    "hutk_unigram_info": (_i32, [_vp, _vp]),
+    "hutk_unigram_ids_capacity": (_i64, [_vp, _i64, _i64]),
+    "hutk_unigram_encode_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_unigram_encode_batch": (_i32, [_vp, _vp, _vp, _i64, _pvp, _pvp, _pvp]),
+    "hutk_debug_unigram_chunk_bytes": (_i32, []),
+    "hutk_debug_unigram_bucket": (_i64, [_vp, _vp, _i64]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -1288,3 +1296,77 @@ class WordPiece(_Owner):
 
 def wordpiece_chunk_bytes():
     return load().hutk_debug_wordpiece_chunk_bytes()
+
+
+UNIGRAM_INFO = ["chunk_bytes", "vocab_size", "table_slots", "flags", "unk_id", "max_piece_bytes", "piece_bytes_bound", "group_lanes"]
+UG_PREPEND, UG_WHITESPACE_SPLIT, UG_COLLAPSE_SPACES = 1, 2, 4
+
+
+class Unigram(_Owner):
+    """Owns one hutk_unigram (Unigram encoding on the GPU, include/hutoken_amd.h): the vocabulary's table and scores on
+    one device."""
+    _destroy = "hutk_unigram_destroy"
+
+    def __init__(self, pieces, scores, unk_id, flags, device=-1):
+        """pieces: the vocabulary, a list of bytes; scores: as many floats"""
+        import numpy as np
+        h = C.c_void_p()
+        offs = np.zeros(len(pieces) + 1, dtype=np.int64)
+        if pieces:
+            np.cumsum(np.fromiter(map(len, pieces), dtype=np.int64, count=len(pieces)), out=offs[1:])
+        data = np.frombuffer(b"".join(pieces) or b"\0", dtype=np.uint8)
+        sc = np.ascontiguousarray(scores, dtype=np.float64)
+        raise_for(load().hutk_unigram_create(C.byref(h), int(device), data.ctypes.data, offs.ctypes.data,
+                                             sc.ctypes.data if len(sc) else None, len(pieces), int(unk_id), int(flags)))
+        self._h = h
+
+    def info(self):
+        import numpy as np
+        out = np.zeros(8, dtype=np.int64)
+        raise_for(load().hutk_unigram_info(self._h, out.ctypes.data))
+        return dict(zip(UNIGRAM_INFO, out.tolist()))
+
+    def ids_capacity(self, n_bytes, n_docs):
+        return load().hutk_unigram_ids_capacity(self._h, n_bytes, n_docs)
+
+    def bucket(self, piece):
+        """hutk_debug_unigram_bucket: the slot the probe of `piece` (folded bytes) starts at"""
+        buf = (C.c_uint8 * max(len(piece), 1)).from_buffer_copy(bytes(piece) or b"\0")
+        return load().hutk_debug_unigram_bucket(self._h, C.cast(buf, C.c_void_p), len(piece))
+
+    def batch_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets, d_word_ids=0, d_err=0, stream=0):
+        """hutk_unigram_encode_batch_device on raw device pointers (ints).  Asynchronous on `stream`, never synchronises."""
+        raise_for(load().hutk_unigram_encode_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                          d_ids or None, ids_cap, d_out_offsets or None, d_word_ids or None,
+                                                          d_err or None, stream or None))
+
+    def batch(self, data, offsets, word_ids=False):
+        """Host numpy buffers in and out (hutk_unigram_encode_batch): -> (ids int32, out_offsets int64[n + 1]) and, with
+        word_ids, the word ids (int32)."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        if n < 0:
+            raise TypeError("offsets must hold at least one entry")
+        if int(offsets[n]) > len(data):
+            raise TypeError("offsets point outside data")
+        L = load()
+        ids, oo, wi = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        raise_for(L.hutk_unigram_encode_batch(self._h, data.ctypes.data if len(data) else None, offsets.ctypes.data, n,
+                                              C.byref(ids), C.byref(oo), C.byref(wi) if word_ids else None))
+        try:
+            r_oo = np.frombuffer((C.c_int64 * (n + 1)).from_address(oo.value), dtype=np.int64).copy()
+            total = int(r_oo[n])
+            r_ids = np.frombuffer((C.c_int32 * max(total, 1)).from_address(ids.value), dtype=np.int32)[:total].copy()
+            r_wi = np.frombuffer((C.c_int32 * max(total, 1)).from_address(wi.value), dtype=np.int32)[:total].copy() if word_ids else None
+        finally:
+            L.hutk_host_free(ids)
+            L.hutk_host_free(oo)
+            if word_ids:
+                L.hutk_host_free(wi)
+        return (r_ids, r_oo, r_wi) if word_ids else (r_ids, r_oo)
+
+
+def unigram_chunk_bytes():
+    return load().hutk_debug_unigram_chunk_bytes()

@@ -245,3 +245,60 @@ def wordpiece_options(tok):
                        lowercase=bool(norm.get("lowercase", True)), strip_accents=norm.get("strip_accents"),
                        clean_text=bool(norm.get("clean_text", True)),
                        handle_chinese_chars=bool(norm.get("handle_chinese_chars", True)))
+
+
+def unigram_options(tok, assume_normalized=False):
+    """What hutoken_amd.Unigram.from_tokenizer reads from a `tokenizers.Tokenizer` or a `transformers` fast tokenizer:
+    -> ([(piece, score)] in id order, dict(unk_id, prepend_scheme, whitespace_split, collapse_spaces, normalize)).
+    Accepted: a model Unigram with byte_fallback false; a pre-tokenizer Metaspace (replacement U+2581, split true, prepend
+    always / first / never, first read as always) or Sequence[WhitespaceSplit, Metaspace]; a normaliser that is absent, or
+    Replace(" {2,}", " "), or one of NFC / NFD / NFKC / NFKD (reported as `normalize`), or a Sequence of those.  Anything
+    else raises ValueError naming the step -- Precompiled, Strip and Lowercase among them; with assume_normalized=True such
+    normaliser steps are dropped instead and the caller vouches for the text.  Nothing is read from disk or network."""
+    js = _backend_json(tok)
+    if js is None and hasattr(tok, "to_str"):
+        js = json.loads(tok.to_str())
+    if js is None:
+        raise ValueError("from_tokenizer needs a tokenizers.Tokenizer or a transformers fast tokenizer, not %s" % type(tok).__name__)
+
+    def kind(node):
+        return "none" if node is None else str(node.get("type"))
+
+    model, norm, pre = js.get("model") or {}, js.get("normalizer"), js.get("pre_tokenizer")
+    if kind(model) != "Unigram":
+        raise ValueError("from_tokenizer: the model is %s, not Unigram" % kind(model))
+    if model.get("byte_fallback"):
+        raise ValueError("from_tokenizer: the model's byte_fallback is on, which is not supported")
+    if model.get("unk_id") is None:
+        raise ValueError("from_tokenizer: the model has no unk_id")
+    steps = pre.get("pretokenizers", []) if kind(pre) == "Sequence" else [pre]
+    names = [kind(s) for s in steps]
+    if names == ["Metaspace"]:
+        split_ws = False
+    elif names == ["WhitespaceSplit", "Metaspace"]:
+        split_ws = True
+    else:
+        raise ValueError("from_tokenizer: the pre-tokenizer is %s, not Metaspace or Sequence[WhitespaceSplit, Metaspace]"
+                         % ("Sequence[%s]" % ", ".join(names) if kind(pre) == "Sequence" else kind(pre)))
+    ms = steps[-1]
+    if ms.get("replacement", "▁") != "▁":
+        raise ValueError("from_tokenizer: Metaspace's replacement is %r, not U+2581" % (ms.get("replacement"),))
+    if ms.get("split", True) is not True:
+        raise ValueError("from_tokenizer: Metaspace's split is off")
+    scheme = ms.get("prepend_scheme", "always")
+    if scheme not in ("always", "first", "never"):
+        raise ValueError("from_tokenizer: Metaspace's prepend_scheme is %r" % (scheme,))
+    form, collapse = None, False
+    for step in ([] if norm is None else norm.get("normalizers", []) if kind(norm) == "Sequence" else [norm]):
+        k = kind(step)
+        pattern = step.get("pattern") or {}
+        if k in ("NFC", "NFD", "NFKC", "NFKD") and form is None and not collapse:
+            form = k
+        elif k == "Replace" and pattern.get("Regex") == " {2,}" and step.get("content") == " ":
+            collapse = True
+        elif not assume_normalized:
+            raise ValueError("from_tokenizer: the normalizer step %s cannot be reproduced (assume_normalized=True drops it: "
+                             "the caller then vouches for the text)" % k)
+    vocab = [(p, float(s)) for p, s in model.get("vocab") or []]
+    return vocab, dict(unk_id=int(model["unk_id"]), prepend_scheme="never" if scheme == "never" else "always",
+                       whitespace_split=split_ws, collapse_spaces=collapse, normalize=form)

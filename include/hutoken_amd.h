@@ -1341,6 +1341,77 @@ int hutk_wordpiece_encode_batch(hutk_wordpiece* h, const uint8_t* bytes, const i
 int hutk_debug_wordpiece_chunk_bytes(void);
 int64_t hutk_debug_wordpiece_bucket(const hutk_wordpiece* h, const uint8_t* bytes, int64_t len, int continuation);
 
+/* ---- Unigram: Metaspace word split and the best path over a word's piece lattice ---------------------------------
+ * The encoder of SentencePiece-style Unigram vocabularies (T5, mT5, ALBERT, XLNet, XLM-R, mBART, Pegasus) on the device
+ * (hutk_unigram.hip, hutk_unigram.h): the pair (uint8 bytes, int64 offsets[n_docs + 1]) in, the
+ * ragged (int32 ids, int64 out_offsets[n_docs + 1]) of hutk_encode_batch_device out.  The reference has no counterpart;
+ * the contract is the `tokenizers` package: models.Unigram(vocab, unk_id, byte_fallback=False) behind
+ * pre_tokenizers.Metaspace(replacement U+2581, split=True), id for id and word id for word id.  Documents are independent.
+ *
+ * WORDS (flags HUTK_UG_*).  An empty document has no words.
+ *   HUTK_UG_COLLAPSE_SPACES runs first: of a run of two or more U+0020 one stays (normalizers.Replace(" {2,}", " ")).
+ *   Without HUTK_UG_WHITESPACE_SPLIT every U+0020 becomes U+2581 (a tab, a newline and U+00A0 are ordinary characters);
+ *   with HUTK_UG_PREPEND (prepend_scheme "always") a U+2581 is put in front of the document unless it starts with a
+ *   space or a literal U+2581; a word starts at every U+2581 and at the document's first character.  "a  b\tab" is
+ *   U+2581 "a", U+2581, U+2581 "b\tab".  A literal U+2581 in the text acts exactly like a space.
+ *   With HUTK_UG_WHITESPACE_SPLIT (pre_tokenizers.Sequence[WhitespaceSplit, Metaspace]; needs HUTK_UG_PREPEND) the words
+ *   are the maximal runs of characters that are not White_Space (Rust's char::is_whitespace: U+0009-000D, 0020, 0085,
+ *   00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000); each run gets a U+2581 in front unless it starts with a
+ *   literal one, and is split further at every literal U+2581 inside it.  The whitespace itself yields nothing.
+ * PIECES of a word, taken as bytes b[0 .. n): encode_optimized with f64 scores.  unk_score = min(all scores) - 10,
+ *   best[0] = 0.  For every character start s in rising order, m being the byte length of the character at s: every
+ *   vocabulary piece equal to b[s .. s + L) is a candidate score(piece) + best[s] for position s + L, which replaces what
+ *   the position holds if it holds nothing yet or if the candidate is strictly greater (so among equal scores the smallest
+ *   s, the longest last piece, wins); if no piece equals the one character b[s .. s + m) the unknown piece (unk_id,
+ *   unk_score) is a candidate for s + m by the same rule.  The path is walked back from n; consecutive ids equal to
+ *   unk_id inside one word fuse into one (never across words; a line that sits at unk_id and matched literally counts).
+ *   Of two equal lines the later id, with its own score, is the one found.  The additions are plain IEEE f64.
+ *   A byte that strict UTF-8 rejects is a character of one byte that no piece matches (`tokenizers` takes str only: this
+ *   is the library's own definition); a sequence that a document's end cuts short is such bytes.
+ *
+ * hutk_unigram_create: a handle on one device (device < 0: the current one); it needs no hutk_ctx.  Piece i of the
+ *   n_pieces is piece_bytes[piece_offsets[i] .. piece_offsets[i + 1]) with scores[i]; its id is i.  HUTK_E_VALUE: no
+ *   piece or 2^30 and more, an empty piece, a score that is not finite, an unk_id outside the vocabulary, a piece of
+ *   more than 256 bytes (a U+2581 counted as one), HUTK_UG_WHITESPACE_SPLIT without HUTK_UG_PREPEND.  The table is built
+ *   on the host and uploaded once: open addressing over the piece bytes, 16 bytes a slot, a load of at most one half,
+ *   all keys in one byte blob, a slot a hit only after its bytes have been compared; the scores as f64 by id; per first
+ *   byte a 64-bit mask of the key lengths that exist.  A key stores a leading U+2581 as the byte 0x20, as the folded
+ *   text does.  A piece that holds a real space, a U+2581 anywhere but at its start, or ill-formed UTF-8 can never
+ *   match and is kept for its id alone.
+ * hutk_unigram_info: out8 = chunk bytes, pieces, table slots, flags, the unk id, the longest key in bytes, the length
+ *   bound (256), the lanes of a group.
+ * hutk_unigram_ids_capacity: n_bytes + n_docs.  An id covers at least one byte of the folded text, a byte of the source
+ *   becomes at most one of the folded text, and the prefixes add at most one per document (a run's prefix under
+ *   HUTK_UG_WHITESPACE_SPLIT takes the place of the whitespace in front of it); DESIGN.md section 8n has the proof.
+ * hutk_unigram_encode_batch_device: asynchronous on hip_stream, never synchronises (growing the handle's workspace for
+ *   a batch larger than any before may wait once).  d_ids[ids_cap], d_out_offsets[n_docs + 1]; d_word_ids (int32 per id,
+ *   may be NULL): the index of the id's word in its document, what `tokenizers` calls word_ids.  d_err (may be NULL) takes
+ *   the first device-side error: HUTK_E_ARG for offsets that do not rise from 0 to n_bytes (the kernels refuse before they
+ *   read through them, and nothing else is written), HUTK_E_CAPACITY for an ids_cap below the total (no id is written).
+ *   The text is cut into chunks of hutk_debug_unigram_chunk_bytes() bytes; a word may cross any number of chunk edges
+ *   and has no length limit.  Alignment of every buffer: that of its element type.  Calls on one handle are serialised.
+ * hutk_unigram_encode_batch: host arrays in; the work is done on the GPU; *out_ids ((*out_offsets)[n_docs] entries),
+ *   *out_offsets (n_docs + 1 entries) and, when out_word_ids is not NULL, *out_word_ids are allocated here and given
+ *   back with hutk_host_free.
+ * hutk_debug_unigram_bucket: the slot the probe of the piece (its folded bytes) starts at (tests build pieces that share
+ *   one); -1 on bad arguments. */
+#define HUTK_UG_PREPEND 1u
+#define HUTK_UG_WHITESPACE_SPLIT 2u
+#define HUTK_UG_COLLAPSE_SPACES 4u
+typedef struct hutk_unigram hutk_unigram;
+int hutk_unigram_create(hutk_unigram** out, int device, const uint8_t* piece_bytes, const int64_t* piece_offsets, const double* scores,
+                        int64_t n_pieces, int64_t unk_id, uint32_t flags);
+void hutk_unigram_destroy(hutk_unigram* h);
+int hutk_unigram_info(const hutk_unigram* h, int64_t* out8);
+int64_t hutk_unigram_ids_capacity(const hutk_unigram* h, int64_t n_bytes, int64_t n_docs);
+int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                     int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err,
+                                     void* hip_stream);
+int hutk_unigram_encode_batch(hutk_unigram* h, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int32_t** out_ids,
+                              int64_t** out_offsets, int32_t** out_word_ids);
+int hutk_debug_unigram_chunk_bytes(void);
+int64_t hutk_debug_unigram_bucket(const hutk_unigram* h, const uint8_t* bytes, int64_t len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,8 @@ SIGNATURES = {
     "hutk_debug_seam2_cut": (_i32, [_vp, _u32, _u32]),
     "hutk_debug_tile_kernel": (_i32, [_vp, _i64]),
     "hutk_debug_exc_counts": (_i32, [_vp, _vp]),
+    "hutk_ctx_word_cache_stats": (_i32, [_vp, _vp]),
+    "hutk_ctx_word_cache_clear": (_i32, [_vp]),
     "hutk_trainer_create": (_i32, [_pvp, _i32]),
     "hutk_trainer_add": (_i32, [_vp, _vp, _vp, _i64]),
     "hutk_trainer_run": (_i32, [_vp, _s32, _vp, _vp, _ps32]),
@@ -438,6 +440,19 @@ class Context(_Owner):
         raise_for(load().hutk_debug_exc_counts(self._h, out.ctypes.data))
         v = out.tolist()
         return {"exc": v[0], "lists": v[1:6], "tail": v[6], "has_multi": bool(v[7])}
+
+    def word_cache_stats(self):
+        """The learned table of multi-token words: {"entries", "capacity" (slots; 0: the context has no table), "appended":
+        candidates the last learning batch handed to the table, "open": it still learns}.  Waits for the context's last call."""
+        import numpy as np
+        out = np.zeros(4, dtype=np.int64)
+        raise_for(load().hutk_ctx_word_cache_stats(self._h, out.ctypes.data))
+        v = out.tolist()
+        return {"entries": v[0], "capacity": v[1], "appended": v[2], "open": bool(v[3])}
+
+    def word_cache_clear(self):
+        """Empty the learned table of multi-token words; it learns again from the next large batch."""
+        raise_for(load().hutk_ctx_word_cache_clear(self._h))
 
     def _encode_host(self, fn, capacity, data, offsets, flags=()):
         """Host numpy buffers through the library's host encode `fn` (its flags, if it takes any, as a 1-tuple) with ids

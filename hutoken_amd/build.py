@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
 HIP_SOURCES = ["hutk_loader.cpp", "hutk_api.cpp", "hutk_kernels.hip", "hutk_ptiles.hip", "hutk_decode.hip", "hutk_train.hip", "hutk_collate.hip", "hutk_spans.hip", "hutk_special.hip", "hutk_fallback.hip", "hutk_normalize.hip", "hutk_presplit.hip", "hutk_features.hip", "hutk_bestfit.hip", "hutk_wordpiece.hip", "hutk_unigram.hip"]
-HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_host.h", "hutk_classify.h", "hutk_lab.h", "hutk_exc.h", "hutk_norm.h", "hutk_presplit.h", "hutk_wave.h", "hutk_philox.h", "hutk_fim.h", "hutk_wordpiece.h", "hutk_unigram.h", os.path.join(INCLUDE, "hutoken_amd.h")]
+HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_host.h", "hutk_classify.h", "hutk_lab.h", "hutk_exc.h", "hutk_norm.h", "hutk_presplit.h", "hutk_wave.h", "hutk_philox.h", "hutk_fim.h", "hutk_wordpiece.h", "hutk_unigram.h", "hutk_wcache.h", os.path.join(INCLUDE, "hutoken_amd.h")]
 
 LIB_HIP = os.path.join(LIBDIR, "libhutoken_amd.so")
 LIB_SYNTH = os.path.join(LIBDIR, "libhutk_synth.so")

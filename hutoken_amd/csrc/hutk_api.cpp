@@ -280,6 +280,7 @@ void destroy(hutk_ctx* c) {
         c->d_pair.release(); c->d_char.release(); c->d_sym_id.release(); c->d_prefix_alone.release();
         c->d_item_sym.release(); c->d_prefix_syms.release(); c->d_prefix_alone_syms.release(); c->d_item_direct.release(); c->d_split_dfa.release(); c->d_seam.release(); c->d_seam2.release(); c->d_item_units.release();
         c->d_bytepair16.release(); c->d_bytepair32.release(); c->w_prof.release();
+        c->d_wc_tab.release(); c->d_wc_list.release(); c->d_wc_tags.release(); c->d_wc_ctl.release();
         c->d_word_tab.release(); c->w_wbits.release(); c->w_gbits.release(); c->w_fbits.release(); c->w_abits.release();
         c->w_run.release(); c->w_exc_tok.release(); c->w_exc_sym.release(); c->w_exc_mrg.release();
         c->w_tile_u32.release(); c->w_doc_pos.release(); c->w_counters.release(); c->w_tile_i64.release();
@@ -399,6 +400,44 @@ int build_word_table(hutk_ctx* c) {
     return HUTK_OK;
 }
 
+// Word cache (hutk_wcache.h): every slot, tag and control word zero -- an empty table that learns.  The device is selected
+// and the context's last call has ended.
+int word_cache_zero(hutk_ctx* c) {
+    if (!c->dt.wc_on) return HUTK_OK;
+    const size_t slots = (size_t)2 << c->dt.wc_log2;
+    // (on the context's own stream, and waited for there: the other streams of the process are left alone)
+    HUTK_HIP_TRY(hipMemsetAsync(c->d_wc_tab.p, 0, slots * sizeof(wc::Slot), c->stream));
+    HUTK_HIP_TRY(hipMemsetAsync(c->d_wc_tags.p, 0, slots * sizeof(uint32_t), c->stream));
+    HUTK_HIP_TRY(hipMemsetAsync(c->d_wc_ctl.p, 0, wc::CTL_DWORDS * sizeof(uint32_t), c->stream));
+    HUTK_HIP_TRY(hipStreamSynchronize(c->stream));
+    return HUTK_OK;
+}
+// Made AFTER build_word_table's verification encodes, so that nothing those learn is in it.  The kernels read it in one
+// instantiation only (byte-encoder mode, 16-bit symbols, rank == symbol order, no multi-unit items); every other
+// context has none.  HUTK_WORD_CACHE=0: none (the switch is read like HUTK_NO_SEAM, when the device tables are made);
+// HUTK_WORD_CACHE_LOG2: log2 of the buckets.  The context's device tables are uploaded once (upload_tables, here in
+// attach_device) and no setter changes what a word encodes to, so nothing but hutk_ctx_word_cache_clear clears it later.
+int word_cache_create(hutk_ctx* c) {
+    const Tables& T = c->tab;
+    c->dt.wc_on = 0;
+    if (getenv("HUTK_WORD_CACHE") && !atoi(getenv("HUTK_WORD_CACHE"))) return HUTK_OK;
+    if (!T.is_byte_encoder || !T.sym16 || !T.rank_is_sym || T.has_multi) return HUTK_OK;
+    int log2 = wc::DEFAULT_LOG2;
+    if (const char* e = getenv("HUTK_WORD_CACHE_LOG2")) log2 = atoi(e);
+    log2 = std::max(0, std::min(log2, wc::MAX_LOG2));
+    const size_t slots = (size_t)2 << log2;
+    HUTK_HIP_TRY(c->d_wc_tab.reserve(slots * (sizeof(wc::Slot) / sizeof(uint4))));
+    HUTK_HIP_TRY(c->d_wc_tags.reserve(slots));
+    HUTK_HIP_TRY(c->d_wc_ctl.reserve(wc::CTL_DWORDS));
+    c->dt.wc_tab = c->d_wc_tab.p;
+    c->dt.wc_tags = c->d_wc_tags.p;
+    c->dt.wc_ctl = c->d_wc_ctl.p;
+    c->dt.wc_log2 = (uint32_t)log2;
+    c->dt.wc_on = 1;
+    c->wc_list_cap = wc::LIST_CAP;
+    return word_cache_zero(c);
+}
+
 // The device half of a context whose host tables are loaded: stream, events, tables and whole-word table on `device`
 // (-1: the calling thread's current device).
 int attach_device(hutk_ctx* c, int device) {
@@ -420,6 +459,7 @@ int attach_device(hutk_ctx* c, int device) {
     if (!ok) return api_set_error(HUTK_E_DEVICE, "hipEventCreate failed");
     int rc = upload_tables(c);
     if (rc == HUTK_OK && !getenv("HUTK_NO_WORD_TABLE")) rc = build_word_table(c);
+    if (rc == HUTK_OK) rc = word_cache_create(c);  // (build_word_table's encodes have come back: their results were read on the host)
     return rc;
 }
 
@@ -554,6 +594,34 @@ int hutk_table_stats(const hutk_ctx* ctx, int64_t* out8) {
     out8[6] = T.ident_ids;
     out8[7] = ctx->n_word_entries;
     return HUTK_OK;
+}
+
+// Word cache of the context's own device (a peer added by hutk_ctx_add_device has its own).  Both calls wait for the
+// context's last asynchronous call: the table is written by that call's last kernel.
+int hutk_ctx_word_cache_stats(hutk_ctx* c, int64_t* out4) {
+    if (!c || !out4) return api_set_error(HUTK_E_ARG, "bad argument");
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to encode on");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (!c->dt.wc_on) return HUTK_OK;
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    if (c->busy_valid) HUTK_HIP_TRY(hipEventSynchronize(c->ev_busy));
+    uint32_t ctl[wc::N_CTL];  // (the words in front of the sub-lists' counts)
+    HUTK_HIP_TRY(hipMemcpy(ctl, c->d_wc_ctl.p, sizeof ctl, hipMemcpyDeviceToHost));
+    out4[0] = ctl[wc::CTL_ENTRIES];
+    out4[1] = (int64_t)2 << c->dt.wc_log2;
+    out4[2] = ctl[wc::CTL_LAST];
+    out4[3] = ctl[wc::CTL_CLOSED] ? 0 : 1;
+    return HUTK_OK;
+}
+int hutk_ctx_word_cache_clear(hutk_ctx* c) {
+    if (!c) return api_set_error(HUTK_E_ARG, "ctx is NULL");
+    if (c->host_only) return api_set_error(HUTK_E_DEVICE, "host-only context: no device to encode on");
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (!c->dt.wc_on) return HUTK_OK;
+    HUTK_HIP_TRY(hipSetDevice(c->device));
+    if (c->busy_valid) HUTK_HIP_TRY(hipEventSynchronize(c->ev_busy));
+    return word_cache_zero(c);
 }
 
 // Diagnostic: per-phase clock64 stamps of k_tiles.  enable, run one batch, then read
@@ -748,6 +816,11 @@ extern "C++" int hutk::encode_device_impl(hutk_ctx* c, const uint8_t* d_bytes, c
     A.gap_bits = d_gap_bits;
     A.first_bits = d_first_bits;
     A.alone_bits = d_alone_bits;
+    if (c->dt.wc_on && !small_tail(A)) {  // the batches whose tail is k_finish learn: its d_learn empties the list
+        HUTK_HIP_TRY(c->d_wc_list.reserve((size_t)c->wc_list_cap * (sizeof(wc::Slot) / sizeof(uint4))));
+        W.wc_list = c->d_wc_list.p;
+        W.wc_list_cap = c->wc_list_cap;
+    }
 
     c->ev_valid = false;
     if (c->timing) HUTK_HIP_TRY(hipEventRecord(c->ev[0], s));

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "hutk_internal.h"
+#include "hutk_wcache.h"
 
 namespace hutk {
 
@@ -87,6 +88,14 @@ struct DevTables {
     const uint32_t* item_units_off;
     const uint32_t* item_units;
     int32_t has_multi, unit_scale;
+    // the learned table of multi-token words (hutk_wcache.h): 2 << wc_log2 slots of 64 bytes, read by k_tiles (byte-encoder
+    // mode, 16-bit symbols, rank == symbol order, no multi-unit items) and written only by k_finish's d_learn, through
+    // the tag words wc_tags[slot]; wc_ctl: the wc::CTL_* words.  wc_on == 0: no table (HUTK_WORD_CACHE=0, other modes)
+    uint4* wc_tab;
+    uint32_t* wc_tags;
+    uint32_t* wc_ctl;
+    uint32_t wc_log2;
+    int32_t wc_on;
 };
 
 // one word the tile kernel hands to the exception kernel
@@ -158,6 +167,10 @@ struct Workspace {
     // only for one that is not (k_tiles).  The kernel that is not chosen returns at once.
     int32_t select;
     uint8_t* one_in;    // k_tiles<..., ONE>: device memory for the batch's offsets and bytes (copied from the caller's host memory once)
+    // word cache: the candidate list the merge loop appends to (64-byte records in the slot's own layout) and its capacity;
+    // 0: this batch does not learn (the small-batch tails, the one-launch kernel, a context without the table)
+    uint4* wc_list;
+    uint32_t wc_list_cap;
     int32_t* one_flag;  // k_tiles<..., ONE>: page-locked host memory; 1 = the batch's ids and offsets are in the caller's buffers, 2 = exception words: the tail is still to run
 };
 constexpr int SELECT_SAMPLE = 16, SELECT_DENSE_DIV = 8, SELECT_BLOCK_STRIDE = 8;  // (k_pre: 256 tiles per workgroup)

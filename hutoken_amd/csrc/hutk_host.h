@@ -115,6 +115,11 @@ struct hutk_ctx {
     DevBuf<uint32_t> d_bytepair16;  // {symbol, merged} as 16 + 16 bits
     DevBuf<hutk::WordSlot> d_word_tab;
     int64_t n_word_entries = 0, n_wordl_entries = 0;  // whole-word table entries in all, and those of the long-word companion
+    // word cache (hutk_wcache.h): slots, their tag words, the control words, and the candidate list of a batch (allocated
+    // by the first batch that learns); wc_list_cap == 0: the context has no table
+    DevBuf<uint4> d_wc_tab, d_wc_list;
+    DevBuf<uint32_t> d_wc_tags, d_wc_ctl;
+    uint32_t wc_list_cap = 0;
     DevBuf<uint64_t> d_bytepair32;  // {symbol, merged} as 32 + 32 bits
     DevBuf<long long> w_prof;
     bool profile = false;

@@ -188,6 +188,9 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
     static_assert(WAVES <= 32, "pool entries keep the tile-in-workgroup index in 6 bits");
     // the merge loop's short form: 16-bit symbols, rank == symbol order (GPT-2-shaped files, and the id-keyed path)
     constexpr bool FAST_TRIPS = RANK_IS_SYM && sizeof(SymT) == 2;
+    // the word cache (hutk_wcache.h) is read and filled by this one instantiation (and read by its ONE form): what the
+    // benchmark's vocabulary runs; every other one compiles it out
+    constexpr bool WCACHE = BYTE_MODE && FAST_TRIPS && !MULTI;
     __shared__ Tile L[WAVES];
     __shared__ uint32_t pool_cnt[3];  // long words, other words, entries of the arena handed out
     // Exception records and places on d_gather_exc's list are claimed per WORKGROUP (one 64-bit atomic for its tiles, in the
@@ -297,6 +300,31 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
         for (int i = 0; i < nb; i++) n += !is_cont(X.sb[ws + LOOKBACK + i]);
         return n;
     };
+    // word cache: the key of the word of nb bytes at position ws of tile X (its bytes out of LDS as nine aligned dwords;
+    // a lane-path word starts below TILE_BYTES, so the reads stay inside the staged window)
+    static_assert(LOOKBACK + TILE_BYTES + 3 + 4 * (wc::KEY_DWORDS + 1) <= WINDOW, "key reads inside the window");
+    [[maybe_unused]] auto wc_key = [&](const Tile& X, int ws, int nb, uint32_t (&k)[wc::KEY_DWORDS]) {
+        const int a = (ws + LOOKBACK) & ~3, o8 = 8 * ((ws + LOOKBACK) & 3);
+        const uint32_t* sw = reinterpret_cast<const uint32_t*>(X.sb + a);
+        uint32_t q[wc::KEY_DWORDS + 1];
+#pragma unroll
+        for (int j = 0; j <= wc::KEY_DWORDS; j++) q[j] = sw[j];
+#pragma unroll
+        for (int j = 0; j < wc::KEY_DWORDS; j++) k[j] = funnel_r(q[j + 1], q[j], o8);
+        wc::make_key(k, nb);
+    };
+    // Does this workgroup's merge loop hand its finished words to the table?  One relaxed load each of the count of its
+    // sub-list (wc::LIST_SHARDS of them, by block index) and of the closed flag, uniform: once the sub-list is full or
+    // the table closed, the workgroups behind pay no atomic.
+    [[maybe_unused]] bool learn_open = false;
+    [[maybe_unused]] const uint32_t wc_shard = blockIdx.x & (wc::LIST_SHARDS - 1u), wc_shard_cap = W.wc_list_cap / wc::LIST_SHARDS;
+    if constexpr (WCACHE && !ONE) {
+        if (T.wc_on && W.wc_list_cap) {
+            const uint32_t cnt = __hip_atomic_load(&T.wc_ctl[wc::ctl_count(wc_shard)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t closed = __hip_atomic_load(&T.wc_ctl[wc::CTL_CLOSED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            learn_open = __builtin_amdgcn_readfirstlane((int)(cnt < wc_shard_cap && closed == 0)) != 0;
+        }
+    }
     const int64_t t0 = tile * TILE_BYTES;
     const int64_t gw = t0 - LOOKBACK;  // global offset of window index 0
     const uint32_t* wmask32 = reinterpret_cast<const uint32_t*>(wmask16);
@@ -807,6 +835,55 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
             }
         }
 
+        // ---- 6a. word cache (the head of the merge phase): the tile's merge-loop words that the context has merged before ----
+        // The tile's pending words (10-40 of them) are dealt to the lanes one each, as in the rounds above, so the probe is
+        // one memory round trip per tile: the key halves of the bucket's two slots, then the symbols of the slot that
+        // matched (the same 128-byte line).  A hit is what the merge loop would have published: the symbols at
+        // S[ws .. ws + n), their units alive, the word out of mergem -- it never enters the pool.  The table is written
+        // only by k_finish's d_learn, in another launch: nothing here can see a slot half written.
+        if constexpr (WCACHE) {
+            if (T.wc_on) {  // (uniform)
+                uint32_t pend = reinterpret_cast<const uint16_t*>(mergem)[lane];
+                uint32_t nP;
+                uint32_t pidx = wave_excl_scan((uint32_t)__popc(pend), lane, &nP);
+                for (uint32_t r0 = 0; r0 < nP; r0 += 64) {
+                    while (pend && pidx - r0 < 64u) {
+                        stage[pidx - r0] = (uint16_t)(16 * lane + __builtin_ctz(pend));
+                        pend &= pend - 1;
+                        pidx++;
+                    }
+                    wave_sync();
+                    if (r0 + lane < nP) {
+                        const int ws = stage[lane];
+                        const int nb = word_units(me, ws);  // (byte mode: a unit per byte)
+                        if (nb >= wc::MIN_BYTES && nb <= wc::KEY_BYTES) {
+                            uint32_t k[wc::KEY_DWORDS];
+                            wc_key(me, ws, nb, k);
+                            const uint4* line = T.wc_tab + (size_t)wc::bucket_of(wc::hash(k), T.wc_log2) * 8u;
+                            uint4 a0 = line[0], a1 = line[1], b0 = line[4], b1 = line[5];
+                            asm volatile("" : "+v"(a0.x), "+v"(a1.x), "+v"(b0.x), "+v"(b1.x));  // (all four in flight together)
+                            const uint32_t s1[wc::KEY_DWORDS] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                            const uint32_t s2[wc::KEY_DWORDS] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+                            const bool hit1 = wc::key_hit(s1, k), hit2 = wc::key_hit(s2, k);
+                            if (hit1 || hit2) {
+                                const uint4* sy = line + (hit1 ? 2 : 6);
+                                const uint4 y0 = sy[0], y1 = sy[1];
+                                const int n = wc::slot_n(hit1 ? a1.w : b1.w);  // 1 .. 16 and <= nb (key_hit)
+                                const uint32_t y[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
+#pragma unroll
+                                for (int i = 0; i < wc::MAX_IDS; i++)
+                                    if (i < n) S[ws + i] = (SymT)(y[i >> 1] >> (16 * (i & 1)));
+                                const uint64_t lm = (uint64_t)(((1u << n) - 1u) & ~1u) << (ws & 31);  // (unit 0 is in livem already)
+                                if ((uint32_t)lm) atomicOr(&livem[ws >> 5], (uint32_t)lm);
+                                if ((uint32_t)(lm >> 32)) atomicOr(&livem[(ws >> 5) + 1], (uint32_t)(lm >> 32));
+                                atomicAnd(&mergem[ws >> 5], ~(1u << (ws & 31)));
+                            }
+                        }
+                    }
+                    wave_sync();
+                }
+            }
+        }
     }
 
     // ---- 6. merge: the workgroup POOLS the merge-loop words of its WAVES tiles ------------------------
@@ -1063,6 +1140,42 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
 #endif
                 if (mine) {  // publish the surviving units (unit 0 is in livem already)
                     publish();
+                }
+                if constexpr (WCACHE && !ONE) {
+                    // Word cache: the finished words go onto the context's candidate list, as records in the slot's own
+                    // layout; k_finish's d_learn puts them into the table (this kernel never writes it).  Places are
+                    // claimed once per wavefront: one ballot, one atomic.
+                    if (learn_open) {  // (uniform)
+                        const int nl = __popc(live);
+                        const bool cand_ok = mine && wc::cacheable(n, nl);  // (byte mode: n units = n bytes)
+                        const unsigned long long cb = __ballot(cand_ok);
+                        if (cb) {
+                            uint32_t first = 0;
+                            if (lane == 0) first = atomicAdd(&T.wc_ctl[wc::ctl_count(wc_shard)], (uint32_t)__popcll(cb));
+                            first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+                            uint32_t at = first + (uint32_t)__popcll(cb & ((1ull << lane) - 1ull));
+                            const bool room = at < wc_shard_cap;  // (beyond the sub-list's capacity: dropped; d_learn clamps the count)
+                            at += wc_shard * wc_shard_cap;
+                            if (cand_ok && room) {
+                                uint32_t k[wc::KEY_DWORDS];
+                                wc_key(X, ws, n, k);
+                                k[7] = wc::with_n(k[7], nl);
+                                uint32_t y[8], lv = live;
+#pragma unroll
+                                for (int i = 0; i < wc::MAX_IDS; i++) {
+                                    uint32_t s = 0;
+                                    if (lv) s = Sw[__builtin_ctz(lv)];
+                                    lv &= lv - 1;
+                                    if (i & 1) y[i >> 1] |= s << 16; else y[i >> 1] = s;
+                                }
+                                uint4* rec = W.wc_list + (size_t)at * 4u;
+                                rec[0] = make_uint4(k[0], k[1], k[2], k[3]);
+                                rec[1] = make_uint4(k[4], k[5], k[6], k[7]);
+                                rec[2] = make_uint4(y[0], y[1], y[2], y[3]);
+                                rec[3] = make_uint4(y[4], y[5], y[6], y[7]);
+                            }
+                        }
+                    }
                 }
                 wave_sync();
             } else {
@@ -1644,11 +1757,95 @@ __device__ __forceinline__ void d_doc_off(const BatchArgs& A, const Workspace& W
 }
 
 
+// ------------------------------------------------------------------------
+// d_learn (k_finish): the candidates k_tiles' merge loop listed -> the word cache (hutk_wcache.h).  This is the table's
+// only writer, and it runs in a launch of its own stream position: behind the batch's k_tiles, in front of the next
+// call's (the context's mutex and StreamScope serialise calls), so no launch that reads the table overlaps it.
+// A workgroup takes the sub-lists vblock, vblock + vgrid, ..., a thread per candidate, and empties them.  A slot is
+// claimed with ONE compare-and-swap on its tag word (zero: free, else a fingerprint of the key); the winner writes the
+// slot with plain stores; a loser that finds its own tag takes the word for listed twice (or, one time in 2^31, for
+// another word: that word is simply not cached); otherwise it tries the bucket's other slot, otherwise the candidate is
+// dropped.  No loop waits for anything.  The workgroup that comes last (a ticket) adds the batch's counts up: the table
+// closes when it is three quarters full or when this batch dropped more than it placed (wc::CLOSE_*).
+// ------------------------------------------------------------------------
+constexpr int LEARN_BLOCKS = 128;
+static_assert(wc::LIST_SHARDS >= (uint32_t)LEARN_BLOCKS, "every d_learn workgroup has a sub-list (and so passes the loop's barriers)");
+__device__ __forceinline__ void d_learn(const DevTables& T, const Workspace& W, uint32_t vblock, uint32_t vgrid) {
+    __shared__ uint32_t s_cnt[3];  // listed, placed, dropped by this workgroup
+    __shared__ uint32_t s_count;   // the sub-list's count, read ONCE for the workgroup
+    uint32_t* const ctl = T.wc_ctl;
+    const uint32_t shard_cap = W.wc_list_cap / wc::LIST_SHARDS;
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    uint32_t won = 0, dropped = 0;
+    for (uint32_t shard = vblock; shard < wc::LIST_SHARDS; shard += vgrid) {  // (the same trips for every thread: the barriers are safe)
+        // The count is final (k_tiles is over, and no other workgroup touches this sub-list), but thread 0 zeroes it below:
+        // one thread reads it, and everybody has it in a register -- the second barrier -- before anybody goes on to
+        // where it is zeroed or, a trip later, read again.  (Each thread reading it for itself let a late wavefront
+        // read the zero and skip its share of the sub-list.)
+        __syncthreads();
+        if (threadIdx.x == 0)
+            s_count = min(__hip_atomic_load(&ctl[wc::ctl_count(shard)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), shard_cap);
+        __syncthreads();
+        const uint32_t count = s_count;  // (not written again before the next trip's first barrier)
+        if (count == 0) continue;  // every sub-list of every warm batch
+        for (uint32_t i = threadIdx.x; i < count; i += blockDim.x) {
+            const uint4* rec = W.wc_list + ((size_t)shard * shard_cap + i) * 4u;
+            const uint4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+            const uint32_t k[wc::KEY_DWORDS] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+            if (!wc::cacheable(wc::slot_nb(r1.w), wc::slot_n(r1.w))) continue;
+            const uint32_t h = wc::hash(k), tag = wc::tag_of(k);
+            const uint32_t slot0 = 2u * wc::bucket_of(h, T.wc_log2);
+            bool placed_or_known = false;
+            for (uint32_t sl = slot0; sl < slot0 + 2u && !placed_or_known; sl++) {
+                const uint32_t old = atomicCAS(&T.wc_tags[sl], 0u, tag);
+                if (old == 0u) {
+                    uint4* dst = T.wc_tab + (size_t)sl * 4u;
+                    dst[0] = r0; dst[1] = r1; dst[2] = r2; dst[3] = r3;
+                    won++;
+                }
+                placed_or_known = old == 0u || old == tag;
+            }
+            if (!placed_or_known) dropped++;
+        }
+        if (threadIdx.x == 0) {
+            atomicAdd(&s_cnt[0], count);
+            __hip_atomic_store(&ctl[wc::ctl_count(shard)], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (won) atomicAdd(&s_cnt[1], won);
+    if (dropped) atomicAdd(&s_cnt[2], dropped);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_cnt[0]) {
+            atomicAdd(&ctl[wc::CTL_B_LISTED], s_cnt[0]);
+            if (s_cnt[1]) atomicAdd(&ctl[wc::CTL_B_WON], s_cnt[1]);
+            if (s_cnt[2]) atomicAdd(&ctl[wc::CTL_B_DROPPED], s_cnt[2]);
+            __threadfence();
+        }
+        if (atomicAdd(&ctl[wc::CTL_TICKET], 1u) == vgrid - 1u) {  // every other workgroup has added its counts
+            const uint32_t listed = atomicAdd(&ctl[wc::CTL_B_LISTED], 0u), placed = atomicAdd(&ctl[wc::CTL_B_WON], 0u);
+            const uint32_t lost = atomicAdd(&ctl[wc::CTL_B_DROPPED], 0u);
+            // (agent-scope accesses throughout: the next launch's workgroups may run on another XCD, behind another L2)
+            auto put = [&](int i, uint32_t v) { __hip_atomic_store(&ctl[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+            const uint32_t slots = 2u << T.wc_log2;
+            const uint32_t entries = __hip_atomic_load(&ctl[wc::CTL_ENTRIES], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + placed;  // (only this thread writes it)
+            put(wc::CTL_ENTRIES, entries);
+            if ((uint64_t)entries * wc::CLOSE_DEN >= (uint64_t)slots * wc::CLOSE_NUM ||
+                (lost > placed && (uint64_t)lost * wc::CLOSE_DROP_DIV >= slots))
+                put(wc::CTL_CLOSED, 1u);
+            put(wc::CTL_LAST, listed);
+            put(wc::CTL_B_LISTED, 0u); put(wc::CTL_B_WON, 0u); put(wc::CTL_B_DROPPED, 0u);
+            put(wc::CTL_TICKET, 0u);
+        }
+    }
+}
+
 // k_finish: everything behind the scan in ONE launch -- the workgroups [0, g_gather) copy tile runs to ids_out,
-// [g_gather, g_gather + g_exc) do the same for the tiles that also hold exception words, the rest write out_offsets.
+// [g_gather, g_gather + g_exc) do the same for the tiles that also hold exception words, the next g_doc write out_offsets,
+// the rest (LEARN_BLOCKS of them in a batch that learns, else none) fill the word cache.
 constexpr int FINISH_EXC_BLOCKS = 2048;  // (18 KB of LDS each: eight per CU, 2048 resident)
 template <typename RunT>
-__global__ __launch_bounds__(64 * GATHER_WAVES) void k_finish(DevTables T, BatchArgs A, Workspace W, uint32_t g_gather) {
+__global__ __launch_bounds__(64 * GATHER_WAVES) void k_finish(DevTables T, BatchArgs A, Workspace W, uint32_t g_gather, uint32_t g_doc) {
     const uint32_t b = blockIdx.x;
     if (b < g_gather) {
         d_gather<RunT>(T, A, W, (int64_t)b * GATHER_WAVES + (threadIdx.x >> 6));
@@ -1663,8 +1860,11 @@ __global__ __launch_bounds__(64 * GATHER_WAVES) void k_finish(DevTables T, Batch
                 for (uint32_t w4 = 0; w4 < (uint32_t)GATHER_WAVES; w4++)
                     d_gather_exc<GATHER_EXC_LDS, 1>(T, A, W, (b - g_gather) * GATHER_WAVES + w4, FINISH_EXC_BLOCKS * GATHER_WAVES, lds_exc);
         }
-    } else {
+    } else if (b < g_gather + FINISH_EXC_BLOCKS + g_doc) {
         d_doc_off(A, W, (int64_t)(b - g_gather - FINISH_EXC_BLOCKS));
+    } else {
+        const uint32_t first = g_gather + FINISH_EXC_BLOCKS + g_doc;
+        d_learn(T, W, b - first, gridDim.x - first);
     }
 }
 
@@ -1919,9 +2119,10 @@ void launch_finish(const DevTables& t, const BatchArgs& a, const Workspace& w, h
     const int64_t per_wg = (int64_t)GATHER_TILES * GATHER_WAVES;
     const unsigned g_gather = (unsigned)((a.n_tiles + per_wg - 1) / per_wg);
     const unsigned g_doc = (unsigned)((a.n_docs + 1 + 64 * GATHER_WAVES - 1) / (64 * GATHER_WAVES));
-    const dim3 g(g_gather + FINISH_EXC_BLOCKS + g_doc), b(64 * GATHER_WAVES);
-    if (t.sym16) hipLaunchKernelGGL(k_finish<uint16_t>, g, b, 0, s, t, a, w, g_gather);
-    else hipLaunchKernelGGL(k_finish<uint32_t>, g, b, 0, s, t, a, w, g_gather);
+    const unsigned g_learn = t.wc_on && w.wc_list_cap ? LEARN_BLOCKS : 0;  // (the same launch: a launch of its own is ~8 us)
+    const dim3 g(g_gather + FINISH_EXC_BLOCKS + g_doc + g_learn), b(64 * GATHER_WAVES);
+    if (t.sym16) hipLaunchKernelGGL(k_finish<uint16_t>, g, b, 0, s, t, a, w, g_gather, g_doc);
+    else hipLaunchKernelGGL(k_finish<uint32_t>, g, b, 0, s, t, a, w, g_gather, g_doc);
 }
 // chunked host path (hutk_api.cpp): document offsets of a chunk made relative to its first byte, and the
 // chunk's out_offsets made absolute by the ids of the chunks before it (a device scalar)

@@ -212,6 +212,20 @@ int hutk_device_ordinal(const hutk_ctx* ctx);
  * encode calls on it fail with HUTK_E_DEVICE. */
 int hutk_table_stats(const hutk_ctx* ctx, int64_t* out8);
 
+/* The learned table of multi-token words.  A byte-encoder context whose symbols fit 16 bits and whose ids rise with
+ * the merge order keeps, on its device, the ids of the words its merge loop has encoded (2 .. 30 bytes, up to 16 ids);
+ * a later occurrence of the same bytes, in this call or any later one, takes them from the table.  Batches of more
+ * than 32 tiles fill it; every batch reads it.  Results are the same with and without it.  It never evicts: once three
+ * quarters of its slots are in use, or a batch's words mostly find their buckets full, it stops learning until it is
+ * cleared.
+ * Environment, read when the context is created: HUTK_WORD_CACHE=0 no table; HUTK_WORD_CACHE_LOG2=k 2^k buckets of two
+ * slots (default 19: 64 MiB).
+ * out4: entries, capacity in slots (0: this context has no table), candidates the last learning batch handed to the
+ * table, 1 while it learns.  Both calls wait for the context's last asynchronous call; clear empties the table and
+ * lets it learn again. */
+int hutk_ctx_word_cache_stats(hutk_ctx* ctx, int64_t* out4);
+int hutk_ctx_word_cache_clear(hutk_ctx* ctx);
+
 /* Device time of the most recent hutk_encode_batch_device/hutk_encode_batch call,
  * from HIP events recorded on the launch stream: the dominant kernel
  * ("encode tiles") and the whole enqueue.  Synchronises on those events. */

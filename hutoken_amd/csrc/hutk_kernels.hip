@@ -51,6 +51,15 @@
 
 #include "hutk_kdev.h"
 #include "hutk_lab.h"
+#include "hutk_wordbits.h"
+// MEASUREMENT ONLY (the per-step builds of profiles/word_rounds_steps.txt): 0 = without the in-place one-byte words /
+// without the short rounds in the default kernel.  Either step alone is slower than neither; see DESIGN.md section 5.6.
+#ifndef HUTK_WR_ONES
+#define HUTK_WR_ONES 1
+#endif
+#ifndef HUTK_WR_SHORT
+#define HUTK_WR_SHORT 1
+#endif
 
 namespace hutk {
 
@@ -565,23 +574,33 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
         reinterpret_cast<uint16_t*>(livem)[lane] = (uint16_t)own;
         uint32_t rest = own;  // my word starts that the general rounds below take
         if constexpr (BYTE_MODE && !MULTI) {
-            if (!A.word_bits && ONE) {  // (uniform; in the one-launch kernel, where a round's length IS the call's latency: 1.5 k cycles a round less)
-                // SHORT words first, in rounds that do nothing else.  The starts of my 16 positions by the length of their word,
-                // all sixteen at once: f32 = my starts and the next lane's; x: bit j = a start among positions j + 1 .. j +
-                // WORD_KEY, i.e. the word at j is at most WORD_KEY bytes (the key of the whole-word table) and ends inside the
-                // classified positions.  With a prefix the first word of a document is an exception word whatever its length
-                // (core.c:364-366, 421-451): left, like the long words, to the general rounds.
+            if (!A.word_bits) {  // (uniform: the automaton's starts; the regex and split-preset paths keep the general rounds)
+                // The starts of my 16 positions by the length of their word, all sixteen at once (hutk_wordbits.h): f32 = my
+                // starts and the next lane's.  With a prefix the first word of a document is an exception word whatever its
+                // length (core.c:364-366, 421-451): left, like the long words, to the general rounds.
                 constexpr int WORD_KEY = sizeof(SymT) == 2 ? WORD_KEY_BYTES_16 : WORD_KEY_BYTES_32;
                 constexpr int KSH = sizeof(SymT) == 2 ? 16 : 32;  // bits of k[3] that are symbol, not key
                 const uint32_t f32 = flags | ((uint32_t)wmask16[lane + 1] << 16);
-                uint32_t x = f32 >> 1;
-                x |= x >> 1;
-                x |= x >> 2;
-                x |= x >> 4;
-                x |= x >> (WORD_KEY - 8);  // 1 .. 8 and WORD_KEY - 7 .. WORD_KEY
-                uint32_t shorts = own & x;
-                if (T.has_prefix) shorts &= ~(uint32_t)bits64(docm, 16 * lane + LOOKBACK);
-                rest = own & ~shorts;
+                uint32_t mine = own;
+                if (T.has_prefix) mine &= ~(uint32_t)bits64(docm, 16 * lane + LOOKBACK);
+                // ONE-BYTE words in place: the lane that owns the byte writes its symbol; they are never staged.  Two
+                // loads in flight per trip (a lane seldom has more than two such words).
+                const uint32_t ones = HUTK_WR_ONES ? mine & wb::one_byte(f32) : 0u;
+                for (uint32_t m = ones; m;) {
+                    const int j0 = __builtin_ctz(m);
+                    m &= m - 1;
+                    const int j1 = m ? __builtin_ctz(m) : j0;
+                    m &= m - 1;
+                    const uint32_t y0 = T.item_sym[sb[LOOKBACK + 16 * lane + j0]], y1 = T.item_sym[sb[LOOKBACK + 16 * lane + j1]];
+                    S[16 * lane + j0] = Sym<SymT>::narrow(y0);
+                    S[16 * lane + j1] = Sym<SymT>::narrow(y1);
+                }
+                rest = own & ~ones;
+                if (HUTK_WR_SHORT || ONE) {
+                // SHORT words (2 .. WORD_KEY bytes, the key of the whole-word table; they end inside the classified positions)
+                // next, in rounds that do nothing else: no prefix, regex or companion-table logic, no symbol gather.
+                uint32_t shorts = mine & wb::within<WORD_KEY>(f32) & ~ones;
+                rest &= ~shorts;
                 uint32_t nS;
                 uint32_t sidx = wave_excl_scan(__popc(shorts), lane, &nS);
                 for (uint32_t r0 = 0; r0 < nS; r0 += 64) {
@@ -593,20 +612,21 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
                     wave_sync();
                     if (r0 + lane < nS) {
                         // One unaligned LDS read each for the start bits behind the word (at least 24 of them: the next start
-                        // is within WORD_KEY) and for its bytes; both table slots and the first byte's symbol loaded together.
+                        // is within WORD_KEY) and for its bytes; both table slots loaded together.
                         const uint32_t ws = stage[lane];
-                        uint32_t wb;
-                        __builtin_memcpy(&wb, reinterpret_cast<const uint8_t*>(wmask16) + ((ws + 1u) >> 3), 4);
-                        const uint32_t nb = 1u + (uint32_t)__builtin_ctz(wb >> ((ws + 1u) & 7u));
+                        uint32_t wb_;
+                        __builtin_memcpy(&wb_, reinterpret_cast<const uint8_t*>(wmask16) + ((ws + 1u) >> 3), 4);
+                        const uint32_t nb = 1u + (uint32_t)__builtin_ctz(wb_ >> ((ws + 1u) & 7u));  // 2 .. WORD_KEY
                         uint4 key;
                         __builtin_memcpy(&key, sb + LOOKBACK + ws, 16);
-                        const uint32_t isym = T.item_sym[key.x & 0xFFu];
                         const uint64_t mlo = nb >= 8 ? ~0ull : ((1ull << (8 * nb)) - 1ull);
                         const uint64_t mhi = nb <= 8 ? 0ull : ((1ull << (8 * (nb - 8))) - 1ull);  // (nb <= 14)
                         const uint32_t k0 = key.x & (uint32_t)mlo, k1 = key.y & (uint32_t)(mlo >> 32);
                         const uint32_t k2 = key.z & (uint32_t)mhi, k3 = key.w & (uint32_t)(mhi >> 32);
-                        bool done = nb == 1;
-                        uint32_t sym = isym;
+                        bool done = false;
+#if !HUTK_WR_ONES
+                        const uint32_t isym = T.item_sym[key.x & 0xFFu];
+#endif
                         if (T.word_mask) {  // (uniform)
                             const uint32_t wh = word_hash(k0, k1, k2, k3);
                             uint4 s1 = reinterpret_cast<const uint4*>(T.word_tab)[wh & T.word_mask];
@@ -615,24 +635,23 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
                             // before it asks for the second -- two memory round trips per round, seen in the ISA)
                             asm volatile("" : "+v"(s1.x), "+v"(s2.x));
                             // bitwise on purpose: with && the compiler fetches one word first and the rest only on a match
-                            // (a one-byte word matches no slot: keys have at least two bytes, an empty slot is all zero)
                             const uint32_t d1 = KSH == 32 ? 0u : (s1.w ^ k3) << (KSH & 31);
                             const uint32_t d2 = KSH == 32 ? 0u : (s2.w ^ k3) << (KSH & 31);
                             const bool hit1 = ((s1.x ^ k0) | (s1.y ^ k1) | (s1.z ^ k2) | d1) == 0;
                             const bool hit2 = ((s2.x ^ k0) | (s2.y ^ k1) | (s2.z ^ k2) | d2) == 0;
-                            if (nb != 1 && (hit1 || hit2)) {
+                            if (hit1 || hit2) {
                                 const uint32_t swd = hit1 ? s1.w : s2.w;
-                                sym = KSH == 32 ? swd : swd >> (KSH & 31);
+                                S[ws] = Sym<SymT>::narrow(KSH == 32 ? swd : swd >> (KSH & 31));
                                 done = true;
                             }
                         }
-                        if (done) {
-                            S[ws] = Sym<SymT>::narrow(sym);
-                        } else {
-                            atomicOr(&mergem[ws >> 5], 1u << (ws & 31));  // needs the merge loop
-                        }
+#if !HUTK_WR_ONES
+                        if (nb == 1) { S[ws] = Sym<SymT>::narrow(isym); done = true; }
+#endif
+                        if (!done) atomicOr(&mergem[ws >> 5], 1u << (ws & 31));  // needs the merge loop
                     }
                     wave_sync();
+                }
                 }
             }
         }

@@ -79,7 +79,8 @@ and an unk id, as T5, mT5, ALBERT, XLNet, XLM-R, mBART and Pegasus use -- and en
 models.Unigram behind a Metaspace pre-tokenizer: the Metaspace word split (or T5's whitespace split in front of it), then
 the best path over every word's piece lattice in f64.  The methods and constructors are WordPiece's
 (`encode_packed_device` with word ids on request, `batch_encode`, `encode`, `from_file` for a tokenizer.json,
-`from_tokenizer`); csrc/hutk_unigram.hip, DESIGN.md section 8n.  It needs no initialised context.
+`from_tokenizer`); csrc/hutk_unigram.hip, DESIGN.md section 8n.  It needs no initialised context.  With `alpha=` and
+`seed=` the three encode methods draw a segmentation of every word instead (subword regularisation, section 8n.1).
 
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
@@ -1948,7 +1949,10 @@ class Unigram:
     normaliser step Replace(" {2,}", " ") of XLM-R and ALBERT.  device: a torch device, an index, or None for the
     current one; the table is uploaded at the first call that needs the GPU, once.  Needs no initialised context.
 
-    Left out: SentencePiece's precompiled normaliser (nmt_nfkc and its kin), byte_fallback, sampling and n-best, decoding,
+    encode_packed_device, batch_encode and encode take alpha=, seed=, first_doc= for subword regularisation: a sampled
+    segmentation in place of the best one.
+
+    Left out: SentencePiece's precompiled normaliser (nmt_nfkc and its kin), byte_fallback, n-best, decoding,
     token spans over the source text, special strings inside text, and binary .model files."""
 
     def __init__(self, vocab, unk_id, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False, device=None):
@@ -2045,14 +2049,40 @@ class Unigram:
                                                          self.unk_id, self._flags, dev.index)
         return h
 
-    def encode_packed_device(self, d_bytes, d_offsets, check=True, return_word_ids=False):
+    @staticmethod
+    def _sample_args(alpha, seed, first_doc):
+        """-> None (the best path, which reads neither seed nor first_doc), or (alpha, seed, first_doc) checked"""
+        import math
+        if alpha is None:
+            return None
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)):
+            raise TypeError("alpha must be a float or None, not %s" % type(alpha).__name__)
+        if not math.isfinite(alpha):
+            raise ValueError("alpha must be finite, not %r" % (alpha,))
+        if seed is None:
+            raise TypeError("alpha needs a seed: the sampled segmentation is a function of (seed, document, position), and seed has no default")
+        if isinstance(first_doc, bool) or not isinstance(first_doc, int):
+            raise TypeError("first_doc must be an int, not %s" % type(first_doc).__name__)
+        if not 0 <= first_doc < 2**62:
+            raise ValueError("first_doc must be in 0 .. 2**62 - 1, not %d" % first_doc)
+        return float(alpha), _seed_arg(seed), first_doc
+
+    def encode_packed_device(self, d_bytes, d_offsets, check=True, return_word_ids=False, alpha=None, seed=None, first_doc=0):
         """Device tensors in (uint8 bytes, int64 offsets[n + 1]), device tensors out: (ids int32, out_offsets int64[n + 1])
         -- the pair every collate_* function and SequencePacker.add take -- and with return_word_ids the index of every
         id's word in its document (int32, what `tokenizers` calls word_ids; mask_tokens(word_ids=) takes it).  Runs on
         the current torch stream.  ids is a view of a buffer of the capacity bound (n_bytes + n_docs); its length is read
         from the device, which is the call's one synchronisation.  check=True: offsets that do not describe d_bytes raise
-        ValueError."""
+        ValueError.
+
+        alpha=None is the best path.  With alpha (a finite float; 0 and negative values are legal) every word gets one
+        segmentation SAMPLED on the GPU with probability proportional to exp(alpha * the sum of its pieces' scores) --
+        subword regularisation, SentencePiece's enable_sampling=True, nbest_size=-1, alpha=alpha -- from Philox draws
+        that depend on (seed, first_doc + the document's index, the position in the document) alone: seed (an int in
+        0 .. 2**64 - 1) is then required and has no default, pass another one every epoch; first_doc is the number of the
+        batch's first document in the data set, so a document's outcome does not depend on its batch."""
         _packed_text_args(d_bytes, d_offsets)
+        sample = self._sample_args(alpha, seed, first_doc)
         import torch
         dev = d_bytes.device
         h = self._handle(dev)
@@ -2064,8 +2094,12 @@ class Unigram:
             oo = torch.zeros(n_docs + 1, dtype=torch.int64, device=dev)
             wi = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if return_word_ids else None
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-            h.batch_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap, oo.data_ptr(),
-                           wi.data_ptr() if return_word_ids else 0, err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            ptrs = (d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, ids.data_ptr(), cap, oo.data_ptr())
+            rest = (wi.data_ptr() if return_word_ids else 0, err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            if sample is None:
+                h.batch_device(*ptrs, *rest)
+            else:
+                h.sample_device(*ptrs, *sample, *rest)
             return (ids, oo, err, wi) if return_word_ids else (ids, oo, err)
 
         res = _on_torch_stream(dev, call, used=(d_bytes, d_offsets))
@@ -2077,12 +2111,14 @@ class Unigram:
         total = int(oo[n_docs].item())
         return (ids[:total], oo, res[3][:total]) if return_word_ids else (ids[:total], oo)
 
-    def batch_encode(self, texts, normalize=None):
+    def batch_encode(self, texts, normalize=None, alpha=None, seed=None, first_doc=0):
         """A list of str -> a list of lists of ids, encoded on the GPU.  normalize="NFC" (.. "NFKD"): the packed text is
-        put into that form on the GPU first (None: the instance's default, which from_tokenizer sets)."""
+        put into that form on the GPU first (None: the instance's default, which from_tokenizer sets).  alpha, seed,
+        first_doc: a sampled segmentation, as encode_packed_device."""
         import numpy as np
         import torch
         from .normalize import form_index  # (by module name: after a reload of the package its attribute `normalize` is the function)
+        self._sample_args(alpha, seed, first_doc)
         form = self.normalize if normalize is None else normalize
         if form is not None:
             form_index(form)
@@ -2100,15 +2136,15 @@ class Unigram:
         if form is not None:
             with torch.cuda.device(dev):
                 d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, form)
-        ids, oo = self.encode_packed_device(d_bytes, d_offs)
+        ids, oo = self.encode_packed_device(d_bytes, d_offs, alpha=alpha, seed=seed, first_doc=first_doc)
         flat, bounds = ids.tolist(), oo.tolist()
         return [flat[bounds[i]:bounds[i + 1]] for i in range(len(chunks))]
 
-    def encode(self, text, normalize=None):
-        """One str -> its list of ids."""
+    def encode(self, text, normalize=None, alpha=None, seed=None, first_doc=0):
+        """One str -> its list of ids (alpha, seed, first_doc: as batch_encode; the text is document first_doc)."""
         if not isinstance(text, str):
             raise TypeError("Invalid arguments. Expected a string.")
-        return self.batch_encode([text], normalize=normalize)[0]
+        return self.batch_encode([text], normalize=normalize, alpha=alpha, seed=seed, first_doc=first_doc)[0]
 
 
 # ---- split presets (hutk_presplit.hip, DESIGN.md section 4d) ----

@@ -170,6 +170,7 @@ SIGNATURES = {
     "hutk_unigram_info": (_i32, [_vp, _vp]),
     "hutk_unigram_ids_capacity": (_i64, [_vp, _i64, _i64]),
     "hutk_unigram_encode_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_unigram_sample_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp]),
     "hutk_unigram_encode_batch": (_i32, [_vp, _vp, _vp, _i64, _pvp, _pvp, _pvp]),
     "hutk_debug_unigram_chunk_bytes": (_i32, []),
     "hutk_debug_unigram_bucket": (_i64, [_vp, _vp, _i64]),
@@ -1354,6 +1355,14 @@ class Unigram(_Owner):
         raise_for(load().hutk_unigram_encode_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
                                                           d_ids or None, ids_cap, d_out_offsets or None, d_word_ids or None,
                                                           d_err or None, stream or None))
+
+    def sample_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets, alpha, seed, first_doc, d_word_ids=0,
+                      d_err=0, stream=0):
+        """hutk_unigram_sample_batch_device on raw device pointers (ints): one sampled segmentation per word."""
+        a = C.c_double(alpha)
+        raise_for(load().hutk_unigram_sample_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                          d_ids or None, ids_cap, d_out_offsets or None, d_word_ids or None,
+                                                          C.addressof(a), seed, first_doc, d_err or None, stream or None))
 
     def batch(self, data, offsets, word_ids=False):
         """Host numpy buffers in and out (hutk_unigram_encode_batch): -> (ids int32, out_offsets int64[n + 1]) and, with

@@ -1,6 +1,6 @@
 // hutk_philox.h -- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), the
 // counter-based generator behind the masked-LM corruption, the span corruption and the fill-in-the-middle cuts of
-// hutk_collate.hip (DESIGN.md sections 8g, 8h, 8k).  Plain C++ for the
+// hutk_collate.hip (DESIGN.md sections 8g, 8h, 8k) and the sampled segmentations of hutk_unigram.hip (section 8n.1).  Plain C++ for the
 // host and the device alike: four 32-bit words out of a 128-bit counter and a 64-bit key, ten rounds of two
 // 32 x 32 -> 64 bit multiplies each, no state.  The known-answer vectors of the Random123 distribution are in
 // tests/test_targets_cpu.py.
@@ -44,8 +44,11 @@ HUTK_PHILOX_HD inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
 // purpose 1 / 2: the draw of word `unit` of side A / B (x: selection in whole-word mode);
 // purpose 3: the span draw of column `unit` (x: whether a noise span starts there, y: its length);
 // purpose 4: the fill-in-the-middle draw of DOCUMENT `row`, unit 0 (x: whether it is transformed, y: PSM or SPM, z and w:
-//            the two cuts; hutk_fim.h).
-constexpr uint32_t DRAW_COLUMN = 0, DRAW_WORD_A = 1, DRAW_WORD_B = 2, DRAW_SPAN = 3, DRAW_FIM = 4;
+//            the two cuts; hutk_fim.h);
+// purpose 5: the Unigram sampling draw of DOCUMENT `row`, unit = low32 of the folded offset, inside the document, of the
+//            character start the sampled path stands at (x and y: the 53 bits of u = ((x << 21) | (y >> 11)) * 2^-53, which
+//            picks the piece that starts there; hutk_unigram.hip).
+constexpr uint32_t DRAW_COLUMN = 0, DRAW_WORD_A = 1, DRAW_WORD_B = 2, DRAW_SPAN = 3, DRAW_FIM = 4, DRAW_UNIGRAM = 5;
 
 HUTK_PHILOX_HD inline Philox4 draw(uint64_t seed, int64_t row, uint32_t unit, uint32_t purpose) {
     return philox4x32_10((uint32_t)(uint64_t)row, (uint32_t)((uint64_t)row >> 32), unit, purpose, (uint32_t)seed,

@@ -18,6 +18,10 @@
 //   k_ug_lattice     word starts of a chunk; a group of 8 lanes takes the next word of the chunk's queue and walks its
 //                    starts: the lanes probe 8 lengths of a start a trip, the best scores of the last max_len + 1
 //                    positions live in a ring in LDS, the backpointers go to a per-byte workspace; lane 0 walks back
+//   k_ug_sample      in k_ug_lattice's place when a segmentation is sampled (hutk_unigram_sample_batch_device): the same
+//                    chunks, queue and groups; a group first sums the word's lattice from its end to its start (beta, a
+//                    log-sum-exp per character start, in the ring and for a word longer than the ring in a per-byte
+//                    workspace as well), then draws the path from the start, one Philox draw a piece
 //   k_ug_count       ids and words per slice and chunk;  k_ug_scan over both
 //   k_ug_docs        out_offsets, and the word count in front of every document
 //   k_ug_write       the ids, compact, and the word ids
@@ -31,6 +35,7 @@
 #include <vector>
 
 #include "hutk_host.h"
+#include "hutk_philox.h"
 #include "hutk_unigram.h"
 #include "hutk_wave.h"
 
@@ -254,6 +259,19 @@ __device__ __forceinline__ void lattice_word(const MatchArgs& a, const U::Text& 
     if (gl == 0) U::backtrack(a.bp, a.V.unk, ws, s, a.tmp);
 }
 
+// The word starts of the chunk at c0, in rising order, into s_ws (as offsets from c0) by the whole workgroup -> their count.
+__device__ __forceinline__ int list_words(const U::Text& f, int64_t c0, int* s_part, uint16_t* s_ws) {
+    const int tid = threadIdx.x;
+    const int64_t at = c0 + (int64_t)tid * U::SLICE_BYTES;
+    uint32_t starts = 0;  // bit i: a word starts at at + i
+    for (int i = 0; i < U::SLICE_BYTES; i++)
+        if (U::word_starts(f, at + i)) starts |= 1u << i;
+    int n_words;
+    int before = hutk::block_excl((int)__popc(starts), s_part, n_words);
+    for (uint32_t m = starts; m; m &= m - 1) s_ws[before++] = (uint16_t)(tid * U::SLICE_BYTES + __ffs(m) - 1);
+    return n_words;
+}
+
 __global__ __launch_bounds__(TB) void k_ug_lattice(const MatchArgs a) {
     extern __shared__ double s_ring[];  // [n_groups][ring]
     __shared__ int s_part[TB / 64];
@@ -265,13 +283,7 @@ __global__ __launch_bounds__(TB) void k_ug_lattice(const MatchArgs a) {
     const int64_t c0 = (int64_t)blockIdx.x * U::CHUNK_BYTES;
     if (c0 >= f.n) return;
     const int tid = threadIdx.x;
-    const int64_t at = c0 + (int64_t)tid * U::SLICE_BYTES;
-    uint32_t starts = 0;  // bit i: a word starts at at + i
-    for (int i = 0; i < U::SLICE_BYTES; i++)
-        if (U::word_starts(f, at + i)) starts |= 1u << i;
-    int n_words;
-    int before = hutk::block_excl((int)__popc(starts), s_part, n_words);
-    for (uint32_t m = starts; m; m &= m - 1) s_ws[before++] = (uint16_t)(tid * U::SLICE_BYTES + __ffs(m) - 1);
+    const int n_words = list_words(f, c0, s_part, s_ws);
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
     for (int i = tid; i < a.n_groups * a.ring; i += TB) s_ring[i] = nan;
     if (tid == 0) s_next = 0;
@@ -285,6 +297,180 @@ __global__ __launch_bounds__(TB) void k_ug_lattice(const MatchArgs a) {
         i = __shfl(i, g0);
         if (i >= n_words) break;
         lattice_word(a, f, c0 + s_ws[i], s_ring + g * a.ring, gl, g0);
+    }
+}
+
+// ---- a sampled segmentation (include/hutoken_amd.h: hutk_unigram_sample_batch_device) ----
+struct SampleArgs {
+    double alpha;
+    uint64_t seed;
+    int64_t first_doc;
+    double* beta;  // [cap + 1]: beta of the character starts of the words that do not fit their group's ring
+};
+
+// bit j: the group's lane j says v
+__device__ __forceinline__ uint32_t group_ballot(bool v, int g0) { return (uint32_t)(__ballot(v) >> g0) & ((1u << GROUP) - 1u); }
+
+// Does a character of the word w[0 .. n) start at p?  A byte that is no continuation byte always does.  A continuation
+// byte lies inside a character iff the nearest byte in front of it that is none -- at most three back, inside the word --
+// starts a well-formed character that reaches past p; every other continuation byte is an ill-formed character of its own.
+__device__ __forceinline__ bool char_starts(const uint8_t* w, int64_t p, int64_t n) {
+    if ((w[p] & 0xC0u) != 0x80u) return true;
+    for (int j = 1; j <= 3 && p - j >= 0; j++)
+        if ((w[p - j] & 0xC0u) != 0x80u) return U::char_len(w, p - j, n) <= j;
+    return true;
+}
+
+// One trip of the probes of the start s of the word w[0 .. n), for the filter and the sampler alike: lane gl takes the
+// length base + gl + 1 over the hash the group walks together, exactly as lattice_word does.  -> the id of the lane's
+// candidate or -1, and alpha * its score in *x.  The unknown edge stands in the first trip: its length m is at most 4, so
+// it is lane m - 1's, which has no candidate of its own when no key is the single character.  state: the hash of the bytes
+// before the trip's.
+__device__ __forceinline__ int32_t sample_trip(const U::Vocab& V, double alpha, const uint8_t* w, int64_t s, int64_t n, int base,
+                                               uint64_t lens, int top, int m, uint32_t& state, int gl, int g0, double* x) {
+    const int idx = base + gl, len = idx + 1;
+    const uint32_t mine = s + idx < n ? w[s + idx] : 0u;
+    uint32_t h = state;
+#pragma unroll
+    for (int j = 0; j < GROUP; j++) {
+        const uint32_t bj = __shfl(mine, g0 + j);
+        if (j <= gl) h = U::hash_step(h, bj);
+    }
+    state = __shfl(h, g0 + GROUP - 1);
+    int32_t id = -1;
+    if (s + len <= n && len <= top && U::has_len(lens, len)) id = U::find(V, U::hash_end(h), w + s, len);
+    double score = id >= 0 ? V.scores[id] : 0.0;
+    if (base == 0) {
+        const bool single = group_ballot(id >= 0 && len == m, g0) != 0;
+        if (!single && len == m) id = V.unk, score = V.unk_score;
+    }
+    *x = alpha * score;
+    return id;
+}
+
+// The word that starts at ws, by the GROUP lanes of one group (as lattice_word: all of them run this with the same
+// arguments).  ring: the group's R values of beta; what another word left there is never read, because a candidate ends
+// at a character start of this word, and those are written before they are read.
+__device__ __forceinline__ void sample_word(const MatchArgs& a, const SampleArgs& sa, const U::Text& f, int64_t ws, double* ring, int gl,
+                                            int g0) {
+    const int R1 = a.ring - 1;
+    const uint8_t* w = f.bytes + ws;
+    int64_t n = 0;  // the word's bytes
+    for (int64_t base = 1; n == 0; base += GROUP) {
+        const uint32_t em = group_ballot(U::word_ends(f, ws + base + gl), g0);
+        if (em) n = base + __ffs(em) - 1;
+    }
+    const bool in_lds = n < a.ring;  // every position of the word has a slot of its own: the sampler needs no global copy
+    group_sync();                    // (the sampler of the group's last word has read the ring)
+    if (gl == 0) ring[(int)(n & R1)] = 0.0;
+
+    // the filter: beta[s] = log sum exp(alpha * score + beta[s + len]), the starts in falling order, eight positions a look
+    for (int64_t hi = n - 1; hi >= 0; hi -= GROUP) {
+        const int64_t p = hi - gl;
+        for (uint32_t sm = group_ballot(p >= 0 && char_starts(w, p, n), g0); sm; sm &= sm - 1) {
+            const int64_t s = hi - (__ffs(sm) - 1);
+            group_sync();  // beta of the starts behind s
+            const uint64_t lens = a.V.lens[w[s]];
+            const int top = U::top_len(lens, a.V.max_len);
+            const int m = U::char_len(w, s, n);
+            double mx = -INFINITY, sum = 0.0;  // the lane's own candidates: their maximum, and the sum of exp(x - mx)
+            uint32_t state = U::HASH_INIT;
+            for (int base = 0; base == 0 || (base < top && s + base < n); base += GROUP) {
+                double x;
+                if (sample_trip(a.V, sa.alpha, w, s, n, base, lens, top, m, state, gl, g0, &x) < 0) continue;
+                x += ring[(int)((s + base + gl + 1) & R1)];
+                if (x > mx) {
+                    sum = sum * exp(mx - x) + 1.0;
+                    mx = x;
+                } else {
+                    sum += exp(x - mx);
+                }
+            }
+            double top_x = mx;
+#pragma unroll
+            for (int d = 1; d < GROUP; d <<= 1) top_x = fmax(top_x, __shfl_xor(top_x, d));
+            double total = sum * exp(mx - top_x);  // (a lane without a candidate: 0 * exp(-inf) = 0)
+#pragma unroll
+            for (int d = 1; d < GROUP; d <<= 1) total += __shfl_xor(total, d);
+            if (gl == 0) {
+                const double b = top_x + log(total);
+                ring[(int)(s & R1)] = b;
+                if (!in_lds) sa.beta[ws + s] = b;
+            }
+        }
+    }
+    if (!in_lds) __threadfence_block();  // lane 0's stores, for the group's other lanes
+    group_sync();
+
+    // the sampler: from the start, a draw a piece
+    int64_t d = 0;
+    for (int64_t hi = a.n_docs; hi - d > 1;) {  // the last document that starts at or before ws
+        const int64_t mid = d + (hi - d) / 2;
+        if (a.offs[mid] <= ws) d = mid;
+        else hi = mid;
+    }
+    const int64_t row = sa.first_doc + d, in_doc = ws - a.offs[d];
+    bool after_unk = false;
+    for (int64_t s = 0; s < n;) {
+        const hutk::Philox4 r = hutk::draw(sa.seed, row, (uint32_t)(uint64_t)(in_doc + s), hutk::DRAW_UNIGRAM);
+        const double u = (double)(((uint64_t)r.x << 21) | (uint64_t)(r.y >> 11)) * 0x1p-53;
+        const double here = in_lds ? ring[(int)(s & R1)] : sa.beta[ws + s];
+        const uint64_t lens = a.V.lens[w[s]];
+        const int top = U::top_len(lens, a.V.max_len);
+        const int m = U::char_len(w, s, n);
+        double carry = 0.0;  // p of the candidates of the trips before
+        int32_t id = -1;     // the piece taken, or the last candidate so far
+        int len = 0;
+        uint32_t state = U::HASH_INIT;
+        for (int base = 0; base == 0 || (base < top && s + base < n); base += GROUP) {
+            double x;
+            const int32_t mine = sample_trip(a.V, sa.alpha, w, s, n, base, lens, top, m, state, gl, g0, &x);
+            double c = 0.0;
+            if (mine >= 0) {
+                const int64_t e = s + base + gl + 1;  // (byte ws + n of the workspace is the next word's first)
+                c = exp(x + (in_lds ? ring[(int)(e & R1)] : e < n ? sa.beta[ws + e] : 0.0) - here);
+            }
+#pragma unroll
+            for (int k = 1; k < GROUP; k <<= 1) {
+                const double before = __shfl_up(c, k);
+                if (gl >= k) c += before;
+            }
+            c += carry;
+            const uint32_t cands = group_ballot(mine >= 0, g0), take = group_ballot(mine >= 0 && u < c, g0);
+            const int from = take ? __ffs(take) - 1 : cands ? 31 - __clz(cands) : -1;
+            if (from >= 0) id = __shfl(mine, g0 + from), len = base + from + 1;
+            if (take) break;
+            carry = __shfl(c, g0 + GROUP - 1);
+        }
+        const bool is_unk = id == a.V.unk;
+        if (gl == 0 && !(is_unk && after_unk)) a.tmp[ws + s] = id | (s == 0 ? U::ID_START : 0);
+        after_unk = is_unk;
+        s += len;
+    }
+}
+
+__global__ __launch_bounds__(TB) void k_ug_sample(const MatchArgs a, const SampleArgs sa) {
+    extern __shared__ double s_ring[];  // [n_groups][ring]
+    __shared__ int s_part[TB / 64];
+    __shared__ int s_next;
+    __shared__ uint16_t s_ws[U::CHUNK_BYTES];
+    if (!*a.ok) return;
+    U::Text f = a.f;
+    f.n = *a.n_dev;
+    const int64_t c0 = (int64_t)blockIdx.x * U::CHUNK_BYTES;
+    if (c0 >= f.n) return;
+    const int tid = threadIdx.x;
+    const int n_words = list_words(f, c0, s_part, s_ws);
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const int gl = tid & (GROUP - 1), g0 = (tid & 63) & ~(GROUP - 1), g = tid / GROUP;
+    if (g >= a.n_groups) return;
+    for (;;) {
+        int i = 0;
+        if (gl == 0) i = atomicAdd(&s_next, 1);
+        i = __shfl(i, g0);
+        if (i >= n_words) break;
+        sample_word(a, sa, f, c0 + s_ws[i], s_ring + g * a.ring, gl, g0);
     }
 }
 
@@ -479,16 +665,17 @@ int64_t hutk_unigram_ids_capacity(const hutk_unigram* h, int64_t n_bytes, int64_
     return n_bytes + n_docs;
 }
 
-int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
-                                     int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err,
-                                     void* hip_stream) {
-    if (!h) return hutk::api_set_error(HUTK_E_ARG, "hutk_unigram_encode_batch_device: the handle is NULL");
+// Both device entries: the best path (sample NULL), or a sampled segmentation with sample's alpha, seed and first_doc.
+static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                            int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err, void* hip_stream,
+                            const SampleArgs* sample, const std::string& who) {
+    if (!h) return hutk::api_set_error(HUTK_E_ARG, who + ": the handle is NULL");
     if (n_docs < 0 || n_bytes < 0 || ids_cap < 0 || !d_offsets || !d_out_offsets || (n_bytes > 0 && !d_bytes) || (ids_cap > 0 && !d_ids))
-        return hutk::api_set_error(HUTK_E_ARG, "hutk_unigram_encode_batch_device: bad arguments");
+        return hutk::api_set_error(HUTK_E_ARG, who + ": bad arguments");
     const int64_t cap_f = n_bytes + n_docs;  // the folded text's bound
     const int64_t src_chunks = (n_bytes + U::CHUNK_BYTES - 1) / U::CHUNK_BYTES, chunks = (cap_f + U::CHUNK_BYTES - 1) / U::CHUNK_BYTES;
     if (chunks > INT32_MAX / 2 || (n_docs + TB) / TB > INT32_MAX)
-        return hutk::api_set_error(HUTK_E_UNSUPPORTED, "hutk_unigram_encode_batch_device: the batch is too large for one launch");
+        return hutk::api_set_error(HUTK_E_UNSUPPORTED, who + ": the batch is too large for one launch");
     std::lock_guard<std::mutex> lock(h->mu);
     HUTK_HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -534,7 +721,14 @@ int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, co
     if (chunks) {
         const unsigned fill = (unsigned)std::min<int64_t>((cap_f + TB - 1) / TB, 1 << 16);
         hipLaunchKernelGGL(k_ug_fill, dim3(fill), dim3(TB), 0, st, m.tmp, n_fold, ok);
-        hipLaunchKernelGGL(k_ug_lattice, dim3((unsigned)chunks), dim3(TB), (size_t)h->n_groups * h->ring * sizeof(double), st, m);
+        const size_t rings = (size_t)h->n_groups * h->ring * sizeof(double);
+        if (sample) {
+            SampleArgs sa = *sample;
+            sa.beta = reinterpret_cast<double*>(h->w_bp.p);  // (this path has no backpointers: their workspace, 8 bytes a byte as well)
+            hipLaunchKernelGGL(k_ug_sample, dim3((unsigned)chunks), dim3(TB), rings, st, m, sa);
+        } else {
+            hipLaunchKernelGGL(k_ug_lattice, dim3((unsigned)chunks), dim3(TB), rings, st, m);
+        }
         hipLaunchKernelGGL(k_ug_count, dim3((unsigned)chunks), dim3(TB), 0, st, m);
     }
     hipLaunchKernelGGL(k_ug_scan, dim3(2), dim3(SCAN_TB), 0, st, m.chunk, chunks + 1, chunks, ok);
@@ -544,6 +738,24 @@ int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, co
     HUTK_HIP_TRY(hipEventRecord(h->ev, st));
     h->ev_recorded = true;
     return HUTK_OK;
+}
+
+int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                     int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err,
+                                     void* hip_stream) {
+    return ug_encode_device(h, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets, d_word_ids, d_err, hip_stream, nullptr,
+                            "hutk_unigram_encode_batch_device");
+}
+
+int hutk_unigram_sample_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                     int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, const double* alpha,
+                                     uint64_t seed, int64_t first_doc, int32_t* d_err, void* hip_stream) {
+    if (!alpha || first_doc < 0 || (n_docs > 0 && first_doc > INT64_MAX - n_docs))  // (first_doc + d stays an int64)
+        return hutk::api_set_error(HUTK_E_ARG, "hutk_unigram_sample_batch_device: bad arguments");
+    if (!std::isfinite(*alpha)) return hutk::api_set_error(HUTK_E_VALUE, "hutk_unigram_sample_batch_device: alpha is not finite");
+    const SampleArgs sa{*alpha, seed, first_doc, nullptr};
+    return ug_encode_device(h, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap, d_out_offsets, d_word_ids, d_err, hip_stream, &sa,
+                            "hutk_unigram_sample_batch_device");
 }
 
 int hutk_unigram_encode_batch(hutk_unigram* h, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int32_t** out_ids,

@@ -1408,7 +1408,31 @@ int64_t hutk_debug_wordpiece_bucket(const hutk_wordpiece* h, const uint8_t* byte
  *   *out_offsets (n_docs + 1 entries) and, when out_word_ids is not NULL, *out_word_ids are allocated here and given
  *   back with hutk_host_free.
  * hutk_debug_unigram_bucket: the slot the probe of the piece (its folded bytes) starts at (tests build pieces that share
- *   one); -1 on bad arguments. */
+ *   one); -1 on bad arguments.
+ *
+ * hutk_unigram_sample_batch_device: subword regularisation (Kudo 2018; SentencePiece's enable_sampling=True,
+ *   nbest_size=-1, alpha): in place of the best path, every word gets ONE segmentation drawn with probability
+ *   proportional to exp(alpha * the sum of its pieces' scores), which is SentencePiece's Lattice::Sample.  Everything
+ *   else -- arguments, capacity bound, error codes, stream and event behaviour, word ids -- is
+ *   hutk_unigram_encode_batch_device's.  THE RULE.  Fold, words, table, candidate pieces and the unknown edge are those
+ *   of the best path.  At a character start s of a word of n folded bytes w[0 .. n) the CANDIDATES are the keys equal to
+ *   w[s .. s + len) and, if none of them is the single character at s (m bytes), the unknown edge (len = m, id = unk_id,
+ *   score = unk_score); their lengths are distinct, and they are taken in the order of rising length.
+ *     FILTER, from the word's end to its start: beta[n] = 0 and, for every character start s in falling order,
+ *       beta[s] = log sum_k exp(alpha * score_k + beta[s + len_k]), in f64 with the maximum taken out of the sum.
+ *       (Keys are well-formed and start at a character start, so only character starts are reached.)
+ *     SAMPLE, from the start to the end: s = 0; until s = n: (x, y, ., .) = draw(seed, first_doc + d, low32(the folded
+ *       offset of s inside its document d), purpose 5) -- Philox4x32-10 with the key and counter layout of
+ *       hutk_rows_mlm_device --, u = ((x << 21) | (y >> 11)) * 2^-53, p_k = exp(alpha * score_k + beta[s + len_k] - beta[s]);
+ *       the piece taken is the first k with u < p_1 + .. + p_k, or the last candidate if there is none; s += len_k.
+ *     OUTPUT as the best path's: the word's first id is marked as such, and an unknown id directly behind an unknown id of
+ *       the same word is dropped (the fusing).
+ *   The order of the f64 additions inside a sum is not part of the rule (the kernel sums across lanes): a result is
+ *   defined up to the rounding of beta and of the cumulated p, that is wherever u is not within about 1e-12 of a boundary.
+ *   A document's outcome depends on (seed, first_doc + its index, its bytes) alone, not on its batch.  alpha points to ONE
+ *   f64 ON THE HOST, read before the call returns (every scalar of this interface is an integer or a float, and alpha
+ *   needs all 64 bits); it must be finite (else HUTK_E_VALUE), zero -- every segmentation equally likely -- and negative
+ *   values are legal.  A NULL alpha, a negative first_doc or one that first_doc + n_docs takes out of an int64: HUTK_E_ARG. */
 #define HUTK_UG_PREPEND 1u
 #define HUTK_UG_WHITESPACE_SPLIT 2u
 #define HUTK_UG_COLLAPSE_SPACES 4u
@@ -1421,6 +1445,9 @@ int64_t hutk_unigram_ids_capacity(const hutk_unigram* h, int64_t n_bytes, int64_
 int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
                                      int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err,
                                      void* hip_stream);
+int hutk_unigram_sample_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                     int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, const double* alpha,
+                                     uint64_t seed, int64_t first_doc, int32_t* d_err, void* hip_stream);
 int hutk_unigram_encode_batch(hutk_unigram* h, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, int32_t** out_ids,
                               int64_t** out_offsets, int32_t** out_word_ids);
 int hutk_debug_unigram_chunk_bytes(void);

@@ -96,7 +96,7 @@ from . import pretokenize as _presplit_tables  # (the module; the package's name
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 from . import wordpiece as _wp_tables
 
-__all__ = ["Unigram", "WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["Unigram", "UnigramTrainer", "train_unigram", "WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -2111,6 +2111,19 @@ class Unigram:
         total = int(oo[n_docs].item())
         return (ids[:total], oo, res[3][:total]) if return_word_ids else (ids[:total], oo)
 
+    def expected_counts_device(self, d_bytes, d_offsets, *, out=None, stats=None, accumulator="table"):
+        """The E-step of Unigram training over one packed batch: -> (expected f64[vocab_size],
+        stats f64[2]) on the device: the posterior of every lattice edge of every word summed per piece (the unknown
+        edge's under unk_id), and (the sum of the words' log-likelihoods Z, the words).  out=, stats=: tensors of an
+        earlier call, which are ADDED to and returned, so a corpus larger than memory streams through batch by batch.
+        accumulator: "table" (a per-workgroup table in LDS in front of the global atomics) or "atomics" (those alone);
+        the results agree up to the order of the f64 additions.  Runs on the current torch stream, never synchronises."""
+        _packed_text_args(d_bytes, d_offsets)
+        if accumulator not in ("table", "atomics"):
+            raise ValueError("accumulator must be \"table\" or \"atomics\", not %r" % (accumulator,))
+        dev = d_bytes.device
+        return _ug_estep(self._handle(dev), self.vocab_size, d_bytes, d_offsets, out, stats, accumulator)
+
     def batch_encode(self, texts, normalize=None, alpha=None, seed=None, first_doc=0):
         """A list of str -> a list of lists of ids, encoded on the GPU.  normalize="NFC" (.. "NFKD"): the packed text is
         put into that form on the GPU first (None: the instance's default, which from_tokenizer sets).  alpha, seed,
@@ -2145,6 +2158,295 @@ class Unigram:
         if not isinstance(text, str):
             raise TypeError("Invalid arguments. Expected a string.")
         return self.batch_encode([text], normalize=normalize, alpha=alpha, seed=seed, first_doc=first_doc)[0]
+
+
+# ---- Unigram training (hutk_unigram_train.h) ----
+def _ug_estep(h, n_pieces, d_bytes, d_offsets, out, stats, accumulator="table"):
+    import torch
+    dev = d_bytes.device
+    for name, t, n in (("out", out, n_pieces), ("stats", stats, 2)):
+        if t is not None and not (hasattr(t, "data_ptr") and t.dtype == torch.float64 and t.device == dev and t.dim() == 1
+                                  and t.numel() == n and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 tensor of %d entries on the batch's device" % (name, n))
+
+    def call():
+        expected = torch.zeros(n_pieces, dtype=torch.float64, device=dev) if out is None else out
+        st = torch.zeros(2, dtype=torch.float64, device=dev) if stats is None else stats
+        h.estep_device(d_bytes.data_ptr(), d_offsets.data_ptr(), d_offsets.numel() - 1, d_bytes.numel(), expected.data_ptr(), st.data_ptr(),
+                       _capi.UG_ESTEP_PLAIN_ATOMICS if accumulator == "atomics" else 0, 0, torch.cuda.current_stream(dev).cuda_stream)
+        return expected, st
+
+    return _on_torch_stream(dev, call, used=(d_bytes, d_offsets) + tuple(t for t in (out, stats) if t is not None))
+
+
+class UnigramTrainer:
+    """Fits a Unigram vocabulary on the GPU: `tokenizers`' UnigramTrainer from the seed on -- EM over the piece lattice of
+    every word occurrence, pruning by the loss of the best-path histogram, finalising (include/hutoken_amd.h states the
+    rule, DESIGN.md section 8n.2 the kernels).  Making the seed is the caller's: an existing Unigram vocabulary, or
+    train(mode="chars") run to several times the target size.
+
+    seed_pieces: a list of str, or of (piece, score) pairs; without scores every piece starts at ln(1 / len(seed_pieces)).
+    seed_pieces[unk_id] is the unknown token's line; its text is never matched.  The other options are Unigram's.
+    Ids are the seed's for the whole training; a dead piece's score is NaN.  ValueError before any device call: an empty
+    seed, duplicate pieces, a piece Unigram refuses.
+
+    e_step(batches) -> (expected, stats) device tensors; m_step() -> the alive count; prune(batches, desired) -> the alive
+    count; `alive`; `scores` (numpy f64, NaN where dead); fit(batches, vocab_size) -> Unigram.  batches: one
+    (d_bytes, d_offsets) pair of device tensors or a list of them."""
+
+    def __init__(self, seed_pieces, unk_id=0, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False, device=None):
+        import math
+        import numpy as np
+        if isinstance(seed_pieces, (str, bytes, dict)) or not hasattr(seed_pieces, "__iter__"):
+            raise TypeError("seed_pieces must be a list of str or of (piece, score) pairs, not %s" % type(seed_pieces).__name__)
+        seed = list(seed_pieces)
+        if not seed:
+            raise ValueError("seed_pieces is empty")
+        if all(isinstance(p, str) for p in seed):
+            seed = [(p, math.log(1.0 / len(seed))) for p in seed]
+        self._shape = Unigram(seed, unk_id, prepend_scheme=prepend_scheme, whitespace_split=whitespace_split,
+                              collapse_spaces=collapse_spaces, device=device)  # (its checks, flags and device)
+        self._pieces, self.unk_id = self._shape._pieces, unk_id
+        if len(set(self._pieces)) != len(self._pieces):
+            seen = set()
+            dup = next(p for p in self._pieces if p in seen or seen.add(p))
+            raise ValueError("seed_pieces holds %r more than once" % (dup,))
+        self._options = dict(prepend_scheme=prepend_scheme, whitespace_split=whitespace_split, collapse_spaces=collapse_spaces)
+        self._host = np.array(self._shape._scores, dtype=np.float64)  # None while the newest scores are on the device only
+        self._host[unk_id] = np.nan
+        self._d_scores = None
+        self._single = np.array([len(p) == 1 and i != unk_id for i, p in enumerate(self._pieces)])
+        self._h = None
+        self._expected = None
+        self.passes = 0  # corpus passes so far: E-steps and histograms
+
+    def _dev(self):
+        import torch
+        d = self._shape._device
+        return torch.device("cuda", torch.cuda.current_device() if d is None else d if isinstance(d, int) else
+                            (d.index if d.index is not None else torch.cuda.current_device()))
+
+    def _handle(self):
+        if self._h is None:
+            import numpy as np
+            dev = self._dev()
+            start = np.where(np.isnan(self._scores), 0.0, self._scores)
+            self._h = _capi.Unigram([t.encode("utf-8", "surrogateescape") for t in self._pieces], start, self.unk_id, self._shape._flags, dev.index)
+            self._h.set_scores(self._scores)
+        return self._h
+
+    @staticmethod
+    def _batches(batches):
+        if isinstance(batches, tuple) and len(batches) == 2 and hasattr(batches[0], "data_ptr"):
+            batches = [batches]
+        batches = list(batches)
+        for b in batches:
+            _packed_text_args(*b)
+        return batches
+
+    @property
+    def _scores(self):
+        if self._host is None:
+            self._host = self._d_scores.cpu().numpy()
+        return self._host
+
+    @property
+    def alive(self):
+        import numpy as np
+        return int(np.count_nonzero(~np.isnan(self._scores)))
+
+    @property
+    def scores(self):
+        return self._scores.copy()
+
+    def set_scores(self, scores):
+        """Scores by seed id, NaN for a dead piece (the unknown line's is ignored)."""
+        import numpy as np
+        scores = np.array(scores, dtype=np.float64)
+        if scores.shape != self._scores.shape:
+            raise ValueError("scores must hold %d entries" % len(self._scores))
+        scores[self.unk_id] = np.nan
+        self._handle().set_scores(scores)
+        self._host = scores
+
+    def e_step(self, batches, accumulator="table"):
+        if accumulator not in ("table", "atomics"):
+            raise ValueError("accumulator must be \"table\" or \"atomics\", not %r" % (accumulator,))
+        h, expected, stats = self._handle(), None, None
+        for db, do in self._batches(batches):
+            expected, stats = _ug_estep(h, len(self._pieces), db, do, expected, stats, accumulator)
+        if expected is None:
+            raise ValueError("e_step needs at least one batch")
+        self._expected, self.passes = expected, self.passes + 1
+        return expected, stats
+
+    def m_step(self, expected=None):
+        """New scores from the expected counts of the last e_step (or those given) -> the alive count (one readback)."""
+        import torch
+        expected = self._expected if expected is None else expected
+        if expected is None:
+            raise ValueError("m_step needs the expected counts of an e_step")
+        dev, h = expected.device, self._handle()
+
+        def call():
+            sc = torch.empty(len(self._pieces), dtype=torch.float64, device=dev)
+            alive = torch.zeros(1, dtype=torch.int64, device=dev)
+            h.mstep_device(expected.data_ptr(), sc.data_ptr(), alive.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return sc, alive
+
+        sc, alive = _on_torch_stream(dev, call, used=(expected,))
+        self._d_scores, self._host = sc, None
+        return int(alive.item())
+
+    def _alternatives(self, outputs):
+        """hutk_unigram_alternatives_device on torch's current stream; outputs: -> (classes, paths, key offsets) on the device"""
+        import torch
+        dev, h, n = self._dev(), self._handle(), len(self._pieces)
+
+        def call():
+            out = ()
+            if outputs:
+                out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(max(h.key_bytes(), 1), dtype=torch.int32, device=dev),
+                       torch.empty(n, dtype=torch.int64, device=dev))
+            h.alternatives_device(*(t.data_ptr() for t in out), stream=torch.cuda.current_stream(dev).cuda_stream)
+            return out or None
+
+        return _on_torch_stream(dev, call)
+
+    def alternatives(self):
+        """-> (classes int32[n] -- 0 dead, 1 kept unconditionally, 2 dropped, 3 has an alternative --, {id: [ids]} of class 3)"""
+        cls, path, at = (t.cpu().numpy() for t in self._alternatives(True))
+        alts = {}
+        for i in (cls == 3).nonzero()[0].tolist():
+            p = self._pieces[i]
+            seg = path[at[i]:at[i] + len(p.encode("utf-8", "surrogateescape")) - 2 * p.count("▁")]
+            alts[i] = [int(v) & (2**30 - 1) for v in seg if v >= 0]
+        return cls, alts
+
+    def histogram(self, batches):
+        """-> int64[n] on the device: the times every id stands on the best path of the batches (alive pieces only)"""
+        import torch
+        h, freq = self._handle(), None
+        for db, do in self._batches(batches):
+            dev = db.device
+            if freq is None:
+                freq = torch.zeros(len(self._pieces), dtype=torch.int64, device=dev)
+
+            def call():
+                h.hist_device(db.data_ptr(), do.data_ptr(), do.numel() - 1, db.numel(), freq.data_ptr(), 0, torch.cuda.current_stream(dev).cuda_stream)
+
+            _on_torch_stream(dev, call, used=(db, do, freq))
+        if freq is None:
+            raise ValueError("histogram needs at least one batch")
+        self.passes += 1
+        return freq
+
+    def losses(self, freq):
+        """-> f64[n] on the device: NaN dead, +inf kept unconditionally, -inf dropped, else the loss (after alternatives())"""
+        import torch
+        dev, h = freq.device, self._handle()
+
+        def call():
+            loss = torch.empty(len(self._pieces), dtype=torch.float64, device=dev)
+            h.prune_loss_device(freq.data_ptr(), loss.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return loss
+
+        return _on_torch_stream(dev, call, used=(freq,))
+
+    @staticmethod
+    def kept(loss, desired, alive=None):
+        """The ids a prune keeps, from the losses (numpy): the unconditional ones, then by loss descending, ties by lower id,
+        until max(desired, floor(0.75 * alive)) are alive.  alive: the pieces alive by score (None: those with a loss; a line
+        that can never be a key is alive until the first M-step and has none)."""
+        import numpy as np
+        if alive is None:
+            alive = int(np.count_nonzero(~np.isnan(loss)))
+        size = max(int(desired), (3 * alive) // 4)
+        keep = np.flatnonzero(loss == np.inf)
+        cand = np.flatnonzero(np.isfinite(loss))
+        cand = cand[np.argsort(-loss[cand], kind="stable")]  # (stable over rising ids: ties by lower id)
+        return np.sort(np.concatenate([keep, cand[:max(size - len(keep), 0)]]))
+
+    def prune(self, batches, desired):
+        """One prune: alternatives, histogram, losses on the GPU; the ordering on the host -> the alive count"""
+        import numpy as np
+        self._alternatives(False)
+        loss = self.losses(self.histogram(batches)).cpu().numpy()
+        scores = np.full_like(self._scores, np.nan)
+        keep = self.kept(loss, desired, self.alive)
+        scores[keep] = self._scores[keep]
+        self.set_scores(scores)
+        return len(keep)
+
+    def _check_size(self, vocab_size):
+        if isinstance(vocab_size, bool) or not isinstance(vocab_size, int):
+            raise TypeError("vocab_size must be an int, not %s" % type(vocab_size).__name__)
+        need = int(self._single.sum()) + 1
+        if vocab_size < need:
+            raise ValueError("vocab_size %d is below the %d lines of the unknown token and the seed's single characters" % (vocab_size, need))
+
+    def finalize(self, vocab_size):
+        """-> [(piece, score)]: the unknown line, the single characters (dead ones restored), the best of the rest"""
+        import numpy as np
+        self._check_size(vocab_size)
+        sc = self._scores
+        low = float(np.nanmin(sc))
+        lines, k = [], 0
+        for i in np.flatnonzero(self._single).tolist():
+            if np.isnan(sc[i]):
+                lines.append((i, low - 1e-4 * (k + 1)))
+                k += 1
+            else:
+                lines.append((i, float(sc[i])))
+        rest = [i for i in np.flatnonzero(~np.isnan(sc)).tolist() if not self._single[i]]
+        rest.sort(key=lambda i: (-sc[i], i))
+        lines += [(i, float(sc[i])) for i in rest[:max(vocab_size - 1 - len(lines), 0)]]
+        lines.sort(key=lambda t: (-t[1], t[0]))
+        return [(self._pieces[self.unk_id], 0.0)] + [(self._pieces[i], s) for i, s in lines]
+
+    def fit(self, batches, vocab_size):
+        """The loop: two (E-step, M-step) pairs, then a prune, until at most vocab_size * 11 // 10 pieces are alive;
+        -> the finalised vocabulary as a Unigram (its unk_id is 0)."""
+        self._check_size(vocab_size)
+        batches = self._batches(batches)
+        desired = vocab_size * 11 // 10
+        while True:
+            for _ in range(2):
+                self.e_step(batches)
+                alive = self.m_step()
+            if alive <= desired:
+                break
+            self.prune(batches, desired)
+        return Unigram(self.finalize(vocab_size), 0, device=self._shape._device, **self._options)
+
+
+def train_unigram(texts, seed_pieces, vocab_size, unk_id=0, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False,
+                  device=None, normalize=None):
+    """UnigramTrainer.fit on a list of str: the texts are packed and uploaded once (normalize="NFC" .. "NFKD": put into
+    that form on the GPU first) -> Unigram."""
+    import numpy as np
+    import torch
+    from .normalize import form_index
+    if normalize is not None:
+        form_index(normalize)
+    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    trainer = UnigramTrainer(seed_pieces, unk_id, prepend_scheme=prepend_scheme, whitespace_split=whitespace_split,
+                             collapse_spaces=collapse_spaces, device=device)
+    trainer._check_size(vocab_size)
+    chunks = [t.encode("utf-8", "surrogateescape") for t in texts]
+    offs = np.zeros(len(chunks) + 1, dtype=np.int64)
+    if chunks:
+        np.cumsum(np.fromiter(map(len, chunks), dtype=np.int64, count=len(chunks)), out=offs[1:])
+    dev = trainer._dev()
+    d_bytes = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()).to(dev)
+    d_offs = torch.from_numpy(offs).to(dev)
+    if normalize is not None:
+        with torch.cuda.device(dev):
+            d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, normalize)
+    ug = trainer.fit((d_bytes, d_offs), vocab_size)
+    ug.normalize = normalize
+    return ug
 
 
 # ---- split presets (hutk_presplit.hip, DESIGN.md section 4d) ----

@@ -172,6 +172,13 @@ SIGNATURES = {
     "hutk_unigram_encode_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "hutk_unigram_sample_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp]),
     "hutk_unigram_encode_batch": (_i32, [_vp, _vp, _vp, _i64, _pvp, _pvp, _pvp]),
+    "hutk_unigram_key_bytes": (_i64, [_vp]),
+    "hutk_unigram_set_scores": (_i32, [_vp, _vp, _vp]),
+    "hutk_unigram_estep_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _u32, _vp, _vp]),
+    "hutk_unigram_mstep_device": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "hutk_unigram_alternatives_device": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "hutk_unigram_hist_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "hutk_unigram_prune_loss_device": (_i32, [_vp, _vp, _vp, _vp]),
     "hutk_debug_unigram_chunk_bytes": (_i32, []),
     "hutk_debug_unigram_bucket": (_i64, [_vp, _vp, _i64]),
 }
@@ -1316,6 +1323,7 @@ def wordpiece_chunk_bytes():
 
 UNIGRAM_INFO = ["chunk_bytes", "vocab_size", "table_slots", "flags", "unk_id", "max_piece_bytes", "piece_bytes_bound", "group_lanes"]
 UG_PREPEND, UG_WHITESPACE_SPLIT, UG_COLLAPSE_SPACES = 1, 2, 4
+UG_ESTEP_PLAIN_ATOMICS = 1
 
 
 class Unigram(_Owner):
@@ -1363,6 +1371,32 @@ class Unigram(_Owner):
         raise_for(load().hutk_unigram_sample_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
                                                           d_ids or None, ids_cap, d_out_offsets or None, d_word_ids or None,
                                                           C.addressof(a), seed, first_doc, d_err or None, stream or None))
+
+    # training (include/hutoken_amd.h, "Unigram training"): raw device pointers (ints), asynchronous on `stream`
+    def key_bytes(self):
+        return load().hutk_unigram_key_bytes(self._h)
+
+    def set_scores(self, scores, stream=0):
+        import numpy as np
+        sc = np.ascontiguousarray(scores, dtype=np.float64)
+        raise_for(load().hutk_unigram_set_scores(self._h, sc.ctypes.data, stream or None))
+
+    def estep_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_expected, d_stats, flags=0, d_err=0, stream=0):
+        raise_for(load().hutk_unigram_estep_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes, d_expected or None,
+                                                   d_stats or None, flags, d_err or None, stream or None))
+
+    def mstep_device(self, d_expected, d_scores_out, d_alive, stream=0):
+        raise_for(load().hutk_unigram_mstep_device(self._h, d_expected or None, d_scores_out or None, d_alive or None, stream or None))
+
+    def alternatives_device(self, d_class=0, d_path=0, d_key_at=0, stream=0):
+        raise_for(load().hutk_unigram_alternatives_device(self._h, d_class or None, d_path or None, d_key_at or None, stream or None))
+
+    def hist_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_freq, d_err=0, stream=0):
+        raise_for(load().hutk_unigram_hist_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes, d_freq or None,
+                                                  d_err or None, stream or None))
+
+    def prune_loss_device(self, d_freq, d_loss, stream=0):
+        raise_for(load().hutk_unigram_prune_loss_device(self._h, d_freq or None, d_loss or None, stream or None))
 
     def batch(self, data, offsets, word_ids=False):
         """Host numpy buffers in and out (hutk_unigram_encode_batch): -> (ids int32, out_offsets int64[n + 1]) and, with

@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
 HIP_SOURCES = ["hutk_loader.cpp", "hutk_api.cpp", "hutk_kernels.hip", "hutk_ptiles.hip", "hutk_decode.hip", "hutk_train.hip", "hutk_collate.hip", "hutk_spans.hip", "hutk_special.hip", "hutk_fallback.hip", "hutk_normalize.hip", "hutk_presplit.hip", "hutk_features.hip", "hutk_bestfit.hip", "hutk_wordpiece.hip", "hutk_unigram.hip"]
-HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_host.h", "hutk_classify.h", "hutk_lab.h", "hutk_exc.h", "hutk_norm.h", "hutk_presplit.h", "hutk_wave.h", "hutk_philox.h", "hutk_fim.h", "hutk_wordpiece.h", "hutk_unigram.h", "hutk_wcache.h", "hutk_wordbits.h", os.path.join(INCLUDE, "hutoken_amd.h")]
+HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_host.h", "hutk_classify.h", "hutk_lab.h", "hutk_exc.h", "hutk_norm.h", "hutk_presplit.h", "hutk_wave.h", "hutk_philox.h", "hutk_fim.h", "hutk_wordpiece.h", "hutk_unigram.h", "hutk_unigram_train.h", "hutk_wcache.h", "hutk_wordbits.h", os.path.join(INCLUDE, "hutoken_amd.h")]
 
 LIB_HIP = os.path.join(LIBDIR, "libhutoken_amd.so")
 LIB_SYNTH = os.path.join(LIBDIR, "libhutk_synth.so")
@@ -90,7 +90,29 @@ def build_hip(force=False, extra_flags=(), out=LIB_HIP):
                        "-Wall", "-Wno-unused-result", "-I" + INCLUDE, "-I" + CSRC,
                        *extra_flags, "-o", out, *srcs, "-lpthread"]
                 _compile(cmd, out)
+                check_f64_atomics(extra_flags)
     return out
+
+
+def check_f64_atomics(extra_flags=()):
+    """The E-step of Unigram training (csrc/hutk_unigram_train.h) adds f64 posteriors into LDS and into global memory.  Both
+    must be the hardware's atomic instructions; a compiler that turns either into a compare-and-swap loop makes the
+    kernel several times slower without failing anything.  So the device code of its file is compiled to assembly once
+    more and k_ug_estep is searched for both: a missing one is an error."""
+    import re
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        asm = os.path.join(tmp, "hutk_unigram.s")
+        subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + INCLUDE, "-I" + CSRC, *extra_flags,
+                               "--cuda-device-only", "-S", "-Wno-unused-command-line-argument", "-o", asm, os.path.join(CSRC, "hutk_unigram.hip")])
+        with open(asm) as f:
+            text = f.read()
+    bodies = re.findall(r"^_Z\w*k_ug_estepILb1E\w*:[^\n]*\n(.*?)\n\ts_endpgm", text, re.S | re.M)
+    if not bodies:
+        raise RuntimeError("k_ug_estep<true> is missing from the assembly of hutk_unigram.hip")
+    missing = [ins for ins in ("ds_add_f64", "global_atomic_add_f64") if ins not in bodies[0]]
+    if missing or "cmpswap" in bodies[0]:
+        raise RuntimeError("k_ug_estep: the f64 atomics are not the hardware's (missing %s%s)" % (missing, ", a compare-and-swap loop" if "cmpswap" in bodies[0] else ""))
 
 
 def build_pyshim(force=False):

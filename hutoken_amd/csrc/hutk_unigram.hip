@@ -25,6 +25,8 @@
 //   k_ug_count       ids and words per slice and chunk;  k_ug_scan over both
 //   k_ug_docs        out_offsets, and the word count in front of every document
 //   k_ug_write       the ids, compact, and the word ids
+// Training (hutk_unigram_train.h, included below: k_ug_estep, k_ug_lattice_train, k_ug_hist and the small kernels of the
+// M-step and the prune) starts from the same front half, ug_front.
 //
 // Nothing synchronises; growing the workspace for a batch larger than any before may wait once.
 #include <algorithm>
@@ -191,13 +193,25 @@ __device__ __forceinline__ void group_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// What the training form of the best path adds (hutk_unigram_train.h): a piece whose score is NaN
+// is dead and no candidate, the unknown edge's score is *low - 10 (low: the lowest score alive, on the device), the
+// score the word's end holds goes to fin[ws] (NaN: nothing reached it), and with bar the edge that spans the whole word
+// is no candidate (it still counts as the single character's key).
+struct TrainArgs {
+    const double* low;
+    double* fin;  // or NULL
+    int32_t bar;
+};
+
 // The word that starts at ws, by the GROUP lanes of one group (all of them run this with the same arguments; gl: the
 // lane's place in the group, g0: the group's first lane in the wavefront).  Starts are taken in rising order; of one
 // start the lanes probe lengths base + 1 .. base + GROUP a trip, each lane the length base + gl + 1, over a hash the
 // group walks together: a lane loads one byte a trip and the others read it by a shuffle.  Only lengths that some key
 // with the start's first byte has are probed.  The word's end is found on the way: it has no length limit.
 // ring: the group's R best scores, NaN where a position holds nothing; all NaN between words.
-__device__ __forceinline__ void lattice_word(const MatchArgs& a, const U::Text& f, int64_t ws, double* ring, int gl, int g0) {
+template <bool TRAIN>
+__device__ __forceinline__ void lattice_word(const MatchArgs& a, const TrainArgs& t, const U::Text& f, int64_t ws, double* ring, int gl,
+                                             int g0) {
     const int R1 = a.ring - 1;
     const uint8_t* w = f.bytes + ws;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
@@ -232,7 +246,12 @@ __device__ __forceinline__ void lattice_word(const MatchArgs& a, const U::Text& 
             const int len = idx + 1;
             int32_t id = -1;
             if (len <= end_at && len <= top && U::has_len(lens, len)) id = U::find(a.V, U::hash_end(h), w + s, len);
-            if (id >= 0) {
+            bool use = id >= 0;
+            if constexpr (TRAIN) {
+                if (id >= 0 && a.V.scores[id] != a.V.scores[id]) id = -1;
+                use = id >= 0 && !(t.bar && s == 0 && U::word_ends(f, ws + len));  // (end_at is known only once a trip has seen the end)
+            }
+            if (use) {
                 const double cand = a.V.scores[id] + here;
                 double* cur = ring + (int)((s + len) & R1);
                 if (U::replaces(cand, *cur)) {
@@ -243,7 +262,8 @@ __device__ __forceinline__ void lattice_word(const MatchArgs& a, const U::Text& 
             single = single || ((uint32_t)(__ballot(id >= 0 && len == m) >> g0) & ((1u << GROUP) - 1u)) != 0;
         }
         if (!single && gl == 0) {  // (no lane wrote position s + m from this start)
-            const double cand = a.V.unk_score + here;
+            double cand = a.V.unk_score + here;
+            if constexpr (TRAIN) cand = (*t.low - 10.0) + here;
             double* cur = ring + (int)((s + m) & R1);
             if (U::replaces(cand, *cur)) {
                 *cur = cand;
@@ -254,6 +274,15 @@ __device__ __forceinline__ void lattice_word(const MatchArgs& a, const U::Text& 
         if (m == end_at) break;  // (m <= end_at: a character does not reach past the word)
     }
     group_sync();
+    if constexpr (TRAIN) {
+        const double end = ring[(int)(s & R1)];
+        if (gl == 0 && t.fin) t.fin[ws] = end;
+        group_sync();
+        if (gl == 0) ring[(int)(s & R1)] = nan;
+        __threadfence_block();
+        if (gl == 0 && end == end) U::backtrack(a.bp, a.V.unk, ws, s, a.tmp);
+        return;
+    }
     if (gl == 0) ring[(int)(s & R1)] = nan;
     __threadfence_block();  // the backpointers of the group's other lanes
     if (gl == 0) U::backtrack(a.bp, a.V.unk, ws, s, a.tmp);
@@ -296,7 +325,7 @@ __global__ __launch_bounds__(TB) void k_ug_lattice(const MatchArgs a) {
         if (gl == 0) i = atomicAdd(&s_next, 1);
         i = __shfl(i, g0);
         if (i >= n_words) break;
-        lattice_word(a, f, c0 + s_ws[i], s_ring + g * a.ring, gl, g0);
+        lattice_word<false>(a, TrainArgs{}, f, c0 + s_ws[i], s_ring + g * a.ring, gl, g0);
     }
 }
 
@@ -573,6 +602,14 @@ struct hutk_unigram {
     DevBuf<uint16_t> w_slice;
     DevBuf<int32_t> w_tmp, w_ok, s_ids, s_wids;
     U::Vocab V{};
+    // training (hutk_unigram_train.h): the lowest score alive, the M-step's sums, and what a prune keeps between its calls
+    // -- the key blob's flags, the best path of every key with its spanning edge barred, that path's score, the classes
+    int64_t n_key_bytes = 0;
+    bool train_ready = false;
+    DevBuf<double> t_low, t_fin;
+    DevBuf<uint8_t> t_kflag;
+    DevBuf<int32_t> t_alt, t_class;
+    DevBuf<U::Back> t_kbp;
     std::mutex mu;
     hipEvent_t ev = nullptr;  // behind the last kernel of the last call: calls share the workspace, so they are serialised
     bool ev_recorded = false;
@@ -593,6 +630,7 @@ void hutk_unigram_destroy(hutk_unigram* h) {
     h->w_bp.release(); h->w_offs.release(); h->w_chunk.release(); h->w_small.release(); h->w_word_base.release(); h->s_offs.release();
     h->s_oo.release(); h->w_slice.release(); h->w_tmp.release(); h->w_ok.release(); h->s_ids.release(); h->s_wids.release();
     for (int i = 0; i < 2; i++) h->w_flag[i].release();
+    h->t_low.release(); h->t_fin.release(); h->t_kflag.release(); h->t_alt.release(); h->t_class.release(); h->t_kbp.release();
     delete h;
 }
 
@@ -618,6 +656,7 @@ int hutk_unigram_create(hutk_unigram** out, int device, const uint8_t* piece_byt
     hutk_unigram* h = new hutk_unigram();
     h->device = device;
     h->flags = flags, h->unk = (int32_t)unk_id, h->max_len = vh.max_len, h->n_pieces = n_pieces, h->n_slots = (int64_t)vh.slots.size();
+    h->n_key_bytes = (int64_t)vh.keys.size();
     h->ring = U::ring_size(vh.max_len);
     h->n_groups = std::min(GROUPS, RING_LDS_BYTES / (8 * h->ring));
     hipError_t e = h->d_slots.reserve(vh.slots.size());
@@ -665,20 +704,19 @@ int64_t hutk_unigram_ids_capacity(const hutk_unigram* h, int64_t n_bytes, int64_
     return n_bytes + n_docs;
 }
 
-// Both device entries: the best path (sample NULL), or a sampled segmentation with sample's alpha, seed and first_doc.
-static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
-                            int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err, void* hip_stream,
-                            const SampleArgs* sample, const std::string& who) {
-    if (!h) return hutk::api_set_error(HUTK_E_ARG, who + ": the handle is NULL");
-    if (n_docs < 0 || n_bytes < 0 || ids_cap < 0 || !d_offsets || !d_out_offsets || (n_bytes > 0 && !d_bytes) || (ids_cap > 0 && !d_ids))
-        return hutk::api_set_error(HUTK_E_ARG, who + ": bad arguments");
+}  // extern "C"
+
+// What every device entry starts with (the caller holds h->mu and has checked h and the batch's arguments): the
+// workspace, the wait for the handle's last call, the check of the offsets, the fold, and the emptied id workspace.
+// -> m: the folded text and the handle's workspace, without the outputs of an encode; chunks: those of the folded text.
+static int ug_front(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes, bool word_ids,
+                    int32_t* d_err, hipStream_t st, const std::string& who, MatchArgs& m, int64_t& chunks) {
     const int64_t cap_f = n_bytes + n_docs;  // the folded text's bound
-    const int64_t src_chunks = (n_bytes + U::CHUNK_BYTES - 1) / U::CHUNK_BYTES, chunks = (cap_f + U::CHUNK_BYTES - 1) / U::CHUNK_BYTES;
+    const int64_t src_chunks = (n_bytes + U::CHUNK_BYTES - 1) / U::CHUNK_BYTES;
+    chunks = (cap_f + U::CHUNK_BYTES - 1) / U::CHUNK_BYTES;
     if (chunks > INT32_MAX / 2 || (n_docs + TB) / TB > INT32_MAX)
         return hutk::api_set_error(HUTK_E_UNSUPPORTED, who + ": the batch is too large for one launch");
-    std::lock_guard<std::mutex> lock(h->mu);
     HUTK_HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)hip_stream;
     HUTK_HIP_TRY(h->w_flag[0].reserve((size_t)n_bytes + 1));
     HUTK_HIP_TRY(h->w_flag[1].reserve((size_t)cap_f + 1));
     HUTK_HIP_TRY(h->w_text.reserve((size_t)cap_f + 16));
@@ -687,7 +725,7 @@ static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64
     HUTK_HIP_TRY(h->w_slice.reserve(2 * (size_t)chunks * TB + 1));
     HUTK_HIP_TRY(h->w_tmp.reserve((size_t)cap_f + 1));
     HUTK_HIP_TRY(h->w_bp.reserve((size_t)cap_f + 1));
-    if (d_word_ids) HUTK_HIP_TRY(h->w_word_base.reserve((size_t)n_docs + 1));
+    if (word_ids) HUTK_HIP_TRY(h->w_word_base.reserve((size_t)n_docs + 1));
     if (h->ev_recorded) HUTK_HIP_TRY(hipStreamWaitEvent(st, h->ev, 0));
     int32_t* ok = h->w_ok.p;
     int32_t* err = d_err ? d_err : h->w_ok.p + 1;
@@ -711,16 +749,42 @@ static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64
     if (src_chunks) hipLaunchKernelGGL(k_ug_fold_write, dim3((unsigned)src_chunks), dim3(TB), 0, st, fa);
     hipLaunchKernelGGL(k_ug_fold_docs, dim3(blocks_for(n_docs)), dim3(TB), 0, st, fa);
 
-    MatchArgs m;
     m.f = U::Text{h->w_text.p, h->w_flag[1].p, cap_f}, m.n_dev = n_fold, m.V = h->V, m.ring = h->ring, m.n_groups = h->n_groups;
     m.tmp = h->w_tmp.p, m.bp = h->w_bp.p;
     m.n_chunks = chunks, m.chunk = h->w_chunk.p, m.slice = h->w_slice.p;
-    m.offs = h->w_offs.p, m.n_docs = n_docs, m.out_offs = d_out_offsets, m.word_base = h->w_word_base.p;
-    m.ids = d_ids, m.ids_cap = ids_cap, m.word_ids = d_word_ids, m.err = err, m.ok = ok;
+    m.offs = h->w_offs.p, m.n_docs = n_docs, m.out_offs = nullptr, m.word_base = h->w_word_base.p;
+    m.ids = nullptr, m.ids_cap = 0, m.word_ids = nullptr, m.err = err, m.ok = ok;
     HUTK_HIP_TRY(hipMemsetAsync(m.chunk, 0, 2 * ((size_t)chunks + 1) * sizeof(int64_t), st));
     if (chunks) {
         const unsigned fill = (unsigned)std::min<int64_t>((cap_f + TB - 1) / TB, 1 << 16);
         hipLaunchKernelGGL(k_ug_fill, dim3(fill), dim3(TB), 0, st, m.tmp, n_fold, ok);
+    }
+    return HUTK_OK;
+}
+
+// Behind a call's last kernel: what was enqueued is checked, and the next call on the handle waits for it.
+static int ug_back(hutk_unigram* h, hipStream_t st) {
+    HUTK_HIP_TRY(hipGetLastError());
+    HUTK_HIP_TRY(hipEventRecord(h->ev, st));
+    h->ev_recorded = true;
+    return HUTK_OK;
+}
+
+// Both device entries: the best path (sample NULL), or a sampled segmentation with sample's alpha, seed and first_doc.
+static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                            int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err, void* hip_stream,
+                            const SampleArgs* sample, const std::string& who) {
+    if (!h) return hutk::api_set_error(HUTK_E_ARG, who + ": the handle is NULL");
+    if (n_docs < 0 || n_bytes < 0 || ids_cap < 0 || !d_offsets || !d_out_offsets || (n_bytes > 0 && !d_bytes) || (ids_cap > 0 && !d_ids))
+        return hutk::api_set_error(HUTK_E_ARG, who + ": bad arguments");
+    std::lock_guard<std::mutex> lock(h->mu);
+    hipStream_t st = (hipStream_t)hip_stream;
+    MatchArgs m;
+    int64_t chunks = 0;
+    if (int rc = ug_front(h, d_bytes, d_offsets, n_docs, n_bytes, d_word_ids != nullptr, d_err, st, who, m, chunks)) return rc;
+    const int32_t* ok = m.ok;
+    m.out_offs = d_out_offsets, m.ids = d_ids, m.ids_cap = ids_cap, m.word_ids = d_word_ids;
+    if (chunks) {
         const size_t rings = (size_t)h->n_groups * h->ring * sizeof(double);
         if (sample) {
             SampleArgs sa = *sample;
@@ -734,11 +798,12 @@ static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64
     hipLaunchKernelGGL(k_ug_scan, dim3(2), dim3(SCAN_TB), 0, st, m.chunk, chunks + 1, chunks, ok);
     hipLaunchKernelGGL(k_ug_docs, dim3(blocks_for(n_docs)), dim3(TB), 0, st, m);
     if (chunks) hipLaunchKernelGGL(k_ug_write, dim3((unsigned)chunks), dim3(TB), 0, st, m);
-    HUTK_HIP_TRY(hipGetLastError());
-    HUTK_HIP_TRY(hipEventRecord(h->ev, st));
-    h->ev_recorded = true;
-    return HUTK_OK;
+    return ug_back(h, st);
 }
+
+#include "hutk_unigram_train.h"  // the training kernels and their entry points, over everything above
+
+extern "C" {
 
 int hutk_unigram_encode_batch_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
                                      int32_t* d_ids, int64_t ids_cap, int64_t* d_out_offsets, int32_t* d_word_ids, int32_t* d_err,

@@ -1453,6 +1453,67 @@ int hutk_unigram_encode_batch(hutk_unigram* h, const uint8_t* bytes, const int64
 int hutk_debug_unigram_chunk_bytes(void);
 int64_t hutk_debug_unigram_bucket(const hutk_unigram* h, const uint8_t* bytes, int64_t len);
 
+/* ---- Unigram training: EM over the piece lattice, and pruning (hutk_unigram_train.h) --------
+ * THE RULE is the `tokenizers` package's (0.22.2) UnigramTrainer FROM THE SEED ON -- run_e_step, run_m_step,
+ * prune_sentence_pieces, finalize -- applied per word occurrence of the folded text; making the seed is the caller's.
+ * Piece ids are the seed's for the whole training and are compacted once, at the end.  A piece is ALIVE or DEAD; on a
+ * handle a dead piece's score is NaN (hutk_unigram_set_scores; a handle that never saw that call holds no NaN and all
+ * its pieces are alive).  On a trainer's handle unk_id's own line is dead: its text is never a key.
+ * unk_score = min(alive scores) - 10, kept on the device and recomputed whenever the scores are set.
+ *   E-STEP.  For a word of n folded bytes the candidates at a character start s are those of
+ *     hutk_unigram_sample_batch_device restricted to alive keys; the unknown edge (unk_id, unk_score, the character's
+ *     length) stands where no alive key equals the single character at s.  With x an edge's score and (s, e) its ends:
+ *     fwd[0] = 0, fwd[e] = log sum exp(fwd[s] + x); bwd[n] = 0, bwd[s] = log sum exp(x + bwd[e]); Z = bwd[0]; an edge's
+ *     posterior is exp(fwd[s] + x + bwd[e] - Z); expected[id] += posterior (the unknown edge adds to expected[unk_id]);
+ *     stats[0] += Z and stats[1] += 1 per word.  The maximum is taken out of every sum; the order of the f64 additions
+ *     is not part of the rule.
+ *   M-STEP.  unk_id is skipped.  A piece with expected < 0.5 dies (single characters too: they are restored at the end,
+ *     as `tokenizers` does).  S = the sum of the survivors' counts; score = digamma(count) - digamma(S), digamma being
+ *     `tokenizers`' own: r = 0; while x < 7: r -= 1 / x, x += 1; x -= 1/2; r + ln x + xx2/24 - 7 xx4/960 + 31 xx4 xx2/8064
+ *     - 127 xx4 xx4/30720 with xx2 = 1/x^2, xx4 = xx2^2.
+ *   ALTERNATIVES, once per prune.  For every alive piece: the best path (the encoder's exact rule and tie rule, over alive
+ *     pieces, unknown ids fused as on every best path) over the piece's own folded bytes WITH THE EDGE THAT SPANS THE
+ *     WHOLE PIECE BARRED.  No such path (a single character): the piece is kept unconditionally.  The path's score is
+ *     strictly greater than the piece's own: the piece is dropped (`tokenizers`' nbests[0].len() >= 2).  Otherwise the
+ *     path's ids are its alternative.  This one barred best path replaces the reference's 2-best search: when the best
+ *     path is the piece itself, the second best is the best path that does not use the spanning edge.
+ *   PRUNE.  freq[id] = the times id stands on the best path of the corpus (alive pieces; an int64 histogram of the ids
+ *     the encoder would give), vsum = sum freq.  Unconditional pieces are kept.  Of the others a piece with freq == 0 is
+ *     dropped, and the loss of piece i is (freq[i] / vsum) * (logprob_sp - logprob_alt), logprob_sp = ln freq[i] - ln vsum,
+ *     logprob_alt = sum over a in alt of (ln(freq[a] + freq[i]) - ln(vsum + freq[i] * (len(alt) - 1))).  Candidates are
+ *     added by loss descending, ties by lower id, until max(desired, floor(0.75 * alive)) pieces are alive; the rest die.
+ *     Scores are unchanged by pruning.
+ *   LOOP.  desired = vocab_size * 11 / 10 (integers).  Repeat: two (E-step, M-step) pairs; stop if alive <= desired; prune.
+ *   FINALISE.  The unk line with score 0; every single-character seed piece, a dead one restored with
+ *     min_alive_score - 1e-4 * (k + 1), k counting the restored characters in seed order; the best-scoring remaining alive
+ *     pieces (ties by seed id) until vocab_size lines; everything behind the unk line ordered by score descending, ties
+ *     by seed id.  The loop and the finalising are the Python layer's (hutoken_amd.UnigramTrainer); the ordering of the
+ *     losses is done on the host and is, with the alive count, the loop's only readback.
+ * All device calls are asynchronous on hip_stream and serialised per handle like the encoder's; d_err as there.
+ * hutk_unigram_set_scores: scores[n_pieces] ON THE HOST, NaN for a dead piece; unk_id's is stored as NaN whatever it
+ *   holds.  HUTK_E_VALUE: an infinite score, or no piece alive.  For a trainer's handles: the encoder's entry points read
+ *   the unknown score of hutk_unigram_create.  The call returns when the copy is done.
+ * hutk_unigram_estep_device: ADDS to d_expected[n_pieces] and d_stats[2] (f64), so a corpus streams through batch by
+ *   batch.  flags: HUTK_UG_ESTEP_PLAIN_ATOMICS accumulates with global atomics alone instead of the table in LDS.
+ * hutk_unigram_mstep_device: new scores on the handle from d_expected; d_scores_out[n_pieces] (may be NULL) takes a
+ *   copy, d_alive[1] the alive count.
+ * hutk_unigram_alternatives_device: classes and paths stay on the handle for hutk_unigram_prune_loss_device; the outputs
+ *   (each may be NULL) are d_class[n_pieces] (0 dead or without a key, 1 unconditional, 2 dropped, 3 alternative),
+ *   d_key_at[n_pieces] (the offset of the piece's key in the key blob, -1: none) and d_path[hutk_unigram_key_bytes()]:
+ *   per key byte the id of the path's piece that starts there (| 1 << 30 on the first), -1 elsewhere.
+ * hutk_unigram_hist_device: ADDS to d_freq[n_pieces].
+ * hutk_unigram_prune_loss_device: d_loss[n_pieces]: NaN dead, +inf unconditional, -inf dropped, else the loss. */
+#define HUTK_UG_ESTEP_PLAIN_ATOMICS 1u
+int64_t hutk_unigram_key_bytes(const hutk_unigram* h);
+int hutk_unigram_set_scores(hutk_unigram* h, const double* scores, void* hip_stream);
+int hutk_unigram_estep_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                              double* d_expected, double* d_stats, uint32_t flags, int32_t* d_err, void* hip_stream);
+int hutk_unigram_mstep_device(hutk_unigram* h, const double* d_expected, double* d_scores_out, int64_t* d_alive, void* hip_stream);
+int hutk_unigram_alternatives_device(hutk_unigram* h, int32_t* d_class, int32_t* d_path, int64_t* d_key_at, void* hip_stream);
+int hutk_unigram_hist_device(hutk_unigram* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                             int64_t* d_freq, int32_t* d_err, void* hip_stream);
+int hutk_unigram_prune_loss_device(hutk_unigram* h, const int64_t* d_freq, double* d_loss, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

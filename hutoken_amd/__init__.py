@@ -81,6 +81,9 @@ the best path over every word's piece lattice in f64.  The methods and construct
 (`encode_packed_device` with word ids on request, `batch_encode`, `encode`, `from_file` for a tokenizer.json,
 `from_tokenizer`); csrc/hutk_unigram.hip, DESIGN.md section 8n.  It needs no initialised context.  With `alpha=` and
 `seed=` the three encode methods draw a segmentation of every word instead (subword regularisation, section 8n.1).
+`UnigramTrainer` fits such a vocabulary on the GPU from a seed (section 8n.2); `UnigramSeeder` makes that seed on the GPU
+from the corpus -- unique words, characters, frequent substrings (section 8n.3) --, so `train_unigram(texts, None, size)`
+and `UnigramTrainer.from_corpus(batches)` need a corpus and a size and nothing else.
 
 Training (reference hutoken.py:163-171, src/lib.c:76-126) runs on the GPU too:
 `bpe_train` / `bbpe_train` are the reference's entry points, `Trainer` and `train`
@@ -96,7 +99,7 @@ from . import pretokenize as _presplit_tables  # (the module; the package's name
 from . import normalize as _norm_tables  # (the module; the name `normalize` of the package is the function below)
 from . import wordpiece as _wp_tables
 
-__all__ = ["Unigram", "UnigramTrainer", "train_unigram", "WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
+__all__ = ["Unigram", "UnigramTrainer", "UnigramSeeder", "train_unigram", "WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
            "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
@@ -2182,8 +2185,8 @@ def _ug_estep(h, n_pieces, d_bytes, d_offsets, out, stats, accumulator="table"):
 class UnigramTrainer:
     """Fits a Unigram vocabulary on the GPU: `tokenizers`' UnigramTrainer from the seed on -- EM over the piece lattice of
     every word occurrence, pruning by the loss of the best-path histogram, finalising (include/hutoken_amd.h states the
-    rule, DESIGN.md section 8n.2 the kernels).  Making the seed is the caller's: an existing Unigram vocabulary, or
-    train(mode="chars") run to several times the target size.
+    rule, DESIGN.md section 8n.2 the kernels).  The seed is the caller's -- an existing Unigram vocabulary, say -- or
+    UnigramSeeder's, made on the GPU from the corpus (from_corpus does both steps).
 
     seed_pieces: a list of str, or of (piece, score) pairs; without scores every piece starts at ln(1 / len(seed_pieces)).
     seed_pieces[unk_id] is the unknown token's line; its text is never matched.  The other options are Unigram's.
@@ -2420,31 +2423,244 @@ class UnigramTrainer:
         return Unigram(self.finalize(vocab_size), 0, device=self._shape._device, **self._options)
 
 
-def train_unigram(texts, seed_pieces, vocab_size, unk_id=0, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False,
-                  device=None, normalize=None):
-    """UnigramTrainer.fit on a list of str: the texts are packed and uploaded once (normalize="NFC" .. "NFKD": put into
-    that form on the GPU first) -> Unigram."""
+    @classmethod
+    def from_corpus(cls, batches, *, seed_size=1_000_000, max_piece_length=16, unk_token="<unk>", prepend_scheme="always",
+                    whitespace_split=False, collapse_spaces=False, device=None):
+        """A trainer whose seed UnigramSeeder makes on the GPU from the batches themselves (unk_id is 0)."""
+        _seed_args(seed_size, max_piece_length, unk_token)
+        batches = cls._batches(batches)
+        shape = dict(prepend_scheme=prepend_scheme, whitespace_split=whitespace_split, collapse_spaces=collapse_spaces)
+        if device is None and batches:
+            device = batches[0][0].device
+        seeder = UnigramSeeder(device=device, **shape)
+        try:
+            seeder.add(batches)
+            seed = seeder.pieces(seed_size, max_piece_length, unk_token)
+        finally:
+            seeder.close()
+        return cls(seed, 0, device=device, **shape)
+
+
+def _seed_args(seed_size, max_piece_length, unk_token):
+    for name, v in (("seed_size", seed_size), ("max_piece_length", max_piece_length)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("%s must be an int, not %s" % (name, type(v).__name__))
+    if not isinstance(unk_token, str):
+        raise TypeError("unk_token must be a str, not %s" % type(unk_token).__name__)
+    if not 1 <= max_piece_length <= 16:
+        raise ValueError("max_piece_length must be in 1 .. 16, not %d" % max_piece_length)
+    if seed_size < 2:
+        raise ValueError("seed_size %d is below the 2 lines of the unknown token and one character" % seed_size)
+
+
+def _pack_texts(texts, dev, normalize):
+    """list of str -> (d_bytes, d_offsets) on dev, put into the form `normalize` there"""
     import numpy as np
     import torch
-    from .normalize import form_index
-    if normalize is not None:
-        form_index(normalize)
-    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
-        raise TypeError("Invalid arguments. Expected a list of strings.")
-    trainer = UnigramTrainer(seed_pieces, unk_id, prepend_scheme=prepend_scheme, whitespace_split=whitespace_split,
-                             collapse_spaces=collapse_spaces, device=device)
-    trainer._check_size(vocab_size)
     chunks = [t.encode("utf-8", "surrogateescape") for t in texts]
     offs = np.zeros(len(chunks) + 1, dtype=np.int64)
     if chunks:
         np.cumsum(np.fromiter(map(len, chunks), dtype=np.int64, count=len(chunks)), out=offs[1:])
-    dev = trainer._dev()
     d_bytes = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()).to(dev)
     d_offs = torch.from_numpy(offs).to(dev)
     if normalize is not None:
         with torch.cuda.device(dev):
             d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, normalize)
-    ug = trainer.fit((d_bytes, d_offs), vocab_size)
+    return d_bytes, d_offs
+
+
+class UnigramSeeder:
+    """Makes the seed of a Unigram training on the GPU from the corpus itself: `tokenizers`' make_seed_sentence_pieces
+    (include/hutoken_amd.h states the rule, DESIGN.md section 8n.3 the kernels).  add(batches) -- one (d_bytes, d_offsets)
+    pair of device tensors or a list of them -- and add_texts(texts) count every word into a device table of unique
+    words; the state accumulates, so a corpus larger than memory streams through and its text never leaves the device.
+    pieces() counts the characters and every substring of 2 .. max_piece_length characters of the unique words on the GPU
+    and returns [(piece, score)] with the unknown line first, ready for UnigramTrainer.  The options are Unigram's."""
+
+    def __init__(self, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False, device=None):
+        self._shape = Unigram([("<unk>", 0.0)], 0, prepend_scheme=prepend_scheme, whitespace_split=whitespace_split,
+                              collapse_spaces=collapse_spaces, device=device)  # (its checks, flags and device)
+        self._h = None
+
+    def _dev(self):
+        import torch
+        d = self._shape._device
+        return torch.device("cuda", torch.cuda.current_device() if d is None else d if isinstance(d, int) else
+                            (d.index if d.index is not None else torch.cuda.current_device()))
+
+    def _handle(self, dev=None):
+        if self._h is None:
+            self._dev_used = self._dev() if dev is None else dev
+            self._h = _capi.UnigramSeed(self._shape._flags, self._dev_used.index)
+        elif dev is not None and dev != self._dev_used:
+            raise ValueError("every batch of a UnigramSeeder must be on its device, %s" % (self._dev_used,))
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            self._h.close()
+            self._h = None
+
+    def add(self, batches):
+        import torch
+        for db, do in UnigramTrainer._batches(batches):
+            dev = db.device
+            h = self._handle(dev)
+
+            def call():
+                err = torch.zeros(1, dtype=torch.int32, device=dev)
+                h.add_device(db.data_ptr(), do.data_ptr(), do.numel() - 1, db.numel(), err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                return err
+
+            code = int(_on_torch_stream(dev, call, used=(db, do)).item())
+            if code:
+                raise ValueError("hutoken_amd: UnigramSeeder.add: device-side error %d (offsets that do not describe d_bytes)" % code)
+        return self
+
+    def add_texts(self, texts, normalize=None):
+        from .normalize import form_index
+        if normalize is not None:
+            form_index(normalize)
+        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+            raise TypeError("Invalid arguments. Expected a list of strings.")
+        self._handle()
+        return self.add(_pack_texts(texts, self._dev_used, normalize))
+
+    @property
+    def n_words(self):
+        """the unique words so far"""
+        return self._handle().info()["n_words"]
+
+    @property
+    def n_occurrences(self):
+        return self._handle().info()["n_occurrences"]
+
+    def words(self):
+        """-> (arena uint8, starts int64[n], lengths int64[n], counts int64[n]) on the device: word i is the folded bytes
+        arena[starts[i] : starts[i] + lengths[i]], behind a 0x00, in the order of first insertion"""
+        import torch
+        h = self._handle()
+        info, dev = h.info(), self._dev_used
+
+        def call():
+            arena = torch.empty(info["arena_bytes"], dtype=torch.uint8, device=dev)
+            out = tuple(torch.empty(max(info["n_words"], 1), dtype=torch.int64, device=dev) for _ in range(3))
+            h.words_device(arena.data_ptr(), *(t.data_ptr() for t in out), stream=torch.cuda.current_stream(dev).cuda_stream)
+            return (arena,) + tuple(t[:info["n_words"]] for t in out)
+
+        return _on_torch_stream(dev, call)
+
+    def pieces(self, seed_size=1_000_000, max_piece_length=16, unk_token="<unk>", *, table_slots=None):
+        """-> [(piece, score)]: the unknown line, every character, then the best candidates, seed_size lines at the most;
+        pieces are str with U+2581 restored.  table_slots: the substring table's first size (a power of two; None: four
+        slots per arena byte, 2^16 .. 2^28); a table that fills is doubled and the pass is run again from the arena, up to
+        the 30 slots per arena byte that cannot fill, 2^32 at the most: RuntimeError beyond."""
+        import math
+        import torch
+        _seed_args(seed_size, max_piece_length, unk_token)
+        if table_slots is not None and (isinstance(table_slots, bool) or not isinstance(table_slots, int) or table_slots < 16
+                                        or table_slots & (table_slots - 1)):
+            raise ValueError("table_slots must be a power of two of at least 16")
+        h = self._handle()
+        info, dev = h.info(), self._dev_used
+
+        def stream():
+            return torch.cuda.current_stream(dev).cuda_stream
+
+        def char_call():
+            counts = torch.empty(_capi.UGSEED_COUNTS, dtype=torch.int64, device=dev)
+            h.char_counts_device(counts.data_ptr(), stream())
+            return counts
+
+        counts = _on_torch_stream(dev, char_call)
+        at = torch.nonzero(counts).flatten()
+        chars = [(bytes([i - 0x110000]) if i >= 0x110000 else chr(i).encode("utf-8", "surrogatepass"), c)
+                 for i, c in zip(at.tolist(), counts[at].tolist())]
+        if seed_size < len(chars) + 1:
+            raise ValueError("seed_size %d is below the %d lines of the unknown token and the corpus' characters" % (seed_size, len(chars) + 1))
+        chars.sort(key=lambda t: (t[1], t[0]), reverse=True)
+        need = seed_size - 1 - len(chars)
+        subs = []
+        if max_piece_length >= 2 and need > 0 and info["n_words"]:
+            slots = table_slots or min(max(1 << (4 * info["arena_bytes"]).bit_length(), 1 << 16), 1 << 28)
+            # an arena byte starts at most 15 substrings: a table of twice that many slots cannot fill
+            most = max(min(1 << (30 * info["arena_bytes"]).bit_length(), 1 << 32), slots)
+            while True:
+                def count_call():
+                    out = torch.empty(2, dtype=torch.int64, device=dev)
+                    h.count_device(max_piece_length, slots, out.data_ptr(), stream())
+                    return out
+                full, used = _on_torch_stream(dev, count_call).tolist()
+                if not full:
+                    break
+                slots *= 2
+                if slots > most:
+                    raise RuntimeError("UnigramSeeder.pieces: the substring table is full at its largest size, %d slots" % most)
+
+            def compact_call():
+                score, pos = (torch.empty(used + 1, dtype=torch.int64, device=dev) for _ in range(2))  # (used: the slots that hold a key)
+                ln = torch.empty(used + 1, dtype=torch.int32, device=dev)
+                n = torch.empty(1, dtype=torch.int64, device=dev)
+                h.compact_device(used + 1, score.data_ptr(), pos.data_ptr(), ln.data_ptr(), n.data_ptr(), stream())
+                return score, pos, ln, n
+
+            score, pos, ln, n = _on_torch_stream(dev, compact_call)
+            n = int(n.item())
+            if n:
+                ordered, order = torch.sort(score[:n], descending=True)
+                take = int((ordered >= ordered[min(need, n) - 1]).sum().item())  # everything above the cut, and all ties at it
+                order = order[:take]
+                pos, ln, ordered = pos[order].contiguous(), ln[order].contiguous(), ordered[:take]
+                ends = torch.cumsum(ln, 0, dtype=torch.int64)
+                dst = (ends - ln).contiguous()
+                total = int(ends[-1].item())
+
+                def gather_call():
+                    blob = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+                    h.gather_device(pos.data_ptr(), ln.data_ptr(), dst.data_ptr(), take, blob.data_ptr(), total, stream())
+                    return blob
+
+                blob = _on_torch_stream(dev, gather_call, used=(pos, ln, dst)).cpu().numpy().tobytes()
+                cuts = dst.tolist() + [total]
+                subs = [(blob[cuts[i]:cuts[i + 1]], s) for i, s in enumerate(ordered.tolist())]
+                subs.sort(key=lambda t: (t[1], t[0]), reverse=True)  # (the tie-break by string is the host's)
+                subs = subs[:need]
+        lines = chars + subs
+        of_all = math.log(sum(s for _b, s in lines)) if lines else 0.0
+
+        def text(b):
+            return ("▁" + b[1:].decode("utf-8", "surrogateescape")) if b[:1] == b" " else b.decode("utf-8", "surrogateescape")
+
+        return [(unk_token, 0.0)] + [(text(b), math.log(s) - of_all) for b, s in lines]
+
+
+def train_unigram(texts, seed_pieces, vocab_size, unk_id=0, *, prepend_scheme="always", whitespace_split=False, collapse_spaces=False,
+                  device=None, normalize=None, seed_size=1_000_000, max_piece_length=16):
+    """UnigramTrainer.fit on a list of str: the texts are packed and uploaded once (normalize="NFC" .. "NFKD": put into
+    that form on the GPU first) -> Unigram.  seed_pieces=None: the seed is made on the GPU from the texts themselves
+    (UnigramSeeder, with seed_size and max_piece_length; unk_id must be 0, where the unknown line "<unk>" then stands)."""
+    from .normalize import form_index
+    if normalize is not None:
+        form_index(normalize)
+    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    shape = dict(prepend_scheme=prepend_scheme, whitespace_split=whitespace_split, collapse_spaces=collapse_spaces)
+    batch = None
+    if seed_pieces is None:
+        _seed_args(seed_size, max_piece_length, "<unk>")
+        if unk_id != 0:
+            raise ValueError("with seed_pieces=None the unknown line is line 0: unk_id must be 0, not %r" % (unk_id,))
+        seeder = UnigramSeeder(device=device, **shape)
+        try:
+            batch = _pack_texts(texts, seeder._dev(), normalize)
+            seed_pieces = seeder.add(batch).pieces(seed_size, max_piece_length)
+        finally:
+            seeder.close()
+    trainer = UnigramTrainer(seed_pieces, unk_id, device=device, **shape)
+    trainer._check_size(vocab_size)
+    if batch is None:
+        batch = _pack_texts(texts, trainer._dev(), normalize)
+    ug = trainer.fit(batch, vocab_size)
     ug.normalize = normalize
     return ug
 

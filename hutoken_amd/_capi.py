@@ -179,6 +179,15 @@ SIGNATURES = {
     "hutk_unigram_alternatives_device": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "hutk_unigram_hist_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "hutk_unigram_prune_loss_device": (_i32, [_vp, _vp, _vp, _vp]),
+    "hutk_ugseed_create": (_i32, [_pvp, _i32, _u32]),
+    "hutk_ugseed_destroy": (None, [_vp]),
+    "hutk_ugseed_info": (_i32, [_vp, _vp]),
+    "hutk_ugseed_add_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "hutk_ugseed_words_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_ugseed_char_counts_device": (_i32, [_vp, _vp, _vp]),
+    "hutk_ugseed_count_device": (_i32, [_vp, _s32, _i64, _vp, _vp]),
+    "hutk_ugseed_compact_device": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hutk_ugseed_gather_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "hutk_debug_unigram_chunk_bytes": (_i32, []),
     "hutk_debug_unigram_bucket": (_i64, [_vp, _vp, _i64]),
 }
@@ -1424,6 +1433,45 @@ class Unigram(_Owner):
             if word_ids:
                 L.hutk_host_free(wi)
         return (r_ids, r_oo, r_wi) if word_ids else (r_ids, r_oo)
+
+
+UGSEED_INFO = ["n_words", "n_occurrences", "arena_bytes", "word_slots", "word_table_grows", "tile_bytes", "halo_bytes", "substring_slots"]
+UGSEED_COUNTS = 0x110000 + 256
+
+
+class UnigramSeed(_Owner):
+    """Owns one hutk_ugseed (the seed of a Unigram training, include/hutoken_amd.h): the unique words of everything added,
+    on one device.  Raw device pointers (ints); only add_device waits, once."""
+    _destroy = "hutk_ugseed_destroy"
+
+    def __init__(self, flags, device=-1):
+        h = C.c_void_p()
+        raise_for(load().hutk_ugseed_create(C.byref(h), int(device), int(flags)))
+        self._h = h
+
+    def info(self):
+        import numpy as np
+        out = np.zeros(8, dtype=np.int64)
+        raise_for(load().hutk_ugseed_info(self._h, out.ctypes.data))
+        return dict(zip(UGSEED_INFO, out.tolist()))
+
+    def add_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_err=0, stream=0):
+        raise_for(load().hutk_ugseed_add_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes, d_err or None, stream or None))
+
+    def words_device(self, d_arena, d_start, d_len, d_count, stream=0):
+        raise_for(load().hutk_ugseed_words_device(self._h, d_arena or None, d_start or None, d_len or None, d_count or None, stream or None))
+
+    def char_counts_device(self, d_counts, stream=0):
+        raise_for(load().hutk_ugseed_char_counts_device(self._h, d_counts or None, stream or None))
+
+    def count_device(self, max_piece_chars, table_slots, d_info, stream=0):
+        raise_for(load().hutk_ugseed_count_device(self._h, max_piece_chars, table_slots, d_info or None, stream or None))
+
+    def compact_device(self, cap, d_score, d_pos, d_len, d_n, stream=0):
+        raise_for(load().hutk_ugseed_compact_device(self._h, cap, d_score or None, d_pos or None, d_len or None, d_n or None, stream or None))
+
+    def gather_device(self, d_pos, d_len, d_dst, n, d_blob, blob_cap, stream=0):
+        raise_for(load().hutk_ugseed_gather_device(self._h, d_pos or None, d_len or None, d_dst or None, n, d_blob or None, blob_cap, stream or None))
 
 
 def unigram_chunk_bytes():

@@ -802,6 +802,7 @@ static int ug_encode_device(hutk_unigram* h, const uint8_t* d_bytes, const int64
 }
 
 #include "hutk_unigram_train.h"  // the training kernels and their entry points, over everything above
+#include "hutk_unigram_seed.h"   // the seed of a training: unique words, characters and substrings of a corpus
 
 extern "C" {
 

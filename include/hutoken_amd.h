@@ -1514,6 +1514,57 @@ int hutk_unigram_hist_device(hutk_unigram* h, const uint8_t* d_bytes, const int6
                              int64_t* d_freq, int32_t* d_err, void* hip_stream);
 int hutk_unigram_prune_loss_device(hutk_unigram* h, const int64_t* d_freq, double* d_loss, void* hip_stream);
 
+/* ---- The seed of a Unigram training, made on the GPU from the corpus (hutk_unigram_seed.h) ----
+ * Modelled on `tokenizers` 0.22.2 UnigramTrainer::make_seed_sentence_pieces; where that function differs, this holds.
+ * The text is the folded text of the encoder under the seeder's flags (HUTK_UG_*).  A word is what its word starts and
+ * ends delimit.  U+2581 is the byte 0x20 and one character.  A byte that strict UTF-8 rejects is a character of one byte.
+ * A byte 0x00 is a boundary like a word's end: no substring holds one and it is not counted as a character.
+ *   1. SENTENCES.  The distinct words of everything added, each with its number of occurrences n_w, in the order of first
+ *      insertion, which does not influence the result.
+ *   2. CHARACTERS.  count(c) = the sum over unique words of n_w x (occurrences of c in the word).  Characters are ordered
+ *      by (count, c) descending; a character's score is its count.
+ *   3. SUBSTRINGS.  Every occurrence of a string s of 2 .. max_piece_chars characters (at most 16, so at most 64 folded
+ *      bytes) inside a unique word counts.  freq(s) = its occurrences over the unique words: each unique word once, not
+ *      n_w times; overlapping occurrences all count (aaa holds aa twice).  The follower of an occurrence is the character
+ *      behind it, or END at the word's end or in front of a 0x00; END is one value, the same for every word.  s is a
+ *      candidate if and only if its occurrences have at least two distinct followers (the internal nodes of the suffix
+ *      tree of the words joined by a separator).  Its score is freq(s) x characters(s) in 64 bits.
+ *   4. SEED.  Every character, then candidates by (score, s) descending until the seed holds seed_size lines with the
+ *      unknown line.  Strings are compared as their folded bytes, byte by byte: for well-formed text that is the order of
+ *      the code points with U+2581 in U+0020's place, below every printable character.  Every score becomes
+ *      ln(score) - ln(the sum of all scores in the seed).  The unknown line goes in front.
+ * The ordering, the tie-break by string and the logarithms are the Python layer's (hutoken_amd.UnigramSeeder).
+ * hutk_ugseed_add_device: the words of one packed batch into the device table of unique words; state accumulates over the
+ *   calls.  Asynchronous on hip_stream up to one wait at its end, for the table's counters (growing the table is the
+ *   host's), and one more for every reallocation of the table, the records or the arena.  HUTK_E_UNSUPPORTED: the word
+ *   table would pass 2^32 slots.  d_err as the encoder's.
+ * hutk_ugseed_info: out8 = unique words, occurrences, arena bytes, word-table slots, growths of the word table, the
+ *   counting kernel's tile bytes, its halo bytes, the substring table's slots.
+ * hutk_ugseed_words_device: d_arena[arena bytes] (every word behind a 0x00), and per unique word its start in the arena,
+ *   its bytes and its occurrences.
+ * hutk_ugseed_char_counts_device: d_counts[0x110000 + 256] is WRITTEN: by code point (U+2581 at 0x20), then by byte value
+ *   for the bytes that are no UTF-8.
+ * hutk_ugseed_count_device: step 3 into a table of table_slots slots (a power of two) on the handle.  d_info[0] != 0: the
+ *   table reached half load and the pass ended early -- call again with twice the slots; d_info[1]: slots in use.
+ *   HUTK_E_UNSUPPORTED: an arena of 2^32 bytes or more (freq is 32 bits).
+ * hutk_ugseed_compact_device: the candidates of the last count as d_score, d_pos (arena position), d_len (bytes), in no
+ *   particular order; d_n[0]: how many there are (more than cap: only cap were written).
+ * hutk_ugseed_gather_device: string i, the d_len[i] arena bytes at d_pos[i], to d_blob + d_dst[i].
+ * Nothing but hutk_ugseed_add_device waits (growing a workspace may, once, as everywhere); calls on a handle are serialised. */
+typedef struct hutk_ugseed hutk_ugseed;
+int hutk_ugseed_create(hutk_ugseed** out, int device, uint32_t flags);
+void hutk_ugseed_destroy(hutk_ugseed* h);
+int hutk_ugseed_info(const hutk_ugseed* h, int64_t* out8);
+int hutk_ugseed_add_device(hutk_ugseed* h, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                           int32_t* d_err, void* hip_stream);
+int hutk_ugseed_words_device(hutk_ugseed* h, uint8_t* d_arena, int64_t* d_start, int64_t* d_len, int64_t* d_count, void* hip_stream);
+int hutk_ugseed_char_counts_device(hutk_ugseed* h, int64_t* d_counts, void* hip_stream);
+int hutk_ugseed_count_device(hutk_ugseed* h, int32_t max_piece_chars, int64_t table_slots, int64_t* d_info, void* hip_stream);
+int hutk_ugseed_compact_device(hutk_ugseed* h, int64_t cap, int64_t* d_score, int64_t* d_pos, int32_t* d_len, int64_t* d_n,
+                               void* hip_stream);
+int hutk_ugseed_gather_device(hutk_ugseed* h, const int64_t* d_pos, const int32_t* d_len, const int64_t* d_dst, int64_t n,
+                              uint8_t* d_blob, int64_t blob_cap, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

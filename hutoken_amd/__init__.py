@@ -16,6 +16,11 @@ GPU every call raises.
 Also here (not in the reference): `encode_packed` / `encode_packed_device`, the
 zero-marshalling entry points for packed UTF-8 + offsets.
 
+BPE-dropout (not in the reference): `encode_packed_device(..., dropout=p, seed=s, first_doc=k)` leaves every candidate
+merge of every step of a word's merge loop out with probability p (Provilkov et al. 2020), from Philox draws that are a
+stated function of (seed, document, byte offset, step); `batch_encode_dropout` and `encode_dropout` are the list forms
+(csrc/hutk_dropout.hip).  `encode` / `batch_encode` never drop a merge.
+
 Collation (not in the reference either): `collate_padded` / `batch_encode_padded` turn the device arrays of
 `encode_packed_device` into padded rows with attention mask and lengths, `SequencePacker` into packed rows of
 `seq_len` tokens with position and segment ids -- one HIP pass each (csrc/hutk_collate.hip).  `collate_windows` /
@@ -100,7 +105,7 @@ from . import normalize as _norm_tables  # (the module; the name `normalize` of 
 from . import wordpiece as _wp_tables
 
 __all__ = ["Unigram", "UnigramTrainer", "UnigramSeeder", "train_unigram", "WordPiece", "packed_cu_seqlens", "packed_lm_labels", "corrupt_spans", "batch_encode_span_corruption", "mask_tokens", "lm_labels", "batch_encode_mlm", "gather_rows", "answer_positions", "token_word_ids_device", "initialize", "encode", "batch_encode", "encode_packed", "encode_packed_device",
-           "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
+           "encode_dropout", "batch_encode_dropout", "decode", "batch_decode", "context", "Trainer", "train", "bpe_train", "bbpe_train",
            "collate_padded", "batch_encode_padded", "SequencePacker", "collate_windows", "batch_encode_windows",
            "token_spans_device", "batch_encode_with_offsets", "encode_with_offsets",
            "set_special_tokens", "encode_special", "batch_encode_special", "encode_special_packed_device",
@@ -321,13 +326,85 @@ def encode_packed(data, offsets):
     return ids, oo, st
 
 
-def encode_packed_device(d_bytes, d_offsets, check=True):
+def encode_packed_device(d_bytes, d_offsets, check=True, *, dropout=None, seed=None, first_doc=0):
     """Device-resident torch tensors in (uint8 bytes, int64 offsets[n+1]), device
     tensors out: (ids int32[capacity], out_offsets int64[n+1]).  The ids of
     document i are ids[out_offsets[i]:out_offsets[i+1]].  Asynchronous on the
     current torch stream unless check=True, which synchronises and raises on a
-    device-side error."""
-    return _encode_on_current_stream("plain", d_bytes, d_offsets, 0, check)
+    device-side error.
+
+    dropout=None is the plain encoding.  With dropout=p in [0, 1] (BPE-dropout, Provilkov et al. 2020) every candidate
+    merge of every step of a word's merge loop is left out with probability p, decided on the GPU by Philox draws that
+    are a function of (seed, first_doc + the document's index, the byte offset in the document, the step) and of nothing
+    else (include/hutoken_amd.h: hutk_encode_dropout_batch_device; csrc/hutk_dropout.hip).  seed (an int below 2**64) is
+    required then and has no default; first_doc is the number of the batch's first document in the corpus, so that a
+    corpus encoded in pieces equals the corpus encoded at once.  p = 0 gives the plain ids, p = 1 one id per byte.  A
+    byte-encoder context without a prefix and without a regex pattern; d_bytes at any alignment.  A word of more than
+    262144 bytes ends its document in front of it, as in the plain encoding."""
+    if dropout is None:
+        return _encode_on_current_stream("plain", d_bytes, d_offsets, 0, check)
+    drop_below, seed, first_doc = _dropout_args(dropout, seed, first_doc)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    return _on_torch_stream(d_bytes.device, lambda: _encode_dropout_device(d_bytes, d_offsets, drop_below, seed, first_doc, check),
+                            used=(d_bytes, d_offsets))
+
+
+def _dropout_args(dropout, seed, first_doc):
+    """What the dropout forms check before any device call -> (drop_below = int(p * 2**32), seed, first_doc)."""
+    p = _fraction_arg("dropout", dropout)
+    if seed is None:
+        raise ValueError("dropout needs a seed: the sampled merges are a function of (seed, document, offset, step), and seed has no default")
+    if isinstance(first_doc, bool) or not isinstance(first_doc, int):
+        raise TypeError("first_doc must be an int, not %s" % type(first_doc).__name__)
+    if not 0 <= first_doc < 2**62:
+        raise ValueError("first_doc must be in 0 .. 2**62 - 1, not %d" % first_doc)
+    return int(p * 2**32), _seed_arg(seed), first_doc
+
+
+def _encode_dropout_device(d_bytes, d_offsets, drop_below, seed, first_doc, check):
+    import torch
+    n_docs, n_bytes, dev = d_offsets.numel() - 1, d_bytes.numel(), d_bytes.device
+    cap = _ctx.ids_capacity(n_bytes, n_docs)
+    ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    oo = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _ctx.encode_dropout_device(d_bytes.data_ptr(), d_offsets.data_ptr(), n_docs, n_bytes, drop_below, seed, first_doc,
+                               ids.data_ptr(), cap, oo.data_ptr(), 0, err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if check:
+        code = int(err.item())
+        if code not in (0, _capi.E_WORD_TOO_LARGE):  # (the note: a document was cut at a word over 262144 bytes)
+            raise RuntimeError(f"hutoken_amd: device-side error {code}")
+    return ids, oo
+
+
+def batch_encode_dropout(texts, dropout, seed, first_doc=0, normalize=None):
+    """list of str -> list of lists of ids with BPE-dropout (encode_packed_device(dropout=, seed=, first_doc=): text i is
+    document first_doc + i).  normalize: a normal form ("NFC" ..) the packed text is put into on the GPU first."""
+    import torch
+    drop_below, seed, first_doc = _dropout_args(dropout, seed, first_doc)
+    _normalize_arg(normalize)
+    if _ctx is None:
+        raise RuntimeError(_NOT_INIT)
+    if not isinstance(texts, list):
+        raise TypeError("Invalid arguments. Expected a list of strings.")
+    data, offs = _pack(texts)
+    dev = torch.device("cuda", _capi.load().hutk_device_ordinal(_ctx.handle))
+    d_bytes = torch.from_numpy(data.copy()).to(dev)  # (a copy: _pack's array is a read-only view of a bytes object)
+    d_offs = torch.from_numpy(offs).to(dev)
+    with torch.cuda.device(dev):
+        if normalize is not None:
+            d_bytes, d_offs = normalize_packed_device(d_bytes, d_offs, normalize)
+        ids, oo = _on_torch_stream(dev, lambda: _encode_dropout_device(d_bytes, d_offs, drop_below, seed, first_doc, True),
+                                   used=(d_bytes, d_offs))
+    return _rows(ids.cpu(), oo.cpu(), len(texts))
+
+
+def encode_dropout(text, dropout, seed):
+    """One str -> its list of ids with BPE-dropout (the text is document 0)."""
+    if not isinstance(text, str):
+        raise TypeError(f"argument 1 must be str, not {type(text).__name__}")
+    return batch_encode_dropout([text], dropout, seed)[0]
 
 
 def _encode_on_current_stream(kind, d_bytes, d_offsets, flags, check):

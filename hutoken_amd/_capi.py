@@ -190,6 +190,8 @@ SIGNATURES = {
     "hutk_ugseed_gather_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "hutk_debug_unigram_chunk_bytes": (_i32, []),
     "hutk_debug_unigram_bucket": (_i64, [_vp, _vp, _i64]),
+    "hutk_encode_dropout_batch_device": (_i32, [_vp, _vp, _vp, _i64, _i64, C.c_uint64, C.c_uint64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hutk_debug_dropout_info": (_i32, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 TRAIN_BYTES, TRAIN_CHARS = 0, 1
@@ -544,6 +546,14 @@ class Context(_Owner):
         rc = load().hutk_encode_batch_device(self._h, d_bytes, d_offsets, n_docs, n_bytes, d_ids, ids_cap,
                                              d_out_offsets, d_status or None, d_err or None, stream or None)
         raise_for(rc)
+
+    def encode_dropout_device(self, d_bytes, d_offsets, n_docs, n_bytes, drop_below, seed, first_doc, d_ids, ids_cap,
+                              d_out_offsets, d_status=0, d_err=0, stream=0):
+        """hutk_encode_dropout_batch_device on raw device pointers (ints); asynchronous on `stream`."""
+        raise_for(load().hutk_encode_dropout_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, n_bytes,
+                                                          drop_below, seed, first_doc, d_ids or None, ids_cap,
+                                                          d_out_offsets or None, d_status or None, d_err or None,
+                                                          stream or None))
 
     def token_spans_device(self, d_bytes, d_offsets, n_docs, n_bytes, d_ids, d_id_offsets, n_ids, unit, out_width,
                            d_spans, d_status=0, d_err=0, stream=0):
@@ -1476,3 +1486,10 @@ class UnigramSeed(_Owner):
 
 def unigram_chunk_bytes():
     return load().hutk_debug_unigram_chunk_bytes()
+
+
+def dropout_info():
+    """hutk_debug_dropout_info -> dict(chunk_bytes, lane_units, wave_lds_units, max_word_bytes)"""
+    out = (C.c_int64 * 4)()
+    raise_for(load().hutk_debug_dropout_info(out))
+    return dict(zip(("chunk_bytes", "lane_units", "wave_lds_units", "max_word_bytes"), out))

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
-HIP_SOURCES = ["hutk_loader.cpp", "hutk_api.cpp", "hutk_kernels.hip", "hutk_ptiles.hip", "hutk_decode.hip", "hutk_train.hip", "hutk_collate.hip", "hutk_spans.hip", "hutk_special.hip", "hutk_fallback.hip", "hutk_normalize.hip", "hutk_presplit.hip", "hutk_features.hip", "hutk_bestfit.hip", "hutk_wordpiece.hip", "hutk_unigram.hip"]
+HIP_SOURCES = ["hutk_loader.cpp", "hutk_api.cpp", "hutk_kernels.hip", "hutk_ptiles.hip", "hutk_decode.hip", "hutk_train.hip", "hutk_collate.hip", "hutk_spans.hip", "hutk_special.hip", "hutk_fallback.hip", "hutk_normalize.hip", "hutk_presplit.hip", "hutk_features.hip", "hutk_bestfit.hip", "hutk_wordpiece.hip", "hutk_unigram.hip", "hutk_dropout.hip"]
 HIP_HEADERS = ["hutk_internal.h", "hutk_seam2.h", "hutk_kdev.h", "hutk_device.h", "hutk_host.h", "hutk_classify.h", "hutk_lab.h", "hutk_exc.h", "hutk_norm.h", "hutk_presplit.h", "hutk_wave.h", "hutk_philox.h", "hutk_fim.h", "hutk_wordpiece.h", "hutk_unigram.h", "hutk_unigram_train.h", "hutk_unigram_seed.h", "hutk_wcache.h", "hutk_wordbits.h", os.path.join(INCLUDE, "hutoken_amd.h")]
 
 LIB_HIP = os.path.join(LIBDIR, "libhutoken_amd.so")

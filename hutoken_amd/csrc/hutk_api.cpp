@@ -292,6 +292,7 @@ void destroy(hutk_ctx* c) {
         c->sp_ok.release();
         c->sxd.release();
         c->fb.release();
+        c->dro.release();
         c->s_bytes.release(); c->s_offsets.release(); c->s_out_offsets.release(); c->s_ids.release();
         c->s_status.release(); c->s_small_in.release(); c->s_small_out.release();
         if (c->small_host) (void)hipHostFree(c->small_host);

@@ -214,6 +214,20 @@ struct hutk_ctx {
         }
     } fb;
 
+    // BPE-dropout (hutk_dropout.hip): the workspace of hutk_encode_dropout_batch_device -- the flag (sound offsets), the
+    // per-byte ids, the three per-byte arrays of the words too long for LDS, the built-in splitter's two bitmaps and the
+    // counts per chunk and slice
+    struct Dropout {
+        DevBuf<int32_t> flags, tmp;
+        DevBuf<uint32_t> link, bits;
+        DevBuf<unsigned long long> bound;
+        DevBuf<int64_t> chunk;
+        DevBuf<uint16_t> slice;
+        void release() {
+            flags.release(); tmp.release(); link.release(); bits.release(); bound.release(); chunk.release(); slice.release();
+        }
+    } dro;
+
     // staging for the host-buffer entry point
     DevBuf<uint8_t> s_bytes;
     DevBuf<int64_t> s_offsets, s_out_offsets;

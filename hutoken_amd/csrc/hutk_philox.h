@@ -47,8 +47,13 @@ HUTK_PHILOX_HD inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
 //            the two cuts; hutk_fim.h);
 // purpose 5: the Unigram sampling draw of DOCUMENT `row`, unit = low32 of the folded offset, inside the document, of the
 //            character start the sampled path stands at (x and y: the 53 bits of u = ((x << 21) | (y >> 11)) * 2^-53, which
-//            picks the piece that starts there; hutk_unigram.hip).
+//            picks the piece that starts there; hutk_unigram.hip);
+// purpose 6: the BPE-dropout draw of DOCUMENT `row`, unit = low32 of the offset, inside the document, of the byte the
+//            candidate's left unit begins at; the fourth counter word is (step << 4) | 6, step = the merges the word has
+//            had applied so far (x: the candidate is dropped for this step iff x < drop_below; hutk_dropout.hip, DESIGN.md
+//            section 4e).  Purposes stay below 16, so a shifted step never collides with one.
 constexpr uint32_t DRAW_COLUMN = 0, DRAW_WORD_A = 1, DRAW_WORD_B = 2, DRAW_SPAN = 3, DRAW_FIM = 4, DRAW_UNIGRAM = 5;
+constexpr uint32_t DRAW_BPE_DROPOUT = 6;
 
 HUTK_PHILOX_HD inline Philox4 draw(uint64_t seed, int64_t row, uint32_t unit, uint32_t purpose) {
     return philox4x32_10((uint32_t)(uint64_t)row, (uint32_t)((uint64_t)row >> 32), unit, purpose, (uint32_t)seed,

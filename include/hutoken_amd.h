@@ -1565,6 +1565,46 @@ int hutk_ugseed_compact_device(hutk_ugseed* h, int64_t cap, int64_t* d_score, in
 int hutk_ugseed_gather_device(hutk_ugseed* h, const int64_t* d_pos, const int32_t* d_len, const int64_t* d_dst, int64_t n,
                               uint8_t* d_blob, int64_t blob_cap, void* hip_stream);
 
+/* ---- BPE-dropout: sampled merges (hutk_dropout.hip) ---------------------------------------
+ * hutk_encode_dropout_batch_device: hutk_encode_batch_device's buffers in and out, with the merge loop of Provilkov et al.
+ * 2020 ("BPE-Dropout", Algorithm 1; models.BPE(dropout=p) of `tokenizers`): at every step of a word's merge loop each
+ * candidate merge is left out with probability p.  The reference has no counterpart.
+ *
+ * THE RULE.  What stays as hutk_encode_batch_device has it: the words (the built-in splitter, or the word starts of the
+ * context's split preset), the initial units of a word (one unit per input byte through the item table), the pair table,
+ * and a pair's rank (smallest first, leftmost on ties).  The seam maps, the whole-word table and the word cache are not
+ * consulted.  Per word of document d (the d-th of the batch), with t = 0:
+ *   1. the candidates are the adjacent live pairs (l, r) for which the pair table gives a merged symbol;
+ *   2. a candidate whose left unit begins at byte offset o INSIDE ITS DOCUMENT is dropped for this step iff
+ *      x < drop_below, x = the first word of philox4x32_10(counter = (low32(D), high32(D), low32(o), (t << 4) | 6),
+ *      key = (low32(seed), high32(seed))), D = first_doc + d.  drop_below = (uint64_t)(p * 2^32) is an integer in
+ *      [0, 2^32] and the comparison is 64-bit, so p = 1 drops everything.  (6: the purpose DRAW_BPE_DROPOUT of
+ *      hutk_philox.h; the purposes stay below 16.)
+ *   3. no candidate, or none that survives: the word is finished;
+ *   4. otherwise the surviving candidate of smallest rank, leftmost on ties, is applied, t += 1, and again from 1.
+ * So a draw is a pure function of (seed, D, o, t): an outcome depends neither on the rest of the batch nor on the order
+ * of evaluation, and a corpus encoded in pieces with first_doc = the documents in front of a piece equals the corpus
+ * encoded at once.  drop_below = 0 is the plain encoding of every word: ids and offsets equal hutk_encode_batch_device's.
+ * drop_below = 2^32 gives the id of every byte's unit.
+ *
+ * LONG WORDS.  A word of more than 262144 bytes ends its document in front of it: d_status[i] = HUTK_DOC_WORD_TOO_LARGE and
+ * *d_err = HUTK_E_WORD_TOO_LARGE (a note), as hutk_encode_batch_device.  Every shorter word is served.
+ * A 0x00 byte: HUTK_E_NUL_BYTE in *d_err.  The offsets are
+ * checked on the device: they rise from 0 to n_bytes, else HUTK_E_ARG in *d_err and nothing else is written.  ids <=
+ * bytes here, so ids_cap >= hutk_ids_capacity() - 1 suffices (HUTK_E_CAPACITY at the call otherwise).  d_bytes at any
+ * alignment.  Enqueued on hip_stream, never synchronises (growing the workspace -- about 24 bytes per input byte -- for
+ * a batch larger than any before waits for the device once); serialised with the context's other calls.
+ * Served: byte-encoder mode without a prefix, one unit per input item, with or without a merges file, the built-in
+ * splitter or a split preset.  HUTK_E_UNSUPPORTED at the call, before anything is launched: character mode, a prefix,
+ * items of several units, a context with a regex pattern.  HUTK_E_VALUE: drop_below > 2^32.  HUTK_E_ARG: first_doc < 0.
+ * Not here: the special-token and byte-fallback encoders, host buffers, several devices behind one context.
+ * hutk_debug_dropout_info: out4 = the chunk's bytes, the longest word one lane merges, the longest word a wavefront
+ * merges in LDS, the longest word (262144). */
+int hutk_encode_dropout_batch_device(hutk_ctx* ctx, const uint8_t* d_bytes, const int64_t* d_offsets, int64_t n_docs, int64_t n_bytes,
+                                     uint64_t drop_below, uint64_t seed, int64_t first_doc, int32_t* d_ids_out, int64_t ids_cap,
+                                     int64_t* d_out_offsets, int32_t* d_status, int32_t* d_err, void* hip_stream);
+int hutk_debug_dropout_info(int64_t* out4);
+
 #ifdef __cplusplus
 }
 #endif
